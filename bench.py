@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- the headline measurement of the search path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[1], the one the metric is quoted on; configs[4] for N > 1):
@@ -159,9 +159,14 @@ def main():
     ap.add_argument("--allow-shared-gpu", action="store_true",
                     help="debugging the N > 1 path on a box with fewer GPUs than ranks: ranks share devices and "
                          "the match exchange goes over gloo; never a valid scaling measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the Match records of the last timed search as DIR/<field>.npy "
+                         "(see dump_outputs): two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.mode == "inproc":
         return main_inproc(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -366,6 +371,8 @@ def main():
     matches, st = last[0], last[1]
     if gather_worker is not None:
         matches = gather_worker.last  # rank 0: the merged rows of the last search; None elsewhere
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, matches)
     el = torch.tensor([elapsed, scan_ms / max(1, args.steps), filter_ms / max(1, args.steps)],
                       dtype=torch.float64, device=coll_device)
     if dist is not None:
@@ -576,6 +583,8 @@ def main_inproc(args):
         r = step() or r
     r = drain(r)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r)
     dom_name = {0: "scan_kernel", 1: "filter_kernel", 2: "filter_dna_kernel", 3: "filter_table_kernel", 4: "filter_count_kernel"}[int(st["filtered"])]
     achieved = n_per / (dom_ms / 1e3) / 1e9 if dom_ms > 0 else 0.0
     ms_per_step = elapsed / args.steps * 1e3
@@ -621,6 +630,33 @@ def main_inproc(args):
         "cpu_baseline_note": "reported by the default mode at N = 1 (python bench.py)",
     }
     print(json.dumps(out), flush=True)
+
+
+DUMP_FIELDS = ("pattern_idx", "text_start", "text_end", "pattern_start", "pattern_end", "cost", "strand")
+DUMP_DATA_BYTES = 63_000_000  # --dump-outputs: at most 64 MB in all, the .npy headers included
+
+
+def dump_outputs(out_dir, matches):
+    """--dump-outputs: the Match records a caller of the timed path received from its last search, in result order, as
+    <out_dir>/<field>.npy: float64 per field of DUMP_FIELDS (strand 0 = '+', 1 = '-'; exact below 2^53) and cigar.npy,
+    float32 [records, longest cigar]: the SAM cigar's bytes, NUL-padded.  row.npy (float64) names the records written:
+    all of them, or, when they would not fit in DUMP_DATA_BYTES, a sample fixed by the record count and seed 0.
+    `matches` is a sassy_amd.Result, or for N > 1 rank 0's merged rows (sassy_amd.multigpu's row layout)."""
+    import numpy as np
+    from sassy_amd import multigpu
+    rows = matches if isinstance(matches, np.ndarray) else multigpu.pack_result_numpy(matches).rows
+    n = rows.shape[0]
+    cigar = np.ascontiguousarray(rows[:, multigpu.FIXED_COLS:]).view(np.uint8).reshape(n, 8 * (rows.shape[1] - multigpu.FIXED_COLS))
+    w = int(np.count_nonzero(cigar, axis=1).max(initial=0))
+    per_row = 8 * (len(DUMP_FIELDS) + 1) + 4 * w
+    keep = np.arange(n)
+    if n * per_row > DUMP_DATA_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_DATA_BYTES // per_row, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for i, f in enumerate(DUMP_FIELDS):
+        np.save(os.path.join(out_dir, f + ".npy"), rows[keep, i].astype(np.float64))
+    np.save(os.path.join(out_dir, "cigar.npy"), cigar[keep, :w].astype(np.float32))
+    np.save(os.path.join(out_dir, "row.npy"), keep.astype(np.float64))
 
 
 def dense_config(sassy_amd, text, pat, k):

@@ -203,16 +203,29 @@ def test_sub_piece_test_never_rejects_a_match(sassy):
 
 
 def test_no_device_fails_loudly(sassy):
-    assert sassy.device_count() == 0
-    s = sassy.Searcher("dna", rc=False)
-    with pytest.raises(sassy.SassyHipError, match="no usable HIP device"):
-        s.search(b"ACGT", b"ACGTACGT", 0)
-    e = s.encode_patterns([b"ACGT"])
-    with pytest.raises(sassy.SassyHipError, match="no usable HIP device"):
-        s.search_encoded_patterns(e, b"ACGTACGT", 0)
-    # invalid IUPAC pattern is rejected before any device work (reference panics: iupac.rs:19-24)
-    with pytest.raises(sassy.SassyHipError, match="not valid IUPAC"):
-        sassy.Searcher("iupac", rc=False).search(b"AC1T", b"ACGT", 0)
+    """Runs in a child process that sees no HIP device (HIP_VISIBLE_DEVICES=-1), so that it means the same on a box
+    with a GPU as on one without."""
+    code = (
+        "import re, sassy_amd\n"
+        "def raises(pattern, f, *args):\n"
+        "    try:\n"
+        "        f(*args)\n"
+        "    except sassy_amd.SassyHipError as e:\n"
+        "        assert re.search(pattern, str(e)), e\n"
+        "    else:\n"
+        "        raise AssertionError('no SassyHipError: ' + pattern)\n"
+        "assert sassy_amd.device_count() == 0, sassy_amd.device_count()\n"
+        "s = sassy_amd.Searcher('dna', rc=False)\n"
+        "raises('no usable HIP device', s.search, b'ACGT', b'ACGTACGT', 0)\n"
+        "e = s.encode_patterns([b'ACGT'])\n"
+        "raises('no usable HIP device', s.search_encoded_patterns, e, b'ACGTACGT', 0)\n"
+        # invalid IUPAC pattern is rejected before any device work (reference panics: iupac.rs:19-24)
+        "raises('not valid IUPAC', sassy_amd.Searcher('iupac', rc=False).search, b'AC1T', b'ACGT', 0)\n"
+        "print('ok')\n"
+    )
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and p.stdout.strip() == "ok", p.stdout + p.stderr
 
 
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="only meaningful on a box without a GPU")
