@@ -174,6 +174,29 @@ int sassy_hip_search(sassy_SearcherType *s, const uint8_t *pattern, size_t patte
                      const uint8_t *text, size_t text_len, size_t k, uint32_t flags,
                      sassy_hip_Result **out);
 
+/* Searcher::search_all_alignments (src/search.rs:702-760, src/alignment_iterator.rs:44-370; Python: src/python.rs:117-135):
+ * every alignment of cost <= k at every end position that search_all without trace reports under this searcher's
+ * settings (strands, only_best_match, the max_n_frac end-position filter).  Per end position a DFS from cell (end, m)
+ * of the pattern-against-text DP matrix (top row 0, left column j) emits every path that reaches row 0 with cost <= k,
+ * taking an edge ('='/'X', 'D', 'I') only if: cost so far + edge + the cell's DP value <= k; it is no leading or
+ * trailing 'D'; it does not leave (by 'I'/'D') a diagonal that matches exactly up to row 0, nor enter one at a cell from
+ * which the diagonal matches exactly down to the last row visited on it (row m if none; this reads text past the end
+ * position); no 'I' while the indels since the last '=' are net deletions, no 'D' while they are net insertions.  The
+ * surviving edges are visited by total cost, ties in the order diagonal, D, I.  The Rc strand runs on the reversed text
+ * with complement(pattern), coordinates mapped back as [n - e', n - s').  Records: pattern_start 0, pattern_end m, the
+ * path's own cost, the cigar as traced Rc matches carry it; with max_n_frac < 1 only alignments whose span passes.
+ * Order: Fwd alignments by ascending text_end, then Rc ones by descending text_start, DFS order inside one end position
+ * (a group = a maximal run of one strand and one anchor: text_end for Fwd, text_start for Rc).  Runs on the device
+ * (sassy_amd/csrc/all_alignments.hip); the result is one flat sassy_hip_Result.  flags: SASSY_HIP_TEXT_ON_DEVICE,
+ * SASSY_HIP_TEXT_UNCHANGED as for sassy_hip_search, anything else is SASSY_HIP_EINVAL.  Overhang searchers (alpha set):
+ * SASSY_HIP_EUNSUPPORTED (the reference asserts, src/alignment_iterator.rs:61-64).  SASSY_HIP_ENOMEM (with the count in
+ * the message) if the result does not fit host memory or its cigar text exceeds 4 GiB.  sassy_hip_get_stats afterwards:
+ * scan_ms / filter_ms of the search, trace_ms = the HIP-event time of the enumeration launches, candidates = end
+ * positions enumerated. */
+int sassy_hip_search_all_alignments(sassy_SearcherType *s, const uint8_t *pattern, size_t pattern_len,
+                                    const uint8_t *text, size_t text_len, size_t k, uint32_t flags,
+                                    sassy_hip_Result **out);
+
 /* Searcher::search_with_fn (src/search.rs:767-784): keep only the end positions for which the
  * callback returns non-zero.  It sees what the reference's closure sees: the pattern, the text up
  * to the end position (text_till_end[0 .. end_pos)) and the strand (0 Fwd, 1 Rc); for the Rc strand

@@ -119,7 +119,7 @@ EXPORTED_SYMBOLS = [
     "sassy_searcher", "sassy_searcher_free", "search", "sassy_matches_free",
     "sassy_hip_last_error", "sassy_hip_version", "sassy_hip_device_count",
     "sassy_hip_searcher_new", "sassy_hip_set_stream", "sassy_hip_get_stats",
-    "sassy_hip_search", "sassy_hip_search_shard", "sassy_hip_required_halo",
+    "sassy_hip_search", "sassy_hip_search_all_alignments", "sassy_hip_search_shard", "sassy_hip_required_halo",
     "sassy_hip_search_shard_begin", "sassy_hip_search_finish", "sassy_hip_set_pipe_depth", "sassy_hip_set_geometry_tuner", "sassy_hip_set_reference_lanes",
     "sassy_hip_result_len", "sassy_hip_result_matches", "sassy_hip_result_cigars",
     "sassy_hip_result_cigars_len", "sassy_hip_pack_rows", "sassy_hip_enable_counters", "sassy_hip_set_timing",
@@ -260,6 +260,8 @@ def lib():
                                            END_FILTER, vp, C.POINTER(vp)]
     L.sassy_hip_search.restype = C.c_int
     L.sassy_hip_search.argtypes = [vp, u8p, sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
+    L.sassy_hip_search_all_alignments.restype = C.c_int
+    L.sassy_hip_search_all_alignments.argtypes = [vp, u8p, sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
     L.sassy_hip_search_shard.restype = C.c_int
     L.sassy_hip_search_shard.argtypes = [vp, u8p, sz, vp, C.c_uint64, C.c_uint64, C.c_uint64,
                                          C.c_uint64, sz, C.c_uint32, C.POINTER(vp)]
@@ -588,6 +590,30 @@ class Searcher:
 
     def search_without_trace(self, pattern: bytes, text, k: int) -> List[Match]:
         return self._search(pattern, text, k, WITHOUT_TRACE).matches
+
+    def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
+        """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k
+        at every end position of search_all, grouped: one list per (strand, anchor) -- the anchor is text_end for
+        Fwd matches and text_start for Rc matches --, Fwd groups by ascending text_end, then Rc groups by descending
+        text_start, alignments in DFS order inside a group.  `text` as for `search` (bytes or a device tensor)."""
+        pattern = bytes(pattern)
+        addr, n, keep, on_dev = _ptr_len(text)
+        flags = 0
+        if on_dev:
+            flags |= TEXT_ON_DEVICE
+            if getattr(self, "_text_unchanged", False):
+                flags |= TEXT_UNCHANGED
+        out = C.c_void_p()
+        _check(lib().sassy_hip_search_all_alignments(self._h, pattern, len(pattern), addr, n, k, flags, C.byref(out)))
+        groups: List[List[Match]] = []
+        last = None
+        for x in Result(out).matches:
+            key = (x.strand, x.text_end if x.strand == "+" else x.text_start)
+            if key != last:
+                groups.append([])
+                last = key
+            groups[-1].append(x)
+        return groups
 
     def search_with_fn(self, pattern: bytes, text: bytes, k: int, all_minima: bool, filter_fn) -> List[Match]:
         """Searcher::search_with_fn (src/search.rs:767-784): keep the end positions for which

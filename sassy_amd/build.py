@@ -36,6 +36,7 @@ UNITS = [
     ("scan_driver.hip", "scan_driver.o", []),
     ("many_patterns.hip", "many_patterns.o", []),
     ("multi_device.hip", "multi_device.o", []),
+    ("all_alignments.hip", "all_alignments.o", []),
     ("c_abi.hip", "c_abi.o", []),
 ]
 HEADERS = ["common.h", "profiles.h", "tiled_step.h", "switches.h", "host_internal.h", os.path.join("..", "..", "include", "sassy.h"),

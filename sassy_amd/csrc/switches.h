@@ -59,7 +59,8 @@ namespace sassy_hip {
   X(overhang_seeded, 1, "0: overhang with many patterns through the per-text tiled scan over everything")                   \
   X(multi_min_text, 16 << 20, "search_encoded: smallest text (bytes) for the multi-pattern prefilter")                       \
   X(tiled, -1, "search_encoded: 1 force / 0 forbid the pattern-tiled scan")                                                 \
-  X(seeded, -1, "search_encoded: 1 force / 0 forbid the seeded search")
+  X(seeded, -1, "search_encoded: 1 force / 0 forbid the seeded search")                                                 \
+  X(aa_batch, 0, "search_all_alignments: at most this many alignments per emit batch (0: 32 MiB of rows / cigar text)")
 
 struct Switches {
 #define SASSY_HIP_SWITCH_FIELD(name, dflt, doc) long name = (dflt);
