@@ -87,7 +87,8 @@ typedef struct sassy_hip_Stats {
                              walked column by column (0 unless counters are enabled) */
   uint32_t pair;          /* != 0: the fused launch ran the PAIRED filter with this many super-pieces of 2 * piece_len
                              rows (one half exact, the other half with <= 1 edit next to it; SASSY_HIP_PAIR=0: never) */
-  uint32_t reserved_;
+  uint32_t pass_patterns; /* searches the text pass of this search served: 2 when a search in flight shared it
+                             (sassy_hip_search_shard_begin), else 1 */
 } sassy_hip_Stats;
 
 const char *sassy_hip_last_error(void);
@@ -252,7 +253,14 @@ uint64_t sassy_hip_required_halo(size_t pattern_len, size_t k);
  * caller likes, each result is exactly what sassy_hip_search_shard returns.  The short, latency-bound tail of
  * search i (chunk list, chunk DP, traceback) then runs underneath the bandwidth-bound prefilter of search
  * i+1.  The pattern is copied; the text must stay valid and unchanged until the ticket is finished.  Every
- * ticket must be finished before the searcher is freed (tickets still open then are dropped).  The calls of
+ * ticket must be finished before the searcher is freed (tickets still open then are dropped).
+ * Searches in flight may share one text pass: a Dna forward search on the fused bit-plane path that is begun while
+ * the searcher's previous pass still streams waits for a second such search over the same buffer (same d_text,
+ * halo_len, shard_len, global_offset, total_len, flags and piece length, at most 8 pieces together), and one launch
+ * filters the text for both (sassy_hip_Stats.pass_patterns = 2).  A waiting search is launched when its group is
+ * full, when a begin finds no pass streaming, before any other kind of search is begun, and when its own ticket is
+ * finished -- no ticket waits on a launch that only a later call would make.  Results are unchanged; SASSY_HIP_SHARED_PASS=0
+ * (sassy_hip_set_option "shared_pass") turns it off.  The calls of
  * one searcher must still come from one thread at a time.  sassy_hip_get_stats describes the search finished last.
  * While a ticket is open the searcher's synchronous entry points (sassy_hip_search, _search_shard, _search_many,
  * _search_encoded, _search_with_fn, the drop-in search) and sassy_hip_set_stream fail with SASSY_HIP_EINVAL: they

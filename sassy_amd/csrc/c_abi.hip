@@ -515,6 +515,51 @@ int sassy_hip_merge_shards(const sassy_hip_Result* const* results, size_t n, int
 
 }  // extern "C"
 
+// ---- shared pass: searches in flight over one buffer filtered by one launch ----
+// A searcher has at most one OPEN GROUP: begun tickets whose pass is not launched yet (at most two: the grouped launch,
+// filter_dna_kernel<.., G = 2>, has two members).  A groupable ticket (ScanJob::group_ok) that is begun while the
+// searcher's last pass still streams waits there for a second one (ScanJob::group_fits); the group is launched when it is
+// full, when a begin finds no pass streaming, before a ticket that cannot join it is begun, and when one of its tickets is
+// finished (shared_pass = 2: before any finish that would wait).  Nothing is left unlaunched across a wait: no deadlock.
+static ScanJob* ticket_job(sassy_hip_Ticket* t) { return static_cast<ScanJob*>(t->job.get()); }
+
+static bool pass_streaming(sassy_SearcherType* s) {
+  if (s->sw.shared_pass == 3) return true;  // (tests: every groupable ticket waits for a partner)
+  if (s->last_pass_lane < 0) return false;
+  const hipError_t e = hipEventQuery(s->lanes[s->last_pass_lane].ev_filter_done);
+  if (e == hipErrorNotReady) {
+    (void)hipGetLastError();  // (not an error)
+    return true;
+  }
+  return false;
+}
+
+// launches the open group: one member as a search of its own, two as one shared pass (member 0's lane runs it)
+static int launch_open_group(sassy_SearcherType* s) {
+  if (s->open_group.empty()) return 0;
+  std::vector<sassy_hip_Ticket*> g;
+  g.swap(s->open_group);
+  ScanJob* a = ticket_job(g[0]);
+  int rc = 0;
+  if (g.size() == 1) {
+    rc = a->enqueue(0);
+  } else {
+    ScanJob* b = ticket_job(g[1]);
+    b->group_leader = a;
+    rc = b->enqueue(0);
+    b->group_leader = nullptr;
+  }
+  for (sassy_hip_Ticket* t : g) {
+    t->pending = false;
+    t->pass_patterns = (uint32_t)g.size();
+    t->launch_rc = rc;
+  }
+  s->last_pass_lane = g[0]->lane;
+  if (rc != 0)
+    for (sassy_hip_Ticket* t : g) (void)hipStreamSynchronize(s->lanes[t->lane].stream);
+  return rc;
+}
+
 extern "C" {
 
 // ---- searches in flight: begin / finish ----
@@ -567,12 +612,38 @@ int sassy_hip_search_shard_begin(sassy_SearcherType* s, const uint8_t* pattern, 
     // the filters of two searches fill each other's ramp-up and drain, a strict sequence leaves those bubbles), and
     // the filter as two half launches with the next search waiting for the event in between (0.65).
     int rc = job->prepare();
-    if (rc == 0 && !job->empty) rc = job->enqueue(0);
     if (rc != 0) {
       (void)hipStreamSynchronize(s->lanes[lane].stream);
       return rc;
     }
     t->job = job;
+    const bool groupable = s->sw.shared_pass != 0 && depth > 1 && job->group_ok();
+    if (groupable && !s->open_group.empty() && !ticket_job(s->open_group[0])->group_fits(*job)) rc = launch_open_group(s);
+    if (rc == 0 && groupable && (!s->open_group.empty() || pass_streaming(s))) {
+      // share a pass: wait for a second search (or, with no pass streaming any more, go now with the one waiting)
+      t->pending = true;
+      s->open_group.push_back(t.get());
+      s->lane_ticket[lane] = t.get();
+      s->last_begun_lane = lane;
+      if (s->open_group.size() == 2 || !pass_streaming(s)) rc = launch_open_group(s);
+      if (rc != 0) {
+        s->lane_ticket[lane] = nullptr;
+        return rc;
+      }
+      *out = t.release();
+      return 0;
+    }
+    if (rc == 0) rc = launch_open_group(s);  // (order: a waiting group goes in front of a search that cannot join it)
+    if (rc == 0 && !job->empty) {
+      rc = job->enqueue(0);
+      s->last_pass_lane = lane;
+    }
+    if (rc != 0) {
+      (void)hipStreamSynchronize(s->lanes[lane].stream);
+      return rc;
+    }
+  } else if (int rc = launch_open_group(s)) {
+    return rc;
   }
   s->lane_ticket[lane] = t.get();
   s->last_begun_lane = lane;
@@ -584,8 +655,18 @@ int sassy_hip_search_finish(sassy_SearcherType* s, sassy_hip_Ticket* t, sassy_hi
   if (!s || !t || t->owner != s) return fail(SASSY_HIP_EINVAL, "not a ticket of this searcher");
   DeviceGuard on_device(s);
   std::unique_ptr<sassy_hip_Ticket> guard(t);
+  // its own pass goes now if it still waits; shared_pass = 2: so does any waiting group when this finish would wait
+  bool would_wait = false;
+  if (s->sw.shared_pass == 2 && !s->open_group.empty() && hipStreamQuery(s->lanes[t->lane].stream) == hipErrorNotReady) {
+    (void)hipGetLastError();  // (not an error)
+    would_wait = true;
+  }
+  const int lrc = (t->pending || would_wait) ? launch_open_group(s) : 0;
   s->lane_ticket[t->lane] = nullptr;
   reset_stats(s);
+  if (t->launch_rc != 0) return t->launch_rc;
+  if (lrc != 0) return lrc;
+  s->stats.pass_patterns = t->pass_patterns;
   std::unique_ptr<sassy_hip_Result> R(new sassy_hip_Result());
   if (t->job) {
     ScanJob* job = static_cast<ScanJob*>(t->job.get());

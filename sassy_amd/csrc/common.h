@@ -214,7 +214,19 @@ struct ScanParams {
   // ---- per-text mode (kScanPerText): where the texts lie in the buffer ----
   const uint64_t* texts_start;  // device: first byte of text t (a multiple of 64)
   const uint64_t* texts_len;    // device: its length
+  // ---- grouped fused pass (filter_dna_kernel<.., G = 2>): one text pass serves two searches ("members") ----
+  // The fields above are member 0's (its pieces, k, m, pattern rows, reports); member1 holds the second search's own.
+  // Bit p of piece_member: piece p of piece_bits / piece_rem is member 1's.
+  struct FuseMember {
+    const uint32_t* row_tab;
+    Candidate* cand;
+    uint32_t* cand_count;     // its control block: fuse word, chunk statistics, tail word
+    TextStash* stash;
+    uint32_t m, k, nwords, wb, flags, cand_cap, stash_cap, pad_;
+  } member1;
+  uint32_t piece_member;
 };
+constexpr uint32_t kFuseGroupMaxWords = 4;  // grouped pass: pattern words per member (the carries leave the tile's upper half free)
 
 // The pattern-tiled scan (tiled_kernel.hip; reference v2, src/pattern_tiling/search.rs:326-425).
 struct TiledParams {

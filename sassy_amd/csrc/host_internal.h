@@ -36,6 +36,7 @@ hipError_t launch_scan_dna(const ScanParams& P, uint32_t grid, size_t smem, hipS
 hipError_t launch_scan_iupac(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_scan_ascii(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_filter_dna(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
+hipError_t launch_filter_group(const ScanParams& P, uint32_t grid, hipStream_t stream);  // (two searches, one pass)
 hipError_t launch_filter_table(const ScanParams& P, uint32_t grid, hipStream_t stream);
 hipError_t launch_filter_dna_multi(const ScanParams& P, uint32_t grid, hipStream_t stream);
 hipError_t launch_filter_count(const ScanParams& P, uint32_t grid, hipStream_t stream);
@@ -251,6 +252,11 @@ struct sassy_hip_Ticket {
   bool empty_shard = false;
   double t0 = 0;
   std::shared_ptr<void> job;     // the ScanJob (defined below)
+  // shared pass (c_abi.hip): begun, but its pass is not launched yet (the searcher's open group holds it); the number of
+  // searches its pass served; what the deferred launch returned
+  bool pending = false;
+  uint32_t pass_patterns = 1;
+  int launch_rc = 0;
 };
 
 struct sassy_hip_Encoded {
@@ -271,6 +277,7 @@ struct ScanLane {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_f = nullptr, ev_filter_done = nullptr;
+  hipEvent_t ev_group = nullptr;  // shared pass: this lane's control block and pattern tables are ready for another lane's pass
   DevBuf<uint8_t> d_state, d_scratch, d_str, d_ctl, d_sort, d_scratch2;
   // The control block has a twin: a search clears the OTHER one behind its last kernel (64 bytes, while the host is busy
   // with this search's result), so the next search on this lane starts with its filter instead of a memset launch.
@@ -418,6 +425,7 @@ struct ScanLane {
     HIP_TRY(hipEventCreate(&ev_f));
     HIP_TRY(hipEventCreateWithFlags(&ev_filter_done, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&ev_group, hipEventDisableTiming));
     ready = true;
     return 0;
   }
@@ -430,7 +438,7 @@ struct ScanLane {
     d_pattern.release(); d_table.release(); d_rowoff.release(); d_ovtab.release(); d_stash.release();
     if (h_pin) g_pin_pool.give(PinBlock{h_pin, h_pin_dev, h_pin_cap, h_pin_device});
     h_pin = nullptr;
-    for (hipEvent_t e : {ev_a, ev_b, ev_c, ev_f, ev_filter_done, ev_done})
+    for (hipEvent_t e : {ev_a, ev_b, ev_c, ev_f, ev_filter_done, ev_done, ev_group})
       if (e) (void)hipEventDestroy(e);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
@@ -559,6 +567,10 @@ struct sassy_SearcherType {
   struct sassy_hip_Ticket* lane_ticket[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
   int last_begun_lane = -1;
   int pipe_depth = 2;
+  // shared pass (switch shared_pass): begun tickets that wait to share one text pass (at most two), and the lane whose
+  // ev_filter_done marks the end of the searcher's last launched pass (-1: none)
+  std::vector<struct sassy_hip_Ticket*> open_group;
+  int last_pass_lane = -1;
   // reporting modes of the reference's Searcher (src/search.rs:442-475)
   float alpha = NAN;             // overhang cost per pattern character (NaN = no overhang), Iupac only
   long max_overhang = -1;        // with_max_overhang(): -1 = none
@@ -596,6 +608,7 @@ struct sassy_SearcherType {
   ~sassy_SearcherType() {
     for (ScanLane& l : lanes)  // searches still in flight (tickets never finished): let their kernels drain
       if (l.stream) (void)hipStreamSynchronize(l.stream);
+    open_group.clear();  // (an unlaunched group is dropped with its tickets)
     for (sassy_hip_Ticket*& t : lane_ticket) { delete t; t = nullptr; }
     d_text.release(); d_rev.release(); d_rc_bitmap.release();
     free_stage();
@@ -739,6 +752,12 @@ struct ScanJob {
   uint8_t* ctl_base = nullptr;       // this search's control block (the lane's d_ctl or its twin)
   bool ctl_pre_cleared = false;      // ... whose first 64 bytes the previous search cleared
   bool wait_ev_done = false;         // the host waits for L.ev_done (the twin's clear follows it in the stream)
+  // shared pass (attempt 0 only): group_leader = the job whose launch also serves this one (this job's filter launch
+  // becomes "wait for the leader's pass"); group_member = the job the leader's launch serves as member 1
+  ScanJob* group_leader = nullptr;
+  ScanJob* group_member = nullptr;
+  bool group_ok() const;                    // this job can be a member of a grouped pass
+  bool group_fits(const ScanJob& b) const;  // ... together with b (same buffer and launch geometry, <= 8 pieces)
   bool pipelined = false;            // one of several searches in flight (sassy_hip_search_shard_begin): the
                                      // bit-plane filter takes only half of a CU's wave slots, so that the previous
                                      // search's small tail kernels find room next to it
@@ -926,7 +945,10 @@ struct ManyDefer {
   ManyPart part{nullptr, nullptr, 0};
   uint32_t str_stride = 0;
 };
-inline void reset_stats(sassy_SearcherType* S) { S->stats = sassy_hip_Stats{}; }
+inline void reset_stats(sassy_SearcherType* S) {
+  S->stats = sassy_hip_Stats{};
+  S->stats.pass_patterns = 1;
+}
 // The synchronous entry points use the searcher's lanes (streams, device buffers, pinned result areas) themselves:
 // with a ticket open they would overwrite what its finish() is going to read.
 inline bool tickets_open(const sassy_SearcherType* s) {

@@ -811,7 +811,8 @@ int ScanJob::enqueue(int attempt) {
   const bool time_head = timing >= 2 || (timing == 1 && !ext_bitmap);
   // (the fused launch carries its events itself: LaunchEvents)
   const bool env_ext_ev = S->sw.ext_events != 0;
-  const bool ext_events = time_head && filtered && fused && attempt == 0 && env_ext_ev;
+  // (a member of another job's pass times it with its own two markers around the wait for it)
+  const bool ext_events = time_head && filtered && fused && attempt == 0 && env_ext_ev && !group_leader;
   if (time_head && !ext_events) HIP_TRY(hipEventRecord(L.ev_a, L.stream));
   hipError_t le;
   if (!filtered) {
@@ -827,10 +828,46 @@ int ScanJob::enqueue(int attempt) {
       F.stash_cap = (uint32_t)std::min<size_t>(L.d_stash.cap, 0xFFFFFEu);
       F.counters = nullptr;
       F.row_tab = P.row_tab;
-      if (ext_events) g_launch_events = LaunchEvents{L.ev_a, L.ev_f};
-      le = launch_filter_any(S->profile, F, fgrid, 1024 + (size_t)kWavesPerGroup * F.lds_per_wave, L.stream);
-      g_launch_events = LaunchEvents{};
-      if (le != hipSuccess) return hip_fail(le, "fused filter kernel launch");
+      if (group_leader && attempt == 0) {
+        // member 1 of a shared pass: the leader's lane waits until this lane's control block and pattern tables are in
+        // place, launches the pass for both, and this lane's tail waits for the end of it
+        HIP_TRY(hipEventRecord(L.ev_group, L.stream));
+        group_leader->group_member = this;
+        const int rc = group_leader->enqueue(0);
+        group_leader->group_member = nullptr;
+        if (rc) return rc;
+        HIP_TRY(hipStreamWaitEvent(L.stream, group_leader->L.ev_filter_done, 0));
+      } else if (group_member && attempt == 0) {
+        // the shared pass: member 0 = this job (F), member 1 = the other job's pieces, pattern rows and report arrays
+        const ScanJob& B = *group_member;
+        ScanParams GP = F;
+        GP.lds_per_wave = F.lds_per_wave + F.fuse_queue_cap * 8u + 16u;  // member 1's queue and count
+        const uint32_t na = F.n_pieces, nb = B.F.n_pieces;
+        GP.piece_member = 0;
+        for (uint32_t pp = 0; pp < 8; ++pp) {  // (slots behind both repeat member 0's first piece)
+          const bool m1 = pp >= na && pp < na + nb;
+          const uint32_t src = m1 ? pp - na : (pp < na ? pp : 0u);
+          const ScanParams& O = m1 ? B.F : F;
+          GP.piece_bits[pp][0] = O.piece_bits[src][0];
+          GP.piece_bits[pp][1] = O.piece_bits[src][1];
+          GP.piece_rem[pp] = O.piece_rem[src];
+          if (m1) GP.piece_member |= 1u << pp;
+        }
+        GP.n_pieces = na + nb;
+        GP.piece_groups = 2;
+        GP.member1 = ScanParams::FuseMember{B.F.row_tab, B.F.cand, B.F.cand_count, B.F.stash, B.F.m, B.F.k, B.F.nwords, B.F.wb,
+                                            B.F.flags, B.F.cand_cap, B.F.stash_cap, 0u};
+        HIP_TRY(hipStreamWaitEvent(L.stream, B.L.ev_group, 0));
+        if (ext_events) g_launch_events = LaunchEvents{L.ev_a, L.ev_f};
+        le = launch_filter_group(GP, fgrid, L.stream);
+        g_launch_events = LaunchEvents{};
+        if (le != hipSuccess) return hip_fail(le, "shared fused filter kernel launch");
+      } else {
+        if (ext_events) g_launch_events = LaunchEvents{L.ev_a, L.ev_f};
+        le = launch_filter_any(S->profile, F, fgrid, 1024 + (size_t)kWavesPerGroup * F.lds_per_wave, L.stream);
+        g_launch_events = LaunchEvents{};
+        if (le != hipSuccess) return hip_fail(le, "fused filter kernel launch");
+      }
     } else if ((attempt == 0 || count_direct) && !ext_bitmap && !ext_desc) {  // the hit bitmap does not depend on buffer sizes: build it once
       // (count_direct: the filter files the descriptors itself -- into a list that may have grown: every attempt runs it)
       if (count_direct) {
@@ -997,6 +1034,23 @@ int ScanJob::enqueue(int attempt) {
     }
   }
   return 0;
+}
+
+// A job that can share its fused pass with another search over the same buffer (c_abi.hip: shared pass): the Dna
+// bit-plane launch of one forward strand, pieces of 7 .. 12 rows, no paired filter, no tuner, pattern words that leave
+// the tile's upper half to the segment state (kFuseGroupMaxWords)
+bool ScanJob::group_ok() const {
+  return !empty && filtered && fused && fkind == kFilterPlanes && S->profile == PROFILE_DNA && pair == 0 && !rc_marked &&
+         !rc_second_pass && !ext_bitmap && !ext_desc && texts.n == 0 && !tuned && F.lin_steps == 0 && F.pair == 0 &&
+         F.piece_len >= 7 && F.piece_len <= 12 && plan.nwords <= kFuseGroupMaxWords && timing <= 1;
+}
+bool ScanJob::group_fits(const ScanJob& b) const {
+  return group_ok() && b.group_ok() && F.n_pieces + b.F.n_pieces <= 8 && F.piece_len == b.F.piece_len && F.text == b.F.text &&
+         F.text_len == b.F.text_len && F.n_blocks == b.F.n_blocks && F.first_owned_block == b.F.first_owned_block &&
+         F.global_offset == b.F.global_offset && F.n_chunks == b.F.n_chunks && F.bpl == b.F.bpl && F.n_iter == b.F.n_iter &&
+         F.group_offset == b.F.group_offset && fgrid == b.fgrid && F.lds_per_wave == b.F.lds_per_wave &&
+         F.fuse_queue_cap == b.F.fuse_queue_cap && F.fuse_press == b.F.fuse_press && F.dp_first_owned == b.F.dp_first_owned &&
+         F.fused == b.F.fused && F.flags == b.F.flags && F.piece_mirror == 0 && b.F.piece_mirror == 0;
 }
 
 // finish_once() may find that the fused launch could not complete the search (a wave's chunk queue overflowed, a

@@ -1924,11 +1924,19 @@ __device__ __forceinline__ bool other_letters16(const uint4 v) { return other_le
 // DPNS (CHECK only): slot masks the chunk DP builds -- 4 for a pattern of plain bases, 8 when the rows BEHIND the filter's
 // pieces hold ambiguity letters (a CRISPR guide: 20 bases + NGG; the pieces themselves are plain, so the filter is the
 // same): masks 8 x 512 B + carries of at most four pattern words fill the tile up to the saved segment state.
-template <int Q, int NPG, bool FUSED, bool CHECK = false, bool PAIR = false, int DPNS = 4>
+// G (fused, NPG = 2 only): the GROUPED pass -- one text pass for two searches in flight over the same buffer (members 0 and
+// 1; ScanParams: the launch's own fields are member 0's, member1 the other's; bit p of piece_member: piece p is member 1's).
+// The text, its code planes and their shifted copies are the same for both; only the piece tests, the runs a lane
+// collects, the chunk queues and the chunk DP are per member.  Each member has a queue of its own behind the other's, its
+// own run in registers, and its own control block: fuse word, statistics, reports -- a member whose reports need the
+// classic chain sends only itself there.  (Both members at most kFuseGroupMaxWords pattern words: their carries then end
+// at 4 KiB, and the segment state of both runs waits in the tile's upper half.)
+template <int Q, int NPG, bool FUSED, bool CHECK = false, bool PAIR = false, int DPNS = 4, int G = 1>
 // (CHECK: four waves per SIMD are asked for -- left to itself the compiler settles for three, 0.59 instead of 0.52 ms)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || PAIR) ? 4 : 1))) void filter_dna_kernel(const ScanParams P) {
   static_assert(!CHECK || FUSED, "the text check exists in the fused launch only");
   static_assert(!PAIR || (FUSED && 2 * Q + 2 <= 31), "the paired filter exists in the fused launch only; its look-back stays inside one plane half");
+  static_assert(G == 1 || (G == 2 && FUSED && !CHECK && !PAIR && NPG == 2), "the grouped pass: two members, fused Dna bit planes, eight piece slots");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int SB = 2;
   constexpr uint32_t kRowBytes = 64u * SB;
@@ -1953,7 +1961,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   // masks and carries, at most eight pattern words, leave free -- and the lane index comes from v_mbcnt, the wave index
   // from a scalar: kept in vector registers across the DP they were spilled to scratch memory, and a kernel that owns a
   // scratch segment starts its waves slower.)
-  constexpr uint32_t kSegState = 6144u;            // tile offset of the saved state: [7][64] u32
+  constexpr uint32_t kSegState = G == 2 ? 4096u : 6144u;  // tile offset of the saved state: [7][64] u32 (G = 2: [11][64])
   uint32_t seg_it = 0;                             // wave-uniform, even
   bool first_segment = true;
   const uint32_t wave_s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1967,6 +1975,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   // the count (16 bytes)
   uint2* queue = reinterpret_cast<uint2*>(tile + kTile);
   uint32_t* qcount = reinterpret_cast<uint32_t*>(tile + kTile + (size_t)Pk->fuse_queue_cap * 8u);
+  // (G = 2: member 1's queue and count behind member 0's)
+  uint2* queue1 = reinterpret_cast<uint2*>(tile + kTile + (size_t)Pk->fuse_queue_cap * 8u + 16u);
+  uint32_t* qcount1 = reinterpret_cast<uint32_t*>(tile + kTile + (size_t)Pk->fuse_queue_cap * 16u + 16u);
   const uint64_t group = (uint64_t)blockIdx.x + Pk->group_offset;
   const uint32_t bpl = Pk->bpl;
   const uint64_t first_owned = Pk->first_owned_block;
@@ -1990,6 +2001,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   if constexpr (FUSED) {
     if (first_segment) {
       if (lane == 0) *qcount = 0;
+      if (G == 2 && lane == 0) *qcount1 = 0;
     }
     if (Pk->fused & 2u) probe_t0 = wall_clock64();
   }
@@ -2017,11 +2029,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
 
   // FUSED: the run of match-end columns this lane is collecting, and the end of the last window it queued
   rep4 run = make_rep4(kRunNone, 0u, 0u, 0u);
+  rep4 run1 = make_rep4(kRunNone, 0u, 0u, 0u);  // (G = 2: member 1's)
   if constexpr (FUSED) {
     if (!first_segment) {
       const uint32_t* sv = reinterpret_cast<const uint32_t*>(tile + kSegState) + lane;
       prev0 = sv[0]; prev1 = sv[64];
       run = make_rep4(sv[128], sv[192], sv[256], sv[320]);
+      if constexpr (G == 2) run1 = make_rep4(sv[448], sv[512], sv[576], sv[640]);
     }
   }
   const uint32_t press_at = Pk->fuse_press;
@@ -2243,7 +2257,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
           lo = (uint32_t)((int64_t)(bb * 64) - col_base);
           hi = (uint32_t)(c_hi - col_base);
         }
-        if (!n_inside) {
+        uint32_t lo1 = kRunNone, hi1 = 0;  // (G = 2: member 1's columns)
+        if constexpr (G == 2) {
+#pragma unroll
+          for (int pp = 0; pp < NP; ++pp) {
+            const uint64_t bits = ((uint64_t)ah[pp] << 32) | al[pp];
+            if (bits != 0) {
+              const bool m1 = (Pk->piece_member >> pp) & 1u;
+              const uint2 r = piece_end_cols(bits, b, (int64_t)Pk->piece_rem[pp], (int64_t)(m1 ? Pk->member1.k : Pk->k),
+                                             (int64_t)(Pk->n_blocks * 64), col_base);
+              if (m1) {
+                lo1 = min(lo1, r.x);
+                hi1 = max(hi1, r.y);
+              } else {
+                lo = min(lo, r.x);
+                hi = max(hi, r.y);
+              }
+            }
+          }
+        }
+        if (G == 1 && !n_inside) {
 #pragma unroll
         for (int pp = 0; pp < NP; ++pp) {
           const uint64_t bits = ((uint64_t)ah[pp] << 32) | al[pp];
@@ -2271,6 +2304,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
         if (lo != kRunNone)
           run = fuse_add_range(queue, qcount, Pk->cand_count + kCtlFuseWord, Pk->fuse_queue_cap, press_at, Pk->m + Pk->k, col_base,
                                fc > 0 ? (uint32_t)fc : 0u, run, lo, hi);
+        if constexpr (G == 2) {
+          if (lo1 != kRunNone)
+            run1 = fuse_add_range(queue1, qcount1, Pk->member1.cand_count + kCtlFuseWord, Pk->fuse_queue_cap, press_at,
+                                  Pk->member1.m + Pk->member1.k, col_base, fc > 0 ? (uint32_t)fc : 0u, run1, lo1, hi1);
+        }
       } else {
 #pragma unroll
         for (int pp = 0; pp < NP; ++pp) {
@@ -2286,7 +2324,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     }
     if constexpr (FUSED) {
       // the queue is filling up: the block pair is done with the tile -- the chunk DP may have it
-      if (sub == 1u && __any((run.w & kRunPressure) != 0u)) { ++it; break; }
+      if (sub == 1u && __any(((run.w | (G == 2 ? run1.w : 0u)) & kRunPressure) != 0u)) { ++it; break; }
     }
   }
   if constexpr (!FUSED) break;
@@ -2296,9 +2334,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     uint32_t nq = __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile uint32_t*>(qcount));
+    uint32_t nq1 = G == 2 ? __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile uint32_t*>(qcount1)) : 0u;
     const bool streamed = it >= n_iter;
     bool last = false;
-    if (streamed && nq + 64u <= Pk->fuse_queue_cap) {  // the runs the lanes still hold (one entry each at most), then the last pass
+    if (streamed && nq + 64u <= Pk->fuse_queue_cap && (G == 1 || nq1 + 64u <= Pk->fuse_queue_cap)) {  // the runs the lanes still hold (one entry each at most), then the last pass
       if constexpr (PAIR) {
         // An A-type sub-piece in the buffer's last DL columns would be detected behind the last block.  The match
         // around it ends in the last k + 1 + DL - Q columns (>= Q rows follow the piece): the lane that owns the last
@@ -2315,9 +2354,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
       if (run.x != kRunNone)
         run = fuse_add_range(queue, qcount, Pk->cand_count + kCtlFuseWord, Pk->fuse_queue_cap, 0xFFFFFFFFu, Pk->m + Pk->k, col_base, 0u, run,
                              kRunNone, 0u);
+      if constexpr (G == 2) {
+        if (run1.x != kRunNone)
+          run1 = fuse_add_range(queue1, qcount1, Pk->member1.cand_count + kCtlFuseWord, Pk->fuse_queue_cap, 0xFFFFFFFFu,
+                                Pk->member1.m + Pk->member1.k, col_base, 0u, run1, kRunNone, 0u);
+      }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
       nq = __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile uint32_t*>(qcount));
+      if constexpr (G == 2) nq1 = __builtin_amdgcn_readfirstlane(*reinterpret_cast<volatile uint32_t*>(qcount1));
       last = true;
     }
     // what the next segment starts from
@@ -2328,6 +2373,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
       sv[0] = prev0; sv[64] = prev1;
       sv[128] = run.x; sv[192] = run.y; sv[256] = run.z; sv[320] = run.w & ~kRunPressure;
       if constexpr (CHECK) sv[384] = npure;
+      if constexpr (G == 2) { sv[448] = run1.x; sv[512] = run1.y; sv[576] = run1.z; sv[640] = run1.w & ~kRunPressure; }
     }
     unsigned long long probe_t1 = 0;
     if (Pk->fused & 2u) probe_t1 = wall_clock64();  // SASSY_HIP_FUSED_PROBE: 100 MHz ticks spent streaming / in the chunk DP
@@ -2335,7 +2381,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
       if (lane == 0) atomicOr(&Pk->cand_count[kCtlFuseWord], kFuseOverflow);
       nq = 0;
     }
-    if ((Pk->fused & 4u) == 0u && nq != 0) {  // (probe bit 4: no chunk DP at all -- timing only, no reports)
+    if (G == 2 && nq1 > Pk->fuse_queue_cap) {
+      if (lane == 0) atomicOr(&Pk->member1.cand_count[kCtlFuseWord], kFuseOverflow);
+      nq1 = 0;
+    }
+    // (G = 2: the members' queues one after the other, each with its own pattern, masks and carries.  The member index is
+    // a compile-time constant: as a loop index -- even unrolled -- it cost the lone launch two VGPRs and a wave per SIMD.)
+    auto member_dp = [&](auto g_c) {
+    constexpr int g = decltype(g_c)::value;
+    const uint32_t nqg = g ? nq1 : nq;
+    if ((Pk->fused & 4u) == 0u && nqg != 0) {  // (probe bit 4: no chunk DP at all -- timing only, no reports)
     // What the DP needs of the launch parameters is read HERE, through a pointer the optimiser cannot see
     // through: read from P they would be loaded at the top of the kernel and held (or spilled to VGPR lanes and
     // read back inside the streaming loop) for the whole life of the wave.
@@ -2359,6 +2414,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     L.dp_first_owned = kp->dp_first_owned;
     L.stash = kp->stash;
     L.stash_cap = kp->stash_cap;
+    if (G == 2 && g) {
+      L.wb = kp->member1.wb;
+      L.m = kp->member1.m;
+      L.k = kp->member1.k;
+      L.nwords = kp->member1.nwords;
+      L.flags = kp->member1.flags;
+      L.cand_cap = kp->member1.cand_cap;
+      L.row_tab = kp->member1.row_tab;
+      L.cand = kp->member1.cand;
+      L.cand_count = kp->member1.cand_count;
+      L.counters = nullptr;
+      L.stash = kp->member1.stash;
+      L.stash_cap = kp->member1.stash_cap;
+    }
     L.rev_n = 0;
     L.alpha = 0.0f;
     L.ov_steps = 0;
@@ -2377,8 +2446,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     uint32_t dwave = __builtin_amdgcn_readfirstlane(wave_s);
     asm volatile("" : "+v"(dlane), "+s"(dwave));
     unsigned char* dtile = smem + (size_t)dwave * kp->lds_per_wave;
-    const uint2* dqueue = reinterpret_cast<const uint2*>(dtile + kTile);
-    const uint32_t n_run = (last || nq < 64u) ? nq : (nq & ~63u);
+    const uint2* dqueue = reinterpret_cast<const uint2*>(dtile + kTile + (size_t)g * (kp->fuse_queue_cap * 8u + 16u));
+    const uint32_t n_run = (last || nqg < 64u) ? nqg : (nqg & ~63u);
     if (dlane == 0) atomicAdd(&L.cand_count[1], n_run);  // statistics: chunks
     // the DP's LDS -- slot masks, per-row carries -- takes the place of the text tile
     unsigned char* mask_bytes = dtile;
@@ -2395,7 +2464,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
       dsc.pad_ = (e.y & 63u) | ((e.y >> 14) << 8);  // byte shift | columns not to report << 8
       list_lanes<CHECK ? (int)PROFILE_IUPAC : (int)PROFILE_DNA, DPNS, true>(L, mask_bytes, carry, dlane, has, dsc, kNoStateSlot);
     }
-    if ((kp->fused & 2u) && dlane == 0) {
+    if ((kp->fused & 2u) && dlane == 0 && g == 0) {
       unsigned long long* pc = reinterpret_cast<unsigned long long*>(L.cand_count + 4);  // the control block's counters
       atomicAdd(&pc[0], probe_t1 - probe_t0);
       atomicAdd(&pc[1], wall_clock64() - probe_t1);
@@ -2403,16 +2472,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
       atomicAdd(&pc[3], 1ull);
     }
     }
+    };  // member_dp
+    member_dp(std::integral_constant<int, 0>{});
+    if constexpr (G == 2) member_dp(std::integral_constant<int, 1>{});
     // the queue keeps what did not fill a batch; the tile is the next segment's: the DP's LDS traffic is complete before
     // its first staging store (one wave, in-order LDS); the fence keeps the compiler from reordering across it
     {
       const uint32_t left = (last || (Pk->fused & 4u) || nq < 64u) ? 0u : (nq & 63u);
       uint2 keep_e = make_uint2(0u, 0u);
       if (lane < left) keep_e = queue[(nq & ~63u) + lane];
+      const uint32_t left1 = (G == 1 || last || (Pk->fused & 4u) || nq1 < 64u) ? 0u : (nq1 & 63u);
+      uint2 keep_e1 = make_uint2(0u, 0u);
+      if (lane < left1) keep_e1 = queue1[(nq1 & ~63u) + lane];
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
       if (lane < left) queue[lane] = keep_e;
       if (lane == 0) *qcount = left;
+      if constexpr (G == 2) {
+        if (lane < left1) queue1[lane] = keep_e1;
+        if (lane == 0) *qcount1 = left1;
+      }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if (last) break;
@@ -3025,6 +3104,30 @@ hipError_t launch_filter_dna(const ScanParams& P, uint32_t grid, size_t smem, hi
 }
 hipError_t launch_list_dna(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
   return launch_list_one<PROFILE_DNA, 4>(P, grid, smem, stream);
+}
+// the grouped pass (filter_dna_kernel<.., G = 2>): two searches, eight piece slots, one text pass; piece lengths 7 .. 12
+template <int Q>
+static hipError_t launch_filter_group_q(const ScanParams& P, uint32_t grid, hipStream_t stream) {
+  const size_t smem = (size_t)kWavesPerGroup * P.lds_per_wave;
+  const LaunchEvents ev = g_launch_events;
+  g_launch_events = LaunchEvents{};
+  if (ev.start)
+    hipExtLaunchKernelGGL((filter_dna_kernel<Q, 2, true, false, false, 4, 2>), dim3(grid), dim3(256), smem, stream, ev.start, ev.stop, 0, P);
+  else hipLaunchKernelGGL((filter_dna_kernel<Q, 2, true, false, false, 4, 2>), dim3(grid), dim3(256), smem, stream, P);
+  return hipGetLastError();
+}
+hipError_t launch_filter_group(const ScanParams& P, uint32_t grid, hipStream_t stream) {
+  if (!P.piece_planes || !P.fused || P.pair || P.lin_steps || P.member1.nwords > kFuseGroupMaxWords || P.nwords > kFuseGroupMaxWords)
+    return hipErrorInvalidValue;
+  switch (P.piece_len) {
+    case 7: return launch_filter_group_q<7>(P, grid, stream);
+    case 8: return launch_filter_group_q<8>(P, grid, stream);
+    case 9: return launch_filter_group_q<9>(P, grid, stream);
+    case 10: return launch_filter_group_q<10>(P, grid, stream);
+    case 11: return launch_filter_group_q<11>(P, grid, stream);
+    case 12: return launch_filter_group_q<12>(P, grid, stream);
+    default: return hipErrorInvalidValue;
+  }
 }
 #else
 #if SASSY_SCAN_PROFILE == 2

@@ -60,6 +60,7 @@ namespace sassy_hip {
   X(multi_min_text, 16 << 20, "search_encoded: smallest text (bytes) for the multi-pattern prefilter")                       \
   X(tiled, -1, "search_encoded: 1 force / 0 forbid the pattern-tiled scan")                                                 \
   X(seeded, -1, "search_encoded: 1 force / 0 forbid the seeded search")                                                 \
+  X(shared_pass, 1, "searches in flight over one buffer share a text pass, two per fused bit-plane launch (0: a pass per search; 2: also launch a waiting search before a finish that has to wait; 3: a groupable search always waits for a partner)") \
   X(aa_batch, 0, "search_all_alignments: at most this many alignments per emit batch (0: 32 MiB of rows / cigar text)")
 
 struct Switches {
