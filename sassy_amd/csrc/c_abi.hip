@@ -973,8 +973,7 @@ int sassy_hip_search_encoded(sassy_SearcherType* s, const sassy_hip_Encoded* e, 
         F.piece_len = mq;
         for (uint32_t pp = 0; pp < 8; ++pp) F.piece_rem[pp] = (uint32_t)e->plen - (p_start[pp] + p_len[pp]);
         F.multi_long = long_mask;
-        F.stage_blocks = 2;
-        F.lds_per_wave = 4096u * 2;
+        F.lds_per_wave = kTileBytes;
         F.hit_bitmap = bm_base;
         F.multi_bits = s->d_multi_bits.p;
         F.multi_n = (uint32_t)nb;

@@ -14,8 +14,10 @@ constexpr uint32_t PROFILE_ASCII_BYTES = 3;
 constexpr int kWave = 64;              // gfx950 wavefront
 constexpr int kWavesPerGroup = 4;      // 256-thread workgroups, every wave works alone
 constexpr uint32_t kCarryListGroups = 1024;  // list_kernel<.., GC>: workgroups that share a long pattern's chunk list
-constexpr int kTileBytes = 64 * 128;   // text tile of one wave: 64 lane chunks x 2 blocks x 64 B,
-                                       // 16-byte slots XOR-swizzled by (owner>>1)&7
+// text tile of one wave: 64 lane chunks x the bytes one staging step fetches per chunk, 16-byte slots XOR-swizzled
+constexpr uint32_t kTileBytes = 64 * 128;     // 2 blocks (a whole 128-byte line), (owner>>1)&7: filter_kernel,
+                                              // filter_dna_kernel, filter_dna_multi_kernel, filter_count_kernel
+constexpr uint32_t kHalfTileBytes = 64 * 64;  // 1 block (half a line), (owner>>2)&3: scan_kernel, filter_table_kernel
 constexpr uint32_t kRegionSlots = 16;  // chunk descriptors a wave of the counting filter can file (count_direct)
 constexpr int kMaxSlots = 64;          // profile slots (distinct pattern letters) per search: Dna 4, Iupac <= 16,
                                        // Ascii <= 64 distinct pattern bytes
@@ -121,7 +123,6 @@ struct ScanParams {
                               // LDS -- patterns beyond ~9 800 rows (scan_kernel<.., GC> / list_kernel<.., GC>)
   uint32_t cand_cap;
   uint32_t n_iter;            // iterations of the block loop
-  uint32_t stage_blocks;      // 1 or 2: text blocks per lane chunk fetched per staging step
   const uint32_t* row_tab;    // device, 8*nwords words: one byte per pattern row = 2 * its profile
                               // slot (row r of word w: byte r&3 of row_tab[8w + (r>>2)])
   Candidate* cand;            // device, cand_cap entries
@@ -139,7 +140,6 @@ struct ScanParams {
   uint32_t piece_last[2];
   // Dna bit-plane filter: per piece, bit j = code bit 0 / code bit 1 of piece row j
   uint32_t piece_planes;      // 1: use filter_dna_kernel (Dna, <= 8 pieces)
-  uint32_t lin_steps;         // != 0: filter_dna_linear_kernel, 128-block steps per wave range
   uint32_t group_offset;      // filter_dna_kernel: first workgroup of this launch (the grid may be split in two launches)
   uint32_t piece_bits[8][2];
   // fused mode of filter_dna_kernel (one launch: filter, then the chunk DP of what the wave itself found):

@@ -59,20 +59,21 @@ __device__ __noinline__ uint4 tail16(const uint8_t* text, uint64_t off, uint64_t
 // A chunk = [lo, hi), a run of candidate blocks, never with kDescClearBefore: the list kernel warms up on the wb blocks in
 // front of it (the chunk builder makes them part of the chunk instead -- the same blocks, the same start).
 // WPG: waves per workgroup.  The q-gram table is per workgroup: sixteen waves around one copy leave room for sixteen
-// waves per CU (four around each of three copies: twelve).
-template <int Q, int R, int SB, int WPG, bool DIRECT = false>
+// waves per CU (four around each of three copies: twelve).  A staging step fetches two blocks (a whole 128-byte line, read
+// with non-temporal loads) per lane chunk.
+template <int Q, int R, int WPG, bool DIRECT = false>
 __global__ __launch_bounds__(64 * WPG) void filter_count_kernel(const ScanParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr uint32_t kTableBytes = 1u << (2 * (Q + R - 1));
-  constexpr uint32_t kRowBytes = 64u * SB;
-  constexpr uint32_t kSlots = 4u * SB;
+  constexpr uint32_t kRowBytes = 128u;
+  constexpr uint32_t kSlots = 8u;
   constexpr uint32_t kOwnersPerInstr = 64u / kSlots;
-  constexpr int kStageInstr = 4 * SB;
+  constexpr int kStageInstr = 8;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
   unsigned char* table = smem;
   unsigned char* tile = smem + kTableBytes + (size_t)wave * P.lds_per_wave;
-  unsigned char* ring = tile + 4096u * SB + lane;  // [slot][lane] bytes
+  unsigned char* ring = tile + kTileBytes + lane;  // [slot][lane] bytes
   {
     const uint4* src = reinterpret_cast<const uint4*>(P.qgram_table);
     uint4* dst = reinterpret_cast<uint4*>(table);
@@ -105,12 +106,12 @@ __global__ __launch_bounds__(64 * WPG) void filter_count_kernel(const ScanParams
   for (int i = 0; i < kStageInstr; ++i) {
     const uint32_t owner = (uint32_t)i * kOwnersPerInstr + lane / kSlots;
     const uint32_t slot = lane % kSlots;
-    const uint32_t j = slot ^ (SB == 2 ? ((owner >> 1) & 7u) : ((owner >> 2) & 3u));
+    const uint32_t j = slot ^ ((owner >> 1) & 7u);
     soff[i] = (uint32_t)((chunk_first_block(first_owned, bpl, back, wave_chunk0 + owner) - wave_blk0) * 64) + j * 16u;
   }
   const uint64_t wave_last = chunk_first_block(first_owned, bpl, back, wave_chunk0 + 63) + P.n_iter + 2;
   const bool interior = wave_last * 64 <= P.text_len;
-  const uint32_t fsw = SB == 2 ? ((lane >> 1) & 7u) : ((lane >> 2) & 3u);
+  const uint32_t fsw = (lane >> 1) & 7u;
   uint32_t rc[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) rc[c] = lane * kRowBytes + (((uint32_t)c ^ (fsw & 3u)) << 4);
@@ -183,15 +184,15 @@ __global__ __launch_bounds__(64 * WPG) void filter_count_kernel(const ScanParams
     if constexpr (DIRECT) {
       if (it) direct_step(it - 1u);
     }
-    const uint32_t sub = SB == 2 ? (it & 1u) : 0u;
+    const uint32_t sub = it & 1u;  // block of the staged pair
     if (sub == 0) {
       if (interior) {
 #pragma unroll
         for (int i = 0; i < kStageInstr; ++i) *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = nxt[i];
-        if (it + SB < P.n_iter) {
+        if (it + 2 < P.n_iter) {
 #pragma unroll
           for (int i = 0; i < kStageInstr; ++i)
-            nxt[i] = stream_load16<SASSY_NT_COUNT>(text_base + (uint64_t)(it + SB) * 64 + soff[i]);
+            nxt[i] = stream_load16<SASSY_NT_COUNT>(text_base + (uint64_t)(it + 2) * 64 + soff[i]);
         }
       } else {
 #pragma unroll
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(64 * WPG) void filter_count_kernel(const ScanParams
         }
       }
     }
-    const uint32_t hs = SB == 2 ? (((sub << 2) ^ (fsw & 4u)) << 4) : 0u;
+    const uint32_t hs = ((sub << 2) ^ (fsw & 4u)) << 4;  // slot bit 2 = block of the pair
     uint32_t x[16];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -280,25 +281,24 @@ __global__ __launch_bounds__(64 * WPG) void filter_count_kernel(const ScanParams
   }
 }
 
-template <int Q, int R, int SB, int WPG, bool DIRECT = false>
+template <int Q, int R, int WPG, bool DIRECT = false>
 hipError_t launch_qr(const ScanParams& P, uint32_t grid, hipStream_t stream) {
   const size_t smem = ((size_t)1 << (2 * (Q + R - 1))) + (size_t)WPG * P.lds_per_wave;
   static DeviceOnce attr_set;  // LDS beyond the 64 KiB default needs an explicit opt-in
   if (attr_set.need()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&filter_count_kernel<Q, R, SB, WPG, DIRECT>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&filter_count_kernel<Q, R, WPG, DIRECT>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     attr_set.done();
   }
-  hipLaunchKernelGGL((filter_count_kernel<Q, R, SB, WPG, DIRECT>), dim3(grid), dim3(64 * WPG), smem, stream, P);
+  hipLaunchKernelGGL((filter_count_kernel<Q, R, WPG, DIRECT>), dim3(grid), dim3(64 * WPG), smem, stream, P);
   return hipGetLastError();
 }
 template <int Q, int R>
-hipError_t launch_sb(const ScanParams& P, uint32_t grid, hipStream_t stream) {
-  if (P.count_direct)  // (whole lines, sixteen or four waves per workgroup; one strand)
-    return P.waves_per_group == 16 ? launch_qr<Q, R, 2, 16, true>(P, grid, stream) : launch_qr<Q, R, 2, 4, true>(P, grid, stream);
-  if (P.waves_per_group == 16) return P.stage_blocks == 2 ? launch_qr<Q, R, 2, 16>(P, grid, stream) : launch_qr<Q, R, 1, 16>(P, grid, stream);
-  return P.stage_blocks == 2 ? launch_qr<Q, R, 2, 4>(P, grid, stream) : launch_qr<Q, R, 1, 4>(P, grid, stream);
+hipError_t launch_wpg(const ScanParams& P, uint32_t grid, hipStream_t stream) {
+  if (P.count_direct)  // (one strand: the kernel files its chunk descriptors itself)
+    return P.waves_per_group == 16 ? launch_qr<Q, R, 16, true>(P, grid, stream) : launch_qr<Q, R, 4, true>(P, grid, stream);
+  return P.waves_per_group == 16 ? launch_qr<Q, R, 16>(P, grid, stream) : launch_qr<Q, R, 4>(P, grid, stream);
 }
 
 }  // namespace
@@ -307,11 +307,11 @@ hipError_t launch_sb(const ScanParams& P, uint32_t grid, hipStream_t stream) {
 hipError_t launch_filter_count(const ScanParams& P, uint32_t grid, hipStream_t stream) {
   const uint32_t key = P.piece_len * 10u + P.count_r;
   switch (key) {
-    case 52: return launch_sb<5, 2>(P, grid, stream);
-    case 61: return launch_sb<6, 1>(P, grid, stream);
-    case 62: return launch_sb<6, 2>(P, grid, stream);
-    case 71: return launch_sb<7, 1>(P, grid, stream);
-    case 72: return launch_sb<7, 2>(P, grid, stream);
+    case 52: return launch_wpg<5, 2>(P, grid, stream);
+    case 61: return launch_wpg<6, 1>(P, grid, stream);
+    case 62: return launch_wpg<6, 2>(P, grid, stream);
+    case 71: return launch_wpg<7, 1>(P, grid, stream);
+    case 72: return launch_wpg<7, 2>(P, grid, stream);
     default: return hipErrorInvalidValue;
   }
 }

@@ -240,8 +240,6 @@ int ScanJob::prepare() {
   P.ov_steps = ov_steps;
   P.rev_n = rev_n;
   bucket = plan.nslots <= 4 ? 4 : plan.nslots <= 8 ? 8 : plan.nslots <= 16 ? 16 : plan.nslots <= 32 ? 32 : 64;
-  const int env_sb = (int)sw.stage_blocks;
-  P.stage_blocks = env_sb == 1 || env_sb == 2 ? (uint32_t)env_sb : 1u;
   for (int s = 0; s < kMaxSlots; ++s) P.slot_val[s] = plan.slot_val[s];
   q = filter_piece_len(plan, k, S);
   // a match that hangs over an end of the text contains only part of the pattern: the pigeonhole
@@ -265,7 +263,7 @@ int ScanJob::prepare() {
   const uint32_t pieces = k + 1;
   // The fused launch (filter + chunk DP in one kernel, see below) takes one strand of one text whose reports the
   // traceback waves rank themselves.  (trace_wave_ok mirrors use_wave of the traceback set-up further down.)
-  const int env_selfrank0 = (int)sw.self_rank, env_lin0 = (int)sw.filter_linear, env_wave0 = (int)sw.trace_wave;
+  const int env_selfrank0 = (int)sw.self_rank, env_wave0 = (int)sw.trace_wave;
   const bool trace_wave_ok = [&] {
     const uint64_t cell = (k + 1 <= 255) ? 1 : 2;
     const uint64_t band = ((uint64_t)(plan.m + 1) * (2ull * k + 3) * cell + 3) / 4 * 4;
@@ -274,7 +272,7 @@ int ScanJob::prepare() {
     return env_wave0 != 0 && 2ull * k + 3 <= 64 && 4 * (((uint64_t)plan.m + 15) / 16 * 16) + 4 * ((raw + 15) / 16 * 16) <= 160 * 1024;
   }();
   const bool fuse_ok = !ext_bitmap && !ext_desc && rc_bitmap == nullptr && rev_n == 0 && S->fuse && !no_fuse &&
-                       L.fuse_backoff == 0 && env_lin0 <= 0 && env_selfrank0 != 0 && do_trace && trace_wave_ok &&
+                       L.fuse_backoff == 0 && env_selfrank0 != 0 && do_trace && trace_wave_ok &&
                        texts.n == 0 && plan.nwords <= 8 && n_blocks < 0x7FFFFFFFull && !S->want_counters;
   // Iupac searcher, pattern of plain A C G T, <= 4 pieces: the Dna bit-plane filter with a check of the text
   // (filter_dna_kernel, CHECK) -- as the fused launch only.  Where the text holds other letters (N runs, ambiguity codes,
@@ -462,7 +460,7 @@ int ScanJob::prepare() {
   // The counting filter of ONE strand files its chunk descriptors itself (count_filter.hip, DIRECT): no hit bitmap (and no
   // 6 MB memset per 3 GB), no chunk-list launch.  Switch count_fused = 0: bitmap + build_chunks_kernel as before.
   count_direct = filtered && fkind == kFilterCount && !rc_marked && !ext_bitmap && !ext_desc && sw.count_fused != 0 &&
-                 sw.count_stage_blocks != 1 && n_blocks < 0xFFFFFFFFull && !no_fuse && L.fuse_backoff == 0;
+                 n_blocks < 0xFFFFFFFFull && !no_fuse && L.fuse_backoff == 0;
   n_words = filtered && !count_direct ? (n_blocks + 63) / 64 : 0;
   {
     // this search takes the lane's other control block (see ScanLane::d_ctl_twin)
@@ -571,11 +569,10 @@ int ScanJob::prepare() {
     // long patterns: the per-row carries (64 bytes per 32 rows and lane) of four waves no longer fit a workgroup's
     // 160 KiB of LDS -- fewer waves per workgroup then; beyond ~9 800 rows not even one wave's: the carries go to global
     // memory (scan_kernel<.., GC>: 512 bytes per pattern word and wave)
-    const bool gc = 4096u * P.stage_blocks + bucket * 512u + (size_t)plan.nwords * 512u > 160 * 1024;
-    if (gc) P.stage_blocks = 1;
+    const bool gc = kHalfTileBytes + bucket * 512u + (size_t)plan.nwords * 512u > 160 * 1024;
     if (int rc = stream_geometry(P, owned, P.wb, &grid, 16, tuned ? &S->tuner_scan : nullptr, sh.d_text, sh.text_len,
                                  1000u + plan.nwords)) return rc;
-    P.lds_per_wave = 4096u * P.stage_blocks + bucket * 512u + (gc ? 0u : plan.nwords * 512u);
+    P.lds_per_wave = kHalfTileBytes + bucket * 512u + (gc ? 0u : plan.nwords * 512u);
     P.waves_per_group = (uint32_t)std::min<size_t>(kWavesPerGroup, (160 * 1024) / P.lds_per_wave);
     grid = (uint32_t)((P.n_chunks + 64ull * P.waves_per_group - 1) / (64ull * P.waves_per_group));
     if (gc) {
@@ -661,7 +658,6 @@ int ScanJob::prepare() {
         }
       }
     }
-    F.stage_blocks = 2u;
     int fwpc = 16;
     // fused: ONE round of workgroups (as many as are resident at once) -- every workgroup ends with the chunk DP of
     // what it found, a phase in which it does not stream; with two rounds the chip goes through that twice (3 GB:
@@ -669,15 +665,12 @@ int ScanJob::prepare() {
     if (fused) fwpc = 8;
     if (fkind == kFilterTable) {
       // one 4 KiB tile per wave + the table per workgroup decide how many workgroups a CU holds
-      F.stage_blocks = 1;
-      const uint32_t wg_lds = (1u << (2 * q - 3)) + 4 * 4096u;
+      const uint32_t wg_lds = (1u << (2 * q - 3)) + kWavesPerGroup * kHalfTileBytes;
       fwpc = 4 * (int)std::min<uint32_t>(8, (160u * 1024u) / wg_lds);
     }
     uint32_t extra_front = 1;
     if (fkind == kFilterCount) {
-      const int env_csb = (int)sw.count_stage_blocks;
-      F.stage_blocks = env_csb == 1 ? 1u : 2u;  // (whole 128-byte lines per lane and step: read with non-temporal loads)
-      const uint32_t per_wave = 4096u * F.stage_blocks + 64u * count_w, table = 1u << (2 * (q + count_r - 1));
+      const uint32_t per_wave = kTileBytes + 64u * count_w, table = 1u << (2 * (q + count_r - 1));
       // the table is per workgroup: sixteen waves around one copy where that fits a CU's LDS, else four
       const int env_wpg = (int)sw.count_wpg;
       count_wpg = (env_wpg == 4 || env_wpg == 16) ? (uint32_t)env_wpg : 16u;
@@ -690,10 +683,10 @@ int ScanJob::prepare() {
     tuned = S->tune && S->timing >= 1 && !ext_bitmap && !ext_desc;
     if (int rc = stream_geometry(F, n_blocks - F.first_owned_block, extra_front, &fgrid, fwpc, tuned ? &S->tuner : nullptr,
                                  sh.d_text, sh.text_len, (uint32_t)fkind * 16u + (rc_marked ? 1u : 0u))) return rc;
-    if (fkind == kFilterPlanes) F.stage_blocks = 2;  // (the bit-plane kernel stages whole 128-byte lines only)
-    F.lds_per_wave = 4096u * F.stage_blocks + (F.piece_planes ? 0u : 2u * bucket * 512u);
+    // the staging tile: one block per lane chunk and step in filter_table_kernel, two (a whole 128-byte line) in the others
+    F.lds_per_wave = (fkind == kFilterTable ? kHalfTileBytes : kTileBytes) + (F.piece_planes ? 0u : 2u * bucket * 512u);
     if (fkind == kFilterCount) {
-      F.lds_per_wave = 4096u * F.stage_blocks + 64u * count_w;
+      F.lds_per_wave = kTileBytes + 64u * count_w;
       F.waves_per_group = count_wpg;
       fgrid = (uint32_t)((F.n_chunks + 64ull * count_wpg - 1) / (64ull * count_wpg));
     }
@@ -720,17 +713,6 @@ int ScanJob::prepare() {
       // 0.63 -> 0.585 ms per search; one search alone: 0.745 -> 0.80 ms, hence only when pipelined).
       const uint32_t pad = pipelined ? 24u * 1024u : 0u;
       if (fkind == kFilterPlanes && pad) F.lds_per_wave += pad / 4u / 16u * 16u;
-    }
-    // the bit-plane filter as a linear stream (filter_dna_linear_kernel): every wave owns one contiguous
-    // range of 128-block steps; SASSY_HIP_FILTER_LINEAR=<waves> sets how many waves the text is cut into
-    F.lin_steps = 0;
-    const int env_lin = (int)sw.filter_linear;
-    if (fkind == kFilterPlanes && env_lin > 0 && !ext_bitmap && !ext_desc) {
-      const uint64_t cover = n_blocks - (F.first_owned_block & ~1ull);
-      const uint64_t steps = std::max<uint64_t>(1, (cover + 128ull * env_lin - 1) / (128ull * env_lin));
-      F.lin_steps = (uint32_t)std::min<uint64_t>(steps, 0x7FFFFFFFu);
-      const uint64_t waves = (cover + 128ull * F.lin_steps - 1) / (128ull * F.lin_steps);
-      fgrid = (uint32_t)((waves + kWavesPerGroup - 1) / kWavesPerGroup);
     }
     F.hit_bitmap = d_bitmap;
     {
@@ -809,10 +791,9 @@ int ScanJob::enqueue(int attempt) {
   if (wait_for && attempt == 0) HIP_TRY(hipStreamWaitEvent(L.stream, wait_for, 0));
   // (a job that only consumes a bitmap has no filter to time: no events at level 1, each costs ~6 us of stream idle)
   const bool time_head = timing >= 2 || (timing == 1 && !ext_bitmap);
-  // (the fused launch carries its events itself: LaunchEvents)
-  const bool env_ext_ev = S->sw.ext_events != 0;
-  // (a member of another job's pass times it with its own two markers around the wait for it)
-  const bool ext_events = time_head && filtered && fused && attempt == 0 && env_ext_ev && !group_leader;
+  // (the fused launch carries its events itself: LaunchEvents; a member of another job's pass times it with its own two
+  // markers around the wait for it)
+  const bool ext_events = time_head && filtered && fused && attempt == 0 && !group_leader;
   if (time_head && !ext_events) HIP_TRY(hipEventRecord(L.ev_a, L.stream));
   hipError_t le;
   if (!filtered) {
@@ -1026,7 +1007,7 @@ int ScanJob::enqueue(int attempt) {
   {
     const int other = L.ctl_cur ^ 1;
     DevBuf<uint8_t>& O = other ? L.d_ctl_twin : L.d_ctl;
-    if (S->sw.ctl_twin != 0 && !L.ctl_clean[other] && O.p != nullptr && O.cap >= 64) {
+    if (!L.ctl_clean[other] && O.p != nullptr && O.cap >= 64) {
       HIP_TRY(hipEventRecord(L.ev_done, L.stream));
       HIP_TRY(hipMemsetAsync(O.p, 0, 64, L.stream));
       L.ctl_clean[other] = true;
@@ -1041,7 +1022,7 @@ int ScanJob::enqueue(int attempt) {
 // the tile's upper half to the segment state (kFuseGroupMaxWords)
 bool ScanJob::group_ok() const {
   return !empty && filtered && fused && fkind == kFilterPlanes && S->profile == PROFILE_DNA && pair == 0 && !rc_marked &&
-         !rc_second_pass && !ext_bitmap && !ext_desc && texts.n == 0 && !tuned && F.lin_steps == 0 && F.pair == 0 &&
+         !rc_second_pass && !ext_bitmap && !ext_desc && texts.n == 0 && !tuned && F.pair == 0 &&
          F.piece_len >= 7 && F.piece_len <= 12 && plan.nwords <= kFuseGroupMaxWords && timing <= 1;
 }
 bool ScanJob::group_fits(const ScanJob& b) const {

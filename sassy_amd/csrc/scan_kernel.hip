@@ -743,17 +743,16 @@ __device__ __forceinline__ bool dp_block(DpWord& V, int& ds, const unsigned char
   return true;
 }
 
-// SB = text blocks per lane chunk fetched by one staging step: 2 = one full 128-byte line per
-// chunk (8 KiB tile), 1 = half lines (4 KiB tile, more waves fit in the LDS).
+// A staging step fetches one text block per lane chunk (half a 128-byte line: a 4 KiB tile, more waves fit in the LDS).
 // GC: the per-row carries in global memory (P.carry_global; patterns whose carries do not fit one wave's LDS).
-template <int PROFILE, int NS, int SB, bool GC = false>
+template <int PROFILE, int NS, bool GC = false>
 __global__ __launch_bounds__(256) void scan_kernel(const ScanParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr uint32_t kRowBytes = 64u * SB;          // tile row = the staged bytes of one lane chunk
-  constexpr uint32_t kSlots = 4u * SB;              // 16-byte slots per row
+  constexpr uint32_t kRowBytes = 64u;               // tile row = the staged bytes of one lane chunk
+  constexpr uint32_t kSlots = 4u;                   // 16-byte slots per row
   constexpr uint32_t kOwnersPerInstr = 64u / kSlots;  // tile rows filled by one 64-lane load
-  constexpr int kStageInstr = 4 * SB;
-  constexpr uint32_t kTile = 64u * kRowBytes;
+  constexpr int kStageInstr = 4;
+  constexpr uint32_t kTile = kHalfTileBytes;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
   unsigned char* wbase = smem + (size_t)wave * P.lds_per_wave;
@@ -803,8 +802,7 @@ __global__ __launch_bounds__(256) void scan_kernel(const ScanParams P) {
 
   // ---- staging geometry: instruction i of a stage loads, for tile row `owner`, the 16-byte
   // chunk that belongs into slot (lane % kSlots) of that row.  Slots are XOR-swizzled so that the
-  // owners' ds_read_b128 of their own rows are bank-conflict free:
-  //   SB = 2: slot = chunk ^ ((owner >> 1) & 7);  SB = 1: slot = chunk ^ ((owner >> 2) & 3).
+  // owners' ds_read_b128 of their own rows are bank-conflict free: slot = chunk ^ ((owner >> 2) & 3).
   const uint64_t wave_blk0 = chunk_blk0(first_owned, bpl, back, wave_chunk0);
   const uint8_t* text_base = P.text + wave_blk0 * 64;
   uint32_t soff[kStageInstr];
@@ -812,17 +810,17 @@ __global__ __launch_bounds__(256) void scan_kernel(const ScanParams P) {
   for (int i = 0; i < kStageInstr; ++i) {
     const uint32_t owner = (uint32_t)i * kOwnersPerInstr + lane / kSlots;
     const uint32_t slot = lane % kSlots;
-    const uint32_t j = slot ^ (SB == 2 ? ((owner >> 1) & 7u) : ((owner >> 2) & 3u));
+    const uint32_t j = slot ^ ((owner >> 2) & 3u);
     soff[i] = (uint32_t)((chunk_blk0(first_owned, bpl, back, wave_chunk0 + owner) - wave_blk0) * 64) + j * 16u;
   }
   // wave-uniform: can every staged byte of this wave be read without a bounds check?
   const uint64_t wave_last = chunk_blk0(first_owned, bpl, back, wave_chunk0 + 63) + P.n_iter + 2;
   const bool interior = wave_last * 64 <= P.text_len;
-  // reading side: the lane's own row, logical chunks 4*sub + c
-  const uint32_t fsw = SB == 2 ? ((lane >> 1) & 7u) : ((lane >> 2) & 3u);
+  // reading side: the lane's own row, logical chunks c
+  const uint32_t fsw = (lane >> 2) & 3u;
   uint32_t rc[4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c) rc[c] = lane * kRowBytes + (((uint32_t)c ^ (fsw & 3u)) << 4);
+  for (int c = 0; c < 4; ++c) rc[c] = lane * kRowBytes + (((uint32_t)c ^ fsw) << 4);
 
   uint32_t st = kStDec;  // dec = true, amb = false
   EmitCtx ctx;
@@ -845,34 +843,30 @@ __global__ __launch_bounds__(256) void scan_kernel(const ScanParams P) {
   int minus_total = 0;                  // -1 deltas on the current block's left edge (none at a fresh start)
 
   for (uint32_t it = 0; it < P.n_iter; ++it) {
-    const uint32_t sub = SB == 2 ? (it & 1u) : 0u;
-    if (sub == 0) {
-      // ---- stage SB blocks for each of the 64 lane chunks: kStageInstr x (64 lanes x 16 B) ----
-      if (interior) {
+    // ---- stage the next block of each of the 64 lane chunks: kStageInstr x (64 lanes x 16 B) ----
+    if (interior) {
 #pragma unroll
-        for (int i = 0; i < kStageInstr; ++i) {
-          const uint4 v = stream_load16<SASSY_NT_SCAN>(text_base + (uint64_t)it * 64 + soff[i]);
-          *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = v;
-        }
-      } else {
+      for (int i = 0; i < kStageInstr; ++i) {
+        const uint4 v = stream_load16<SASSY_NT_SCAN>(text_base + (uint64_t)it * 64 + soff[i]);
+        *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = v;
+      }
+    } else {
 #pragma unroll
-        for (int i = 0; i < kStageInstr; ++i) {
-          const uint64_t off = wave_blk0 * 64 + (uint64_t)it * 64 + soff[i];
-          uint4 v;
-          if (off + 16 <= P.text_len) v = *reinterpret_cast<const uint4*>(P.text + off);
-          else v = load_tail16(P.text, off, P.text_len, tail_pad);
-          *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = v;
-        }
+      for (int i = 0; i < kStageInstr; ++i) {
+        const uint64_t off = wave_blk0 * 64 + (uint64_t)it * 64 + soff[i];
+        uint4 v;
+        if (off + 16 <= P.text_len) v = *reinterpret_cast<const uint4*>(P.text + off);
+        else v = load_tail16(P.text, off, P.text_len, tail_pad);
+        *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = v;
       }
     }
 
     // ---- the lane's own 64 text bytes -> profile masks -> LDS ----
     {
-      const uint32_t hs = SB == 2 ? (((sub << 2) ^ (fsw & 4u)) << 4) : 0u;  // slot bit 2 = block of the pair
       uint32_t x[16];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const uint4 v = *reinterpret_cast<const uint4*>(tile + rc[c] + hs);
+        const uint4 v = *reinterpret_cast<const uint4*>(tile + rc[c]);
         x[4 * c] = v.x; x[4 * c + 1] = v.y; x[4 * c + 2] = v.z; x[4 * c + 3] = v.w;
       }
       uint2 msk[NS];
@@ -931,22 +925,23 @@ __global__ __launch_bounds__(256) void scan_kernel(const ScanParams P) {
 // Pigeonhole: cut the first n_pieces * piece_len pattern rows into n_pieces = k+1 disjoint pieces;
 // an alignment with <= k edits leaves at least one piece untouched, so every cell <= k in the
 // last DP row at column c implies an EXACT occurrence of some piece ending at a text position
-// e in [c - (m+k), c].  This kernel streams over the text exactly like the DP kernel (same
-// staging, same lane-parallel profile), but per block it only evaluates, for every piece, the
+// e in [c - (m+k), c].  This kernel streams over the text like the DP kernel (same lane chunks,
+// same lane-parallel profile), but per block it only evaluates, for every piece, the
 // bit-parallel exact-match word  E_p = AND_j (mask[slot(p,j)] << (piece_len-1-j))  with the bits
 // shifted in from the previous block's masks, and records the blocks in which some piece ends.
 // Blocks far from every recorded block cannot hold a cell <= k and never see the DP.
 // (The piece test uses the same slot masks as the scan, so it is exact for every profile.)
 // NPG: 0 = any number of pieces (row table in LDS), 1 / 2 = up to 4 / 8 pieces with the row table
 // in scalar registers and all pieces advanced side by side (independent chains hide LDS latency).
-template <int PROFILE, int NS, int SB, int NPG>
+// A staging step fetches two blocks (a whole 128-byte line) per lane chunk; the DP kernel fetches one.
+template <int PROFILE, int NS, int NPG>
 __global__ __launch_bounds__(256) void filter_kernel(const ScanParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr uint32_t kRowBytes = 64u * SB;
-  constexpr uint32_t kSlots = 4u * SB;
+  constexpr uint32_t kRowBytes = 128u;
+  constexpr uint32_t kSlots = 8u;
   constexpr uint32_t kOwnersPerInstr = 64u / kSlots;
-  constexpr int kStageInstr = 4 * SB;
-  constexpr uint32_t kTile = 64u * kRowBytes;
+  constexpr int kStageInstr = 8;
+  constexpr uint32_t kTile = kTileBytes;
   constexpr uint32_t kTermTabBytes = 1024;  // LDS offset of the slot mask of every piece row
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
@@ -985,12 +980,12 @@ __global__ __launch_bounds__(256) void filter_kernel(const ScanParams P) {
   for (int i = 0; i < kStageInstr; ++i) {
     const uint32_t owner = (uint32_t)i * kOwnersPerInstr + lane / kSlots;
     const uint32_t slot = lane % kSlots;
-    const uint32_t j = slot ^ (SB == 2 ? ((owner >> 1) & 7u) : ((owner >> 2) & 3u));
+    const uint32_t j = slot ^ ((owner >> 1) & 7u);
     soff[i] = (uint32_t)((chunk_blk0(first_owned, bpl, back, wave_chunk0 + owner) - wave_blk0) * 64) + j * 16u;
   }
   const uint64_t wave_last = chunk_blk0(first_owned, bpl, back, wave_chunk0 + 63) + P.n_iter + 2;
   const bool interior = wave_last * 64 <= P.text_len;
-  const uint32_t fsw = SB == 2 ? ((lane >> 1) & 7u) : ((lane >> 2) & 3u);
+  const uint32_t fsw = (lane >> 1) & 7u;
   uint32_t rc[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) rc[c] = lane * kRowBytes + (((uint32_t)c ^ (fsw & 3u)) << 4);
@@ -998,7 +993,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const ScanParams P) {
   const uint32_t q = P.piece_len;
 
   for (uint32_t it = 0; it < P.n_iter; ++it) {
-    const uint32_t sub = SB == 2 ? (it & 1u) : 0u;
+    const uint32_t sub = it & 1u;  // block of the staged pair
     if (sub == 0) {
       if (interior) {
 #pragma unroll
@@ -1020,7 +1015,7 @@ __global__ __launch_bounds__(256) void filter_kernel(const ScanParams P) {
     unsigned char* cur = mask_bytes + (it & 1u) * (NS * 512);
     const unsigned char* prv = mask_bytes + ((it & 1u) ^ 1u) * (NS * 512);
     {
-      const uint32_t hs = SB == 2 ? (((sub << 2) ^ (fsw & 4u)) << 4) : 0u;
+      const uint32_t hs = ((sub << 2) ^ (fsw & 4u)) << 4;  // slot bit 2 = block of the pair
       uint32_t x[16];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -1127,158 +1122,6 @@ __device__ __noinline__ void mark_piece_ends(unsigned long long* bitmap, uint64_
   for (uint64_t x = r.x; x <= (uint64_t)r.y; ++x) atomicOr(&bitmap[x >> 6], 1ull << (x & 63));
 }
 
-// ====================================================================== K0 for Dna, linear streaming
-// Same bit-plane evaluation as filter_dna_kernel, other data movement: a wave walks ONE contiguous text
-// range, 128 consecutive blocks (8 KiB) per step, lane l taking blocks 2l and 2l+1 of the step.  The
-// loads of a wave are then one contiguous 8 KiB read per step (the access pattern the HBM likes best,
-// profiles/r01_stream_read.txt) instead of 64 streams bpl * 64 bytes apart, whose speed depends on how
-// that stride and the lane count fall onto the channel mapping (host.hip: GeoTuner).  What a block
-// needs from its predecessor -- the high halves of its two code planes -- comes from the neighbour
-// lane by DPP (wave_shr:1; lane 0 gets the previous step's last block through the `old` operand), the
-// second block of a lane from its own first.  Every block is evaluated exactly once; a wave primes its
-// planes with one extra step in front of its range.
-template <int NPG>
-__global__ __launch_bounds__(256) void filter_dna_linear_kernel(const ScanParams P) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int NP = 4 * NPG;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = threadIdx.x >> 6;
-  unsigned char* tile = smem + (size_t)wave * 8192u;
-
-  const uint64_t cover_lo = P.first_owned_block & ~1ull;  // rows are pairs of blocks = aligned 128-byte lines
-  const uint64_t range = 128ull * P.lin_steps;
-  const uint64_t w_lo = cover_lo + ((uint64_t)blockIdx.x * kWavesPerGroup + wave) * range;
-  if (w_lo >= P.n_blocks) return;  // wave-uniform
-  const uint64_t w_hi = w_lo + range;
-
-  // staging: instruction i fetches the 128-byte rows of lanes 8i .. 8i+7 (1 KiB contiguous), the 16-byte
-  // pieces of a row swizzled so that the owners' ds_read_b128 are conflict free (as in filter_dna_kernel)
-  uint32_t soff[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint32_t owner = (uint32_t)i * 8u + lane / 8u;
-    const uint32_t slot = lane % 8u;
-    const uint32_t j = slot ^ ((owner >> 1) & 7u);
-    soff[i] = owner * 128u + j * 16u;
-  }
-  const uint32_t fsw = (lane >> 1) & 7u;
-  uint32_t rc[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) rc[c] = lane * 128u + (((uint32_t)c ^ (fsw & 3u)) << 4);
-
-  const uint32_t q = P.piece_len;
-  uint32_t nb0[NP], nb1[NP];
-#pragma unroll
-  for (int pp = 0; pp < NP; ++pp) {
-    nb0[pp] = ~P.piece_bits[pp][0];
-    nb1[pp] = ~P.piece_bits[pp][1];
-  }
-  // steps: one priming step in front of the range (unless the range starts the buffer), then lin_steps
-  const bool prime = w_lo >= 128;
-  const uint64_t base0 = prime ? w_lo - 128 : w_lo;
-  const uint32_t n_steps = P.lin_steps + (prime ? 1u : 0u);
-  const bool interior = (base0 + 128ull * n_steps) * 64 <= P.text_len;
-  const uint8_t* text_base = P.text + base0 * 64;
-  uint32_t carry0 = 0, carry1 = 0;  // plane high halves of the last block of the previous step
-
-  uint4 nxt[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    nxt[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (interior) nxt[i] = stream_load16<SASSY_NT_DNA>(text_base + soff[i]);
-  }
-  for (uint32_t st = 0; st < n_steps; ++st) {
-    const uint64_t base = base0 + 128ull * st;
-    if (base >= P.n_blocks) break;  // wave-uniform
-    if (interior) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = nxt[i];
-      if (st + 1 < n_steps) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          nxt[i] = stream_load16<SASSY_NT_DNA>(text_base + (uint64_t)(st + 1) * 8192 + soff[i]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const uint64_t off = base * 64 + soff[i];
-        uint4 v;
-        if (off + 16 <= P.text_len) v = *reinterpret_cast<const uint4*>(P.text + off);
-        else v = load_tail16(P.text, off, P.text_len);
-        *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = v;
-      }
-    }
-    // the planes of the lane's two blocks
-    uint2 ta0, ta1, tb0, tb1;
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-      const uint32_t hs = ((((uint32_t)sub << 2) ^ (fsw & 4u)) << 4);
-      uint32_t x[16];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const uint4 v = *reinterpret_cast<const uint4*>(tile + rc[c] + hs);
-        x[4 * c] = v.x; x[4 * c + 1] = v.y; x[4 * c + 2] = v.z; x[4 * c + 3] = v.w;
-      }
-      if (sub == 0) { ta0 = bit_plane<1>(x); ta1 = bit_plane<2>(x); }
-      else { tb0 = bit_plane<1>(x); tb1 = bit_plane<2>(x); }
-    }
-    // predecessor of block 2l: block 2l-1 = the neighbour lane's second block (lane 0: the previous step's)
-    const uint32_t pa0 = (uint32_t)__builtin_amdgcn_update_dpp((int)carry0, (int)tb0.y, 0x138, 0xF, 0xF, false);  // wave_shr:1
-    const uint32_t pa1 = (uint32_t)__builtin_amdgcn_update_dpp((int)carry1, (int)tb1.y, 0x138, 0xF, 0xF, false);
-    carry0 = (uint32_t)__builtin_amdgcn_readlane((int)tb0.y, 63);
-    carry1 = (uint32_t)__builtin_amdgcn_readlane((int)tb1.y, 63);
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-      const uint2 t0 = sub == 0 ? ta0 : tb0, t1 = sub == 0 ? ta1 : tb1;
-      const uint32_t prev0 = sub == 0 ? pa0 : ta0.y, prev1 = sub == 0 ? pa1 : ta1.y;
-      uint32_t al[NP], ah[NP];
-#pragma unroll
-      for (int pp = 0; pp < NP; ++pp) { al[pp] = 0xFFFFFFFFu; ah[pp] = 0xFFFFFFFFu; }
-#pragma unroll
-      for (int d = 0; d < 12; ++d) {
-        if ((uint32_t)d < q) {  // wave-uniform
-          uint32_t s0l, s0h, s1l, s1h;
-          if (d == 0) {
-            s0l = t0.x; s0h = t0.y; s1l = t1.x; s1h = t1.y;
-          } else {
-            s0l = __builtin_amdgcn_alignbit(t0.x, prev0, 32 - d);
-            s0h = __builtin_amdgcn_alignbit(t0.y, t0.x, 32 - d);
-            s1l = __builtin_amdgcn_alignbit(t1.x, prev1, 32 - d);
-            s1h = __builtin_amdgcn_alignbit(t1.y, t1.x, 32 - d);
-          }
-          const uint32_t j = q - 1u - (uint32_t)d;
-#pragma unroll
-          for (int pp = 0; pp < NP; ++pp) {
-            const uint32_t n0 = 0u - ((nb0[pp] >> j) & 1u);
-            const uint32_t n1 = 0u - ((nb1[pp] >> j) & 1u);
-            al[pp] = bitop3<0x60>(al[pp], s0l, n0);  // a & (b ^ c)
-            ah[pp] = bitop3<0x60>(ah[pp], s0h, n0);
-            al[pp] = bitop3<0x60>(al[pp], s1l, n1);
-            ah[pp] = bitop3<0x60>(ah[pp], s1h, n1);
-          }
-        }
-      }
-      uint32_t hit = 0;
-#pragma unroll
-      for (int pp = 0; pp < NP; ++pp) hit |= al[pp] | ah[pp];
-      const uint64_t b = base + 2ull * lane + (uint64_t)sub;
-      const bool evaluate = b >= w_lo && b < w_hi && b >= P.first_owned_block && b < P.n_blocks;
-      if (evaluate && hit != 0) {
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp) {
-          const uint64_t bits = ((uint64_t)ah[pp] << 32) | al[pp];
-          if (bits != 0) {
-            const bool mirror = (P.piece_mirror >> pp) & 1u;
-            mark_piece_ends(mirror ? P.hit_bitmap_rc : P.hit_bitmap, bits, b,
-                            mirror ? (int64_t)P.text_len + (int64_t)q : (int64_t)-1, (int64_t)P.piece_rem[pp], (int64_t)P.k,
-                            P.n_blocks);
-          }
-        }
-      }
-    }
-  }
-}
-
 // ====================================================================== K0 for many Dna patterns
 // search_encoded_patterns with thousands of equal-length patterns (CRISPR guides): the text bytes,
 // the two code bit planes and their q shifted copies are the same for every pattern, only the
@@ -1288,14 +1131,15 @@ __global__ __launch_bounds__(256) void filter_dna_linear_kernel(const ScanParams
 // and marks, in its own bitmap, the blocks a match around a piece occurrence can end in (as
 // filter_dna_kernel does).  The chunk list / DP / rank / traceback stages then run per pattern.
 // Q: piece length (compile time: the shifts, the bit positions of the piece rows and the unrolling
-// depend on it); up to 8 pieces per pattern.
-template <int SB, int Q>
+// depend on it); up to 8 pieces per pattern.  A staging step fetches two blocks (a whole 128-byte
+// line) per lane chunk.
+template <int Q>
 __global__ __launch_bounds__(256) void filter_dna_multi_kernel(const ScanParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr uint32_t kRowBytes = 64u * SB;
-  constexpr uint32_t kSlots = 4u * SB;
+  constexpr uint32_t kRowBytes = 128u;
+  constexpr uint32_t kSlots = 8u;
   constexpr uint32_t kOwnersPerInstr = 64u / kSlots;
-  constexpr int kStageInstr = 4 * SB;
+  constexpr int kStageInstr = 8;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
   unsigned char* tile = smem + (size_t)wave * P.lds_per_wave;
@@ -1318,12 +1162,12 @@ __global__ __launch_bounds__(256) void filter_dna_multi_kernel(const ScanParams 
   for (int i = 0; i < kStageInstr; ++i) {
     const uint32_t owner = (uint32_t)i * kOwnersPerInstr + lane / kSlots;
     const uint32_t slot = lane % kSlots;
-    const uint32_t j = slot ^ (SB == 2 ? ((owner >> 1) & 7u) : ((owner >> 2) & 3u));
+    const uint32_t j = slot ^ ((owner >> 1) & 7u);
     soff[i] = (uint32_t)((chunk_blk0(first_owned, bpl, back, wave_chunk0 + owner) - wave_blk0) * 64) + j * 16u;
   }
   const uint64_t wave_last = chunk_blk0(first_owned, bpl, back, wave_chunk0 + 63) + P.n_iter + 2;
   const bool interior = wave_last * 64 <= P.text_len;
-  const uint32_t fsw = SB == 2 ? ((lane >> 1) & 7u) : ((lane >> 2) & 3u);
+  const uint32_t fsw = (lane >> 1) & 7u;
   uint32_t rc[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) rc[c] = lane * kRowBytes + (((uint32_t)c ^ (fsw & 3u)) << 4);
@@ -1455,14 +1299,14 @@ template <int Q>
 __global__ __launch_bounds__(256) void filter_table_kernel(const ScanParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr uint32_t kTableBytes = 1u << (2 * Q - 3);
-  constexpr uint32_t kRowBytes = 64u;   // SB = 1: more waves per CU, the kernel is VALU / LDS bound
+  constexpr uint32_t kRowBytes = 64u;   // one block per staging step: more waves per CU, the kernel is VALU / LDS bound
   constexpr uint32_t kSlots = 4u;
   constexpr uint32_t kOwnersPerInstr = 16u;
   constexpr int kStageInstr = 4;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = threadIdx.x >> 6;
   unsigned char* table = smem;
-  unsigned char* tile = smem + kTableBytes + (size_t)wave * 4096u;
+  unsigned char* tile = smem + kTableBytes + (size_t)wave * kHalfTileBytes;
   {
     const uint4* src = reinterpret_cast<const uint4*>(P.qgram_table);
     uint4* dst = reinterpret_cast<uint4*>(table);
@@ -2906,50 +2750,40 @@ __global__ __launch_bounds__(256) void list_rows_kernel(const ScanParams P) {
 }
 
 // ------------------------------------------------------------------ launcher
-template <int PROFILE, int NS, int SB>
-static hipError_t launch_sb(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
+template <int PROFILE, int NS>
+static hipError_t launch_one(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
+  if (P.carry_global) {  // (long patterns: the carries in global memory)
+    hipLaunchKernelGGL((scan_kernel<PROFILE, NS, true>), dim3(grid), dim3(64u * (P.waves_per_group ? P.waves_per_group : 4u)), smem, stream, P);
+    return hipGetLastError();
+  }
   static DeviceOnce attr_set;  // LDS beyond the 64 KiB default needs an explicit opt-in
   if (attr_set.need()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_kernel<PROFILE, NS, SB>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scan_kernel<PROFILE, NS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     attr_set.done();
   }
-  hipLaunchKernelGGL((scan_kernel<PROFILE, NS, SB>), dim3(grid), dim3(64u * (P.waves_per_group ? P.waves_per_group : 4u)), smem, stream, P);
+  hipLaunchKernelGGL((scan_kernel<PROFILE, NS>), dim3(grid), dim3(64u * (P.waves_per_group ? P.waves_per_group : 4u)), smem, stream, P);
   return hipGetLastError();
 }
-template <int PROFILE, int NS>
-static hipError_t launch_one(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
-  if (P.carry_global) {  // (long patterns: half-line staging, the carries in global memory)
-    hipLaunchKernelGGL((scan_kernel<PROFILE, NS, 1, true>), dim3(grid), dim3(64u * (P.waves_per_group ? P.waves_per_group : 4u)), smem, stream, P);
-    return hipGetLastError();
-  }
-  return P.stage_blocks == 1 ? launch_sb<PROFILE, NS, 1>(P, grid, smem, stream)
-                             : launch_sb<PROFILE, NS, 2>(P, grid, smem, stream);
-}
 
-template <int PROFILE, int NS, int SB, int NPG>
+template <int PROFILE, int NS, int NPG>
 static hipError_t launch_filter_npg(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
   static DeviceOnce attr_set;
   if (attr_set.need()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&filter_kernel<PROFILE, NS, SB, NPG>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&filter_kernel<PROFILE, NS, NPG>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     attr_set.done();
   }
-  hipLaunchKernelGGL((filter_kernel<PROFILE, NS, SB, NPG>), dim3(grid), dim3(256), smem, stream, P);
+  hipLaunchKernelGGL((filter_kernel<PROFILE, NS, NPG>), dim3(grid), dim3(256), smem, stream, P);
   return hipGetLastError();
-}
-template <int PROFILE, int NS, int SB>
-static hipError_t launch_filter_sb(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
-  if (P.piece_groups == 1) return launch_filter_npg<PROFILE, NS, SB, 1>(P, grid, smem, stream);
-  if (P.piece_groups == 2) return launch_filter_npg<PROFILE, NS, SB, 2>(P, grid, smem, stream);
-  return launch_filter_npg<PROFILE, NS, SB, 0>(P, grid, smem, stream);
 }
 template <int PROFILE, int NS>
 static hipError_t launch_filter_one(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
-  return P.stage_blocks == 1 ? launch_filter_sb<PROFILE, NS, 1>(P, grid, smem, stream)
-                             : launch_filter_sb<PROFILE, NS, 2>(P, grid, smem, stream);
+  if (P.piece_groups == 1) return launch_filter_npg<PROFILE, NS, 1>(P, grid, smem, stream);
+  if (P.piece_groups == 2) return launch_filter_npg<PROFILE, NS, 2>(P, grid, smem, stream);
+  return launch_filter_npg<PROFILE, NS, 0>(P, grid, smem, stream);
 }
 template <int PROFILE, int NS>
 static hipError_t launch_list_one(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
@@ -3058,16 +2892,16 @@ static hipError_t launch_filter_planes(const ScanParams& P, uint32_t grid, hipSt
 }
 template <int Q>
 static hipError_t launch_filter_table_q(const ScanParams& P, uint32_t grid, hipStream_t stream) {
-  const size_t smem = (1u << (2 * Q - 3)) + 4 * 4096u;
+  const size_t smem = (1u << (2 * Q - 3)) + kWavesPerGroup * kHalfTileBytes;
   hipLaunchKernelGGL((filter_table_kernel<Q>), dim3(grid), dim3(256), smem, stream, P);
   return hipGetLastError();
 }
 template <int Q>
 static hipError_t launch_filter_dna_multi_q(const ScanParams& P, uint32_t grid, hipStream_t stream) {
-  hipLaunchKernelGGL((filter_dna_multi_kernel<2, Q>), dim3(grid), dim3(256), (size_t)kWavesPerGroup * P.lds_per_wave, stream, P);
+  hipLaunchKernelGGL((filter_dna_multi_kernel<Q>), dim3(grid), dim3(256), (size_t)kWavesPerGroup * P.lds_per_wave, stream, P);
   return hipGetLastError();
 }
-// piece lengths 6 .. 12 (stage_blocks = 2)
+// piece lengths 6 .. 12
 hipError_t launch_filter_dna_multi(const ScanParams& P, uint32_t grid, hipStream_t stream) {
   switch (P.piece_len) {
     case 6: return launch_filter_dna_multi_q<6>(P, grid, stream);
@@ -3090,13 +2924,6 @@ hipError_t launch_filter_table(const ScanParams& P, uint32_t grid, hipStream_t s
   }
 }
 hipError_t launch_filter_dna(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
-  if (P.piece_planes && P.lin_steps) {  // linear streaming variant (grid sized by the host for its wave ranges)
-    if (P.piece_groups == 1)
-      hipLaunchKernelGGL((filter_dna_linear_kernel<1>), dim3(grid), dim3(256), (size_t)kWavesPerGroup * 8192u, stream, P);
-    else
-      hipLaunchKernelGGL((filter_dna_linear_kernel<2>), dim3(grid), dim3(256), (size_t)kWavesPerGroup * 8192u, stream, P);
-    return hipGetLastError();
-  }
   if (P.piece_planes && P.pair) return launch_filter_pair(P, grid, stream);
   if (P.piece_planes)  // <= 8 pieces: the bit-plane kernel (lds_per_wave = the staging tile, + the chunk queue when fused)
     return P.piece_groups == 1 ? launch_filter_planes<1>(P, grid, stream) : launch_filter_planes<2>(P, grid, stream);
@@ -3117,7 +2944,7 @@ static hipError_t launch_filter_group_q(const ScanParams& P, uint32_t grid, hipS
   return hipGetLastError();
 }
 hipError_t launch_filter_group(const ScanParams& P, uint32_t grid, hipStream_t stream) {
-  if (!P.piece_planes || !P.fused || P.pair || P.lin_steps || P.member1.nwords > kFuseGroupMaxWords || P.nwords > kFuseGroupMaxWords)
+  if (!P.piece_planes || !P.fused || P.pair || P.member1.nwords > kFuseGroupMaxWords || P.nwords > kFuseGroupMaxWords)
     return hipErrorInvalidValue;
   switch (P.piece_len) {
     case 7: return launch_filter_group_q<7>(P, grid, stream);

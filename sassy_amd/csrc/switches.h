@@ -19,23 +19,18 @@ namespace sassy_hip {
   X(pipe_depth, 2, "searches in flight per searcher (1 .. 4) for search_shard_begin / _finish")                          \
   X(tune, 0, "1: the on-line geometry tuner tries neighbouring lane-chunk lengths during a resident text's first searches") \
   X(timing, 1, "HIP-event timing: 0 none, 1 the dominant kernel, 2 every phase")                                            \
-  X(ctl_twin, 1, "a search clears the lane's other control block behind its last kernel, the next search starts without a memset launch (0: a memset in front of every search)") \
   X(row_cut, 1, "0: the DP kernels compute every pattern row of every block (no wave-voted stop)")                         \
-  X(stage_blocks, 0, "streaming DP: text blocks per lane and staging step (1 / 2; 0 = default 1)")                         \
   X(filter_kind, 0, "force a prefilter kernel where it applies: 1 slot masks, 2 bit planes, 3 q-gram table, 4 q-gram counting") \
   X(self_rank, 1, "0: separate rank kernels instead of the traceback waves ranking their reports themselves")               \
-  X(filter_linear, 0, "> 0: filter_dna_linear_kernel with the text cut into this many wave ranges")                         \
   X(trace_wave, 1, "0: thread-per-report traceback only")                                                                   \
   X(iupac_planes, 1, "0: Iupac searchers with plain patterns take the Iupac chain, never the bit-plane launch with the text check") \
   X(short_pieces, 1, "0: no fused launch for shapes whose pigeonhole pieces are 6 rows")                                    \
   X(pair, 1, "0: no paired filter; 2: the counting filter keeps the shapes it is selective for")                            \
   X(pair_rc, 1, "0: both strands of a paired-filter shape through the forward strand's streaming DP with Rc marks")         \
-  X(count_stage_blocks, 0, "counting filter: 1 = half lines per staging step (default: whole lines)")                       \
   X(count_wpg, 0, "counting filter: waves per workgroup, 4 or 16 (0: by LDS fit)")                                          \
   X(count_fused, 1, "the counting filter hands its candidate blocks to the chunk DP without bitmap and chunk-list launch (0: classic chain)") \
   X(fused_probe, 0, "1: the fused launch reports where its waves spend their time; 2: no chunk DP at all (timing only, no reports)") \
   X(fused_press, 0, "> 0: a wave of the fused launch runs a chunk-DP pass once this many windows are queued")              \
-  X(ext_events, 1, "0: timing events around the fused launch instead of carried by the dispatch")                           \
   X(list_words, 1, "multi-word chunk DP of few chunks: 1 a lane per block (list_rows_kernel), 2 a lane per pattern word, 0 the lane-per-chunk kernel only")                                              \
   X(trace_threads, 0, ">= 64: threads of the thread-per-report traceback launch")                                           \
   X(trace_probe, 0, "1: the traceback waves report microseconds per phase to stderr")                                       \

@@ -2480,8 +2480,7 @@ def _env_allows_fusing():
     """False in the forced-path processes whose switches take the fused launch out of the picture."""
     e = os.environ
     return not (e.get("SASSY_HIP_FUSED") == "0" or e.get("SASSY_HIP_PREFILTER") == "0" or e.get("SASSY_HIP_FILTER_KIND", "2") != "2" or
-                e.get("SASSY_HIP_FILTER_LINEAR") or e.get("SASSY_HIP_SELF_RANK") == "0" or e.get("SASSY_HIP_TRACE_WAVE") == "0" or
-                e.get("SASSY_HIP_LANES"))
+                e.get("SASSY_HIP_SELF_RANK") == "0" or e.get("SASSY_HIP_TRACE_WAVE") == "0" or e.get("SASSY_HIP_LANES"))
 
 
 def test_fused_filter_equals_classic_chain_and_oracle(sassy):
@@ -2872,16 +2871,13 @@ _CORE = ("test_fuzz_small_texts or test_low_complexity_and_seams or test_long_pa
 _FORCED = [
     {"SASSY_HIP_PREFILTER": "0"},                    # streaming DP over every block (scan_kernel), also multi-word
     {"SASSY_HIP_PREFILTER": "0", "SASSY_HIP_ROW_CUT": "0"},   # ... every row of every block
-    {"SASSY_HIP_PREFILTER": "0", "SASSY_HIP_STAGE_BLOCKS": "2"},
     {"SASSY_HIP_PREFILTER": "1"},                    # prefilter even with 2-row pieces
     {"SASSY_HIP_PREFILTER": "1", "SASSY_HIP_FUSED": "0"},
     {"SASSY_HIP_FILTER_KIND": "1"},                  # filter_kernel (slot masks in LDS)
     {"SASSY_HIP_FILTER_KIND": "3"},                  # filter_table_kernel
     {"SASSY_HIP_FILTER_KIND": "4"},                  # filter_count_kernel
-    {"SASSY_HIP_FILTER_KIND": "4", "SASSY_HIP_COUNT_STAGE_BLOCKS": "1"},  # (half lines per step; the default is whole lines)
     {"SASSY_HIP_ROW_CUT": "0"},                      # list kernels without bounded rows
     {"SASSY_HIP_FUSED": "0"},                        # classic chain: bitmap -> chunk list -> list kernel
-    {"SASSY_HIP_FILTER_LINEAR": "64"},               # filter_dna_linear_kernel
     {"SASSY_HIP_TRACE_WAVE": "0"},                   # thread-per-report traceback only
     {"SASSY_HIP_SELF_RANK": "0"},                    # rank_count / rank_scatter kernels
     {"SASSY_HIP_RC_FUSED": "0"},                     # Rc strand from a reversed copy
@@ -2890,13 +2886,13 @@ _FORCED = [
     {"SASSY_HIP_IUPAC_PLANES": "0"},                 # Iupac searches with plain patterns through the Iupac chain only
     {"SASSY_HIP_FILTER_KIND": "4", "SASSY_HIP_COUNT_WPG": "4"},  # the counting filter with four waves per workgroup
     {"SASSY_HIP_BIG_PIN": "0", "SASSY_HIP_SHORT_PIECES": "0"},   # dense results through the host's vectors; no 5- / 6-row pieces
-    {"SASSY_HIP_FUSED_PRESS": "8", "SASSY_HIP_EXT_EVENTS": "0"},  # a pass of the fused launch's waves every 8 queued windows
+    {"SASSY_HIP_FUSED_PRESS": "8"},                  # a pass of the fused launch's waves every 8 queued windows
     {"SASSY_HIP_PAIR": "0"},                         # no paired filter: 5- / 6-row shapes through the paths of round 4
     {"SASSY_HIP_STRANDS_IN_FLIGHT": "0"},            # two strands that are two searches: one after the other
     # (round 6: the switches of csrc/switches.h that had no forced run)
     {"SASSY_HIP_PAIR_RC": "0", "SASSY_HIP_COMPACT_CIGARS": "0", "SASSY_HIP_ADOPT": "0", "SASSY_HIP_TRACE_THREADS": "256"},
     {"SASSY_HIP_FUSED_PROBE": "1", "SASSY_HIP_TRACE_PROBE": "1", "SASSY_HIP_TIMING": "2", "SASSY_HIP_TUNE": "1", "SASSY_HIP_PIPE_DEPTH": "3"},
-    {"SASSY_HIP_COUNT_FUSED": "0", "SASSY_HIP_CTL_TWIN": "0"},  # the counting filter's classic chain: bitmap + build_chunks_kernel; a memset in front of every search
+    {"SASSY_HIP_COUNT_FUSED": "0"},                  # the counting filter's classic chain: bitmap + build_chunks_kernel
 ]
 
 

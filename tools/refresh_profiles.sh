@@ -42,7 +42,7 @@ print('   ms_per_search', d['ms_per_step'], 'scan_kernel_ms', d['dominant_kernel
 # ---- searches in flight: depth, filter occupancy, chaining
 { echo "# python bench.py --steps 400 --warmup 50 (3 GB, config 2): ms per search by searches in flight and switches";
   for v in "--in-flight 1" "--in-flight 2" "--in-flight 3" "--in-flight 4"; do echo "$v: $(python bench.py --steps 400 --warmup 50 --no-cpu-baseline $v 2>/dev/null | grep -o '"ms_per_step": [0-9.]*')"; done;
-  for e in "SASSY_HIP_FILTER_LINEAR=8192" "SASSY_HIP_PIPE_DEPTH=3"; do echo "--in-flight 2 $e: $(env $e python bench.py --steps 400 --warmup 50 --no-cpu-baseline 2>/dev/null | grep -o '"ms_per_step": [0-9.]*')"; done; } > $OUT/${TAG}_in_flight.txt 2>&1
+  for e in "SASSY_HIP_PIPE_DEPTH=3"; do echo "--in-flight 2 $e: $(env $e python bench.py --steps 400 --warmup 50 --no-cpu-baseline 2>/dev/null | grep -o '"ms_per_step": [0-9.]*')"; done; } > $OUT/${TAG}_in_flight.txt 2>&1
 # ---- lane-chunk geometry: default vs the opt-in tuner, lone searches and searches in flight, several text sizes
 { echo "# bench.py --steps 300 --warmup 60 --tune-searches 40: ms per search (in flight 2) | latency of a lone search; SASSY_HIP_TUNE=1 = opt-in tuner";
   for n in 1000000000 2000000000 2700000000 3000000000 3700000000 5000000000; do for t in 0 1; do
