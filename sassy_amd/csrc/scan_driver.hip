@@ -710,7 +710,8 @@ int ScanJob::prepare() {
       // kernels would only run in the gaps between filter rounds.  Asking for 56 KB of LDS per workgroup
       // caps the filter at 2 workgroups = 8 waves per CU: two filters in flight still fill the chip, and a
       // tail kernel always finds registers, LDS and wave slots (measured, 3 GB, two searches in flight:
-      // 0.63 -> 0.585 ms per search; one search alone: 0.745 -> 0.80 ms, hence only when pipelined).
+      // 0.63 -> 0.585 ms per search; one search alone: 0.745 -> 0.80 ms, hence only when pipelined).  A grouped
+      // pass (enqueue) sizes its LDS without the pad.
       const uint32_t pad = pipelined ? 24u * 1024u : 0u;
       if (fkind == kFilterPlanes && pad) F.lds_per_wave += pad / 4u / 16u * 16u;
     }
@@ -822,7 +823,10 @@ int ScanJob::enqueue(int attempt) {
         // the shared pass: member 0 = this job (F), member 1 = the other job's pieces, pattern rows and report arrays
         const ScanJob& B = *group_member;
         ScanParams GP = F;
-        GP.lds_per_wave = F.lds_per_wave + F.fuse_queue_cap * 8u + 16u;  // member 1's queue and count
+        // The tile and both members' queues and counts, WITHOUT the pipelining pad of prepare(): 4 x (8192 + 2 x 1552) =
+        // 45 184 bytes per workgroup, so three workgroups per CU stream the text instead of two (the kernel's VGPRs allow
+        // three waves per SIMD).  The pass keeps the members' geometry (the pad, the geometry and why).
+        GP.lds_per_wave = kTileBytes + 2u * (F.fuse_queue_cap * 8u + 16u);
         const uint32_t na = F.n_pieces, nb = B.F.n_pieces;
         GP.piece_member = 0;
         for (uint32_t pp = 0; pp < 8; ++pp) {  // (slots behind both repeat member 0's first piece)
