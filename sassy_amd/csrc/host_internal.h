@@ -1,6 +1,6 @@
 // host_internal.h -- what the host units of libsassy_hip.so share: the searcher, its lanes and buffers, one scan job,
 // the scan queue, the result types, and the functions one unit calls in another.  Units:
-//   scan_driver.hip   one pattern over one buffer: ScanJob (prepare / enqueue / finish), sub-shards, strands, search_text
+//   scan_driver.hip   one pattern over one buffer: ScanJob (prepare / enqueue / finish), strands, search_text
 //   many_patterns.hip search_encoded / search_many: pattern-tiled scan, seeded search, lists -> reports -> records
 //   multi_device.hip  sassy_hip_multi_*: one text over several devices inside one process
 //   c_abi.hip         the C-ABI of include/sassy.h + sassy_hip.h, the switch table, synthetic inputs
@@ -269,9 +269,9 @@ struct sassy_hip_Encoded {
 
 // Everything one scan pipeline (filter -> chunk list -> DP -> rank -> traceback) needs for itself:
 // a stream, its timing events, its device work buffers and the pinned, device-mapped host buffer
-// its kernels write the results into.  A searcher owns several lanes so that a long text can be
-// cut into sub-shards whose pipelines overlap (the next sub-shard's bandwidth-bound filter runs
-// while the previous one's latency-bound DP / rank / traceback kernels finish).
+// its kernels write the results into.  A searcher owns several lanes so that searches in flight
+// overlap (the next search's bandwidth-bound filter runs while the previous one's latency-bound
+// DP / rank / traceback kernels finish).
 constexpr int kMaxLanes = 4;
 struct ScanLane {
   hipStream_t stream = nullptr;
@@ -511,8 +511,8 @@ struct sassy_SearcherType {
   sassy_SearcherType() { apply_switches(); }
   Profile profile = PROFILE_DNA;
   bool rc = false;
-  // lanes[0].stream doubles as the searcher's stream: text / pattern uploads and everything that
-  // is not split into sub-shards run on it (sassy_hip_set_stream replaces it)
+  // lanes[0].stream doubles as the searcher's stream: text / pattern uploads and every search that
+  // is not one of several in flight run on it (sassy_hip_set_stream replaces it)
   ScanLane lanes[kMaxLanes];
   hipStream_t stream = nullptr;
   hipStream_t user_stream = nullptr;
@@ -702,6 +702,40 @@ static_assert(sizeof(MatchOut) == sizeof(sassy_hip_Match) && sizeof(MatchOut) ==
 
 inline uint32_t warmup_blocks(uint32_t m, uint32_t k) { return (m + k + 1 + 63) / 64; }
 
+// One report's traceback slice (trace_kernel.hip), from the shape (m, k) alone: the byte sizes of its parts, the slice
+// stride of either kernel shape, and what follows from them.  Every host site that fills a TraceParams reads this.
+struct TraceShape {
+  uint64_t band;           // (m + 1) rows of 2k + 3 cells (two bytes per cell from k = 255 on)
+  uint64_t win;            // the text window, whole 16-byte chunks
+  uint64_t ops;            // the edit operations, one byte each
+  uint64_t str;            // = TraceParams::str_stride: one record's cigar string
+  uint64_t raw;            // band + win + ops + str
+  uint64_t pat_bytes;      // the pattern next to the slices
+  uint64_t wave_stride;    // wave kernel: raw + kTraceWaveDummy (the band rows' lanes outside the band store there, unmasked;
+                           // the kernel finds them at scratch_stride - kTraceWaveDummy)
+  uint64_t thread_stride;  // thread kernel: raw, bumped to an odd number of LDS words (conflict-free slices)
+  bool wave_fits;          // a band row fits a wavefront, and four slices with their patterns fit a CU's LDS
+  bool thread_in_lds;      // the thread kernel's 64 slices per workgroup fit LDS (else: global memory)
+  uint64_t thread_count;   // slices in LDS: threads of a launch with as many workgroups as the chip holds at once
+};
+inline TraceShape trace_shape(uint32_t m, uint32_t k) {
+  TraceShape s{};
+  const uint64_t cell = (k + 1 <= 255) ? 1 : 2;
+  s.band = ((uint64_t)(m + 1) * (2ull * k + 3) * cell + 3) / 4 * 4;
+  s.win = ((uint64_t)m + k + 15 + 15) / 16 * 16;
+  s.ops = ((uint64_t)m + k + 1 + 3) / 4 * 4;
+  s.str = (2ull * (m + k + 1) + 2 + 15) / 16 * 16;
+  s.raw = s.band + s.win + s.ops + s.str;
+  s.pat_bytes = ((uint64_t)m + 15) / 16 * 16;
+  s.wave_stride = (s.raw + kTraceWaveDummy + 15) / 16 * 16;
+  s.thread_stride = s.raw + ((s.raw / 4) % 2 == 0 ? 4 : 0);
+  s.wave_fits = 2ull * k + 3 <= 64 && 4 * s.pat_bytes + 4 * s.wave_stride <= 160 * 1024;
+  const uint64_t wg_bytes = 64 * s.thread_stride + s.pat_bytes;
+  s.thread_in_lds = wg_bytes <= kTraceLdsLimit;
+  s.thread_count = std::min<uint64_t>(256ull * 64ull * std::max<uint64_t>(1, (160ull * 1024) / wg_bytes), 131072);
+  return s;
+}
+
 // The three prefilter kernels (scan_kernel.hip): which one evaluates the pieces.
 enum FilterKind : uint32_t {
   kFilterGeneric = 1,  // filter_kernel: slot masks in LDS, any profile, <= 255 piece rows
@@ -710,7 +744,7 @@ enum FilterKind : uint32_t {
   kFilterCount = 4,    // filter_count_kernel: q-gram lemma (count the pattern's q-grams per window), Dna / Iupac
 };
 
-// One scan of one buffer (shard or sub-shard) on one lane, in three phases so that several can be
+// One scan of one buffer (a whole text or a shard) on one lane, in three phases so that several can be
 // in flight: prepare() sizes everything and uploads what the pattern needs, enqueue() queues the
 // whole kernel pipeline on the lane's stream without waiting, finish() waits for it, grows buffers
 // and re-runs on overflow, and turns the device output into resolved reports.
@@ -747,7 +781,6 @@ struct ScanJob {
   bool rc_second_pass = false;       // more than 4 pieces: the Rc pieces get their own filter launch
   ScanParams F2{};
   uint64_t rev_n = 0;
-  hipEvent_t wait_for = nullptr;     // pipelining: the previous sub-shard's "filter done"
   bool signal_filter_done = false;   // pipelining: record L.ev_filter_done behind this filter
   uint8_t* ctl_base = nullptr;       // this search's control block (the lane's d_ctl or its twin)
   bool ctl_pre_cleared = false;      // ... whose first 64 bytes the previous search cleared

@@ -57,11 +57,8 @@ static int finish_pattern_list(sassy_SearcherType* s, const sassy_hip_Encoded* e
   std::string pool;
   uint32_t str_stride = 0;
   if (!wo) {
-    const uint64_t band = ((uint64_t)(m + 1) * (2ull * k + 3) + 3) / 4 * 4;
-    const uint64_t win = ((uint64_t)m + k + 15 + 15) / 16 * 16;
-    const uint64_t opsb = ((uint64_t)m + k + 1 + 3) / 4 * 4;
-    const uint64_t strb = ((2ull * (m + k + 1) + 2 + 15) / 16 * 16);
-    const uint64_t wstride = (band + win + opsb + strb + kTraceWaveDummy + 15) / 16 * 16;
+    const TraceShape ts = trace_shape(m, k);  // (the callers made sure of 2k + 3 <= 64: one-byte cells)
+    const uint64_t strb = ts.str;
     str_stride = (uint32_t)strb;
     if ((uint64_t)n_rep * strb > 0xFFFFFFFFull)
       return fail(SASSY_HIP_EUNSUPPORTED, "cigar pool of one result exceeds 4 GiB");
@@ -79,13 +76,13 @@ static int finish_pattern_list(sassy_SearcherType* s, const sassy_hip_Encoded* e
     T.profile = (uint32_t)s->profile;
     T.pattern = s->d_tiled_pat.p;
     T.pattern_stride = m;
-    T.scratch_stride = (uint32_t)wstride;
-    T.band_bytes = (uint32_t)band;
-    T.win_bytes = (uint32_t)win;
+    T.scratch_stride = (uint32_t)ts.wave_stride;
+    T.band_bytes = (uint32_t)ts.band;
+    T.win_bytes = (uint32_t)ts.win;
     T.out = LT.d_trace.p;
     T.out_str = LT.d_str.p;
     T.str_stride = str_stride;
-    T.ops_bytes = (uint32_t)opsb;
+    T.ops_bytes = (uint32_t)ts.ops;
     T.wave_mode = 1;
     T.count_min = 0;
     T.count_max = 0xFFFFFFFFu;
@@ -108,15 +105,11 @@ static int finish_pattern_list(sassy_SearcherType* s, const sassy_hip_Encoded* e
       const int env_tt = (int)s->sw.encoded_trace_threads;
       const bool env_off = env_tt == 0;
       const uint32_t from = env_tt > 0 ? (uint32_t)env_tt : 65536u;
-      uint64_t stride_t = band + win + opsb + strb;
-      if ((stride_t / 4) % 2 == 0) stride_t += 4;  // odd number of LDS words: conflict-free slices
-      const uint64_t pat_bytes = ((uint64_t)m + 15) / 16 * 16;
-      if (!env_off && k <= 6 && !T.use_alpha && n_rep >= from && 64 * stride_t + pat_bytes <= kTraceLdsLimit) {
+      if (!env_off && k <= 6 && !T.use_alpha && n_rep >= from && ts.thread_in_lds) {
         T.wave_mode = 0;
         T.scratch = nullptr;
-        T.scratch_stride = (uint32_t)stride_t;
-        const uint64_t nthreads = std::min<uint64_t>(256ull * 64ull * std::max<uint64_t>(1, (160ull * 1024) / (64 * stride_t + pat_bytes)), 131072);
-        trace_grid = (uint32_t)(nthreads / 64);
+        T.scratch_stride = (uint32_t)ts.thread_stride;
+        trace_grid = (uint32_t)(ts.thread_count / 64);
       }
     }
     le = launch_trace(T, trace_grid, st);

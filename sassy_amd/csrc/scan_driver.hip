@@ -1,5 +1,5 @@
 // scan_driver.hip -- one pattern over one buffer: the scan job (prepare / enqueue / finish: prefilter -> chunk DP -> rank ->
-// traceback on one lane), a search cut into sub-shards, the reference-lane mode, both strands, the report filters.
+// traceback on one lane), the reference-lane mode, both strands, the report filters.
 // Mirror of the reference's Searcher<P>::search path (src/search.rs:510-937).
 #include "host_internal.h"
 
@@ -47,6 +47,14 @@ static size_t plain_prefix(const uint8_t* pat, size_t m) {
   return j;
 }
 static bool plain_acgt(const uint8_t* pat, size_t m) { return plain_prefix(pat, m) == m; }
+// May this searcher take the paired filter for this pattern and k, and with which S and Q?  The part of the answer that
+// ScanJob::prepare() (one job's route) and search_text() (two strands as two searches) share; each adds what only it knows.
+// An Iupac searcher: the filter's 2 S Q rows are plain bases -- the rows behind them may hold ambiguity letters, a guide's NGG.
+static bool pair_eligible(const sassy_SearcherType* S, const uint8_t* pat, uint32_t m, uint32_t k, uint32_t* s_out, uint32_t* q_out) {
+  if (S->sw.pair == 0 || prefilter_mode(S) >= 0 || !pair_geometry(m, k, s_out, q_out)) return false;
+  if (S->profile == PROFILE_DNA) return true;
+  return S->profile == PROFILE_IUPAC && *s_out <= 3 && plain_prefix(pat, m) >= (size_t)2 * *s_out * *q_out;
+}
 
 
 // Bit table of every q-gram (2 bits per char, first piece row most significant; codes A0 C1 T2 G3)
@@ -262,17 +270,11 @@ int ScanJob::prepare() {
   }
   const uint32_t pieces = k + 1;
   // The fused launch (filter + chunk DP in one kernel, see below) takes one strand of one text whose reports the
-  // traceback waves rank themselves.  (trace_wave_ok mirrors use_wave of the traceback set-up further down.)
-  const int env_selfrank0 = (int)sw.self_rank, env_wave0 = (int)sw.trace_wave;
-  const bool trace_wave_ok = [&] {
-    const uint64_t cell = (k + 1 <= 255) ? 1 : 2;
-    const uint64_t band = ((uint64_t)(plan.m + 1) * (2ull * k + 3) * cell + 3) / 4 * 4;
-    const uint64_t raw = band + ((uint64_t)plan.m + k + 15 + 15) / 16 * 16 + ((uint64_t)plan.m + k + 1 + 3) / 4 * 4 +
-                         ((2ull * (plan.m + k + 1) + 2 + 15) / 16 * 16);
-    return env_wave0 != 0 && 2ull * k + 3 <= 64 && 4 * (((uint64_t)plan.m + 15) / 16 * 16) + 4 * ((raw + 15) / 16 * 16) <= 160 * 1024;
-  }();
+  // traceback waves rank themselves: the wave-per-report traceback must be this job's (use_wave).
+  const TraceShape ts = trace_shape(plan.m, k);
+  use_wave = do_trace && sw.trace_wave != 0 && ts.wave_fits;
   const bool fuse_ok = !ext_bitmap && !ext_desc && rc_bitmap == nullptr && rev_n == 0 && S->fuse && !no_fuse &&
-                       L.fuse_backoff == 0 && env_selfrank0 != 0 && do_trace && trace_wave_ok &&
+                       L.fuse_backoff == 0 && sw.self_rank != 0 && use_wave &&
                        texts.n == 0 && plan.nwords <= 8 && n_blocks < 0x7FFFFFFFull && !S->want_counters;
   // Iupac searcher, pattern of plain A C G T, <= 4 pieces: the Dna bit-plane filter with a check of the text
   // (filter_dna_kernel, CHECK) -- as the fused launch only.  Where the text holds other letters (N runs, ambiguity codes,
@@ -303,15 +305,12 @@ int ScanJob::prepare() {
   // q-gram counting filter keeps the shapes it is selective for.
   const int env_pair = (int)sw.pair;
   uint32_t pair_s = 0, pair_q = 0;
-  const bool pair_ok = env_pair != 0 && q == 0 && env_pre < 0 && fuse_ok && !overhang && !ext_bitmap && !ext_desc && !plan.bytes &&
-                       pair_geometry(plan.m, k, &pair_s, &pair_q) &&
-                       // (an Iupac searcher: the filter's 2 S Q rows are plain bases -- the rows behind them may hold
-                       // ambiguity letters, a guide's NGG: the chunk DP then builds up to eight slot masks)
-                       (S->profile == PROFILE_DNA ||
-                        (S->profile == PROFILE_IUPAC && env_iupac_planes != 0 && pair_s <= 3 &&
-                         plain_prefix(pat, plan.m) >= (size_t)2 * pair_s * pair_q &&
-                         (plan.nslots <= 4 || (plan.nslots <= 8 && plan.nwords <= 4)))) &&
-                       (env_kind == 0 || env_kind == kFilterPlanes);
+  // (this side only, search_text() does not ask: an Iupac searcher's launch is the bit-plane launch with the text check
+  // (switch iupac_planes), and its chunk DP builds up to eight slot masks for the rows behind the plain prefix)
+  const bool pair_iupac_dp_ok = S->profile != PROFILE_IUPAC ||
+                                (env_iupac_planes != 0 && (plan.nslots <= 4 || (plan.nslots <= 8 && plan.nwords <= 4)));
+  const bool pair_ok = pair_eligible(S, pat, plan.m, k, &pair_s, &pair_q) && pair_iupac_dp_ok && q == 0 && fuse_ok && !overhang &&
+                       !ext_bitmap && !ext_desc && !plan.bytes && (env_kind == 0 || env_kind == kFilterPlanes);
   pair = 0;
   // q-gram counting (count_filter.hip): per (Q, R) variant the threshold t = m + 1 - (k+1) Q, the
   // window W, and how often a window of random text reaches t by chance (the pattern's q-grams,
@@ -492,41 +491,28 @@ int ScanJob::prepare() {
   T = TraceParams{};
   Tw = TraceParams{};
   trace_blocks = wave_blocks = 0;
-  use_wave = use_thread = false;
-  if (do_trace) {
-    const uint64_t cell = (k + 1 <= 255) ? 1 : 2;
-    const uint64_t band = ((uint64_t)(plan.m + 1) * (2ull * k + 3) * cell + 3) / 4 * 4;
-    const uint64_t win = ((uint64_t)plan.m + k + 15 + 15) / 16 * 16;  // whole 16-byte chunks
-    const uint64_t opsb = ((uint64_t)plan.m + k + 1 + 3) / 4 * 4;
-    const uint64_t strb = ((2ull * (plan.m + k + 1) + 2 + 15) / 16 * 16);  // = T.str_stride
-    const uint64_t raw = band + win + opsb + strb;
-    const uint64_t pat_bytes = ((uint64_t)plan.m + 15) / 16 * 16;
-    const int env_wave = (int)sw.trace_wave;
-    // (+ 128: a byte pair per lane behind the slice -- the band rows' lanes outside the band store there, unmasked)
-    const uint64_t wstride = (raw + kTraceWaveDummy + 15) / 16 * 16;
-    use_wave = env_wave != 0 && 2ull * k + 3 <= 64 && 4 * pat_bytes + 4 * wstride <= 160 * 1024;
+  use_thread = false;
+  if (do_trace) {  // (use_wave: decided with the shape, in front of the route choice)
     use_thread = !use_wave || (k <= 6 && !overhang);  // overhang: wave shape or the generic thread shape
-    uint64_t stride = raw;
-    if ((stride / 4) % 2 == 0) stride += 4;  // odd number of LDS words: conflict-free slices
+    const uint64_t stride = ts.thread_stride;
     if (stride > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "pattern/k too large for the traceback band");
     if (use_thread) {
       // Threads of the thread-per-report launch.  With the slices in LDS (64 per workgroup) as many workgroups as the chip
       // holds at once -- a dense result (10^5 .. 10^6 reports) is bound by how many reports are in flight: 16 384 threads
       // were one wave on a quarter of the SIMDs, 2.3 ms for 743 000 reports.  Slices in global memory: 256 MB of them.
       const int env_tt = (int)sw.trace_threads;
-      const bool slices_in_lds = 64 * stride + pat_bytes <= kTraceLdsLimit;
+      const bool slices_in_lds = ts.thread_in_lds;
       uint64_t nthreads = (256ull << 20) / stride;
-      uint64_t cap_threads = 16384;
-      if (slices_in_lds) cap_threads = std::min<uint64_t>(256ull * 64ull * std::max<uint64_t>(1, (160ull * 1024) / (64 * stride + pat_bytes)), 131072);
+      uint64_t cap_threads = slices_in_lds ? ts.thread_count : 16384;
       if (env_tt >= 64) cap_threads = (uint64_t)env_tt;
       nthreads = std::max<uint64_t>(64, std::min<uint64_t>(cap_threads, slices_in_lds ? cap_threads : nthreads)) / 64 * 64;
       trace_blocks = (uint32_t)(nthreads / 64);
-      if (64 * stride + pat_bytes > kTraceLdsLimit)  // slices in global memory
+      if (!slices_in_lds)  // slices in global memory
         if (int rc = L.d_scratch.reserve(nthreads * stride)) return rc;
     }
     wave_blocks = 1024;  // 4096 wavefronts, grid-stride over the reports
-    T.band_bytes = (uint32_t)band;
-    T.win_bytes = (uint32_t)win;
+    T.band_bytes = (uint32_t)ts.band;
+    T.win_bytes = (uint32_t)ts.win;
     T.text = sh.d_text;
     T.rev_n = rev_n;
     T.global_offset = sh.global_offset;
@@ -538,8 +524,8 @@ int ScanJob::prepare() {
     T.pattern = L.d_pattern.p;
     T.scratch = L.d_scratch.p;
     T.scratch_stride = (uint32_t)stride;
-    T.str_stride = (2 * (plan.m + k + 1) + 2 + 15) / 16 * 16;
-    T.ops_bytes = (uint32_t)opsb;
+    T.str_stride = (uint32_t)ts.str;
+    T.ops_bytes = (uint32_t)ts.ops;
     T.use_alpha = overhang ? 1u : 0u;
     T.alpha = overhang ? S->alpha : 0.0f;
     T.max_overhang = S->max_overhang >= 0 ? (uint32_t)std::min<long>(S->max_overhang, 0x7FFFFFFF) : 0xFFFFFFFFu;
@@ -548,14 +534,14 @@ int ScanJob::prepare() {
     T.count_max = 0xFFFFFFFFu;
     Tw = T;
     Tw.wave_mode = 1;
-    Tw.scratch_stride = (uint32_t)wstride;
+    Tw.scratch_stride = (uint32_t)ts.wave_stride;
     Tw.count_min = 0;
     Tw.count_max = use_thread ? kTraceWaveMax : 0xFFFFFFFFu;
   }
 
   // ---- one launch for filter + chunk DP?  (bit-plane filter, one strand, one text, reports ranked by the
   // traceback waves themselves; the chunk DP's masks and carries must fit the filter's 8 KiB tile)
-  fused = filtered && fkind == kFilterPlanes && fuse_ok && use_wave;
+  fused = filtered && fkind == kFilterPlanes && fuse_ok;
   if (S->profile == PROFILE_IUPAC && fkind == kFilterPlanes && !fused && !ext_bitmap && !ext_desc)
     return fail(SASSY_HIP_EUNSUPPORTED, "internal: the Iupac bit-plane filter exists as the fused launch only");
   if (L.fuse_backoff && !no_fuse) --L.fuse_backoff;
@@ -787,9 +773,6 @@ int ScanJob::enqueue(int attempt) {
   ctl_pre_cleared = false;
   wait_ev_done = false;
   if (ext_wait && attempt == 0) HIP_TRY(hipStreamWaitEvent(L.stream, ext_wait, 0));
-  // pipelined sub-shards: this lane's filter starts when the previous sub-shard's filter is done,
-  // so that the previous lane's DP / rank / traceback kernels overlap this bandwidth-bound one
-  if (wait_for && attempt == 0) HIP_TRY(hipStreamWaitEvent(L.stream, wait_for, 0));
   // (a job that only consumes a bitmap has no filter to time: no events at level 1, each costs ~6 us of stream idle)
   const bool time_head = timing >= 2 || (timing == 1 && !ext_bitmap);
   // (the fused launch carries its events itself: LaunchEvents; a member of another job's pass times it with its own two
@@ -1493,11 +1476,9 @@ int ScanJob::finish_once(ScanOut& out, bool& redo) {
 }
 
 // One buffer on the searcher's first lane: prepare, queue, wait.
-static int run_scan_single(sassy_SearcherType* S, const ShardView& sh, const PatternPlan& plan, uint32_t k,
-                           bool all_minima, const uint8_t* pat, bool do_trace, uint64_t total_len, ScanOut& out,
-                           const TextTable& texts = TextTable{}) {
+int run_scan(sassy_SearcherType* S, const ShardView& sh, const PatternPlan& plan, uint32_t k,
+             bool all_minima, const uint8_t* pat, bool do_trace, uint64_t total_len, ScanOut& out) {
   ScanJob job(S, S->lanes[0], sh, plan, k, all_minima, pat, do_trace, total_len);
-  job.texts = texts;
   job.texts.all_minima = all_minima ? 1u : 0u;
   if (int rc = job.prepare()) return rc;
   if (!job.empty)
@@ -1510,102 +1491,6 @@ uint64_t required_halo_bytes(size_t pattern_len, size_t k) {
   const uint64_t wb = warmup_blocks((uint32_t)pattern_len, (uint32_t)k);
   uint64_t h = std::max<uint64_t>(64 * (wb + 4), pattern_len + k);
   return (h + 127) / 128 * 128;
-}
-
-// Optional (SASSY_HIP_LANES=2..4; default 1 = off): long buffers are cut into sub-shards, one per
-// lane.  The prefilter of sub-shard j+1 waits for the prefilter of sub-shard j (they would only
-// share the HBM bandwidth), so that the chunk list / DP / rank / traceback kernels of sub-shard j --
-// short, latency-bound, few waves -- could run underneath the next prefilter instead of after it.
-// The sub-shards are exact shards (halo to the left, seam protocol of DESIGN.md 5.1); their results
-// are concatenated with the plateau state handed from one to the next (parity-tested with
-// SASSY_HIP_SUBSHARD_MIN=2048).  Measured on MI355X (config 2): 0.81 ms with 1 lane, 0.97 / 1.00 /
-// 1.22 ms with 2 / 3 / 4 lanes -- the prefilter's long-lived workgroups fill every CU, so the
-// other queue's small kernels do not get scheduled underneath it and the extra launches only add
-// time.  Hence off by default; the lanes stay as the unit a future scheduler can build on.
-int run_scan(sassy_SearcherType* S, const ShardView& sh, const PatternPlan& plan, uint32_t k,
-                    bool all_minima, const uint8_t* pat, bool do_trace, uint64_t total_len, ScanOut& out) {
-  const int env_lanes = (int)S->sw.lanes;
-  const uint64_t min_sub = (uint64_t)std::max<long>(1, S->sw.subshard_min);
-  const uint64_t halo = required_halo_bytes(plan.m, k);
-  const uint64_t own0 = sh.halo_len;
-  const uint64_t owned_bytes = sh.text_len > own0 ? sh.text_len - own0 : 0;
-  uint64_t nl = std::min<uint64_t>(std::min<int>(env_lanes, kMaxLanes), owned_bytes / std::max<uint64_t>(min_sub, 2 * halo + 64));
-  if (nl < 2 || filter_piece_len(plan, k, S) == 0)
-    return run_scan_single(S, sh, plan, k, all_minima, pat, do_trace, total_len, out);
-
-  const uint64_t owned_blocks = (owned_bytes + 63) / 64;
-  const uint64_t per = (owned_blocks + nl - 1) / nl;  // blocks per sub-shard
-  std::vector<std::unique_ptr<ScanJob>> jobs;
-  for (uint64_t j = 0; j < nl; ++j) {
-    const uint64_t a = own0 + j * per * 64;
-    if (a >= sh.text_len) break;
-    const uint64_t b = std::min<uint64_t>(sh.text_len, a + per * 64);
-    const uint64_t h = j == 0 ? own0 : halo;
-    ShardView sub{sh.d_text + (a - h), h + (b - a), h, sh.global_offset + (a - h), j == 0 && sh.text_start,
-                  b == sh.text_len && sh.text_end};
-    jobs.emplace_back(new ScanJob(S, S->lanes[j], sub, plan, k, all_minima, pat, do_trace, total_len));
-  }
-  const size_t n = jobs.size();
-  for (size_t j = 0; j < n; ++j) {
-    ScanJob& job = *jobs[j];
-    if (j == 1) {
-      // the uploads prepare() of sub-shard 0 queued on the searcher's stream must be done before any
-      // other lane reads the pattern tables (and the text, if this call uploaded it)
-      HIP_TRY(hipEventRecord(S->ev_inputs, S->stream));
-    }
-    if (j >= 1) HIP_TRY(hipStreamWaitEvent(S->lanes[j].stream, S->ev_inputs, 0));
-    if (int rc = job.prepare()) return rc;
-    job.wait_for = j >= 1 ? S->lanes[j - 1].ev_filter_done : nullptr;
-    job.signal_filter_done = j + 1 < n;
-    if (!job.empty)
-      if (int rc = job.enqueue(0)) return rc;
-  }
-  std::vector<ScanOut> outs(n);
-  int first_rc = 0;
-  for (size_t j = 0; j < n; ++j) {  // always wait for every lane, also after an error
-    const int rc = jobs[j]->finish(outs[j]);
-    if (rc && !first_rc) first_rc = rc;
-  }
-  if (first_rc) {
-    for (size_t j = 0; j < n; ++j) (void)hipStreamSynchronize(S->lanes[j].stream);
-    return first_rc;
-  }
-
-  // ---- concatenate, handing the plateau state across the sub-shard seams ----
-  out = ScanOut();
-  size_t total = 0;
-  for (const ScanOut& o : outs) total += o.cands.size();
-  out.cands.reserve(total);
-  if (do_trace) out.matches.reserve(total);
-  int incoming = sh.text_start ? kStateDecTrue : kStatePass;  // decreasing-state arriving at sub-shard j
-  for (size_t j = 0; j < n; ++j) {
-    ScanOut& o = outs[j];
-    const size_t base = out.pool.size();
-    if (base + o.pool.size() > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "cigar pool of one result exceeds 4 GiB");
-    out.pool.append(o.pool);
-    for (size_t i = 0; i < o.cands.size(); ++i) {
-      Candidate c = o.cands[i];
-      if ((int64_t)i == o.conditional_index) {
-        if (incoming == kStateDecFalse) continue;  // its plateau was entered by an increase: not a report
-        if (incoming == kStateDecTrue) c.flags &= ~kCandCond;
-        else {
-          if (out.conditional_index >= 0)  // two reports that depend on the previous shard: give up pipelining
-            return run_scan_single(S, sh, plan, k, all_minima, pat, do_trace, total_len, out);
-          out.conditional_index = (int64_t)out.cands.size();
-        }
-      }
-      out.cands.push_back(c);
-      if (do_trace) {
-        sassy_hip_Match r = o.matches[i];
-        r.cigar_off = (uint32_t)(r.cigar_off + base);
-        out.matches.push_back(r);
-      }
-    }
-    out.cond_seen += o.cond_seen;
-    if (o.exit_state != kStatePass) incoming = o.exit_state;
-  }
-  out.exit_state = incoming;
-  return 0;
 }
 
 // The reference's lane reports (opt-in: sassy_hip_set_reference_lanes / SASSY_HIP_REF_LANES = 4 | 8).
@@ -1955,11 +1840,8 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
   // SASSY_HIP_PAIR_RC=0: as before.
   const int env_pair_rc = (int)S->sw.pair_rc;
   uint32_t ps_ = 0, pq_ = 0;
-  const bool pair_strands = env_pair_rc != 0 && S->sw.pair != 0 && prefilter_mode(S) < 0 && S->fuse && !wo && k <= 0xFFFFu &&
-                            pair_geometry(plan.m, (uint32_t)k, &ps_, &pq_) &&
-                            (S->profile == PROFILE_DNA ||
-                             (S->profile == PROFILE_IUPAC && ps_ <= 3 && pair_geometry(plan.m, (uint32_t)k, &ps_, &pq_) &&
-                              plain_prefix(pattern, plen) >= (size_t)2 * ps_ * pq_));
+  const bool pair_strands = env_pair_rc != 0 && S->fuse && !wo && k <= 0xFFFFu &&
+                            pair_eligible(S, pattern, plan.m, (uint32_t)k, &ps_, &pq_);
   const bool can_fuse = fwd_strand && rc_strand && env_fuse != 0 && !ef.fn && std::isnan(S->max_n_frac) &&
                         std::isnan(S->alpha) && S->profile != PROFILE_ASCII && ref_lanes == 0 && !pair_strands;
   bool rc_by_bitmap = false;
@@ -1969,8 +1851,7 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
   // strand's chunk DP tail and traceback run under the Rc strand's filter (m = 23, k = 3: 1.32 -> 1.1x ms).
   // SASSY_HIP_STRANDS_IN_FLIGHT=0: one after the other.
   const bool env_two = S->sw.strands_in_flight != 0;
-  const bool env_one_lane = S->sw.lanes <= 1;
-  if (fwd_strand && rc_strand && !can_fuse && env_two && env_one_lane && ref_lanes == 0 && !ef.fn && std::isnan(S->alpha) &&
+  if (fwd_strand && rc_strand && !can_fuse && env_two && ref_lanes == 0 && !ef.fn && std::isnan(S->alpha) &&
       S->profile != PROFILE_ASCII) {
     const bool reuse = on_dev && (flags & SASSY_HIP_TEXT_UNCHANGED) && S->rev_src == d_fwd && S->rev_len == tlen &&
                        S->d_rev.p != nullptr;

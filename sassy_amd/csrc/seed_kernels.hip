@@ -22,7 +22,7 @@
 //            for nothing -- the hits of a wave are consumed where they are found, the text around them still in L2.)
 //   the list holds ALL positions with cost <= k (some twice: a match seen through two pieces), which is what the
 //   report rule needs: sort, drop duplicates, flag the reports per run (sort_kernels.hip), trace them
-//   (trace_wave_kernel) -- the tail of the pattern-tiled search (host.hip: finish_pattern_list).
+//   (trace_wave_kernel) -- the tail of the pattern-tiled search (many_patterns.hip: finish_pattern_list).
 //
 // Cost at config 4: 3.7 table hits per text position, 162 VALU per 64 hits -- the test 84, queueing 30,
 // verification 26 (4 % of the hits pass), table look-ups 11, the passed queue 8 -- at 0.83 of the VALU issue rate; never
@@ -144,7 +144,7 @@ __device__ __forceinline__ bool test_finish(const SeedParams& P, const uint32_t*
 #pragma unroll
   for (uint32_t u = 0; u < 8; ++u) {
     if (u <= k) {
-      // row fields (host.hip): 2a | (32 - 2 len) << 8 | 2 (off & 15) << 16 | (off >> 4) << 24
+      // row fields (many_patterns.hip: seed_test_rows): 2a | (32 - 2 len) << 8 | 2 (off & 15) << 16 | (off >> 4) << 24
       const uint32_t want = (uint32_t)(pp >> (ent[u] & 0xFFu));
       uint32_t mask = 0xFFFFFFFFu >> ((ent[u] >> 8) & 0xFFu);
       if (MODE >= 3) mask &= (uint32_t)(care >> (ent[u] & 0xFFu));
@@ -531,7 +531,7 @@ __global__ __launch_bounds__(256) void seed_search_kernel(const SeedParams P) {
 // ---------------------------------------------------------------- texts with other letters than ACGT (Iupac searcher)
 // The seeded search reads Dna codes, so it is exact only where the m + k characters in front of an end position are
 // plain.  Around every run of other letters ("dirty": N, R, Y, ..., non-letters) the end positions are computed by
-// the pattern-tiled scan on a gathered copy of those neighbourhoods instead (host.hip: search_encoded_seeded):
+// the pattern-tiled scan on a gathered copy of those neighbourhoods instead (many_patterns.hip: search_encoded_seeded):
 //   dirty_scan_kernel      finds the runs: their first positions, their end positions, and the positions of dirty
 //                          letters that are not full wildcards (a run of full wildcards -- N, non-letters -- longer
 //                          than m + 1 is cut out of the gathered copy: every pattern's cost is constant inside);

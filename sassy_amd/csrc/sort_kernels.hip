@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void assign_texts_kernel(Candidate* __restrict
 }
 
 // ---- search_many over a batch of texts, both strands: the records of the two strands' passes into result order ----
-// (host.hip: assemble_many).  The result order is the one a stable sort by (pattern, text) of [forward records, Rc
+// (many_patterns.hip: assemble_many).  The result order is the one a stable sort by (pattern, text) of [forward records, Rc
 // records] gives; the Rc pass saw the batch reversed: text r of its buffer is text n_texts - 1 - r, and its
 // coordinates count from the text's end (src/search.rs:859-873).
 // (flip: the Rc pass saw the batch reversed AS A WHOLE -- its text r is text n_texts - 1 - r; else every text was reversed
@@ -411,7 +411,7 @@ hipError_t launch_assign_texts(Candidate* d_rep, uint32_t count, const TextTable
 }
 
 
-// ---- host.hip: finish_pattern_list, dense results of search_encoded ----
+// ---- many_patterns.hip: finish_pattern_list, dense results of search_encoded ----
 // The rows of a one-pass search of many patterns as the traceback left them (pattern_idx = the rc-expanded pattern, in
 // (pattern, end position) order) -> the records of the result in the order sassy_hip_search_encoded documents and its host
 // path sorts into: (pattern_idx mod P, text_start, text_end, cost, strand) -- the key the reference's own differential
@@ -522,7 +522,7 @@ hipError_t launch_assemble_encoded(const MatchOut* d_rows_in, const char* d_strs
   return hipGetLastError();
 }
 
-// ---- host.hip: ScanJob::finish, dense results of one pattern ----
+// ---- scan_driver.hip: ScanJob::finish, dense results of one pattern ----
 // The cigar strings of rows[0 .. *count_ptr) out of their slots (str_stride bytes each: 2 (m + k + 1) + 2 rounded up, a
 // dozen of them used) into one pool without the padding; the rows learn their new offsets; total[0] = the pool's bytes.
 // A dense result's strings were 60 of the 108 MB that crossed the PCIe link for 743 000 matches.
@@ -580,7 +580,7 @@ hipError_t launch_compact_cigars(MatchOut* d_rows, const char* d_strs, uint32_t 
   return hipGetLastError();
 }
 
-// ---- host.hip: assemble_many ----
+// ---- many_patterns.hip: assemble_many ----
 size_t many_scratch_bytes(uint32_t count) {
   size_t temp = 0;
   (void)rocprim::radix_sort_pairs(nullptr, temp, static_cast<unsigned long long*>(nullptr),

@@ -37,8 +37,6 @@ namespace sassy_hip {
   X(big_pin, 1, "0: dense results through the host's vectors instead of one pinned block")                                  \
   X(compact_cigars, 1, "0: dense results keep their cigar slots' padding")                                                  \
   X(adopt, 1, "0: results are copied out of the pinned block the kernels wrote them into")                                  \
-  X(lanes, 1, "2 .. 4: one search cut into sub-shards on that many streams")                                                \
-  X(subshard_min, 128 << 20, "smallest sub-shard in bytes for lanes > 1")                                                   \
   X(rc_fused, 1, "0: the Rc strand from a reversed copy instead of Rc marks made by the forward pass")                      \
   X(strands_in_flight, 1, "0: two strands that are two searches run one after the other")                                   \
   X(encoded_trace_threads, -1, "search_encoded: threads of the dense traceback launch (-1: by result size)")                \

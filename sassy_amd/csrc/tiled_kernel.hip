@@ -12,7 +12,7 @@
 // column (Vp = 1^m, cost = m) -- after m + k characters every value <= k is exact -- and owns
 // the end positions inside its chunk.  Runs of positions <= k are complete in the candidate list whatever the
 // chunking (chunks own disjoint position ranges), so the host applies the report rule to each run exactly, with
-// no seam bookkeeping (host.hip: search_encoded_tiled).
+// no seam bookkeeping (many_patterns.hip: search_encoded_tiled).
 //
 // Used where the pigeonhole prefilter path (filter_dna_multi_kernel: one pass per 64 patterns at HBM speed plus
 // chains per pattern) does not apply or is launch-bound: many patterns on short / medium texts, texts with

@@ -32,7 +32,7 @@ HEAD_WORDS = 4   # rows, exit state, conditional index, error flag
 
 def cigar_bytes_for(pattern_len: int, k: int) -> int:
     """Width of the cigar field that holds every cigar a search with this (m, k) can produce: the
-    device's string slot 2 (m + k + 1) + 2 (host.hip: T.str_stride), in whole 8-byte words."""
+    device's string slot 2 (m + k + 1) + 2 (host_internal.h: TraceShape::str, what T.str_stride is set from), in whole 8-byte words."""
     return (2 * (pattern_len + k + 1) + 2 + 7) // 8 * 8
 
 

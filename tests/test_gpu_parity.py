@@ -596,7 +596,7 @@ def test_cli_search_tsv(sassy, tmp_path, capsys):
 
 
 def test_batched_texts(sassy):
-    """Many short texts go through ONE buffer with 'X' separators (host.hip: search_many_batched).
+    """Many short texts go through ONE buffer with 'X' separators (many_patterns.hip: search_many_batched).
     Every (pattern, text) pair must equal the independent search: matches cut by the text end
     (end-of-text rule -> a plateau that runs into the separator), matches at the text start, empty
     and tiny texts, search_all, without_trace, only_best_match, max_n_frac, both strands."""
@@ -1006,8 +1006,8 @@ def test_encoded_pattern_tiled(sassy):
 
 def test_seeded_test_geometry_sweep(sassy):
     """The sub-piece test in front of the seeded search's verification reads ONE text window for all pieces, laid out from
-    the pattern's shape (host.hip: reach, win_left, offsets within 48 characters, lengths capped by the shifts;
-    seed_kernels.hip: test_issue / test_finish).  A wrong offset shows as a LOST match, so: every pattern length 8 .. 32
+    the pattern's shape (many_patterns.hip, seed_test_rows: reach, win_left, offsets within 48 characters, lengths capped by
+    the shifts; seed_kernels.hip: test_issue / test_finish).  A wrong offset shows as a LOST match, so: every pattern length 8 .. 32
     with every k the path takes, matches planted with exactly k edits (substitutions, insertions and deletions at random
     rows: next to the seed, at sub-piece borders, at the pattern's ends), plain patterns and patterns with ambiguity
     letters (care words), against the oracle."""
@@ -1375,7 +1375,7 @@ def test_pack_result_for_gather(sassy):
 
 
 def test_per_text_lanes(sassy):
-    """search_many in "one lane per text" mode (host.hip: search_many_pertext): overhang searches,
+    """search_many in "one lane per text" mode (many_patterns.hip: search_many_pertext): overhang searches,
     the Ascii profile and unfilterable patterns over many short texts must equal the pair-by-pair
     searches -- incl. overhang at every text's own start and end."""
     rng = random.Random(808)
@@ -2017,7 +2017,7 @@ def test_dna_profile_text_with_other_letters(sassy):
 def test_search_many_pattern_tiled(sassy):
     """search_many with patterns of one length through the one-pass kernels over the whole batch of texts --
     the pattern-tiled scan (SASSY_HIP_MANY_TILED=1) and, for plain-ACGT patterns and texts, the seeded search
-    (SASSY_HIP_MANY_SEEDED=1; host.hip: search_many_batched + finish_pattern_list with text tables) -- against
+    (SASSY_HIP_MANY_SEEDED=1; many_patterns.hip: search_many_batched + finish_pattern_list with text tables) -- against
     one oracle search per (pattern, text) pair: both strands (the Rc strand runs complement(pattern) over the
     reversed batch, coordinates mapped back), matches at the first and last characters of a text, empty and
     one-character texts, search_all (reports inside separators are dropped, else moved to the text end)."""
@@ -2061,7 +2061,7 @@ def test_search_many_pattern_tiled(sassy):
                     assert gk == sorted(wk), (mode, profile, m, k, npat, allm, rc, len(gk), len(wk))
                     assert len(wk) >= 15
                     if not allm:
-                        # the records were put in result order on the device (host.hip: assemble_many): the same
+                        # the records were put in result order on the device (many_patterns.hip: assemble_many): the same
                         # records in the same order as the host's way (per-strand copies, append, stable sort)
                         s.set_option("many_assemble", 0)
                         try:
@@ -2480,7 +2480,7 @@ def _env_allows_fusing():
     """False in the forced-path processes whose switches take the fused launch out of the picture."""
     e = os.environ
     return not (e.get("SASSY_HIP_FUSED") == "0" or e.get("SASSY_HIP_PREFILTER") == "0" or e.get("SASSY_HIP_FILTER_KIND", "2") != "2" or
-                e.get("SASSY_HIP_SELF_RANK") == "0" or e.get("SASSY_HIP_TRACE_WAVE") == "0" or e.get("SASSY_HIP_LANES"))
+                e.get("SASSY_HIP_SELF_RANK") == "0" or e.get("SASSY_HIP_TRACE_WAVE") == "0")
 
 
 def test_fused_filter_equals_classic_chain_and_oracle(sassy):
@@ -2711,7 +2711,7 @@ _PAIR_SHAPES = [(23, 3), (20, 3), (24, 3), (27, 3), (32, 4), (34, 4), (32, 5), (
 
 
 def _pair_geometry(m, k):
-    """(super-pieces S, rows per sub-piece Q) of the paired filter for a shape (host.hip: pair_s / pair_q)."""
+    """(super-pieces S, rows per sub-piece Q) of the paired filter for a shape (scan_driver.hip: pair_geometry)."""
     s_ = (k + 2) // 2
     return s_, m // (2 * s_)
 
@@ -2882,7 +2882,6 @@ _FORCED = [
     {"SASSY_HIP_SELF_RANK": "0"},                    # rank_count / rank_scatter kernels
     {"SASSY_HIP_RC_FUSED": "0"},                     # Rc strand from a reversed copy
     {"SASSY_HIP_LIST_WORDS": "0"},                   # multi-word chunk DP by the lane-per-chunk kernel
-    {"SASSY_HIP_LANES": "3", "SASSY_HIP_SUBSHARD_MIN": "2048"},  # one search cut into sub-shards on several streams
     {"SASSY_HIP_IUPAC_PLANES": "0"},                 # Iupac searches with plain patterns through the Iupac chain only
     {"SASSY_HIP_FILTER_KIND": "4", "SASSY_HIP_COUNT_WPG": "4"},  # the counting filter with four waves per workgroup
     {"SASSY_HIP_BIG_PIN": "0", "SASSY_HIP_SHORT_PIECES": "0"},   # dense results through the host's vectors; no 5- / 6-row pieces

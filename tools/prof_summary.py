@@ -21,7 +21,7 @@ for f in find("*kernel_stats.csv"):
             print(f"{name:60s} calls={row.get('Calls')} avg_ns={row.get('AverageNs')} "
                   f"min_ns={row.get('MinNs')} max_ns={row.get('MaxNs')} pct={row.get('Percentage')}")
 
-# The first ~36 searches of the run are the library's geometry trials (host.hip: GeoTuner) and the very first call
+# The first ~36 searches of the run are the library's geometry trials (host_internal.h: GeoTuner) and the very first call
 # is cold: the steady state is the LAST 100 dispatches of every kernel, from the kernel trace of the same run.
 print("== steady state: the last 100 dispatches of each kernel (same run, kernel trace) ==")
 for f in find("*kernel_trace.csv"):
