@@ -75,7 +75,8 @@ typedef struct sassy_hip_Stats {
                             3: q-gram piece table (filter_table_kernel); 4: q-gram counting (filter_count_kernel);
                             5: the pattern-tiled scan of search_encoded (tiled_kernel: all patterns in one pass);
                             6: the seeded search of search_encoded (seed_kernels: seed table lookups, one lane per hit) */
-  double filter_ms;      /* HIP-event time of the prefilter kernel (part of scan_ms) */
+  double filter_ms;      /* HIP-event time of the prefilter kernel (part of scan_ms); a search in flight whose text pass
+                            was served by several launches (see pass_patterns): the sum of their durations */
   uint64_t hit_blocks;   /* text blocks in which an exact pattern piece ends */
   uint32_t piece_len;    /* rows per pattern piece (k+1 pieces) / q-gram length Q (filtered = 4), 0 when unfiltered */
   uint32_t fused;        /* 1: the bit-plane prefilter ran the chunk DP of what it found itself (one launch for
@@ -87,8 +88,8 @@ typedef struct sassy_hip_Stats {
                              walked column by column (0 unless counters are enabled) */
   uint32_t pair;          /* != 0: the fused launch ran the PAIRED filter with this many super-pieces of 2 * piece_len
                              rows (one half exact, the other half with <= 1 edit next to it; SASSY_HIP_PAIR=0: never) */
-  uint32_t pass_patterns; /* searches the text pass of this search served: 2 when a search in flight shared it
-                             (sassy_hip_search_shard_begin), else 1 */
+  uint32_t pass_patterns; /* the largest number of searches a launch of this search's text pass served: 2 when a search
+                             in flight shared one of them (sassy_hip_search_shard_begin), else 1 */
 } sassy_hip_Stats;
 
 const char *sassy_hip_last_error(void);
@@ -254,12 +255,15 @@ uint64_t sassy_hip_required_halo(size_t pattern_len, size_t k);
  * search i (chunk list, chunk DP, traceback) then runs underneath the bandwidth-bound prefilter of search
  * i+1.  The pattern is copied; the text must stay valid and unchanged until the ticket is finished.  Every
  * ticket must be finished before the searcher is freed (tickets still open then are dropped).
- * Searches in flight may share one text pass: a Dna forward search on the fused bit-plane path that is begun while
- * the searcher's previous pass still streams waits for a second such search over the same buffer (same d_text,
- * halo_len, shard_len, global_offset, total_len, flags and piece length, at most 8 pieces together), and one launch
- * filters the text for both (sassy_hip_Stats.pass_patterns = 2).  A waiting search is launched when its group is
- * full, when a begin finds no pass streaming, before any other kind of search is begun, and when its own ticket is
- * finished -- no ticket waits on a launch that only a later call would make.  Results are unchanged; SASSY_HIP_SHARED_PASS=0
+ * Searches in flight may share their text pass: a Dna forward search on the fused bit-plane path can be served together
+ * with a second such search over the same buffer (same d_text, halo_len, shard_len, global_offset, total_len, flags
+ * and piece length, at most 8 pieces together) by one launch that filters the text for both
+ * (sassy_hip_Stats.pass_patterns = 2).  The pass of such a search is cut in two halves of its grid: a begin launches the
+ * previous search's second half together with this search's first half, so a search is complete one begin after its
+ * own and a launch is always queued behind the running one.  A search that finds neither a partner nor a pass
+ * streaming is launched whole; a search that cannot share is begun behind what the open ones still need; finish
+ * launches what its own ticket still needs -- no ticket waits on a launch that only a later call would make.
+ * Results are unchanged; SASSY_HIP_SHARED_PASS=0
  * (sassy_hip_set_option "shared_pass") turns it off.  The calls of
  * one searcher must still come from one thread at a time.  sassy_hip_get_stats describes the search finished last.
  * While a ticket is open the searcher's synchronous entry points (sassy_hip_search, _search_shard, _search_many,

@@ -39,7 +39,7 @@ UNITS = [
     ("all_alignments.hip", "all_alignments.o", []),
     ("c_abi.hip", "c_abi.o", []),
 ]
-HEADERS = ["common.h", "profiles.h", "tiled_step.h", "switches.h", "host_internal.h", os.path.join("..", "..", "include", "sassy.h"),
+HEADERS = ["common.h", "profiles.h", "tiled_step.h", "switches.h", "pass_planner.h", "host_internal.h", os.path.join("..", "..", "include", "sassy.h"),
            os.path.join("..", "..", "include", "sassy_hip.h")]
 
 

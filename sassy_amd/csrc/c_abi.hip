@@ -515,18 +515,25 @@ int sassy_hip_merge_shards(const sassy_hip_Result* const* results, size_t n, int
 
 }  // extern "C"
 
-// ---- shared pass: searches in flight over one buffer filtered by one launch ----
-// A searcher has at most one OPEN GROUP: begun tickets whose pass is not launched yet (at most two: the grouped launch,
-// filter_dna_kernel<.., G = 2>, has two members).  A groupable ticket (ScanJob::group_ok) that is begun while the
-// searcher's last pass still streams waits there for a second one (ScanJob::group_fits); the group is launched when it is
-// full, when a begin finds no pass streaming, before a ticket that cannot join it is begun, and when one of its tickets is
-// finished (shared_pass = 2: before any finish that would wait).  Nothing is left unlaunched across a wait: no deadlock.
+// ---- shared pass: searches in flight over one buffer filtered by shared launches ----
+// The fused filter's workgroups are independent, so a ticket's text pass is served by up to two launches over the halves
+// H0 = workgroups [0, ceil(fgrid / 2)) and H1 = the rest, each with one or two members (filter_dna_kernel<.., G = 2>).
+// The searcher's PassPlanner (pass_planner.h) knows which ticket still needs which half and answers every begin / finish
+// with the launches to queue now; run_pass_launch() queues one.  shared_pass = 1 (default) staggers the tickets: begin(i)
+// launches { ticket i-1: its second half, ticket i: its first half }, so every begin queues one half launch of two members,
+// ticket i-1 is complete with it (its tail is queued at once, on its own lane, behind the events of both launches that
+// served it), and when the host blocks in finish(i-2) the next half pass is already queued behind the running one: the
+// device never idles between passes.  A ticket that finds no partner and no pass streaming is launched whole; one that
+// finds a pass streaming launches H0 alone and keeps H1 back for the next begin (shared_pass = 4: always).  A ticket
+// that cannot join (ScanJob::group_ok / group_fits) is begun behind what open tickets still need; finish() launches what
+// its ticket still needs.  Nothing is left unlaunched across a wait: no deadlock.  shared_pass = 2 / 3: the whole-pass
+// groups of the planner's grouped policy.
 static ScanJob* ticket_job(sassy_hip_Ticket* t) { return static_cast<ScanJob*>(t->job.get()); }
 
 static bool pass_streaming(sassy_SearcherType* s) {
   if (s->sw.shared_pass == 3) return true;  // (tests: every groupable ticket waits for a partner)
-  if (s->last_pass_lane < 0) return false;
-  const hipError_t e = hipEventQuery(s->lanes[s->last_pass_lane].ev_filter_done);
+  if (!s->last_pass_event) return false;
+  const hipError_t e = hipEventQuery(s->last_pass_event);
   if (e == hipErrorNotReady) {
     (void)hipGetLastError();  // (not an error)
     return true;
@@ -534,29 +541,74 @@ static bool pass_streaming(sassy_SearcherType* s) {
   return false;
 }
 
-// launches the open group: one member as a search of its own, two as one shared pass (member 0's lane runs it)
-static int launch_open_group(sassy_SearcherType* s) {
-  if (s->open_group.empty()) return 0;
-  std::vector<sassy_hip_Ticket*> g;
-  g.swap(s->open_group);
-  ScanJob* a = ticket_job(g[0]);
+static bool tickets_fit(void* ctx, int a, int b) {
+  sassy_SearcherType* s = static_cast<sassy_SearcherType*>(ctx);
+  sassy_hip_Ticket *ta = s->lane_ticket[a], *tb = s->lane_ticket[b];
+  return ta && tb && ta->job && tb->job && ticket_job(ta)->group_fits(*ticket_job(tb));
+}
+
+static PassSlot* take_pass_slot(sassy_SearcherType* s, int users) {
+  for (PassSlot& ps : s->pass_slots) {
+    if (ps.users != 0) continue;
+    if (!ps.ev_done) {
+      if (hipEventCreate(&ps.ev_start) != hipSuccess || hipEventCreate(&ps.ev_stop) != hipSuccess ||
+          hipEventCreateWithFlags(&ps.ev_done, hipEventDisableTiming) != hipSuccess)
+        return nullptr;
+    }
+    ps.users = users;
+    return &ps;
+  }
+  return nullptr;
+}
+
+// queues one launch of the planner: a whole launch of a ticket on its own is the search's plain chain (ScanJob::enqueue);
+// everything else is head (at the ticket's first launch), the launch over the range, and the tail of every member that
+// needs nothing more
+static int run_pass_launch(sassy_SearcherType* s, const PassLaunch& pl) {
+  sassy_hip_Ticket* ta = s->lane_ticket[pl.leader];
+  sassy_hip_Ticket* tb = pl.member >= 0 ? s->lane_ticket[pl.member] : nullptr;
+  ScanJob* a = ticket_job(ta);
+  ScanJob* b = tb ? ticket_job(tb) : nullptr;
   int rc = 0;
-  if (g.size() == 1) {
+  if (!b && pl.range == kPassWhole && !ta->head_done) {
     rc = a->enqueue(0);
+    s->last_pass_event = s->lanes[ta->lane].ev_filter_done;
   } else {
-    ScanJob* b = ticket_job(g[1]);
-    b->group_leader = a;
-    rc = b->enqueue(0);
-    b->group_leader = nullptr;
+    const uint32_t mid = (a->fgrid + 1) / 2;
+    const uint32_t g0 = pl.range == kPassH1 ? mid : 0u, g1 = pl.range == kPassH0 ? mid : a->fgrid;
+    for (sassy_hip_Ticket* t : {ta, tb})
+      if (rc == 0 && t && !t->head_done) {
+        rc = ticket_job(t)->enqueue_head(0, true);
+        t->head_done = true;
+      }
+    PassSlot* slot = rc == 0 ? take_pass_slot(s, b ? 2 : 1) : nullptr;
+    if (rc == 0 && !slot) rc = fail(SASSY_HIP_ENOMEM, "shared pass: no free launch slot");
+    if (rc == 0) {
+      ta->slots.push_back(slot);
+      if (tb) tb->slots.push_back(slot);
+      rc = a->enqueue_pass(b, g0, g1, *slot);
+      s->last_pass_event = slot->ev_done;
+    }
+    for (sassy_hip_Ticket* t : {ta, tb})
+      if (rc == 0 && t && s->planner.need(t->lane) == 0) rc = ticket_job(t)->enqueue_tail(0);
   }
-  for (sassy_hip_Ticket* t : g) {
-    t->pending = false;
-    t->pass_patterns = (uint32_t)g.size();
-    t->launch_rc = rc;
-  }
-  s->last_pass_lane = g[0]->lane;
+  for (sassy_hip_Ticket* t : {ta, tb})
+    if (t) {
+      t->pass_patterns = std::max<uint32_t>(t->pass_patterns, b ? 2u : 1u);
+      if (rc != 0) t->launch_rc = rc;
+    }
   if (rc != 0)
-    for (sassy_hip_Ticket* t : g) (void)hipStreamSynchronize(s->lanes[t->lane].stream);
+    for (sassy_hip_Ticket* t : {ta, tb})
+      if (t) (void)hipStreamSynchronize(s->lanes[t->lane].stream);
+  return rc;
+}
+
+static int run_pass_launches(sassy_SearcherType* s, const std::vector<PassLaunch>& launches) {
+  int rc = 0;
+  for (const PassLaunch& pl : launches) {
+    const int r = run_pass_launch(s, pl);
+    if (rc == 0) rc = r;
+  }
   return rc;
 }
 
@@ -617,32 +669,20 @@ int sassy_hip_search_shard_begin(sassy_SearcherType* s, const uint8_t* pattern, 
       return rc;
     }
     t->job = job;
-    const bool groupable = s->sw.shared_pass != 0 && depth > 1 && job->group_ok();
-    if (groupable && !s->open_group.empty() && !ticket_job(s->open_group[0])->group_fits(*job)) rc = launch_open_group(s);
-    if (rc == 0 && groupable && (!s->open_group.empty() || pass_streaming(s))) {
-      // share a pass: wait for a second search (or, with no pass streaming any more, go now with the one waiting)
-      t->pending = true;
-      s->open_group.push_back(t.get());
-      s->lane_ticket[lane] = t.get();
-      s->last_begun_lane = lane;
-      if (s->open_group.size() == 2 || !pass_streaming(s)) rc = launch_open_group(s);
-      if (rc != 0) {
-        s->lane_ticket[lane] = nullptr;
-        return rc;
-      }
-      *out = t.release();
-      return 0;
-    }
-    if (rc == 0) rc = launch_open_group(s);  // (order: a waiting group goes in front of a search that cannot join it)
-    if (rc == 0 && !job->empty) {
-      rc = job->enqueue(0);
-      s->last_pass_lane = lane;
-    }
-    if (rc != 0) {
-      (void)hipStreamSynchronize(s->lanes[lane].stream);
-      return rc;
-    }
-  } else if (int rc = launch_open_group(s)) {
+  }
+  // the planner says what to queue now: this ticket's launch (whole, or the half it shares with a ticket that holds one
+  // back) and, in front of a ticket that cannot join, what open tickets still need
+  const bool has_pass = t->job && !ticket_job(t.get())->empty;
+  const bool groupable = has_pass && s->sw.shared_pass != 0 && depth > 1 && ticket_job(t.get())->group_ok();
+  const bool splittable = groupable && ticket_job(t.get())->fgrid >= 2;
+  s->lane_ticket[lane] = t.get();
+  std::vector<PassLaunch> launches;
+  s->planner.begin(lane, groupable, splittable, has_pass, groupable && pass_streaming(s), (int)s->sw.shared_pass, tickets_fit, s, launches);
+  if (int rc = run_pass_launches(s, launches)) {
+    s->planner.drop(lane);
+    for (PassSlot* ps : t->slots) ps->users -= 1;
+    s->lane_ticket[lane] = nullptr;
+    (void)hipStreamSynchronize(s->lanes[lane].stream);
     return rc;
   }
   s->lane_ticket[lane] = t.get();
@@ -655,13 +695,17 @@ int sassy_hip_search_finish(sassy_SearcherType* s, sassy_hip_Ticket* t, sassy_hi
   if (!s || !t || t->owner != s) return fail(SASSY_HIP_EINVAL, "not a ticket of this searcher");
   DeviceGuard on_device(s);
   std::unique_ptr<sassy_hip_Ticket> guard(t);
-  // its own pass goes now if it still waits; shared_pass = 2: so does any waiting group when this finish would wait
+  // what it still needs goes now; shared_pass = 2: so does any waiting group when this finish would wait
   bool would_wait = false;
-  if (s->sw.shared_pass == 2 && !s->open_group.empty() && hipStreamQuery(s->lanes[t->lane].stream) == hipErrorNotReady) {
+  if (s->sw.shared_pass == 2 && s->planner.any_open() && hipStreamQuery(s->lanes[t->lane].stream) == hipErrorNotReady) {
     (void)hipGetLastError();  // (not an error)
     would_wait = true;
   }
-  const int lrc = (t->pending || would_wait) ? launch_open_group(s) : 0;
+  std::vector<PassLaunch> launches;
+  s->planner.finish(t->lane, would_wait, (int)s->sw.shared_pass, tickets_fit, s, launches);
+  const int lrc = run_pass_launches(s, launches);
+  if (t->job && (t->launch_rc != 0 || lrc != 0)) (void)hipStreamSynchronize(s->lanes[t->lane].stream);
+  for (PassSlot* ps : t->slots) ps->users -= 1;  // (read by ScanJob::finish below: nobody takes a slot before this call returns)
   s->lane_ticket[t->lane] = nullptr;
   reset_stats(s);
   if (t->launch_rc != 0) return t->launch_rc;

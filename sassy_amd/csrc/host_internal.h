@@ -26,6 +26,7 @@
 #include "common.h"
 #include "profiles.h"
 #include "switches.h"
+#include "pass_planner.h"
 
 namespace sassy_hip {
 // (thread_local LaunchEvents g_launch_events: defined in scan_driver.hip, declared in common.h)
@@ -252,12 +253,24 @@ struct sassy_hip_Ticket {
   bool empty_shard = false;
   double t0 = 0;
   std::shared_ptr<void> job;     // the ScanJob (defined below)
-  // shared pass (c_abi.hip): begun, but its pass is not launched yet (the searcher's open group holds it); the number of
-  // searches its pass served; what the deferred launch returned
-  bool pending = false;
+  // shared pass (c_abi.hip): the largest member count among the launches that served it; what a launch made for it after
+  // its begin returned; the launches' event slots it holds until it is finished
   uint32_t pass_patterns = 1;
   int launch_rc = 0;
+  bool head_done = false;  // ScanJob::enqueue_head ran (a ticket served by range launches)
+  std::vector<struct PassSlot*> slots;
 };
+
+// One launch of the shared pass (c_abi.hip): the events the dispatch carries (timing level >= 1) and the event the lanes of
+// the tickets it serves wait for.  A searcher owns a few; a slot is taken for a launch and given back when the last ticket
+// the launch served is finished.
+struct PassSlot {
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_done = nullptr;
+  int users = 0;
+  bool timed = false;
+  const void* lane = nullptr;  // the lane whose stream carries the launch
+};
+constexpr int kPassSlots = 8;  // (four tickets, two launches each)
 
 struct sassy_hip_Encoded {
   Profile profile;
@@ -567,10 +580,11 @@ struct sassy_SearcherType {
   struct sassy_hip_Ticket* lane_ticket[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
   int last_begun_lane = -1;
   int pipe_depth = 2;
-  // shared pass (switch shared_pass): begun tickets that wait to share one text pass (at most two), and the lane whose
-  // ev_filter_done marks the end of the searcher's last launched pass (-1: none)
-  std::vector<struct sassy_hip_Ticket*> open_group;
-  int last_pass_lane = -1;
+  // shared pass (switch shared_pass): which ticket still needs which half of its pass (pass_planner.h), the launches' event
+  // slots, and the event that marks the end of the searcher's last launched pass
+  sassy_hip::PassPlanner planner;
+  PassSlot pass_slots[kPassSlots];
+  hipEvent_t last_pass_event = nullptr;
   // reporting modes of the reference's Searcher (src/search.rs:442-475)
   float alpha = NAN;             // overhang cost per pattern character (NaN = no overhang), Iupac only
   long max_overhang = -1;        // with_max_overhang(): -1 = none
@@ -608,7 +622,10 @@ struct sassy_SearcherType {
   ~sassy_SearcherType() {
     for (ScanLane& l : lanes)  // searches still in flight (tickets never finished): let their kernels drain
       if (l.stream) (void)hipStreamSynchronize(l.stream);
-    open_group.clear();  // (an unlaunched group is dropped with its tickets)
+    // (halves that were never launched are dropped with their tickets)
+    for (PassSlot& ps : pass_slots)
+      for (hipEvent_t e : {ps.ev_start, ps.ev_stop, ps.ev_done})
+        if (e) (void)hipEventDestroy(e);
     for (sassy_hip_Ticket*& t : lane_ticket) { delete t; t = nullptr; }
     d_text.release(); d_rev.release(); d_rc_bitmap.release();
     free_stage();
@@ -785,10 +802,9 @@ struct ScanJob {
   uint8_t* ctl_base = nullptr;       // this search's control block (the lane's d_ctl or its twin)
   bool ctl_pre_cleared = false;      // ... whose first 64 bytes the previous search cleared
   bool wait_ev_done = false;         // the host waits for L.ev_done (the twin's clear follows it in the stream)
-  // shared pass (attempt 0 only): group_leader = the job whose launch also serves this one (this job's filter launch
-  // becomes "wait for the leader's pass"); group_member = the job the leader's launch serves as member 1
-  ScanJob* group_leader = nullptr;
-  ScanJob* group_member = nullptr;
+  // shared pass (attempt 0 only): the launches that served this job (its own lane's or another's), in place of the whole
+  // launch of enqueue_filter
+  std::vector<PassSlot*> passes;
   bool group_ok() const;                    // this job can be a member of a grouped pass
   bool group_fits(const ScanJob& b) const;  // ... together with b (same buffer and launch geometry, <= 8 pieces)
   bool pipelined = false;            // one of several searches in flight (sassy_hip_search_shard_begin): the
@@ -838,7 +854,16 @@ struct ScanJob {
       : S(S_), L(L_), sh(sh_), plan(plan_), k(k_), all_minima(all_), pat(pat_), do_trace(do_trace_),
         total_len(total_len_) {}
   int prepare();
+  // enqueue = head (buffers, control block, what the filter launch reads), the search's own whole filter launch, tail
+  // (everything behind the filter).  The shared pass calls head and tail itself and serves the job with enqueue_pass
+  // launches in between (with_group_event: another lane's launch will read this lane's control block and tables).
   int enqueue(int attempt);
+  int enqueue_head(int attempt, bool with_group_event = false);
+  int enqueue_filter(int attempt);
+  int enqueue_tail(int attempt);
+  // the fused filter over the workgroups [g0, g1) for this job alone (the G = 1 launch) or with `other` (the G = 2
+  // launch) on this job's lane; slot: the launch's events
+  int enqueue_pass(ScanJob* other, uint32_t g0, uint32_t g1, PassSlot& slot);
   int finish(ScanOut& out);
   int finish_once(ScanOut& out, bool& redo);
 };

@@ -748,6 +748,12 @@ int ScanJob::prepare() {
 }
 
 int ScanJob::enqueue(int attempt) {
+  if (int rc = enqueue_head(attempt)) return rc;
+  if (int rc = enqueue_filter(attempt)) return rc;
+  return enqueue_tail(attempt);
+}
+
+int ScanJob::enqueue_head(int attempt, bool with_group_event) {
   P.cand = L.d_cand.p;
   P.cand_cap = (uint32_t)std::min<size_t>(L.d_cand.cap, 0xFFFFFFFFu);
   // (the buffer may be large from an earlier, denser search: the cigar pool of this one holds at most 4 GiB)
@@ -773,69 +779,40 @@ int ScanJob::enqueue(int attempt) {
   ctl_pre_cleared = false;
   wait_ev_done = false;
   if (ext_wait && attempt == 0) HIP_TRY(hipStreamWaitEvent(L.stream, ext_wait, 0));
+  passes.clear();
+  if (filtered && fused) {  // the filter appends the reports itself: it needs the list (every attempt runs the whole launch)
+    F.cand = P.cand;
+    F.cand_cap = P.cand_cap;
+    F.cand_count = P.cand_count;
+    if (int rc = L.d_stash.reserve(std::min<size_t>(P.cand_cap, 1u << 18))) return rc;
+    F.stash = L.d_stash.p;
+    F.stash_cap = (uint32_t)std::min<size_t>(L.d_stash.cap, 0xFFFFFEu);
+    F.counters = nullptr;
+    F.row_tab = P.row_tab;
+  }
+  // (shared pass: this lane's control block and pattern tables are in place for a launch on another lane's stream)
+  if (with_group_event) HIP_TRY(hipEventRecord(L.ev_group, L.stream));
+  return 0;
+}
+
+// The search's own filter: one whole launch (the streaming DP where no prefilter applies), its timing events and the
+// event searches in flight look at.
+int ScanJob::enqueue_filter(int attempt) {
   // (a job that only consumes a bitmap has no filter to time: no events at level 1, each costs ~6 us of stream idle)
   const bool time_head = timing >= 2 || (timing == 1 && !ext_bitmap);
-  // (the fused launch carries its events itself: LaunchEvents; a member of another job's pass times it with its own two
-  // markers around the wait for it)
-  const bool ext_events = time_head && filtered && fused && attempt == 0 && !group_leader;
+  // (the fused launch carries its events itself: LaunchEvents)
+  const bool ext_events = time_head && filtered && fused && attempt == 0;
   if (time_head && !ext_events) HIP_TRY(hipEventRecord(L.ev_a, L.stream));
   hipError_t le;
   if (!filtered) {
     le = launch_scan_any(S->profile, P, grid, (size_t)P.waves_per_group * P.lds_per_wave, L.stream);
     if (le != hipSuccess) return hip_fail(le, "scan kernel launch");
   } else {
-    if (fused) {  // the filter appends the reports itself: it needs the list (every attempt runs the whole launch)
-      F.cand = P.cand;
-      F.cand_cap = P.cand_cap;
-      F.cand_count = P.cand_count;
-      if (int rc = L.d_stash.reserve(std::min<size_t>(P.cand_cap, 1u << 18))) return rc;
-      F.stash = L.d_stash.p;
-      F.stash_cap = (uint32_t)std::min<size_t>(L.d_stash.cap, 0xFFFFFEu);
-      F.counters = nullptr;
-      F.row_tab = P.row_tab;
-      if (group_leader && attempt == 0) {
-        // member 1 of a shared pass: the leader's lane waits until this lane's control block and pattern tables are in
-        // place, launches the pass for both, and this lane's tail waits for the end of it
-        HIP_TRY(hipEventRecord(L.ev_group, L.stream));
-        group_leader->group_member = this;
-        const int rc = group_leader->enqueue(0);
-        group_leader->group_member = nullptr;
-        if (rc) return rc;
-        HIP_TRY(hipStreamWaitEvent(L.stream, group_leader->L.ev_filter_done, 0));
-      } else if (group_member && attempt == 0) {
-        // the shared pass: member 0 = this job (F), member 1 = the other job's pieces, pattern rows and report arrays
-        const ScanJob& B = *group_member;
-        ScanParams GP = F;
-        // The tile and both members' queues and counts, WITHOUT the pipelining pad of prepare(): 4 x (8192 + 2 x 1552) =
-        // 45 184 bytes per workgroup, so three workgroups per CU stream the text instead of two (the kernel's VGPRs allow
-        // three waves per SIMD).  The pass keeps the members' geometry (the pad, the geometry and why).
-        GP.lds_per_wave = kTileBytes + 2u * (F.fuse_queue_cap * 8u + 16u);
-        const uint32_t na = F.n_pieces, nb = B.F.n_pieces;
-        GP.piece_member = 0;
-        for (uint32_t pp = 0; pp < 8; ++pp) {  // (slots behind both repeat member 0's first piece)
-          const bool m1 = pp >= na && pp < na + nb;
-          const uint32_t src = m1 ? pp - na : (pp < na ? pp : 0u);
-          const ScanParams& O = m1 ? B.F : F;
-          GP.piece_bits[pp][0] = O.piece_bits[src][0];
-          GP.piece_bits[pp][1] = O.piece_bits[src][1];
-          GP.piece_rem[pp] = O.piece_rem[src];
-          if (m1) GP.piece_member |= 1u << pp;
-        }
-        GP.n_pieces = na + nb;
-        GP.piece_groups = 2;
-        GP.member1 = ScanParams::FuseMember{B.F.row_tab, B.F.cand, B.F.cand_count, B.F.stash, B.F.m, B.F.k, B.F.nwords, B.F.wb,
-                                            B.F.flags, B.F.cand_cap, B.F.stash_cap, 0u};
-        HIP_TRY(hipStreamWaitEvent(L.stream, B.L.ev_group, 0));
-        if (ext_events) g_launch_events = LaunchEvents{L.ev_a, L.ev_f};
-        le = launch_filter_group(GP, fgrid, L.stream);
-        g_launch_events = LaunchEvents{};
-        if (le != hipSuccess) return hip_fail(le, "shared fused filter kernel launch");
-      } else {
-        if (ext_events) g_launch_events = LaunchEvents{L.ev_a, L.ev_f};
-        le = launch_filter_any(S->profile, F, fgrid, 1024 + (size_t)kWavesPerGroup * F.lds_per_wave, L.stream);
-        g_launch_events = LaunchEvents{};
-        if (le != hipSuccess) return hip_fail(le, "fused filter kernel launch");
-      }
+    if (fused) {
+      if (ext_events) g_launch_events = LaunchEvents{L.ev_a, L.ev_f};
+      le = launch_filter_any(S->profile, F, fgrid, 1024 + (size_t)kWavesPerGroup * F.lds_per_wave, L.stream);
+      g_launch_events = LaunchEvents{};
+      if (le != hipSuccess) return hip_fail(le, "fused filter kernel launch");
     } else if ((attempt == 0 || count_direct) && !ext_bitmap && !ext_desc) {  // the hit bitmap does not depend on buffer sizes: build it once
       // (count_direct: the filter files the descriptors itself -- into a list that may have grown: every attempt runs it)
       if (count_direct) {
@@ -864,6 +841,17 @@ int ScanJob::enqueue(int attempt) {
     }
     if (time_head && attempt == 0 && !ext_events) HIP_TRY(hipEventRecord(L.ev_f, L.stream));
     if (signal_filter_done && attempt == 0) HIP_TRY(hipEventRecord(L.ev_filter_done, L.stream));
+  }
+  return 0;
+}
+
+// Everything behind the filter: chunk list and list kernel (classic chain), rank, traceback, the twin's clear.  After a
+// shared pass: behind the events of all launches that served this job on other lanes' streams.
+int ScanJob::enqueue_tail(int attempt) {
+  hipError_t le;
+  for (const PassSlot* ps : passes)
+    if (ps->lane != &L) HIP_TRY(hipStreamWaitEvent(L.stream, ps->ev_done, 0));
+  if (filtered) {
     if (!fused) {
     maxlen = 16;
     while (maxlen < 8u * P.wb && maxlen < 128u) maxlen <<= 1;
@@ -1004,6 +992,50 @@ int ScanJob::enqueue(int attempt) {
   return 0;
 }
 
+// One launch of the shared pass: the fused filter over the workgroups [g0, g1) of the grid, for this job alone or for
+// this job (member 0: F) and `other` (member 1: its pieces, pattern rows and report arrays), on this job's lane.  The
+// workgroups are independent (each wave owns its lane chunks, its LDS queues and its reports; the control block takes
+// atomics only), so the launches that serve a job may run in any order and side by side.
+int ScanJob::enqueue_pass(ScanJob* other, uint32_t g0, uint32_t g1, PassSlot& slot) {
+  if (g0 >= g1 || g1 > fgrid) return fail(SASSY_HIP_EINVAL, "shared pass: workgroup range outside the grid");
+  ScanParams GP = F;
+  GP.group_offset = F.group_offset + g0;
+  if (other) {
+    const ScanJob& B = *other;
+    // The tile and both members' queues and counts, WITHOUT the pipelining pad of prepare(): 4 x (8192 + 2 x 1552) =
+    // 45 184 bytes per workgroup, so three workgroups per CU stream the text instead of two (the kernel's VGPRs allow
+    // three waves per SIMD).  The pass keeps the members' geometry (the pad, the geometry and why).
+    GP.lds_per_wave = kTileBytes + 2u * (F.fuse_queue_cap * 8u + 16u);
+    const uint32_t na = F.n_pieces, nb = B.F.n_pieces;
+    GP.piece_member = 0;
+    for (uint32_t pp = 0; pp < 8; ++pp) {  // (slots behind both repeat member 0's first piece)
+      const bool m1 = pp >= na && pp < na + nb;
+      const uint32_t src = m1 ? pp - na : (pp < na ? pp : 0u);
+      const ScanParams& O = m1 ? B.F : F;
+      GP.piece_bits[pp][0] = O.piece_bits[src][0];
+      GP.piece_bits[pp][1] = O.piece_bits[src][1];
+      GP.piece_rem[pp] = O.piece_rem[src];
+      if (m1) GP.piece_member |= 1u << pp;
+    }
+    GP.n_pieces = na + nb;
+    GP.piece_groups = 2;
+    GP.member1 = ScanParams::FuseMember{B.F.row_tab, B.F.cand, B.F.cand_count, B.F.stash, B.F.m, B.F.k, B.F.nwords, B.F.wb,
+                                        B.F.flags, B.F.cand_cap, B.F.stash_cap, 0u};
+    HIP_TRY(hipStreamWaitEvent(L.stream, B.L.ev_group, 0));
+  }
+  slot.lane = &L;
+  slot.timed = timing >= 1 || (other && other->timing >= 1);
+  if (slot.timed) g_launch_events = LaunchEvents{slot.ev_start, slot.ev_stop};
+  const hipError_t le = other ? launch_filter_group(GP, g1 - g0, L.stream)
+                              : launch_filter_any(S->profile, GP, g1 - g0, 1024 + (size_t)kWavesPerGroup * GP.lds_per_wave, L.stream);
+  g_launch_events = LaunchEvents{};
+  if (le != hipSuccess) return hip_fail(le, other ? "shared fused filter kernel launch" : "fused filter kernel launch");
+  HIP_TRY(hipEventRecord(slot.ev_done, L.stream));
+  passes.push_back(&slot);
+  if (other) other->passes.push_back(&slot);
+  return 0;
+}
+
 // A job that can share its fused pass with another search over the same buffer (c_abi.hip: shared pass): the Dna
 // bit-plane launch of one forward strand, pieces of 7 .. 12 rows, no paired filter, no tuner, pattern words that leave
 // the tile's upper half to the segment state (kFuseGroupMaxWords)
@@ -1068,7 +1100,13 @@ int ScanJob::finish_once(ScanOut& out, bool& redo) {
       if (!filtered && tuned && attempt == 0) S->tuner_scan.report(P.bpl, ms);
     }
     S->stats.scan_launches += 1;
-    if (filtered && attempt == 0 && (timing >= 2 || (timing == 1 && !ext_bitmap))) {
+    if (filtered && attempt == 0 && !passes.empty()) {  // shared pass: the sum of the launches that served this job
+      for (const PassSlot* ps : passes)
+        if (ps->timed) {
+          HIP_TRY(hipEventElapsedTime(&ms, ps->ev_start, ps->ev_stop));
+          S->stats.filter_ms += ms;
+        }
+    } else if (filtered && attempt == 0 && (timing >= 2 || (timing == 1 && !ext_bitmap))) {
       HIP_TRY(hipEventElapsedTime(&ms, L.ev_a, L.ev_f));
       S->stats.filter_ms += ms;
       if (tuned) S->tuner.report(F.bpl, ms);
