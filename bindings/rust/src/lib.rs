@@ -47,6 +47,8 @@ struct RawTicket {
 pub const ALL_MINIMA: u32 = 1;
 pub const WITHOUT_TRACE: u32 = 2;
 pub const TEXT_ON_DEVICE: u32 = 4;
+/// `min_costs` / `best_pattern`: no match of cost <= k.
+pub const NO_MATCH: u8 = 255;
 
 extern "C" {
     fn sassy_hip_searcher_new(alphabet: *const c_char, rc: bool, alpha: f32) -> *mut RawSearcher;
@@ -62,6 +64,13 @@ extern "C" {
     fn sassy_hip_encoded_free(e: *mut RawEncoded);
     fn sassy_hip_search_encoded(s: *mut RawSearcher, e: *const RawEncoded, text: *const u8, text_len: usize,
                                 k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
+    // best-cost search (include/sassy_hip.h): one cost per (pattern, text) pair / the best pattern per text, no records
+    fn sassy_hip_min_costs(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                           texts: *const *const u8, text_lens: *const usize, n_texts: usize, k: usize, flags: u32,
+                           out_cost: *mut u8, out_strand: *mut u8) -> c_int;
+    fn sassy_hip_best_pattern(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                              texts: *const *const u8, text_lens: *const usize, n_texts: usize, k: usize, flags: u32,
+                              out_cost: *mut u8, out_pattern: *mut u32, out_strand: *mut u8) -> c_int;
     fn sassy_hip_result_len(r: *const RawResult) -> usize;
     fn sassy_hip_result_matches(r: *const RawResult) -> *const RawMatch;
     fn sassy_hip_result_cigars(r: *const RawResult) -> *const c_char;
@@ -259,6 +268,34 @@ impl<P: Profile> Searcher<P> {
         let rc = unsafe { sassy_hip_search_encoded(self.raw, encoded.raw, text.as_ptr(), text.len(), k, 0, &mut res) };
         assert_eq!(rc, 0, "{}", last_error());
         unsafe { collect(res) }
+    }
+
+    /// The smallest cost of any match of pattern p in text t, row-major `[p * texts.len() + t]`, `NO_MATCH` where there is
+    /// none of cost <= k (what `only_best_match().without_trace()` under `search_many` gives per pair, reduced).
+    pub fn min_costs(&mut self, patterns: &[&[u8]], texts: &[&[u8]], k: usize) -> Vec<u8> {
+        let (pp, pl): (Vec<*const u8>, Vec<usize>) = patterns.iter().map(|p| (p.as_ptr(), p.len())).unzip();
+        let (tp, tl): (Vec<*const u8>, Vec<usize>) = texts.iter().map(|t| (t.as_ptr(), t.len())).unzip();
+        let mut cost = vec![NO_MATCH; patterns.len() * texts.len()];
+        let rc = unsafe {
+            sassy_hip_min_costs(self.raw, pp.as_ptr(), pl.as_ptr(), pp.len(), tp.as_ptr(), tl.as_ptr(), tp.len(), k, 0,
+                                cost.as_mut_ptr(), std::ptr::null_mut())
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        cost
+    }
+
+    /// Per text: (cost, pattern, strand) of the best pattern -- lowest cost, then lowest index, then Fwd; cost `NO_MATCH` and
+    /// pattern `u32::MAX` where no pattern matches with cost <= k.
+    pub fn best_pattern(&mut self, patterns: &[&[u8]], texts: &[&[u8]], k: usize) -> Vec<(u8, u32, Strand)> {
+        let (pp, pl): (Vec<*const u8>, Vec<usize>) = patterns.iter().map(|p| (p.as_ptr(), p.len())).unzip();
+        let (tp, tl): (Vec<*const u8>, Vec<usize>) = texts.iter().map(|t| (t.as_ptr(), t.len())).unzip();
+        let (mut cost, mut pat, mut strand) = (vec![NO_MATCH; texts.len()], vec![u32::MAX; texts.len()], vec![0u8; texts.len()]);
+        let rc = unsafe {
+            sassy_hip_best_pattern(self.raw, pp.as_ptr(), pl.as_ptr(), pp.len(), tp.as_ptr(), tl.as_ptr(), tp.len(), k, 0,
+                                   cost.as_mut_ptr(), pat.as_mut_ptr(), strand.as_mut_ptr())
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        (0..texts.len()).map(|t| (cost[t], pat[t], if strand[t] != 0 { Strand::Rc } else { Strand::Fwd })).collect()
     }
 
     /// A stream of searches over a text that lives in HBM: queue one and go on (up to two in flight).

@@ -220,6 +220,43 @@ int sassy_hip_search_many(sassy_SearcherType *s, const uint8_t *const *patterns,
                           const size_t *text_lens, size_t n_texts, size_t k, uint32_t flags,
                           sassy_hip_Result **out);
 
+/* Best-cost search: the smallest cost per (pattern, text) pair, or per text the best pattern, without the records.
+ * Definition (for every searcher configuration): group the matches sassy_hip_search_many returns for the same searcher,
+ * inputs and k by (pattern_idx, text_idx); a pair's value is the minimum `cost` of its group.  (The report rule keeps
+ * every local minimum and the global minimum of a pair is one, so without an end-position filter this is the minimum of
+ * the DP's last row where it is <= k.)
+ *  - strands: as the searcher (rc); Ascii with rc: SASSY_HIP_EUNSUPPORTED, as search_many;
+ *  - overhang searchers (alpha, max_overhang): the cost includes the overhang price, as in the records;
+ *  - max_n_frac set: only matches that pass the N filter count;
+ *  - only_best_match does not change the answer (it can, together with max_n_frac: then the definition above holds);
+ *  - flags: SASSY_HIP_TEXT_ON_DEVICE as for search_many, anything else SASSY_HIP_EINVAL; k > 254: SASSY_HIP_EINVAL;
+ *    empty texts, k >= pattern_len, n_patterns == 0 / n_texts == 0: what search_many gives, reduced;
+ *  - refused while tickets are open, like the other synchronous entry points.
+ * Where search_many runs a batch of host texts in one pass (seeded search / pattern-tiled scan over the laid-out batch,
+ * the per-text tiled scan of overhang searchers) the scan's (pattern, position, cost) list is reduced on the device
+ * (sassy_amd/csrc/min_costs.hip): no sort, no report rule, no traceback, no records.  With max_n_frac that path needs
+ * a batch of plain A C G T (the N filter cannot touch it), and best_pattern's takes fewer than 2^24 patterns;
+ * everything else -- Ascii, other letters under a Dna searcher or the N filter, device-resident texts, one text,
+ * patterns of several lengths -- runs
+ * search_many (without trace where the N filter allows it) and reduces its records on the host.  Option
+ * min_cost_device = 0: always that general path.  SASSY_HIP_ENOMEM (with the size in the message) if the device matrix
+ * cannot be had.  sassy_hip_get_stats afterwards: scan_ms / filter_ms as for the search, trace_ms = the HIP-event time
+ * of the reduction launches (timing level 2), candidates = list entries reduced.
+ *
+ * sassy_hip_min_costs: out_cost[p * n_texts + t] = that minimum over the strands searched, SASSY_HIP_NO_MATCH if there
+ * is no match of cost <= k.  out_strand (may be NULL), same shape: the strand of the minimum, 0 Fwd / 1 Rc, Fwd on a
+ * tie, 0 where there is no match. */
+#define SASSY_HIP_NO_MATCH 255u
+int sassy_hip_min_costs(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                        size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
+                        size_t k, uint32_t flags, uint8_t *out_cost, uint8_t *out_strand);
+/* Per text the best pattern: out_cost[t] as above, minimised over the patterns as well; out_pattern[t] the pattern that
+ * attains it (lowest index on a tie, then Fwd before Rc; UINT32_MAX where there is no match), out_strand[t] its strand.
+ * out_pattern / out_strand may be NULL (a pure filter asks for out_cost only). */
+int sassy_hip_best_pattern(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                           size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
+                           size_t k, uint32_t flags, uint8_t *out_cost, uint32_t *out_pattern, uint8_t *out_strand);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is
@@ -315,7 +352,8 @@ int sassy_hip_multi_search_encoded(sassy_hip_Multi *m, const uint8_t *patterns, 
                                    size_t k, uint32_t flags, sassy_hip_Result **out);
 /* search_many over several devices shards the TEXTS (host pointers; whole texts, contiguous runs of about equal total
  * length per device; src/search.rs:531-603 does the same over threads): every device searches all patterns in its
- * texts, text_idx refers to the caller's list.  Needs no resident text. */
+ * texts, text_idx refers to the caller's list.  Needs no resident text.  (There is no multi-device sassy_hip_min_costs /
+ * _best_pattern: shard the texts over one searcher per device -- each fills its own columns.) */
 int sassy_hip_multi_search_many(sassy_hip_Multi *m, const uint8_t *const *patterns, const size_t *pattern_lens,
                                 size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
                                 size_t k, uint32_t flags, sassy_hip_Result **out);
@@ -388,10 +426,10 @@ void sassy_hip_result_free(sassy_hip_Result *r);
  * npat patterns of equal length plen (<= 64) stored back to back.
  * The many-pattern calls (this one and sassy_hip_search_many): the reports are the definition's (one left-to-right
  * pass per pattern and text) -- as in the reference, whose lanes hold whole texts / patterns there (no lane seams:
- * sassy_hip_set_reference_lanes has nothing to reproduce).  Limit: with an overhang
- * searcher (alpha) the one-pass kernels (seeded search, pattern-tiled scan) are not used: the patterns then run
- * one kernel chain each, correct but at the speed of single searches (the reference's v2 scans overhang in its
- * tiled loop, src/pattern_tiling/search.rs:222-323). */
+ * sassy_hip_set_reference_lanes has nothing to reproduce).  An overhang searcher (alpha) takes one pass as well where
+ * the shape allows it (>= 4 Iupac patterns of one length <= 64 with seeds, plain-base text: the seeded search lists the
+ * inside of the text, the per-text tiled scan its two edges; the reference's v2 scans overhang in its tiled loop,
+ * src/pattern_tiling/search.rs:222-323); other overhang shapes run one kernel chain per pattern. */
 sassy_hip_Encoded *sassy_hip_encode_patterns(sassy_SearcherType *s, const uint8_t *patterns,
                                              size_t npat, size_t plen);
 void sassy_hip_encoded_free(sassy_hip_Encoded *e);

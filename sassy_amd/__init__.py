@@ -32,6 +32,7 @@ if os.environ.get("SASSY_HIP_LIBRARY"):  # A/B timing of two builds on one box (
 ALL_MINIMA = 1
 WITHOUT_TRACE = 2
 TEXT_ON_DEVICE = 4
+NO_MATCH = 255  # min_costs / best_pattern: no match of cost <= k
 TEXT_UNCHANGED = 8
 UINT64_MAX = (1 << 64) - 1
 
@@ -130,7 +131,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_multi_new", "sassy_hip_multi_shards", "sassy_hip_multi_device", "sassy_hip_multi_searcher",
     "sassy_hip_multi_set_text", "sassy_hip_multi_generate_dna", "sassy_hip_multi_plant", "sassy_hip_multi_search",
     "sassy_hip_multi_free",
-    "sassy_hip_search_many", "sassy_hip_tsv_header", "sassy_hip_format_tsv",
+    "sassy_hip_search_many", "sassy_hip_min_costs", "sassy_hip_best_pattern", "sassy_hip_tsv_header", "sassy_hip_format_tsv",
     "sassy_hip_result_exit_state", "sassy_hip_result_conditional_index", "sassy_hip_result_free",
     "sassy_hip_encode_patterns", "sassy_hip_encoded_free", "sassy_hip_search_encoded",
     "sassy_hip_multi_set_rc", "sassy_hip_multi_set_replicated", "sassy_hip_multi_search_encoded", "sassy_hip_multi_search_many",
@@ -251,6 +252,9 @@ def lib():
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t,
                                         C.c_uint32, C.POINTER(vp)]
     L.sassy_hip_tsv_header.restype = C.c_char_p
+    for fn, extra in ((L.sassy_hip_min_costs, [vp, vp]), (L.sassy_hip_best_pattern, [vp, vp, vp])):
+        fn.restype = C.c_int
+        fn.argtypes = list(L.sassy_hip_search_many.argtypes[:-1]) + extra
     L.sassy_hip_tsv_header.argtypes = []
     L.sassy_hip_format_tsv.restype = C.c_long
     L.sassy_hip_format_tsv.argtypes = [vp, C.POINTER(_HipMatch), C.c_char_p, C.c_char_p, C.c_char_p, vp, C.c_size_t,
@@ -630,10 +634,11 @@ class Searcher:
                                               ALL_MINIMA if all_minima else 0, cb, None, C.byref(out)))
         return Result(out).matches
 
-    def search_many(self, patterns: Sequence[bytes], texts: Sequence, k: int, all_minima: bool = False, as_result: bool = False):
-        """Searcher::search_many in SearchMode::Single order (src/search.rs:531-560): every pattern in
-        every text, pattern-major; matches carry pattern_idx and text_idx.  as_result: the Result itself (numpy `.array`,
-        `.lazy_matches`) instead of a list of Match objects."""
+    @staticmethod
+    def _marshal_many(patterns: Sequence[bytes], texts: Sequence):
+        """(pattern pointers, pattern lengths, n_patterns, text pointers, text lengths, n_texts, texts on the device, what
+        must stay alive during the call) for the many-pattern calls; `texts` a list or a TextBatch."""
+        held = None
         patterns = [bytes(p) for p in patterns]
         pp = (C.c_char_p * len(patterns))(*patterns)
         pl = (C.c_size_t * len(patterns))(*[len(p) for p in patterns])
@@ -654,6 +659,7 @@ class Searcher:
             lens = np.fromiter(map(len, texts), dtype=np.uint64, count=n_texts)
             tp = addr.ctypes.data_as(C.POINTER(C.c_void_p))
             tl = lens.ctypes.data_as(C.POINTER(C.c_size_t))
+            held = (held, addr, lens)
         else:
             infos = [_ptr_len(t) for t in texts]
             on_dev = [i[3] for i in infos]
@@ -662,11 +668,46 @@ class Searcher:
             n_texts, on_device = len(infos), bool(infos and on_dev[0])
             tp = (C.c_void_p * n_texts)(*[i[0] for i in infos])
             tl = (C.c_size_t * n_texts)(*[i[1] for i in infos])
+            held = infos
+        return pp, pl, len(patterns), tp, tl, n_texts, on_device, (patterns, texts, held, tp, tl)
+
+    def search_many(self, patterns: Sequence[bytes], texts: Sequence, k: int, all_minima: bool = False, as_result: bool = False):
+        """Searcher::search_many in SearchMode::Single order (src/search.rs:531-560): every pattern in
+        every text, pattern-major; matches carry pattern_idx and text_idx.  as_result: the Result itself (numpy `.array`,
+        `.lazy_matches`) instead of a list of Match objects."""
+        pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
         flags = (ALL_MINIMA if all_minima else 0) | (TEXT_ON_DEVICE if on_device else 0)
         out = C.c_void_p()
-        _check(lib().sassy_hip_search_many(self._h, pp, pl, len(patterns), tp, tl, n_texts, k, flags, C.byref(out)))
+        _check(lib().sassy_hip_search_many(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, flags, C.byref(out)))
         r = Result(out)
         return r if as_result else r.matches
+
+    def min_costs(self, patterns: Sequence[bytes], texts: Sequence, k: int, strands: bool = False):
+        """The smallest cost of any match of pattern p in text t (what min(m.cost) over search_many's matches of the pair
+        gives), NO_MATCH (255) where there is none of cost <= k: a numpy uint8 array (n_patterns, n_texts).  strands=True:
+        (costs, strands) -- the strand of each minimum, 0 Fwd / 1 Rc, Fwd on a tie.  A batch of host texts is reduced on
+        the device from the scan's own list: no records, no traceback.  `texts` a list or a TextBatch, as search_many."""
+        import numpy as np
+        pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
+        cost = np.empty((n_patterns, n_texts), dtype=np.uint8)
+        strand = np.empty((n_patterns, n_texts), dtype=np.uint8) if strands else None
+        _check(lib().sassy_hip_min_costs(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, TEXT_ON_DEVICE if on_device else 0,
+                                         cost.ctypes.data, strand.ctypes.data if strands else None))
+        return (cost, strand) if strands else cost
+
+    def best_pattern(self, patterns: Sequence[bytes], texts: Sequence, k: int):
+        """Per text the best pattern: (cost uint8, pattern uint32, strand uint8) arrays of n_texts entries -- the smallest
+        cost over all patterns and strands (NO_MATCH = 255: no match of cost <= k), the pattern that attains it (lowest
+        index on a tie, then Fwd before Rc; 0xFFFFFFFF where there is no match) and its strand.  Demultiplexing, and
+        `filter`: a record is kept when its cost is not NO_MATCH."""
+        import numpy as np
+        pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
+        cost = np.empty(n_texts, dtype=np.uint8)
+        pattern = np.empty(n_texts, dtype=np.uint32)
+        strand = np.empty(n_texts, dtype=np.uint8)
+        _check(lib().sassy_hip_best_pattern(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, TEXT_ON_DEVICE if on_device else 0,
+                                            cost.ctypes.data, pattern.ctypes.data, strand.ctypes.data))
+        return cost, pattern, strand
 
     def search_patterns(self, patterns: Sequence[bytes], text, k: int) -> List[Match]:
         """Searcher::search_patterns (src/search.rs:648-678): equal-length patterns in one text."""

@@ -1,4 +1,4 @@
-"""`python -m sassy_amd search ...` -- the match-table front end of the reference CLI on the GPU path.
+"""`python -m sassy_amd search | filter ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
 
 Mirrors `sassy search` (reference: bin/grep.rs:30-157 arguments, :465-470 header, :623-660 pattern
 sources, :710-757 rows; FASTA/FASTQ records as bin/input_iterator.rs:125-137 reads them): every
@@ -8,7 +8,14 @@ pattern against every record of the given FASTA / FASTQ files (plain or gzip), o
 
 Defaults follow the reference: alphabet iupac, reverse complement on, max_n_frac 0.2.  Rows come
 text record by text record, patterns in input order (the reference's order depends on its thread
-scheduling).  Not mirrored: grep / filter output modes, --v2, threads.
+scheduling).
+
+`filter` mirrors `sassy filter` (bin/grep.rs:660-673): the same pattern and searcher arguments; every input record
+that holds a match of ANY pattern with cost <= k (`-v / --invert`: that holds none) is written to stdout as it was
+read, in input order -- FASTQ records as `@id`, sequence, `+`, quality; FASTA records as `>id` and the sequence on one
+line.  It asks `Searcher.best_pattern` for one cost per record: no match records are made.
+
+Not mirrored: grep output modes, --v2, threads.
 """
 from __future__ import annotations
 
@@ -16,7 +23,7 @@ import argparse
 import sys
 from typing import List, Tuple
 
-from . import Searcher
+from . import NO_MATCH, Searcher
 
 BATCH_BYTES = 64 << 20  # input bytes per search_many call (a longer record is a batch of its own; the reader reuses its buffers)
 
@@ -36,10 +43,8 @@ def load_patterns(args) -> List[Tuple[str, bytes]]:
     raise SystemExit("No --pattern, --pattern-file, or --pattern-fasta provided!")
 
 
-def main(argv=None) -> int:
-    ap = argparse.ArgumentParser(prog="python -m sassy_amd", description=__doc__.split("\n\n")[0])
-    sub = ap.add_subparsers(dest="cmd", required=True)
-    sp = sub.add_parser("search", help="write all matches as TSV to stdout")
+def add_search_arguments(sp) -> None:
+    """The pattern sources and searcher settings `search` and `filter` share (bin/grep.rs:30-157)."""
     g = sp.add_mutually_exclusive_group()
     g.add_argument("-p", "--pattern")
     g.add_argument("-l", "--pattern-file")
@@ -50,12 +55,54 @@ def main(argv=None) -> int:
                     help="cost per base of overhang alignment in [0, 1] (iupac only); default disabled")
     sp.add_argument("--no-rc", action="store_true")
     sp.add_argument("--max-n-frac", type=float, default=0.2)
+
+
+def kept_records(cost, invert: bool):
+    """Indices of the records `filter` writes: those whose best cost is a match (invert: is NO_MATCH), in input order."""
+    import numpy as np
+    cost = np.asarray(cost)
+    return np.flatnonzero((cost == NO_MATCH) if invert else (cost != NO_MATCH))
+
+
+def write_records(out, batch, indices) -> None:
+    """Records `indices` of a RecordBatch to the binary stream `out` in the reference's shape (bin/grep.rs:660-673)."""
+    for i in indices:
+        i = int(i)
+        quality = batch.quality(i)
+        if quality:  # (as the reference: a record with a quality line is written as FASTQ, any other as FASTA)
+            out.write(b"@" + batch.id(i).encode() + b"\n" + batch.sequence(i) + b"\n+\n" + quality + b"\n")
+        else:
+            out.write(b">" + batch.id(i).encode() + b"\n" + batch.sequence(i) + b"\n")
+
+
+def run_filter(args, searcher, pats, out) -> int:
+    for path in args.paths:
+        for batch in read_fastx_batches(path, BATCH_BYTES):
+            if not len(batch):
+                continue
+            cost, _, _ = searcher.best_pattern(pats, batch.texts, args.k)
+            write_records(out, batch, kept_records(cost, args.invert))
+    out.flush()
+    return 0
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m sassy_amd", description=__doc__.split("\n\n")[0])
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    sp = sub.add_parser("search", help="write all matches as TSV to stdout")
+    add_search_arguments(sp)
     sp.add_argument("--sam", action="store_true")
     sp.add_argument("paths", nargs="+")
+    fp = sub.add_parser("filter", help="write the records that hold a match (-v: that hold none) to stdout")
+    add_search_arguments(fp)
+    fp.add_argument("-v", "--invert", action="store_true", help="write the records WITHOUT a match")
+    fp.add_argument("paths", nargs="+")
     args = ap.parse_args(argv)
 
     patterns = load_patterns(args)
     searcher = Searcher(args.alphabet, rc=not args.no_rc, alpha=args.overhang).with_max_n_frac(args.max_n_frac)
+    if args.cmd == "filter":
+        return run_filter(args, searcher, [p for _, p in patterns], sys.stdout.buffer)
     out = sys.stdout
     out.write("pat_id\ttext_id\tcost\tstrand\tstart\tend\tmatch_region\tcigar\n")
     pats = [p for _, p in patterns]

@@ -147,6 +147,23 @@ struct DevBuf {
   }
 };
 
+// sassy_hip_min_costs / _best_pattern in progress (min_costs.hip): where the one-pass batch paths of search_many reduce
+// their (pattern, position, cost) list instead of sorting, reporting and tracing it.  The batch functions fill in the
+// batch's geometry and arm the sink per batch and strand; an unarmed sink leaves the path as search_many runs it.
+struct MinSink {
+  uint32_t* d_cells = nullptr;  // device: per pair [pattern * n_cols + text], per text [text]; 0xFFFFFFFF = no match
+  bool per_text = false;        // cells hold cost << 25 | pattern << 1 | strand (else cost << 1 | strand)
+  uint64_t n_cols = 0;          // texts of the whole call
+  uint64_t n_cells = 0;         // cells of the whole call
+  bool armed = false;           // this batch's lists are reduced here
+  uint64_t col0 = 0;            // the batch's first text
+  uint32_t nt = 0;              // texts in the batch
+  bool flip = false;            // the Rc strand saw the batch reversed as a whole: its text r is text nt - 1 - r
+  uint32_t strand = 0;
+  bool used = false;            // some list was reduced into the cells
+};
+hipError_t launch_min_reduce(const Candidate* d_list, uint32_t count, const TextTable& texts, const MinSink& sink, hipStream_t stream);
+
 }  // namespace sassy_hip
 
 using namespace sassy_hip;
@@ -601,6 +618,10 @@ struct sassy_SearcherType {
   DevBuf<uint8_t> d_tiled_pat;
   DevBuf<uint32_t> d_tiled_cnt, d_tiled_rtext;
   DevBuf<Candidate> d_tiled_sel, d_tiled_list;  // (the list is not a lane's d_cand: its size must not leak into single searches)
+  // best-cost search (min_costs.hip): the 32-bit cells of the device reduction, the narrowed outputs; the call in progress
+  DevBuf<uint32_t> d_min_cells;
+  DevBuf<uint8_t> d_min_out;
+  sassy_hip::MinSink* min_sink = nullptr;
   // seeded search (search_encoded_seeded): the piece tables; sub-piece table, packed text and patterns
   DevBuf<uint32_t> d_seed_start[2], d_seed_entries[2], d_seed_sub, d_seed_packed, d_seed_bits, d_seed_e16;
   // ... on texts with other letters (seeded_dirty_zones): run lists / tables, the gathered neighbourhoods, their scan
@@ -631,6 +652,7 @@ struct sassy_SearcherType {
     free_stage();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
+    d_min_cells.release(); d_min_out.release();
     for (int t = 0; t < 2; ++t) { d_seed_start[t].release(); d_seed_entries[t].release(); }
     d_seed_sub.release(); d_seed_packed.release(); d_seed_bits.release(); d_seed_e16.release();
     d_zone_u64.release(); d_zone_tab.release(); d_zone_peq.release(); d_zone_text.release(); d_zone_list.release();
@@ -1060,6 +1082,8 @@ int search_encoded_overhang(sassy_SearcherType* s, const sassy_hip_Encoded* e, c
                             uint64_t text_len, uint32_t k, bool all, bool wo, sassy_hip_Result* R, bool* done);
 bool many_tiled_wanted(const sassy_SearcherType* s, const size_t* pattern_lens, size_t n_patterns, uint64_t total, size_t k);
 bool acgt_only(const uint8_t* p, size_t n);
+// min_costs.hip
+int reduce_pattern_list(sassy_SearcherType* s, uint32_t count, const TextTable* tt);
 // scan_driver.hip
 int stream_geometry(ScanParams& P, uint64_t owned, uint32_t extra_front, uint32_t* grid, int wpc = 16,
                     GeoTuner* tuner = nullptr, const void* tune_text = nullptr, uint64_t tune_len = 0, uint32_t tune_kind = 0);

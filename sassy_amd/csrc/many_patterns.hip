@@ -408,6 +408,7 @@ int search_encoded_tiled(sassy_SearcherType* s, const sassy_hip_Encoded* e, cons
   s->stats.candidates += count;
   *done = true;
   if (count == 0) return 0;
+  if (s->min_sink && s->min_sink->armed) return reduce_pattern_list(s, count, tt);  // (best-cost search: no records)
   return finish_pattern_list(s, e, plan0, tptr, h_text, text_len, k, all, wo, count, false, R, tt, ht, defer);
 }
 
@@ -998,6 +999,7 @@ int search_encoded_seeded(sassy_SearcherType* s, const sassy_hip_Encoded* e, con
   s->stats.candidates += out_count;
   *done = true;
   if (out_count == 0) return 0;
+  if (s->min_sink && s->min_sink->armed) return reduce_pattern_list(s, out_count, tt);  // (best-cost search: no records)
   return finish_pattern_list(s, e, plan0, tptr, h_text, text_len, k, all, wo, out_count, true, R, tt, ht, defer);
 }
 
@@ -1109,6 +1111,43 @@ static int assemble_many(sassy_SearcherType* s, const ManyDefer& fwd, const Many
   return 0;
 }
 
+// Does the batch in s->d_text hold plain bases (and the 'X' padding) only?
+static int batch_is_plain(sassy_SearcherType* s, uint64_t total, bool* plain) {
+  *plain = false;
+  if (int rc = s->d_ncount.reserve(4)) return rc;
+  HIP_TRY(hipMemsetAsync(s->d_ncount.p, 0, 4, s->stream));
+  hipError_t le = launch_acgt_check(s->d_text.p, total, s->d_ncount.p, s->stream, 1);
+  if (le != hipSuccess) return hip_fail(le, "text check kernel launch");
+  uint32_t bad = 1;
+  HIP_TRY(hipMemcpyAsync(&bad, s->d_ncount.p, 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  *plain = !bad;
+  return 0;
+}
+// Best-cost search (MinSink): may this batch's lists be reduced on the device?  Without the N filter always; with it only
+// a batch of plain bases, which the filter cannot touch (known_plain: the caller has checked already).
+static int arm_min_sink(sassy_SearcherType* s, uint64_t total, bool known_plain, uint64_t col0, size_t nt, bool flip) {
+  MinSink* sink = s->min_sink;
+  if (!sink) return 0;
+  sink->armed = false;
+  if (!sink->d_cells) return 0;
+  bool ok = std::isnan(s->max_n_frac);
+  if (!ok && s->max_n_frac >= 0.0f) {
+    ok = known_plain;
+    if (!ok)
+      if (int rc = batch_is_plain(s, total, &ok)) return rc;
+  }
+  sink->armed = ok;
+  sink->col0 = col0;
+  sink->nt = (uint32_t)nt;
+  sink->flip = flip;
+  return 0;
+}
+struct MinSinkDisarm {  // (a batch function leaves the sink unarmed, whichever way it returns)
+  sassy_SearcherType* s;
+  ~MinSinkDisarm() { if (s->min_sink) s->min_sink->armed = false; }
+};
+
 int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens,
                                size_t n_patterns, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts,
                                size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled, bool tiled_only) {
@@ -1132,6 +1171,7 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
     ~ProfileGuard() { s->profile = saved; }
   } guard{s, s->profile};
   s->profile = PROFILE_IUPAC;
+  MinSinkDisarm disarm{s};
 
   const bool all = (flags & SASSY_HIP_ALL_MINIMA) != 0;
   const bool wo = (flags & SASSY_HIP_WITHOUT_TRACE) != 0;
@@ -1197,16 +1237,8 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
           const double est_tile = (double)total * (double)((n_patterns + 63) / 64) / 2.8e10 + 1.5e-4;
           bool plain = env_seed != 0 && (env_seed > 0 || est_seed < est_tile);
           for (size_t pi = 0; plain && pi < n_patterns; ++pi) plain = acgt_only(patterns[pi], pattern_lens[pi]);
-          if (plain) {
-            if (int rc = s->d_ncount.reserve(4)) return rc;
-            HIP_TRY(hipMemsetAsync(s->d_ncount.p, 0, 4, s->stream));
-            hipError_t le = launch_acgt_check(s->d_text.p, total, s->d_ncount.p, s->stream, 1);
-            if (le != hipSuccess) return hip_fail(le, "text check kernel launch");
-            uint32_t bad = 1;
-            HIP_TRY(hipMemcpyAsync(&bad, s->d_ncount.p, 4, hipMemcpyDeviceToHost, s->stream));
-            HIP_TRY(hipStreamSynchronize(s->stream));
-            plain = !bad;
-          }
+          if (plain)
+            if (int rc = batch_is_plain(s, total, &plain)) return rc;
           seed_batch = plain;
         }
         if (use) {
@@ -1215,13 +1247,17 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
           // the whole call is this one batch, traced, every report is a record: the records are put in order on the
           // device (assemble_many; SASSY_HIP_MANY_ASSEMBLE=0: by the host, as for several batches)
           const bool env_noasm = s->sw.many_assemble == 0;
+          // (best-cost search: the lists are reduced where they lie; a Dna searcher's batch is plain, the host has looked)
+          if (int rc = arm_min_sink(s, total, seed_batch || guard.saved == PROFILE_DNA, t0, nt, true)) return rc;
+          const bool reduce_only = s->min_sink && s->min_sink->armed;  // no records at all: nothing to assemble
           // (the device's sort key packs pattern << 33 | text << 1 | strand into bits 0 .. 58: many_keys_kernel)
-          const bool on_device = !env_noasm && !wo && !all && std::isnan(s->max_n_frac) && !s->only_best && t0 == 0 &&
+          const bool on_device = !reduce_only && !env_noasm && !wo && !all && std::isnan(s->max_n_frac) && !s->only_best && t0 == 0 &&
                                  t1 == n_texts && batch_first == 0 && pool_first == 0 && !R->pin.h &&
                                  (uint64_t)n_patterns < (1ull << 25) && (uint64_t)n_texts < (1ull << 31);
           ManyDefer defer[2];
           defer[1].lane = 1;
           for (int strand = 0; strand < (s->rc ? 2 : 1) && tiled_done; ++strand) {
+            if (s->min_sink) s->min_sink->strand = (uint32_t)strand;
             sassy_hip_Encoded tmp;
             tmp.profile = s->profile;
             tmp.rc = false;
@@ -1258,6 +1294,7 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
           if (tiled_done && on_device) {
             if (int rc = assemble_many(s, defer[0], defer[1], (uint32_t)nt, d_tab + nt, t0, R)) return rc;
           }
+          if (s->min_sink) s->min_sink->armed = false;
           if (!tiled_done) {  // too many end positions for one list: back to one chain per pattern for this batch
             R->matches.resize(batch_first);
             R->pool.resize(pool_first);
@@ -1413,6 +1450,7 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
   if (!overhang && s->profile != PROFILE_ASCII && filterable) return 0;  // search_many_batched takes it
   handled = true;
   if (int rc = s->ensure_device()) return rc;
+  MinSinkDisarm disarm{s};
   const bool all = (flags & SASSY_HIP_ALL_MINIMA) != 0;
   const bool wo = (flags & SASSY_HIP_WITHOUT_TRACE) != 0;
   // virtual columns behind a text's end (overhang): at most max_m; padded with 'N' (any other profile
@@ -1517,16 +1555,8 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
       std::string err;
       if (tiled_ov) {
         bool seed_this = seed_ov;
-        if (seed_this) {  // the seeded search reads Dna codes: the batch must hold plain bases (and the padding) only
-          if (int rc = s->d_ncount.reserve(4)) return rc;
-          HIP_TRY(hipMemsetAsync(s->d_ncount.p, 0, 4, s->stream));
-          hipError_t le = launch_acgt_check(s->d_text.p, total, s->d_ncount.p, s->stream, 1);
-          if (le != hipSuccess) return hip_fail(le, "text check kernel launch");
-          uint32_t bad = 1;
-          HIP_TRY(hipMemcpyAsync(&bad, s->d_ncount.p, 4, hipMemcpyDeviceToHost, s->stream));
-          HIP_TRY(hipStreamSynchronize(s->stream));
-          seed_this = !bad;
-        }
+        if (seed_this)  // the seeded search reads Dna codes: the batch must hold plain bases (and the padding) only
+          if (int rc = batch_is_plain(s, total, &seed_this)) return rc;
         const size_t batch_first = R->matches.size(), pool_first = R->pool.size();
         TextTable tto = tt;
         tto.per_text = 0;
@@ -1538,12 +1568,16 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
         // the whole call is this one batch, traced, every report a record: both strands' records stay on the device and are
         // put in order there (assemble_many: every text was reversed in its own slot -- no index flip)
         const bool env_noasm = s->sw.many_assemble == 0;
-        const bool on_device = !env_noasm && !wo && !all && std::isnan(s->max_n_frac) && !s->only_best && t0 == 0 && t1 == n_texts &&
-                               batch_first == 0 && pool_first == 0 && !R->pin.h && (uint64_t)n_patterns < (1ull << 25) &&
+        // (best-cost search: the lists are reduced where they lie; every text was reversed in its own slot -- no index flip)
+        if (int rc = arm_min_sink(s, total, seed_this, t0, nt, false)) return rc;
+        const bool reduce_only = s->min_sink && s->min_sink->armed;  // no records at all: nothing to assemble
+        const bool on_device = !reduce_only && !env_noasm && !wo && !all && std::isnan(s->max_n_frac) && !s->only_best && t0 == 0 &&
+                               t1 == n_texts && batch_first == 0 && pool_first == 0 && !R->pin.h && (uint64_t)n_patterns < (1ull << 25) &&
                                (uint64_t)n_texts < (1ull << 31);
         ManyDefer defer[2];
         defer[1].lane = 1;
         for (int strand = 0; strand < (s->rc ? 2 : 1) && ok_all; ++strand) {
+          if (s->min_sink) s->min_sink->strand = (uint32_t)strand;
           sassy_hip_Encoded tmp;
           tmp.profile = s->profile;
           tmp.rc = false;
@@ -1574,6 +1608,7 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
             m.text_idx += t0;
           }
         }
+        if (s->min_sink) s->min_sink->armed = false;
         if (ok_all && on_device)
           if (int rc = assemble_many(s, defer[0], defer[1], (uint32_t)nt, d_tab + nt, t0, R, false)) return rc;
         if (ok_all) {

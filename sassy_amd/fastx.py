@@ -29,11 +29,25 @@ NL, CR, GT, AT, PLUS = 10, 13, 62, 64, 43
 
 
 class RecordBatch:
-    """Records of one batch: `texts` (a TextBatch over `buffer`), ids on demand."""
+    """Records of one batch: `texts` (a TextBatch over `buffer`), ids and FASTQ quality lines on demand (offsets into the
+    file's bytes: nothing is copied until somebody asks)."""
 
-    def __init__(self, texts: TextBatch, raw: np.ndarray, id_starts: np.ndarray, id_lens: np.ndarray):
+    def __init__(self, texts: TextBatch, raw: np.ndarray, id_starts: np.ndarray, id_lens: np.ndarray,
+                 qual_starts: Optional[np.ndarray] = None, qual_lens: Optional[np.ndarray] = None):
         self.texts = texts
         self._raw, self._id_starts, self._id_lens = raw, id_starts, id_lens
+        self._qual_starts, self._qual_lens = qual_starts, qual_lens
+
+    @property
+    def is_fastq(self) -> bool:
+        return self._qual_starts is not None
+
+    def quality(self, i: int) -> Optional[bytes]:
+        """The quality line of FASTQ record i (None for FASTA)."""
+        if self._qual_starts is None:
+            return None
+        a, n = int(self._qual_starts[i]), int(self._qual_lens[i])
+        return self._raw[a:a + n].tobytes()
 
     def __len__(self) -> int:
         return len(self.texts)
@@ -86,8 +100,9 @@ def _parse_single_line_records(raw: np.ndarray, lines_per_record: int) -> Option
         return None  # (an empty record followed by a header: not this shape)
     ll = _strip_cr(raw, ls, ll)
     seq_s, seq_l = ls[1::lines_per_record], ll[1::lines_per_record]
+    qual = (ls[3::4], ll[3::4]) if lines_per_record == 4 else (None, None)
     return RecordBatch(TextBatch(raw, seq_s.astype(np.uint64), seq_l.astype(np.uint64)), raw, ls[0::lines_per_record] + 1,
-                       ll[0::lines_per_record] - 1)
+                       ll[0::lines_per_record] - 1, *qual)
 
 
 def _big(n: int):

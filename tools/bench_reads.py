@@ -5,6 +5,11 @@ v2 116.8 GB/s pattern*text with 16 threads).  Synthetic reads: random ACGT, one 
 (<= k edits) per read.
 
     python tools/bench_reads.py [--reads N] [--read-len L] [--patterns P] [--k K]
+
+--min-costs / --best-pattern: the best-cost calls on the same reads and barcodes (same seed) next to search_many and to
+search_many with without_trace + only_best_match (the nearest thing to them among the record calls): wall time of the
+whole call from Python over a TextBatch, warmed, --reps repetitions, median and spread; one JSON line, also written to
+--out (profiles/min_costs_bench.json).
 """
 import argparse
 import json
@@ -20,6 +25,67 @@ import numpy as np  # noqa: E402
 import sassy_amd  # noqa: E402
 
 
+def bench_best_cost(args, pats, texts, total):
+    """Wall time of whole calls over one TextBatch: search_many (records as a numpy array), search_many without trace +
+    only_best_match, and the best-cost calls asked for -- with the device reduction and with min_cost_device = 0."""
+    batch = sassy_amd.TextBatch.from_list(texts)
+    mk = lambda: sassy_amd.Searcher(args.profile, rc=not args.fwd, alpha=args.overhang)
+    plain, best, new, host = mk(), mk().only_best_match(), mk(), mk()
+    host.set_option("min_cost_device", 0)
+    wo_flags = sassy_amd.WITHOUT_TRACE
+
+    def search_many_wo(s):
+        import ctypes as C
+        pp, pl, n_p, tp, tl, n_t, _, _alive = s._marshal_many(pats, batch)
+        out = C.c_void_p()
+        sassy_amd._check(sassy_amd.lib().sassy_hip_search_many(s._h, pp, pl, n_p, tp, tl, n_t, args.k, wo_flags, C.byref(out)))
+        return sassy_amd.Result(out)
+
+    calls = {"search_many": lambda: plain.search_many(pats, batch, args.k, as_result=True),
+             "search_many_without_trace_only_best": lambda: search_many_wo(best)}
+    if args.min_costs:
+        calls["min_costs"] = lambda: new.min_costs(pats, batch, args.k)
+        calls["min_costs_general_path"] = lambda: host.min_costs(pats, batch, args.k)
+    if args.best_pattern:
+        calls["best_pattern"] = lambda: new.best_pattern(pats, batch, args.k)
+        calls["best_pattern_general_path"] = lambda: host.best_pattern(pats, batch, args.k)
+    if args.only_new:
+        calls = {n: f for n, f in calls.items() if n in ("min_costs", "best_pattern")}
+    res = {}
+    for name, f in calls.items():
+        f(); f()  # warm-up: kernels loaded, buffers grown
+        ts = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            r = f()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            del r
+        ts = np.array(ts)
+        res[name] = {"median_ms": round(float(np.median(ts)), 3), "min_ms": round(float(ts.min()), 3), "max_ms": round(float(ts.max()), 3),
+                     "p10_ms": round(float(np.percentile(ts, 10)), 3), "p90_ms": round(float(np.percentile(ts, 90)), 3), "reps": args.reps}
+    for name, s in (("min_costs" if args.min_costs else "best_pattern", new), ("search_many", plain)):
+        if name not in calls:
+            continue
+        s.set_timing(2)
+        calls[name]()
+        st = s.stats()
+        res[name]["kernel_ms_timing_level_2"] = {x: round(st[x], 3) for x in ("scan_ms", "filter_ms", "trace_ms")}
+        res[name]["candidates"] = st["candidates"]
+    doc = {"workload": f"{args.patterns} x {args.pattern_len} bp patterns, {args.reads} reads x {args.read_len} bp ({total / 1e6:.0f} MB), "
+                       f"k={args.k}, {args.profile}, {'forward strand' if args.fwd else 'both strands'}",
+           "what": "wall ms of the whole Python call over a TextBatch, warmed", "calls": res}
+    line = json.dumps(doc)
+    print(line)
+    if args.out:
+        prev = []
+        if os.path.exists(args.out):
+            with open(args.out) as fh:
+                prev = json.load(fh)
+        with open(args.out, "w") as fh:
+            json.dump(prev + [doc], fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=100_000)
@@ -30,6 +96,11 @@ def main():
     ap.add_argument("--profile", default="iupac")
     ap.add_argument("--overhang", type=float, default=None)
     ap.add_argument("--fwd", action="store_true", help="forward strand only (the reference's nanopore bench, evals/src/sassy2/bench.rs)")
+    ap.add_argument("--min-costs", action="store_true", help="time Searcher.min_costs next to search_many")
+    ap.add_argument("--best-pattern", action="store_true", help="time Searcher.best_pattern next to search_many")
+    ap.add_argument("--only-new", action="store_true", help="with --min-costs / --best-pattern: only these calls' device path (a kernel trace of it alone)")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "min_costs_bench.json"))
     args = ap.parse_args()
     rng = np.random.default_rng(7)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -42,6 +113,8 @@ def main():
         flat[r, at[r]:at[r] + args.pattern_len] = p
     texts = [flat[r].tobytes() for r in range(args.reads)]
     total = args.reads * args.read_len
+    if args.min_costs or args.best_pattern:
+        return bench_best_cost(args, pats, texts, total)
     s = sassy_amd.Searcher(args.profile, rc=not args.fwd, alpha=args.overhang)
     s.search_many(pats[:2], texts[:100], args.k)  # warm-up (kernels loaded)
     s.search_many(pats, texts, args.k)             # first full-size call: grows the staging / device buffers
