@@ -71,6 +71,10 @@ extern "C" {
     fn sassy_hip_best_pattern(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
                               texts: *const *const u8, text_lens: *const usize, n_texts: usize, k: usize, flags: u32,
                               out_cost: *mut u8, out_pattern: *mut u32, out_strand: *mut u8) -> c_int;
+    // best matches (include/sassy_hip.h): per text the one best match as a complete record
+    fn sassy_hip_best_matches(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                              texts: *const *const u8, text_lens: *const usize, n_texts: usize, k: usize, flags: u32,
+                              out: *mut *mut RawResult) -> c_int;
     fn sassy_hip_result_len(r: *const RawResult) -> usize;
     fn sassy_hip_result_matches(r: *const RawResult) -> *const RawMatch;
     fn sassy_hip_result_cigars(r: *const RawResult) -> *const c_char;
@@ -296,6 +300,20 @@ impl<P: Profile> Searcher<P> {
         };
         assert_eq!(rc, 0, "{}", last_error());
         (0..texts.len()).map(|t| (cost[t], pat[t], if strand[t] != 0 { Strand::Rc } else { Strand::Fwd })).collect()
+    }
+
+    /// Per text the one best match over all patterns and strands as a complete record: lowest cost, then lowest pattern
+    /// index, then Fwd before Rc, then the rightmost end in the strand's scan direction (the reference's `only_best_match`
+    /// rule, src/search.rs:1392-1412).  At most one `Match` per text, in ascending `text_idx`.
+    pub fn best_matches(&mut self, patterns: &[&[u8]], texts: &[&[u8]], k: usize) -> Vec<Match> {
+        let (pp, pl): (Vec<*const u8>, Vec<usize>) = patterns.iter().map(|p| (p.as_ptr(), p.len())).unzip();
+        let (tp, tl): (Vec<*const u8>, Vec<usize>) = texts.iter().map(|t| (t.as_ptr(), t.len())).unzip();
+        let mut res = std::ptr::null_mut();
+        let rc = unsafe {
+            sassy_hip_best_matches(self.raw, pp.as_ptr(), pl.as_ptr(), pp.len(), tp.as_ptr(), tl.as_ptr(), tp.len(), k, 0, &mut res)
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        unsafe { collect(res) }
     }
 
     /// A stream of searches over a text that lives in HBM: queue one and go on (up to two in flight).

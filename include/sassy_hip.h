@@ -257,6 +257,36 @@ int sassy_hip_best_pattern(sassy_SearcherType *s, const uint8_t *const *patterns
                            size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
                            size_t k, uint32_t flags, uint8_t *out_cost, uint32_t *out_pattern, uint8_t *out_strand);
 
+/* Best matches: per text the one best match over all patterns and strands, as a complete record -- where best_pattern
+ * says which pattern, at what cost and on which strand, this also says where.
+ * Definition (for every searcher configuration): take R = the records sassy_hip_search_many returns for the same
+ * searcher with only_best_match off and default flags.  The best match of text t is the record of R with text_idx == t
+ * that is smallest under this order:
+ *   1. lowest cost;  2. lowest pattern_idx;  3. Fwd before Rc;
+ *   4. the rightmost end in the strand's scan direction: the largest text_end for Fwd, the smallest text_start for Rc
+ *      (the Rc strand is scanned on the reversed text) -- the reference's only_best_match rule, "rightmost match with
+ *      minimal cost", src/search.rs:1392-1412.  (Overhang searchers: of two matches that end behind the text's end the
+ *      one that hangs over further, i.e. with the smaller pattern_end, ends further right.)
+ * Rules 1-3 are best_pattern's tie rule: (cost, pattern_idx, strand) of the result equal best_pattern's output text by
+ * text.  A text with no match of cost <= k has no record.  The record is complete and byte for byte what search_many
+ * carries for that match: text_start, text_end, pattern_start, pattern_end, cost, strand, cigar, pattern_idx, text_idx.
+ * *out is an ordinary result (sassy_hip_result_free) with at most n_texts records in ascending text_idx.
+ *  - flags: SASSY_HIP_TEXT_ON_DEVICE as for search_many, SASSY_HIP_WITHOUT_TRACE (end and cost only, as elsewhere: no
+ *    cigar, text_start / pattern_start and the far text coordinate UINT64_MAX); anything else SASSY_HIP_EINVAL;
+ *  - k > 254: SASSY_HIP_EINVAL; Ascii with rc: SASSY_HIP_EUNSUPPORTED; max_n_frac set: only matches that pass the N
+ *    filter count; the searcher's only_best_match setting does not change the answer;
+ *  - refused while tickets are open, like the other synchronous entry points.
+ * The device path (sassy_amd/csrc/best_matches.hip) takes the call where best_pattern's device reduction does -- a batch
+ * of >= 2 host texts, patterns of one length <= 64, 2k + 3 <= 64, not Ascii, fewer than 2^24 patterns, through the
+ * one-pass paths -- when max_n_frac is unset, every text is shorter than 2^31 - 128 and the batch is the whole call (at
+ * most 1 GiB laid out): the scan's list is reduced to one 64-bit cell per text that keeps the winning end position, one
+ * candidate per text goes straight to the traceback (no sort, no report rule), and one record and cigar per text come
+ * back in the pinned block the result keeps.  Everything else runs search_many and reduces its records on the host by
+ * the order above; option best_match_device = 0: always that general path. */
+int sassy_hip_best_matches(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                           size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
+                           size_t k, uint32_t flags, sassy_hip_Result **out);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is

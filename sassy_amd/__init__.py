@@ -131,7 +131,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_multi_new", "sassy_hip_multi_shards", "sassy_hip_multi_device", "sassy_hip_multi_searcher",
     "sassy_hip_multi_set_text", "sassy_hip_multi_generate_dna", "sassy_hip_multi_plant", "sassy_hip_multi_search",
     "sassy_hip_multi_free",
-    "sassy_hip_search_many", "sassy_hip_min_costs", "sassy_hip_best_pattern", "sassy_hip_tsv_header", "sassy_hip_format_tsv",
+    "sassy_hip_search_many", "sassy_hip_min_costs", "sassy_hip_best_pattern", "sassy_hip_best_matches", "sassy_hip_tsv_header", "sassy_hip_format_tsv",
     "sassy_hip_result_exit_state", "sassy_hip_result_conditional_index", "sassy_hip_result_free",
     "sassy_hip_encode_patterns", "sassy_hip_encoded_free", "sassy_hip_search_encoded",
     "sassy_hip_multi_set_rc", "sassy_hip_multi_set_replicated", "sassy_hip_multi_search_encoded", "sassy_hip_multi_search_many",
@@ -255,6 +255,8 @@ def lib():
     for fn, extra in ((L.sassy_hip_min_costs, [vp, vp]), (L.sassy_hip_best_pattern, [vp, vp, vp])):
         fn.restype = C.c_int
         fn.argtypes = list(L.sassy_hip_search_many.argtypes[:-1]) + extra
+    L.sassy_hip_best_matches.restype = C.c_int
+    L.sassy_hip_best_matches.argtypes = list(L.sassy_hip_search_many.argtypes)
     L.sassy_hip_tsv_header.argtypes = []
     L.sassy_hip_format_tsv.restype = C.c_long
     L.sassy_hip_format_tsv.argtypes = [vp, C.POINTER(_HipMatch), C.c_char_p, C.c_char_p, C.c_char_p, vp, C.c_size_t,
@@ -708,6 +710,21 @@ class Searcher:
         _check(lib().sassy_hip_best_pattern(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, TEXT_ON_DEVICE if on_device else 0,
                                             cost.ctypes.data, pattern.ctypes.data, strand.ctypes.data))
         return cost, pattern, strand
+
+    def best_matches(self, patterns: Sequence[bytes], texts: Sequence, k: int, as_result: bool = False, without_trace: bool = False):
+        """Per text the one best match over all patterns and strands, as a complete record (where best_pattern says which
+        pattern, this also says where): of search_many's records of a text -- only_best_match off -- the one with the
+        lowest cost, then the lowest pattern_idx, then Fwd before Rc, then the rightmost end in the strand's scan
+        direction (largest text_end for Fwd, smallest text_start for Rc).  At most one Match per text, ascending text_idx;
+        a text without a match of cost <= k has none.  A batch of host texts is reduced and traced on the device: one
+        traceback per text.  without_trace: end and cost only.  as_result: the Result itself.  `texts` a list or a
+        TextBatch, as search_many."""
+        pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
+        flags = (WITHOUT_TRACE if without_trace else 0) | (TEXT_ON_DEVICE if on_device else 0)
+        out = C.c_void_p()
+        _check(lib().sassy_hip_best_matches(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, flags, C.byref(out)))
+        r = Result(out)
+        return r if as_result else r.matches
 
     def search_patterns(self, patterns: Sequence[bytes], text, k: int) -> List[Match]:
         """Searcher::search_patterns (src/search.rs:648-678): equal-length patterns in one text."""

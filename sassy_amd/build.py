@@ -38,6 +38,7 @@ UNITS = [
     ("multi_device.hip", "multi_device.o", []),
     ("all_alignments.hip", "all_alignments.o", []),
     ("min_costs.hip", "min_costs.o", []),
+    ("best_matches.hip", "best_matches.o", []),
     ("c_abi.hip", "c_abi.o", []),
 ]
 HEADERS = ["common.h", "profiles.h", "tiled_step.h", "switches.h", "pass_planner.h", "host_internal.h", os.path.join("..", "..", "include", "sassy.h"),

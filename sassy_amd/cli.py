@@ -15,6 +15,9 @@ that holds a match of ANY pattern with cost <= k (`-v / --invert`: that holds no
 read, in input order -- FASTQ records as `@id`, sequence, `+`, quality; FASTA records as `>id` and the sequence on one
 line.  It asks `Searcher.best_pattern` for one cost per record: no match records are made.
 
+`search --best` writes at most one row per record: its best match over all patterns and strands (lowest cost, then
+the first pattern, then the forward strand, then the rightmost end), through `Searcher.best_matches`.
+
 Not mirrored: grep output modes, --v2, threads.
 """
 from __future__ import annotations
@@ -92,6 +95,8 @@ def main(argv=None) -> int:
     sp = sub.add_parser("search", help="write all matches as TSV to stdout")
     add_search_arguments(sp)
     sp.add_argument("--sam", action="store_true")
+    sp.add_argument("--best", action="store_true",
+                    help="at most one row per record: its best match over all patterns and strands (Searcher.best_matches)")
     sp.add_argument("paths", nargs="+")
     fp = sub.add_parser("filter", help="write the records that hold a match (-v: that hold none) to stdout")
     add_search_arguments(fp)
@@ -116,7 +121,10 @@ def main(argv=None) -> int:
         for batch in read_fastx_batches(path, BATCH_BYTES):
             if not len(batch):
                 continue
-            res = searcher.search_many(pats, batch.texts, args.k, as_result=True)
+            if args.best:  # (one record per text at most, in text order already)
+                res = searcher.best_matches(pats, batch.texts, args.k, as_result=True)
+            else:
+                res = searcher.search_many(pats, batch.texts, args.k, as_result=True)
             arr = res.array
             order = np.lexsort((np.arange(len(arr)), arr["pattern_idx"], arr["text_idx"]))  # stable: keeps each pair's match order
             ms = res.lazy_matches

@@ -96,7 +96,7 @@ hipError_t launch_tiled_pertext(const TiledParams& P, hipStream_t stream);
 size_t many_scratch_bytes(uint32_t count);
 hipError_t launch_assemble_many(const ManyPart& a, const ManyPart& b, uint32_t n_texts, const uint64_t* d_text_len,
                                 uint64_t first_text, uint32_t str_stride, MatchOut* d_rows, char* d_strs, uint32_t* d_flags,
-                                void* d_scratch, size_t scratch_bytes, hipStream_t stream, int flip = 1);
+                                void* d_scratch, size_t scratch_bytes, hipStream_t stream, int flip = 1, int text_major = 0);
 hipError_t launch_assign_texts(Candidate* d_rep, uint32_t count, const TextTable& texts, uint32_t* d_report_text,
                                hipStream_t stream);
 hipError_t launch_keep_interior(const Candidate* d_rec, uint32_t count, const TextTable& texts, uint32_t edge, unsigned char* d_keep,
@@ -161,7 +161,23 @@ struct MinSink {
   bool flip = false;            // the Rc strand saw the batch reversed as a whole: its text r is text nt - 1 - r
   uint32_t strand = 0;
   bool used = false;            // some list was reduced into the cells
+  // sassy_hip_best_matches (best_matches.hip): one 64-bit cell per text that keeps the winning end position too; when both
+  // strands of the batch are reduced, the batch function traces one candidate per cell (finish_best_matches)
+  unsigned long long* d_located = nullptr;  // device: [text]; all ones = no match.  != nullptr: this is the call
+  bool without_trace = false;   // end and cost only: the records are made from the cells by the host
+  bool located = false;         // the result holds the best matches, one record per text that has one
 };
+hipError_t launch_locate_reduce(const Candidate* d_list, uint32_t count, const TextTable& texts, const MinSink& sink, hipStream_t stream);
+// every non-empty cell of texts [col0, col0 + nt) -> the candidate the traceback tail takes, per strand: cand[strand][i] /
+// rtext[strand][i] (the text's index in that strand's table), i < d_count[strand] (zeroed by the caller)
+hipError_t launch_best_candidates(const unsigned long long* d_cells, uint32_t nt, const TextTable& fwd, const TextTable& rcs, uint32_t flip,
+                                  Candidate* d_cand, uint32_t* d_rtext, uint32_t* d_count, hipStream_t stream);
+// a cell's fields (the key's layout: best_matches.hip)
+constexpr unsigned long long kNoLocated = ~0ull;
+inline uint32_t located_cost(unsigned long long c) { return (uint32_t)(c >> 56); }
+inline uint32_t located_pattern(unsigned long long c) { return (uint32_t)(c >> 32) & 0xFFFFFFu; }
+inline uint32_t located_strand(unsigned long long c) { return (uint32_t)(c >> 31) & 1u; }
+inline uint64_t located_end(unsigned long long c) { return 0x7FFFFFFFull - (c & 0x7FFFFFFFull); }
 hipError_t launch_min_reduce(const Candidate* d_list, uint32_t count, const TextTable& texts, const MinSink& sink, hipStream_t stream);
 
 }  // namespace sassy_hip
@@ -622,6 +638,11 @@ struct sassy_SearcherType {
   DevBuf<uint32_t> d_min_cells;
   DevBuf<uint8_t> d_min_out;
   sassy_hip::MinSink* min_sink = nullptr;
+  // best_matches (best_matches.hip): the 64-bit cells; both strands' candidates, their texts and patterns for the traceback
+  DevBuf<unsigned long long> d_best_cells;
+  DevBuf<Candidate> d_best_cand;
+  DevBuf<uint32_t> d_best_rtext;
+  DevBuf<uint8_t> d_best_pat;
   // seeded search (search_encoded_seeded): the piece tables; sub-piece table, packed text and patterns
   DevBuf<uint32_t> d_seed_start[2], d_seed_entries[2], d_seed_sub, d_seed_packed, d_seed_bits, d_seed_e16;
   // ... on texts with other letters (seeded_dirty_zones): run lists / tables, the gathered neighbourhoods, their scan
@@ -653,6 +674,7 @@ struct sassy_SearcherType {
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();
+    d_best_cells.release(); d_best_cand.release(); d_best_rtext.release(); d_best_pat.release();
     for (int t = 0; t < 2; ++t) { d_seed_start[t].release(); d_seed_entries[t].release(); }
     d_seed_sub.release(); d_seed_packed.release(); d_seed_bits.release(); d_seed_e16.release();
     d_zone_u64.release(); d_zone_tab.release(); d_zone_peq.release(); d_zone_text.release(); d_zone_list.release();

@@ -5,6 +5,77 @@
 
 namespace sassy_hip {
 
+// The traceback of a report list of many patterns: one wavefront per report (or a thread per report for dense lists), the
+// report's pattern comes with it in its flags; records and cigar strings stay in LT's buffers.  The launch lies between the
+// searcher's two "multi" events.
+static int trace_reports(sassy_SearcherType* s, const uint8_t* tptr, uint64_t text_len, uint32_t m, uint32_t k, const Candidate* d_rep,
+                         const uint32_t* d_count, uint32_t n_rep, const uint8_t* d_patterns, const TextTable* tt,
+                         const uint32_t* d_rtext, ScanLane& LT, uint32_t* str_stride_out) {
+  hipStream_t st = s->stream;
+  uint32_t str_stride = 0;
+  {
+    const TraceShape ts = trace_shape(m, k);  // (the callers made sure of 2k + 3 <= 64: one-byte cells)
+    const uint64_t strb = ts.str;
+    str_stride = (uint32_t)strb;
+    if ((uint64_t)n_rep * strb > 0xFFFFFFFFull)
+      return fail(SASSY_HIP_EUNSUPPORTED, "cigar pool of one result exceeds 4 GiB");
+    if (int rc = LT.d_trace.reserve(n_rep)) return rc;
+    if (int rc = LT.d_str.reserve((size_t)n_rep * strb)) return rc;
+    TraceParams T{};
+    T.text = tptr;
+    T.total_len = text_len;
+    T.cand = d_rep;
+    T.cand_count = d_count;
+    T.cand_cap = n_rep;
+    T.m = m;
+    T.k = k;
+    T.profile = (uint32_t)s->profile;
+    T.pattern = d_patterns;
+    T.pattern_stride = m;
+    T.scratch_stride = (uint32_t)ts.wave_stride;
+    T.band_bytes = (uint32_t)ts.band;
+    T.win_bytes = (uint32_t)ts.win;
+    T.out = LT.d_trace.p;
+    T.out_str = LT.d_str.p;
+    T.str_stride = str_stride;
+    T.ops_bytes = (uint32_t)ts.ops;
+    T.wave_mode = 1;
+    T.count_min = 0;
+    T.count_max = 0xFFFFFFFFu;
+    T.max_overhang = 0xFFFFFFFFu;
+    if (!std::isnan(s->alpha)) {  // overhang (the one-pass search of a batch: search_many_pertext)
+      T.use_alpha = 1u;
+      T.alpha = s->alpha;
+      T.max_overhang = s->max_overhang >= 0 ? (uint32_t)std::min<long>(s->max_overhang, 0x7FFFFFFF) : 0xFFFFFFFFu;
+    }
+    if (tt) {
+      T.texts = *tt;
+      T.report_text = d_rtext;
+    }
+    HIP_TRY(hipEventRecord(s->ev_a_multi(), st));
+    uint32_t trace_grid = (uint32_t)std::min<uint64_t>(1024, ((uint64_t)n_rep + 3) / 4);
+    {
+      // Dense lists (a guide set on a genome: 10^7 reports) with a narrow band (k <= 6: the band row in registers): a
+      // thread per report, as many workgroups as the chip holds -- 0.7 ns per report against the wavefront shape's 2.3.
+      // (SASSY_HIP_ENCODED_TRACE_THREADS=0: never; =<n>: from n reports on -- read per call: tests flip it)
+      const int env_tt = (int)s->sw.encoded_trace_threads;
+      const bool env_off = env_tt == 0;
+      const uint32_t from = env_tt > 0 ? (uint32_t)env_tt : 65536u;
+      if (!env_off && k <= 6 && !T.use_alpha && n_rep >= from && ts.thread_in_lds) {
+        T.wave_mode = 0;
+        T.scratch = nullptr;
+        T.scratch_stride = (uint32_t)ts.thread_stride;
+        trace_grid = (uint32_t)(ts.thread_count / 64);
+      }
+    }
+    hipError_t le = launch_trace(T, trace_grid, st);
+    if (le != hipSuccess) return hip_fail(le, "trace kernel launch");
+    HIP_TRY(hipEventRecord(s->ev_multi, st));
+  }
+  *str_stride_out = str_stride;
+  return 0;
+}
+
 static int finish_pattern_list(sassy_SearcherType* s, const sassy_hip_Encoded* e, const PatternPlan& plan0,
                                const uint8_t* tptr, const uint8_t* h_text, uint64_t text_len, uint32_t k, bool all,
                                bool wo, uint32_t count, bool copies, sassy_hip_Result* R,
@@ -57,64 +128,10 @@ static int finish_pattern_list(sassy_SearcherType* s, const sassy_hip_Encoded* e
   std::string pool;
   uint32_t str_stride = 0;
   if (!wo) {
-    const TraceShape ts = trace_shape(m, k);  // (the callers made sure of 2k + 3 <= 64: one-byte cells)
-    const uint64_t strb = ts.str;
-    str_stride = (uint32_t)strb;
-    if ((uint64_t)n_rep * strb > 0xFFFFFFFFull)
-      return fail(SASSY_HIP_EUNSUPPORTED, "cigar pool of one result exceeds 4 GiB");
+    const uint64_t strb = trace_shape(m, k).str;
     ScanLane& LT = defer ? s->lanes[defer->lane] : L;  // (the same stream: only the buffers are the other lane's)
-    if (int rc = LT.d_trace.reserve(n_rep)) return rc;
-    if (int rc = LT.d_str.reserve((size_t)n_rep * strb)) return rc;
-    TraceParams T{};
-    T.text = tptr;
-    T.total_len = text_len;
-    T.cand = d_rep;
-    T.cand_count = s->d_tiled_cnt.p + 1;
-    T.cand_cap = n_rep;
-    T.m = m;
-    T.k = k;
-    T.profile = (uint32_t)s->profile;
-    T.pattern = s->d_tiled_pat.p;
-    T.pattern_stride = m;
-    T.scratch_stride = (uint32_t)ts.wave_stride;
-    T.band_bytes = (uint32_t)ts.band;
-    T.win_bytes = (uint32_t)ts.win;
-    T.out = LT.d_trace.p;
-    T.out_str = LT.d_str.p;
-    T.str_stride = str_stride;
-    T.ops_bytes = (uint32_t)ts.ops;
-    T.wave_mode = 1;
-    T.count_min = 0;
-    T.count_max = 0xFFFFFFFFu;
-    T.max_overhang = 0xFFFFFFFFu;
-    if (!std::isnan(s->alpha)) {  // overhang (the one-pass search of a batch: search_many_pertext)
-      T.use_alpha = 1u;
-      T.alpha = s->alpha;
-      T.max_overhang = s->max_overhang >= 0 ? (uint32_t)std::min<long>(s->max_overhang, 0x7FFFFFFF) : 0xFFFFFFFFu;
-    }
-    if (tt) {
-      T.texts = *tt;
-      T.report_text = s->d_tiled_rtext.p;
-    }
-    HIP_TRY(hipEventRecord(s->ev_a_multi(), st));
-    uint32_t trace_grid = (uint32_t)std::min<uint64_t>(1024, ((uint64_t)n_rep + 3) / 4);
-    {
-      // Dense lists (a guide set on a genome: 10^7 reports) with a narrow band (k <= 6: the band row in registers): a
-      // thread per report, as many workgroups as the chip holds -- 0.7 ns per report against the wavefront shape's 2.3.
-      // (SASSY_HIP_ENCODED_TRACE_THREADS=0: never; =<n>: from n reports on -- read per call: tests flip it)
-      const int env_tt = (int)s->sw.encoded_trace_threads;
-      const bool env_off = env_tt == 0;
-      const uint32_t from = env_tt > 0 ? (uint32_t)env_tt : 65536u;
-      if (!env_off && k <= 6 && !T.use_alpha && n_rep >= from && ts.thread_in_lds) {
-        T.wave_mode = 0;
-        T.scratch = nullptr;
-        T.scratch_stride = (uint32_t)ts.thread_stride;
-        trace_grid = (uint32_t)(ts.thread_count / 64);
-      }
-    }
-    le = launch_trace(T, trace_grid, st);
-    if (le != hipSuccess) return hip_fail(le, "trace kernel launch");
-    HIP_TRY(hipEventRecord(s->ev_multi, st));
+    if (int rc = trace_reports(s, tptr, text_len, m, k, d_rep, s->d_tiled_cnt.p + 1, n_rep, s->d_tiled_pat.p, tt,
+                               tt ? s->d_tiled_rtext.p : nullptr, LT, &str_stride)) return rc;
     if (defer) {
       defer->part = ManyPart{LT.d_trace.p, reinterpret_cast<const char*>(LT.d_str.p), n_rep};
       defer->str_stride = str_stride;
@@ -1069,7 +1086,8 @@ bool many_tiled_wanted(const sassy_SearcherType* s, const size_t* pattern_lens, 
 // the records through vectors, an append, a loop per strand and a stable sort of 64-byte rows: 35 of the 49 ms of
 // 96 barcodes x 330 000 reads.
 static int assemble_many(sassy_SearcherType* s, const ManyDefer& fwd, const ManyDefer& rcd, uint32_t n_texts,
-                         const uint64_t* d_text_len, uint64_t first_text, sassy_hip_Result* R, bool flip = true) {
+                         const uint64_t* d_text_len, uint64_t first_text, sassy_hip_Result* R, bool flip = true,
+                         bool text_major = false) {
   const uint64_t n = (uint64_t)fwd.part.n + rcd.part.n;
   if (n == 0) return 0;
   if (n > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "more than 2^32 records in one result");
@@ -1084,7 +1102,8 @@ static int assemble_many(sassy_SearcherType* s, const ManyDefer& fwd, const Many
   if (int rc = L.d_flags.reserve(4)) return rc;
   HIP_TRY(hipMemsetAsync(L.d_flags.p, 0, 4, st));
   hipError_t le = launch_assemble_many(fwd.part, rcd.part, n_texts, d_text_len, first_text, strb, LO.d_trace.p,
-                                       reinterpret_cast<char*>(LO.d_str.p), L.d_flags.p, L.d_sort.p, L.d_sort.cap, st, flip ? 1 : 0);
+                                       reinterpret_cast<char*>(LO.d_str.p), L.d_flags.p, L.d_sort.p, L.d_sort.cap, st, flip ? 1 : 0,
+                                       text_major ? 1 : 0);
   if (le != hipSuccess) return hip_fail(le, "result assembly launch");
   const size_t rows_off = 256, strs_off = (rows_off + n * sizeof(MatchOut) + 255) / 256 * 256;
   const size_t bytes = strs_off + n * strb + 256;
@@ -1126,13 +1145,16 @@ static int batch_is_plain(sassy_SearcherType* s, uint64_t total, bool* plain) {
 }
 // Best-cost search (MinSink): may this batch's lists be reduced on the device?  Without the N filter always; with it only
 // a batch of plain bases, which the filter cannot touch (known_plain: the caller has checked already).
-static int arm_min_sink(sassy_SearcherType* s, uint64_t total, bool known_plain, uint64_t col0, size_t nt, bool flip) {
+// (best_matches -- a locating sink -- only when the batch is the whole call: its records go into the result's one pinned block)
+static int arm_min_sink(sassy_SearcherType* s, uint64_t total, bool known_plain, uint64_t col0, size_t nt, bool flip, bool whole_call) {
   MinSink* sink = s->min_sink;
   if (!sink) return 0;
   sink->armed = false;
-  if (!sink->d_cells) return 0;
+  if (!sink->d_cells && !sink->d_located) return 0;
   bool ok = std::isnan(s->max_n_frac);
-  if (!ok && s->max_n_frac >= 0.0f) {
+  if (sink->d_located) {
+    ok = ok && whole_call;
+  } else if (!ok && s->max_n_frac >= 0.0f) {
     ok = known_plain;
     if (!ok)
       if (int rc = batch_is_plain(s, total, &ok)) return rc;
@@ -1147,6 +1169,75 @@ struct MinSinkDisarm {  // (a batch function leaves the sink unarmed, whichever 
   sassy_SearcherType* s;
   ~MinSinkDisarm() { if (s->min_sink) s->min_sink->armed = false; }
 };
+
+// sassy_hip_best_matches (best_matches.hip): both strands' lists of the batch are reduced to one 64-bit cell per text.  Every
+// non-empty cell becomes the candidate the traceback tail takes -- strand, pattern, absolute end position, cost; no sort, no
+// report rule: the rightmost end position at the smallest cost is one the report rule reports --, split per
+// strand (the Rc strand's are traced on the reversed buffer with the complemented patterns), and assemble_many puts the
+// records in text order into the pinned block the result keeps.  Without trace: the records are made from the cells here.
+static int finish_best_matches(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                               uint32_t k, uint64_t total, const TextTable& tt_fwd, const TextTable& tt_rc, const size_t* text_lens,
+                               bool flip, sassy_hip_Result* R) {
+  MinSink* sink = s->min_sink;
+  const uint32_t nt = sink->nt, m = (uint32_t)pattern_lens[0];
+  const unsigned long long* d_cells = sink->d_located + sink->col0;
+  hipStream_t st = s->stream;
+  sink->located = true;
+  if (!sink->used) return 0;  // (no end position of cost <= k in any text)
+  if (sink->without_trace) {  // (reference: src/search.rs:1464-1475, 859-873 -- as append_matches and the strand loops make them)
+    std::vector<unsigned long long> cells(nt);
+    HIP_TRY(hipMemcpyAsync(cells.data(), d_cells, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t t = 0; t < nt; ++t) {
+      const unsigned long long c = cells[t];
+      if (c == kNoLocated) continue;
+      const uint64_t len = text_lens[t], end = located_end(c), inside = std::min(end, len);
+      sassy_hip_Match r{};
+      r.pattern_idx = located_pattern(c);
+      r.text_idx = sink->col0 + t;
+      r.strand = (uint8_t)located_strand(c);
+      r.text_start = r.strand ? len - inside : UINT64_MAX;
+      r.text_end = r.strand ? UINT64_MAX : inside;
+      r.pattern_start = UINT64_MAX;
+      r.pattern_end = m - (end > len ? std::min<uint64_t>(end - len, m) : 0);
+      r.cost = (int32_t)located_cost(c);
+      R->matches.push_back(r);
+    }
+    if (R->pool.empty()) R->pool.push_back('\0');
+    return 0;
+  }
+  if (int rc = s->d_best_cand.reserve(2 * (size_t)nt)) return rc;
+  if (int rc = s->d_best_rtext.reserve(2 * (size_t)nt)) return rc;
+  if (int rc = s->d_best_pat.reserve(2 * n_patterns * (size_t)m + 64)) return rc;
+  if (int rc = s->d_tiled_cnt.reserve(16)) return rc;
+  uint32_t* d_count = s->d_tiled_cnt.p + 2;
+  HIP_TRY(hipMemsetAsync(d_count, 0, 8, st));
+  hipError_t le = launch_best_candidates(d_cells, nt, tt_fwd, tt_rc, flip ? 1u : 0u, s->d_best_cand.p, s->d_best_rtext.p, d_count, st);
+  if (le != hipSuccess) return hip_fail(le, "best-match candidates launch");
+  uint32_t n[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(n, d_count, 8, hipMemcpyDeviceToHost, st));
+  std::vector<uint8_t> flat(2 * n_patterns * (size_t)m);  // both strands' patterns: as given, complemented
+  for (size_t pi = 0; pi < n_patterns; ++pi)
+    for (uint32_t j = 0; j < m; ++j) {
+      flat[pi * m + j] = patterns[pi][j];
+      flat[(n_patterns + pi) * m + j] = complement_char(s->profile, patterns[pi][j]);
+    }
+  HIP_TRY(hipMemcpyAsync(s->d_best_pat.p, flat.data(), flat.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (n[0] > nt || n[1] > nt) return fail(SASSY_HIP_EINVAL, "internal: more best-match candidates than texts");
+  ManyDefer defer[2];
+  defer[1].lane = 1;
+  for (int strand = 0; strand < 2; ++strand) {
+    if (n[strand] == 0) continue;
+    if (strand && !s->rc) return fail(SASSY_HIP_EINVAL, "internal: an Rc candidate of a forward search");
+    if (int rc = trace_reports(s, strand ? s->d_rev.p : s->d_text.p, total, m, k, s->d_best_cand.p + (size_t)strand * nt, d_count + strand,
+                               n[strand], s->d_best_pat.p + (size_t)strand * n_patterns * m, strand ? &tt_rc : &tt_fwd,
+                               s->d_best_rtext.p + (size_t)strand * nt, s->lanes[defer[strand].lane], &defer[strand].str_stride)) return rc;
+    ScanLane& LT = s->lanes[defer[strand].lane];
+    defer[strand].part = ManyPart{LT.d_trace.p, reinterpret_cast<const char*>(LT.d_str.p), n[strand]};
+  }
+  return assemble_many(s, defer[0], defer[1], nt, tt_fwd.len, sink->col0, R, flip, true);
+}
 
 int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens,
                                size_t n_patterns, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts,
@@ -1248,7 +1339,7 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
           // device (assemble_many; SASSY_HIP_MANY_ASSEMBLE=0: by the host, as for several batches)
           const bool env_noasm = s->sw.many_assemble == 0;
           // (best-cost search: the lists are reduced where they lie; a Dna searcher's batch is plain, the host has looked)
-          if (int rc = arm_min_sink(s, total, seed_batch || guard.saved == PROFILE_DNA, t0, nt, true)) return rc;
+          if (int rc = arm_min_sink(s, total, seed_batch || guard.saved == PROFILE_DNA, t0, nt, true, t0 == 0 && t1 == n_texts)) return rc;
           const bool reduce_only = s->min_sink && s->min_sink->armed;  // no records at all: nothing to assemble
           // (the device's sort key packs pattern << 33 | text << 1 | strand into bits 0 .. 58: many_keys_kernel)
           const bool on_device = !reduce_only && !env_noasm && !wo && !all && std::isnan(s->max_n_frac) && !s->only_best && t0 == 0 &&
@@ -1294,6 +1385,8 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
           if (tiled_done && on_device) {
             if (int rc = assemble_many(s, defer[0], defer[1], (uint32_t)nt, d_tab + nt, t0, R)) return rc;
           }
+          if (tiled_done && reduce_only && s->min_sink->d_located)
+            if (int rc = finish_best_matches(s, patterns, pattern_lens, n_patterns, (uint32_t)k, total, tt, tt_rev, text_lens + t0, true, R)) return rc;
           if (s->min_sink) s->min_sink->armed = false;
           if (!tiled_done) {  // too many end positions for one list: back to one chain per pattern for this batch
             R->matches.resize(batch_first);
@@ -1569,7 +1662,7 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
         // put in order there (assemble_many: every text was reversed in its own slot -- no index flip)
         const bool env_noasm = s->sw.many_assemble == 0;
         // (best-cost search: the lists are reduced where they lie; every text was reversed in its own slot -- no index flip)
-        if (int rc = arm_min_sink(s, total, seed_this, t0, nt, false)) return rc;
+        if (int rc = arm_min_sink(s, total, seed_this, t0, nt, false, t0 == 0 && t1 == n_texts)) return rc;
         const bool reduce_only = s->min_sink && s->min_sink->armed;  // no records at all: nothing to assemble
         const bool on_device = !reduce_only && !env_noasm && !wo && !all && std::isnan(s->max_n_frac) && !s->only_best && t0 == 0 &&
                                t1 == n_texts && batch_first == 0 && pool_first == 0 && !R->pin.h && (uint64_t)n_patterns < (1ull << 25) &&
@@ -1608,6 +1701,8 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
             m.text_idx += t0;
           }
         }
+        if (ok_all && reduce_only && s->min_sink->d_located)
+          if (int rc = finish_best_matches(s, patterns, pattern_lens, n_patterns, (uint32_t)k, total, tto, tto, text_lens + t0, false, R)) return rc;
         if (s->min_sink) s->min_sink->armed = false;
         if (ok_all && on_device)
           if (int rc = assemble_many(s, defer[0], defer[1], (uint32_t)nt, d_tab + nt, t0, R, false)) return rc;

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void min_narrow_texts_kernel(const uint32_t* _
 // The list of one strand's pass over a batch (s->d_tiled_list, `count` entries) into the cells of the call in progress.
 int reduce_pattern_list(sassy_SearcherType* s, uint32_t count, const TextTable* tt) {
   MinSink* sink = s->min_sink;
-  if (!sink || !sink->armed || !sink->d_cells || !tt || tt->n == 0)
+  if (!sink || !sink->armed || (!sink->d_cells && !sink->d_located) || !tt || tt->n == 0)
     return fail(SASSY_HIP_EINVAL, "internal: list reduction without a batch of texts");
   MinReduceParams P{};
   P.list = s->d_tiled_list.p;
@@ -110,8 +110,15 @@ int reduce_pattern_list(sassy_SearcherType* s, uint32_t count, const TextTable* 
   hipStream_t st = s->stream;
   const bool timed = s->timing >= 2;
   if (timed) HIP_TRY(hipEventRecord(s->ev_a_multi(), st));
-  hipLaunchKernelGGL(min_reduce_kernel, dim3((uint32_t)(((uint64_t)count + 255) / 256)), dim3(256), 0, st, P);  // (lists hold at most 2^28 + 2^27 entries)
-  hipError_t le = hipGetLastError();
+  hipError_t le;
+  if (sink->d_located) {  // (best_matches: the cell keeps the end position too -- best_matches.hip)
+    MinSink one = *sink;
+    one.flip = P.flip != 0;
+    le = launch_locate_reduce(P.list, count, *tt, one, st);
+  } else {
+    hipLaunchKernelGGL(min_reduce_kernel, dim3((uint32_t)(((uint64_t)count + 255) / 256)), dim3(256), 0, st, P);  // (lists hold at most 2^28 + 2^27 entries)
+    le = hipGetLastError();
+  }
   if (le != hipSuccess) return hip_fail(le, "list reduction launch");
   if (timed) {
     HIP_TRY(hipEventRecord(s->ev_multi, st));

@@ -149,14 +149,15 @@ __global__ __launch_bounds__(256) void assign_texts_kernel(Candidate* __restrict
 // coordinates count from the text's end (src/search.rs:859-873).
 // (flip: the Rc pass saw the batch reversed AS A WHOLE -- its text r is text n_texts - 1 - r; else every text was reversed
 // in its own slot: the per-text layout of the overhang searches)
-__global__ __launch_bounds__(256) void many_keys_kernel(const ManyPart a, const ManyPart b, uint32_t n_texts, int flip,
+// (text_major: the key is (text, strand) alone -- best_matches: one record per text, in text order)
+__global__ __launch_bounds__(256) void many_keys_kernel(const ManyPart a, const ManyPart b, uint32_t n_texts, int flip, int text_major,
                                                         unsigned long long* __restrict__ keys, uint32_t* __restrict__ idx) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n + b.n) return;
   const bool rc = i >= a.n;
   const MatchOut* row = rc ? b.rows + (i - a.n) : a.rows + i;
   const unsigned long long text = (rc && flip) ? (unsigned long long)(n_texts - 1) - row->text_idx : row->text_idx;
-  keys[i] = (row->pattern_idx << 33) | (text << 1) | (rc ? 1ull : 0ull);
+  keys[i] = (text_major ? 0ull : row->pattern_idx << 33) | (text << 1) | (rc ? 1ull : 0ull);
   idx[i] = i;
 }
 
@@ -590,7 +591,7 @@ size_t many_scratch_bytes(uint32_t count) {
 }
 hipError_t launch_assemble_many(const ManyPart& a, const ManyPart& b, uint32_t n_texts, const uint64_t* d_text_len,
                                 uint64_t first_text, uint32_t str_stride, MatchOut* d_rows, char* d_strs, uint32_t* d_flags,
-                                void* d_scratch, size_t scratch_bytes, hipStream_t stream, int flip) {
+                                void* d_scratch, size_t scratch_bytes, hipStream_t stream, int flip, int text_major) {
   const uint32_t count = a.n + b.n;
   if (count == 0) return hipSuccess;
   const size_t kb = ((size_t)count * 8 + 255) / 256 * 256, ib = ((size_t)count * 4 + 255) / 256 * 256;
@@ -602,7 +603,7 @@ hipError_t launch_assemble_many(const ManyPart& a, const ManyPart& b, uint32_t n
   uint32_t* idx_out = reinterpret_cast<uint32_t*>(base + 2 * kb + ib);
   void* temp = base + 2 * kb + 2 * ib;
   size_t temp_bytes = scratch_bytes - (2 * kb + 2 * ib);
-  hipLaunchKernelGGL(many_keys_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, a, b, n_texts, flip, keys_in, idx_in);
+  hipLaunchKernelGGL(many_keys_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, a, b, n_texts, flip, text_major, keys_in, idx_in);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, idx_in, idx_out, (size_t)count, 0, 58, stream);

@@ -10,6 +10,10 @@ v2 116.8 GB/s pattern*text with 16 threads).  Synthetic reads: random ACGT, one 
 search_many with without_trace + only_best_match (the nearest thing to them among the record calls): wall time of the
 whole call from Python over a TextBatch, warmed, --reps repetitions, median and spread; one JSON line, also written to
 --out (profiles/min_costs_bench.json).
+
+--best-matches: Searcher.best_matches (default shape: 330 000 reads) next to the two ways to the same answer without it --
+search_many followed by the host's reduction of its records, and search_many on an only_best_match searcher followed by
+the same reduction -- and to best_pattern, the lower bound; --out defaults to profiles/best_matches_bench.json.
 """
 import argparse
 import json
@@ -86,9 +90,78 @@ def bench_best_cost(args, pats, texts, total):
             fh.write("\n")
 
 
+def reduce_to_best(arr):
+    """The best record per text of a search_many result by best_matches' definition, as row indices (numpy on the host:
+    what a user does without the call)."""
+    rc = arr["strand"].astype(bool)
+    end = np.where(rc, arr["text_start"].astype(np.int64), -arr["text_end"].astype(np.int64))
+    order = np.lexsort((end, arr["strand"], arr["pattern_idx"], arr["cost"], arr["text_idx"]))
+    ti = arr["text_idx"][order]
+    first = np.ones(len(order), dtype=bool)
+    first[1:] = ti[1:] != ti[:-1]
+    return order[first]
+
+
+def bench_best_matches(args, pats, texts, total):
+    batch = sassy_amd.TextBatch.from_list(texts)
+    mk = lambda: sassy_amd.Searcher(args.profile, rc=not args.fwd, alpha=args.overhang)
+    plain, only_best, new, host, lower = mk(), mk().only_best_match(), mk(), mk(), mk()
+    host.set_option("best_match_device", 0)
+
+    def via(s):
+        r = s.search_many(pats, batch, args.k, as_result=True)
+        return r, reduce_to_best(r.array)
+
+    calls = {"search_many_then_host_reduction": lambda: via(plain),
+             "search_many_only_best_match_then_host_reduction": lambda: via(only_best),
+             "best_matches": lambda: new.best_matches(pats, batch, args.k, as_result=True),
+             "best_matches_without_trace": lambda: new.best_matches(pats, batch, args.k, as_result=True, without_trace=True),
+             "best_matches_general_path": lambda: host.best_matches(pats, batch, args.k, as_result=True),
+             "best_pattern": lambda: lower.best_pattern(pats, batch, args.k)}
+    if args.only_new:
+        calls = {"best_matches": calls["best_matches"]}
+    else:  # the same answer all ways
+        r, idx = via(plain)
+        want = r.array[idx]
+        for name in ("best_matches", "best_matches_general_path"):
+            got = calls[name]().array
+            for f in ("text_idx", "pattern_idx", "cost", "strand", "text_start", "text_end", "pattern_start", "pattern_end", "cigar_len"):
+                assert np.array_equal(got[f], want[f]), (name, f)
+    res = {}
+    for name, f in calls.items():
+        f(); f()  # warm-up: kernels loaded, buffers grown
+        ts = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            r = f()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            del r
+        ts = np.array(ts)
+        res[name] = {"median_ms": round(float(np.median(ts)), 3), "min_ms": round(float(ts.min()), 3), "max_ms": round(float(ts.max()), 3),
+                     "p10_ms": round(float(np.percentile(ts, 10)), 3), "p90_ms": round(float(np.percentile(ts, 90)), 3), "reps": args.reps}
+    new.set_timing(2)
+    n = len(calls["best_matches"]())
+    st = new.stats()
+    res["best_matches"]["records"] = n
+    res["best_matches"]["candidates"] = st["candidates"]
+    res["best_matches"]["kernel_ms_timing_level_2"] = {x: round(st[x], 3) for x in ("scan_ms", "filter_ms", "trace_ms")}
+    doc = {"workload": f"{args.patterns} x {args.pattern_len} bp patterns, {args.reads} reads x {args.read_len} bp ({total / 1e6:.0f} MB), "
+                       f"k={args.k}, {args.profile}, {'forward strand' if args.fwd else 'both strands'}",
+           "what": "wall ms of the whole Python call over a TextBatch, warmed", "calls": res}
+    print(json.dumps(doc))
+    if args.out:
+        prev = []
+        if os.path.exists(args.out):
+            with open(args.out) as fh:
+                prev = json.load(fh)
+        with open(args.out, "w") as fh:
+            json.dump(prev + [doc], fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reads", type=int, default=100_000)
+    ap.add_argument("--reads", type=int, default=None, help="default 100 000; 330 000 with --best-matches")
     ap.add_argument("--read-len", type=int, default=1000)
     ap.add_argument("--patterns", type=int, default=96)
     ap.add_argument("--pattern-len", type=int, default=24)
@@ -98,10 +171,15 @@ def main():
     ap.add_argument("--fwd", action="store_true", help="forward strand only (the reference's nanopore bench, evals/src/sassy2/bench.rs)")
     ap.add_argument("--min-costs", action="store_true", help="time Searcher.min_costs next to search_many")
     ap.add_argument("--best-pattern", action="store_true", help="time Searcher.best_pattern next to search_many")
-    ap.add_argument("--only-new", action="store_true", help="with --min-costs / --best-pattern: only these calls' device path (a kernel trace of it alone)")
+    ap.add_argument("--best-matches", action="store_true", help="time Searcher.best_matches next to search_many + host reduction")
+    ap.add_argument("--only-new", action="store_true", help="with --min-costs / --best-pattern / --best-matches: only these calls' device path (a kernel trace of it alone)")
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "min_costs_bench.json"))
+    ap.add_argument("--out", default=None, help="default profiles/min_costs_bench.json; profiles/best_matches_bench.json with --best-matches")
     args = ap.parse_args()
+    if args.reads is None:
+        args.reads = 330_000 if args.best_matches else 100_000
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "best_matches_bench.json" if args.best_matches else "min_costs_bench.json")
     rng = np.random.default_rng(7)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
     pats = [bytes(acgt[rng.integers(0, 4, args.pattern_len)]) for _ in range(args.patterns)]
@@ -113,6 +191,8 @@ def main():
         flat[r, at[r]:at[r] + args.pattern_len] = p
     texts = [flat[r].tobytes() for r in range(args.reads)]
     total = args.reads * args.read_len
+    if args.best_matches:
+        return bench_best_matches(args, pats, texts, total)
     if args.min_costs or args.best_pattern:
         return bench_best_cost(args, pats, texts, total)
     s = sassy_amd.Searcher(args.profile, rc=not args.fwd, alpha=args.overhang)

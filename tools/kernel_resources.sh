@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/kernel_resources.sh [unit ...] -- VGPRs / scratch / occupancy of every kernel (hipcc -Rpass-analysis=kernel-resource-usage)
 cd "$(dirname "$0")/../sassy_amd/csrc"
-units=${@:-"scan_kernel.hip:1 scan_kernel.hip:2 scan_kernel.hip:0 count_filter.hip trace_kernel.hip aux_kernels.hip seed_kernels.hip tiled_kernel.hip sort_kernels.hip min_costs.hip"}
+units=${@:-"scan_kernel.hip:1 scan_kernel.hip:2 scan_kernel.hip:0 count_filter.hip trace_kernel.hip aux_kernels.hip seed_kernels.hip tiled_kernel.hip sort_kernels.hip min_costs.hip best_matches.hip"}
 for u in $units; do
   f=${u%%:*}; d=""; [[ "$u" == *:* ]] && d="-DSASSY_SCAN_PROFILE=${u##*:}"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $d -Rpass-analysis=kernel-resource-usage -c $f -o /tmp/kr_$$.o 2>&1 | python3 -c "
