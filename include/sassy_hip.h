@@ -33,6 +33,11 @@ extern "C" {
                                        previous call with this pointer and length (many patterns, one resident
                                        text): the reversed copy the Rc strand scans is reused, not rebuilt */
 
+#define SASSY_HIP_LINE_SPANS 16u    /* sassy_hip_search only: also resolve every match to the lines it lies in, while the text
+                                       is still resident (sassy_hip_result_line_spans); every other call that takes flags
+                                       refuses the bit with SASSY_HIP_EUNSUPPORTED, and so does sassy_hip_search together with
+                                       SASSY_HIP_WITHOUT_TRACE (no match start to resolve) */
+
 /* Full match record = reference Match (src/search.rs:35-62).  cigar is the SAM text the
  * reference's Cigar::to_string gives ("3=1X"), stored in the result's string pool.
  * without_trace: text_start = pattern_start = UINT64_MAX and an empty cigar, as the reference. */
@@ -50,6 +55,19 @@ typedef struct sassy_hip_Match {
                          are unspecified) */
   uint32_t cigar_len;
 } sassy_hip_Match;
+
+/* Where a span [first, last] of text positions lies, line-wise; '\n' (0x0A) is the only separator.  For a position p of a
+ * text t of n bytes: line_no(p) = 1 + the number of '\n' in t[0:p]; line_start(p) = 1 + the index of the last '\n' in
+ * t[0:p], 0 if there is none; line_end(p) = the index of the first '\n' in t[p:n], n if there is none.  The line of the
+ * span is t[line_start:line_end) (without its '\n'); a span that contains newlines has last_line_no > line_no. */
+typedef struct sassy_hip_LineSpan {
+  uint64_t line_no;      /* line_no(first), 1-based */
+  uint64_t last_line_no; /* line_no(last) */
+  uint64_t line_start;   /* line_start(first) */
+  uint64_t line_end;     /* line_end(last) */
+} sassy_hip_LineSpan;
+/* The line index counts newlines per tile of this many text bytes (sassy_hip_line_tile() returns the same). */
+#define SASSY_HIP_LINE_TILE 4096u
 
 typedef struct sassy_hip_Result sassy_hip_Result;       /* opaque, owns matches + cigar pool */
 typedef struct sassy_hip_Encoded sassy_hip_Encoded;     /* opaque EncodedPatterns */
@@ -101,6 +119,10 @@ int sassy_hip_device_count(void); /* number of visible HIP devices, 0 if none / 
  * pattern may hang over either end of the text at alpha per overhanging character: matches then
  * carry pattern_start > 0 / pattern_end < pattern_len.  Overhang searches stream the full DP (the
  * pigeonhole prefilter does not cover partial patterns) and report nothing for an empty text. */
+/* Alphabets: "dna", "iupac", "ascii" (src/c.rs:52-70) and "ascii_ci", in any letter case.  "ascii_ci" is the reference's
+ * CaseInsensitiveAscii (src/profiles.rs:5): two bytes match iff u8::eq_ignore_ascii_case -- only A-Z and a-z fold, every
+ * other byte (0x80-0xFF included) matches only itself -- in the scan and in the traceback alike.  It is accepted wherever
+ * "ascii" is and behaves like it otherwise (no reverse complement, no overhang, the general search paths). */
 sassy_SearcherType *sassy_hip_searcher_new(const char *alphabet, bool rc, float alpha);
 /* The HIP device a searcher works on.  A searcher binds itself to the calling thread's current device at its first
  * search (HIP's current device is per host thread); sassy_hip_set_device chooses one before that.  From then on
@@ -175,6 +197,21 @@ int sassy_hip_set_max_n_frac(sassy_SearcherType *s, float max_n_frac);
 int sassy_hip_search(sassy_SearcherType *s, const uint8_t *pattern, size_t pattern_len,
                      const uint8_t *text, size_t text_len, size_t k, uint32_t flags,
                      sassy_hip_Result **out);
+
+/* Line resolution on the device (sassy_amd/csrc/line_index.hip): out[i] = the span of [first[i], last[i]] in the text, for
+ * n spans with first[i] <= last[i] <= text_len (anything else: SASSY_HIP_EINVAL; last == text_len is the empty position
+ * behind the text).  A match [text_start, text_end) is the span first = text_start, last = max(text_start, text_end - 1).
+ * flags: SASSY_HIP_TEXT_ON_DEVICE (a device pointer as for sassy_hip_search) or 0 (the text is uploaded); first, last and
+ * out are host arrays.  One pass over the text counts the newlines per tile, a second launch resolves all spans, one
+ * wavefront each, at a cost that does not depend on the length of the lines.  n == 0: success, nothing is launched.
+ * The index is rebuilt by every call.  sassy_hip_search with SASSY_HIP_LINE_SPANS does the same for its own matches
+ * (sassy_hip_result_line_spans: one span per record, parallel to sassy_hip_result_matches; NULL without the flag);
+ * sassy_hip_merge_shards does not carry spans. */
+int sassy_hip_line_spans(sassy_SearcherType *s, const void *text, size_t text_len, uint32_t flags, const uint64_t *first,
+                         const uint64_t *last, size_t n, sassy_hip_LineSpan *out);
+uint32_t sassy_hip_line_tile(void);
+/* HIP-event times (ms) of the last line-span call's index pass (count + scan) and resolve pass; timing level 2. */
+int sassy_hip_line_span_times(const sassy_SearcherType *s, double *index_ms, double *resolve_ms);
 
 /* Searcher::search_all_alignments (src/search.rs:702-760, src/alignment_iterator.rs:44-370; Python: src/python.rs:117-135):
  * every alignment of cost <= k at every end position that search_all without trace reports under this searcher's
@@ -436,6 +473,7 @@ int sassy_hip_set_pipe_depth(sassy_SearcherType *s, int depth);
 
 size_t sassy_hip_result_len(const sassy_hip_Result *r);
 const sassy_hip_Match *sassy_hip_result_matches(const sassy_hip_Result *r);
+const sassy_hip_LineSpan *sassy_hip_result_line_spans(const sassy_hip_Result *r); /* NULL unless SASSY_HIP_LINE_SPANS was set */
 const char *sassy_hip_result_cigars(const sassy_hip_Result *r); /* string pool */
 size_t sassy_hip_result_cigars_len(const sassy_hip_Result *r);   /* bytes in the pool */
 /* Wire format of the multi-GPU match gather (sassy_amd/multigpu.py): one row of 7 + cigar_bytes/8

@@ -34,6 +34,7 @@ WITHOUT_TRACE = 2
 TEXT_ON_DEVICE = 4
 NO_MATCH = 255  # min_costs / best_pattern: no match of cost <= k
 TEXT_UNCHANGED = 8
+LINE_SPANS = 16  # sassy_hip_search only: resolve the matches to their lines (Result.line_spans)
 UINT64_MAX = (1 << 64) - 1
 
 
@@ -66,6 +67,16 @@ class _HipMatch(C.Structure):
         ("pad_", C.c_uint8 * 3),
         ("cigar_off", C.c_uint32),
         ("cigar_len", C.c_uint32),
+    ]
+
+
+class LineSpan(C.Structure):
+    """include/sassy_hip.h: sassy_hip_LineSpan (32 bytes)."""
+    _fields_ = [
+        ("line_no", C.c_uint64),
+        ("last_line_no", C.c_uint64),
+        ("line_start", C.c_uint64),
+        ("line_end", C.c_uint64),
     ]
 
 
@@ -138,6 +149,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_multi_set_pipe_depth", "sassy_hip_multi_search_begin", "sassy_hip_multi_search_finish", "sassy_hip_multi_layout", "sassy_hip_seed_layout", "sassy_hip_seed_test_rows",
     "sassy_hip_generate_dna", "sassy_hip_generate_genome_like", "sassy_hip_plant",
     "sassy_hip_malloc", "sassy_hip_free", "sassy_hip_memcpy_h2d", "sassy_hip_memcpy_d2h",
+    "sassy_hip_line_spans", "sassy_hip_result_line_spans", "sassy_hip_line_tile", "sassy_hip_line_span_times",
 ]
 
 _lib = None
@@ -316,6 +328,15 @@ def lib():
     L.sassy_hip_plant_phase.restype = C.c_int
     L.sassy_hip_plant_phase.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u8p, sz, sz,
                                         C.c_uint64, C.c_uint64, vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "sassy_hip_line_spans"):
+        L.sassy_hip_line_spans.restype = C.c_int
+        L.sassy_hip_line_spans.argtypes = [vp, vp, sz, C.c_uint32, vp, vp, sz, vp]
+        L.sassy_hip_result_line_spans.restype = vp
+        L.sassy_hip_result_line_spans.argtypes = [vp]
+        L.sassy_hip_line_tile.restype = C.c_uint32
+        L.sassy_hip_line_tile.argtypes = []
+        L.sassy_hip_line_span_times.restype = C.c_int
+        L.sassy_hip_line_span_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sassy_hip_malloc.restype = vp
     L.sassy_hip_malloc.argtypes = [sz]
     L.sassy_hip_free.restype = None
@@ -364,6 +385,17 @@ def match_dtype():
                      ("cigar_off", "<u4"), ("cigar_len", "<u4")])
 
 
+def line_span_dtype():
+    """numpy view of include/sassy_hip.h: sassy_hip_LineSpan (32 bytes)."""
+    import numpy as np
+    return np.dtype([("line_no", "<u8"), ("last_line_no", "<u8"), ("line_start", "<u8"), ("line_end", "<u8")])
+
+
+def line_tile() -> int:
+    """Text bytes per tile of the device's line index (sassy_hip_line_tile)."""
+    return lib().sassy_hip_line_tile()
+
+
 def _bytes_at(addr, size: int) -> bytes:
     """`size` bytes at a C address (ctypes.string_at takes an int-sized length: results above 2 GiB need the array form)."""
     if not size:
@@ -380,7 +412,7 @@ class Result:
     ``pool`` the cigar string pool; ``matches`` materialises reference-style Match objects on
     first use (a Python object per match is far slower than the search itself)."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, flags: int = 0):
         # The C call has left the finished records on the host (sassy_hip_Result); they are copied into
         # Python objects only when somebody looks at them (`array`, `pool`, `matches`).
         L = lib()
@@ -391,6 +423,8 @@ class Result:
         self._array = None
         self._pool = None
         self._matches = None
+        self._line_spans = None
+        self._flags = flags  # of the call: LINE_SPANS decides whether `line_spans` is an array (empty, too) or None
 
     def _materialise(self):
         if self._array is not None:
@@ -406,6 +440,9 @@ class Result:
             plen = L.sassy_hip_result_cigars_len(h)
             pool = L.sassy_hip_result_cigars(h)
             self._pool = _bytes_at(pool, plen)
+            if self._flags & LINE_SPANS:  # (an empty result has no array to point at: n == 0 reads nothing)
+                spans = L.sassy_hip_result_line_spans(h)
+                self._line_spans = np.frombuffer(_bytes_at(spans, n * 32), dtype=line_span_dtype())
         finally:
             L.sassy_hip_result_free(h)
 
@@ -423,6 +460,13 @@ class Result:
         """The C match array copied once into a numpy structured array (match_dtype)."""
         self._materialise()
         return self._array
+
+    @property
+    def line_spans(self):
+        """The matches' lines as a numpy structured array (line_span_dtype), parallel to `array` -- None unless the search
+        ran with LINE_SPANS (Searcher.search_lines)."""
+        self._materialise()
+        return self._line_spans
 
     @property
     def pool(self) -> bytes:
@@ -596,6 +640,30 @@ class Searcher:
 
     def search_without_trace(self, pattern: bytes, text, k: int) -> List[Match]:
         return self._search(pattern, text, k, WITHOUT_TRACE).matches
+
+    def line_spans(self, text, first, last):
+        """Where the spans [first[i], last[i]] of text positions lie, line-wise ('\\n' is the only separator): a numpy
+        structured array (line_span_dtype) -- line_no / last_line_no (1-based) of the two ends, line_start of the first,
+        line_end of the last; text[line_start:line_end] is the line without its newline.  first <= last <= len(text); a
+        match is the span (text_start, max(text_start, text_end - 1)).  Resolved on the device (csrc/line_index.hip) in one
+        pass over the text plus one wavefront per span.  `text` as for `search`: bytes, numpy, or a device tensor."""
+        import numpy as np
+        addr, n, keep, on_dev = _ptr_len(text)
+        first = np.ascontiguousarray(first, dtype=np.uint64)
+        last = np.ascontiguousarray(last, dtype=np.uint64)
+        if first.shape != last.shape or first.ndim != 1:
+            raise SassyHipError("line_spans: first and last must be one-dimensional and of one length")
+        out = np.empty(len(first), dtype=line_span_dtype())
+        _check(lib().sassy_hip_line_spans(self._h, addr, n, TEXT_ON_DEVICE if on_dev else 0, first.ctypes.data, last.ctypes.data,
+                                          len(first), out.ctypes.data))
+        return out
+
+    def search_lines(self, pattern: bytes, text, k: int, all_minima: bool = False):
+        """`search` (or `search_all`) plus the line every match lies in: (matches, spans) -- spans as `line_spans` gives
+        them, parallel to the matches, resolved by the same call while the text is resident (a host text is uploaded
+        once)."""
+        r = self._search(pattern, text, k, LINE_SPANS | (ALL_MINIMA if all_minima else 0))
+        return r.matches, r.line_spans
 
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k
@@ -896,7 +964,7 @@ class Searcher:
                 flags |= TEXT_UNCHANGED
         out = C.c_void_p()
         _check(lib().sassy_hip_search(self._h, pattern, len(pattern), addr, n, k, flags, C.byref(out)))
-        return Result(out)
+        return Result(out, flags)
 
 
 def required_halo(pattern_len: int, k: int) -> int:

@@ -27,6 +27,7 @@ UNITS = [
     ("scan_kernel.hip", "scan_ascii.o", ["-DSASSY_SCAN_PROFILE=0"]),
     ("scan_kernel.hip", "scan_dna.o", ["-DSASSY_SCAN_PROFILE=1"]),
     ("scan_kernel.hip", "scan_iupac.o", ["-DSASSY_SCAN_PROFILE=2"]),
+    ("scan_kernel.hip", "scan_ascii_ci.o", ["-DSASSY_SCAN_PROFILE=4"]),
     ("count_filter.hip", "count_filter.o", []),
     ("aux_kernels.hip", "aux_kernels.o", []),
     ("sort_kernels.hip", "sort_kernels.o", []),
@@ -39,6 +40,7 @@ UNITS = [
     ("all_alignments.hip", "all_alignments.o", []),
     ("min_costs.hip", "min_costs.o", []),
     ("best_matches.hip", "best_matches.o", []),
+    ("line_index.hip", "line_index.o", []),
     ("c_abi.hip", "c_abi.o", []),
 ]
 HEADERS = ["common.h", "profiles.h", "tiled_step.h", "switches.h", "pass_planner.h", "host_internal.h", os.path.join("..", "..", "include", "sassy.h"),

@@ -18,7 +18,14 @@ line.  It asks `Searcher.best_pattern` for one cost per record: no match records
 `search --best` writes at most one row per record: its best match over all patterns and strands (lowest cost, then
 the first pattern, then the forward strand, then the rightmost end), through `Searcher.best_matches`.
 
-Not mirrored: grep output modes, --v2, threads.
+`agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
+files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
+one block per match, sorted by (start, end): `PATH:LINE:COL:COST:` and the line(s) the match lies in -- LINE and the line's
+bounds come from the device (`Searcher.search_lines`), COL is the 1-based byte column of the match's start.  `-C N` adds up to
+N lines of context as `PATH-LINE-` rows, `--` between blocks that do not touch.  The per-cost histogram goes to stderr.
+Exit status 0: something matched, 1: nothing did, 2: error.
+
+Not mirrored: coloured output, --v2, threads.
 """
 from __future__ import annotations
 
@@ -26,7 +33,7 @@ import argparse
 import sys
 from typing import List, Tuple
 
-from . import NO_MATCH, Searcher
+from . import NO_MATCH, SassyHipError, Searcher
 
 BATCH_BYTES = 64 << 20  # input bytes per search_many call (a longer record is a batch of its own; the reader reuses its buffers)
 
@@ -53,7 +60,8 @@ def add_search_arguments(sp) -> None:
     g.add_argument("-l", "--pattern-file")
     g.add_argument("-f", "--pattern-fasta")
     sp.add_argument("-k", type=int, required=True)
-    sp.add_argument("-a", "--alphabet", choices=["dna", "iupac"], default="iupac")
+    sp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac", "ascii", "ascii_ci"], default="iupac",
+                    help="ascii / ascii_ci (case-insensitive) have no reverse complement: they are searched forward only")
     sp.add_argument("--overhang", type=float, default=None,
                     help="cost per base of overhang alignment in [0, 1] (iupac only); default disabled")
     sp.add_argument("--no-rc", action="store_true")
@@ -89,9 +97,122 @@ def run_filter(args, searcher, pats, out) -> int:
     return 0
 
 
+def _line_after(text: bytes, end: int):
+    """(start, end) of the line behind the one that ends at `end` (the index of its newline, or len(text)); None at the
+    end of the text -- a final newline opens no further line."""
+    start = end + 1
+    if start >= len(text):
+        return None
+    stop = text.find(b"\n", start)
+    return start, len(text) if stop < 0 else stop
+
+
+def _line_before(text: bytes, start: int):
+    """(start, end) of the line in front of the one that begins at `start`; None at the start of the text."""
+    if start == 0:
+        return None
+    return text.rfind(b"\n", 0, start - 1) + 1, start - 1
+
+
+def format_agrep(path: str, text: bytes, matches, spans, context: int = 0) -> str:
+    """The agrep blocks of one file.  `matches`: records with text_start / text_end / cost; `spans`: their line spans
+    (line_no, last_line_no, line_start, line_end; Searcher.search_lines), parallel.  Blocks come by (text_start,
+    text_end).  A match row is `PATH:LINE:COL:COST:` and text[line_start:line_end] (a match across a newline shows all its
+    lines).  context > 0: up to that many lines in front of and behind the match's lines as `PATH-LINE-` rows, found by
+    walking outward from the span; a line is shown as context once and never behind its own match row; `--` stands between
+    two blocks whose lines do not touch."""
+    order = sorted(range(len(matches)), key=lambda i: (matches[i].text_start, matches[i].text_end))
+    out = []
+    shown = 0  # the last line number written
+    for at, i in enumerate(order):
+        m = matches[i]
+        line_no, last_line_no = int(spans[i]["line_no"]), int(spans[i]["last_line_no"])
+        line_start, line_end = int(spans[i]["line_start"]), int(spans[i]["line_end"])
+        before = []
+        pos, no = line_start, line_no
+        while len(before) < context and no - 1 > shown:
+            prev = _line_before(text, pos)
+            if prev is None:
+                break
+            no -= 1
+            before.append((no, prev))
+            pos = prev[0]
+        first_row = before[-1][0] if before else line_no
+        if context and shown and first_row > shown + 1:
+            out.append("--\n")
+        for no, (a, b) in reversed(before):
+            out.append(f"{path}-{no}-{text[a:b].decode(errors='replace')}\n")
+        col = m.text_start - line_start + 1
+        out.append(f"{path}:{line_no}:{col}:{m.cost}:{text[line_start:line_end].decode(errors='replace')}\n")
+        shown = max(shown, last_line_no)
+        # lines behind the match, up to the next match's own line
+        stop_at = int(spans[order[at + 1]]["line_no"]) if at + 1 < len(order) else None
+        pos, no = line_end, last_line_no
+        for _ in range(context):
+            nxt = _line_after(text, pos)
+            if nxt is None or (stop_at is not None and no + 1 >= stop_at):
+                break
+            no += 1
+            if no > shown:
+                out.append(f"{path}-{no}-{text[nxt[0]:nxt[1]].decode(errors='replace')}\n")
+                shown = no
+            pos = nxt[1]
+    return "".join(out)
+
+
+def format_histogram(hist) -> str:
+    """The per-cost statistics the reference's agrep prints last (bin/grep.rs:309-328), without the bold type."""
+    digits = len(str(max(hist, default=0)))
+    return (f"\nStatistics: total {sum(hist)}\n"
+            "dist: " + "".join(f"{i:>{digits}} " for i in range(len(hist))) + "\n"
+            "cnt:  " + "".join(f"{c:>{digits}} " for c in hist) + "\n")
+
+
+def agrep_parser(sub=None):
+    doc = "fuzzy search of plain text files: one block per match, PATH:LINE:COL:COST:line"
+    ap = sub.add_parser("agrep", help=doc) if sub is not None else argparse.ArgumentParser(prog="python -m sassy_amd agrep", description=doc)
+    ap.add_argument("-i", "--ignore-case", action="store_true", help="the ascii_ci profile: A-Z and a-z match each other")
+    ap.add_argument("-C", "--context", type=int, default=0, metavar="N", help="lines of context around every match")
+    ap.add_argument("pattern")
+    ap.add_argument("k", type=int)
+    ap.add_argument("paths", nargs="*", help="files to search; none or '-': standard input")
+    return ap
+
+
+def run_agrep(args, stdin=None, out=None, err=None) -> int:
+    stdin = sys.stdin.buffer if stdin is None else stdin
+    out = sys.stdout if out is None else out
+    err = sys.stderr if err is None else err
+    if args.k < 0 or args.context < 0:
+        err.write("agrep: K and -C must not be negative\n")
+        return 2
+    pattern = args.pattern.encode()
+    hist = [0] * (args.k + 1)
+    try:
+        searcher = Searcher("ascii_ci" if args.ignore_case else "ascii", rc=False)
+        for path in args.paths or ["-"]:
+            if path == "-":
+                name, text = "(stdin)", stdin.read()
+            else:
+                name = path
+                with open(path, "rb") as fh:
+                    text = fh.read()
+            matches, spans = searcher.search_lines(pattern, text, args.k)
+            for m in matches:
+                hist[m.cost] += 1
+            out.write(format_agrep(name, text, matches, spans, args.context))
+    except (OSError, SassyHipError) as e:
+        err.write(f"agrep: {e}\n")
+        return 2
+    out.flush()
+    err.write(format_histogram(hist))
+    return 0 if sum(hist) else 1
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m sassy_amd", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
+    agrep_parser(sub)
     sp = sub.add_parser("search", help="write all matches as TSV to stdout")
     add_search_arguments(sp)
     sp.add_argument("--sam", action="store_true")
@@ -103,9 +224,12 @@ def main(argv=None) -> int:
     fp.add_argument("-v", "--invert", action="store_true", help="write the records WITHOUT a match")
     fp.add_argument("paths", nargs="+")
     args = ap.parse_args(argv)
+    if args.cmd == "agrep":
+        return run_agrep(args)
 
     patterns = load_patterns(args)
-    searcher = Searcher(args.alphabet, rc=not args.no_rc, alpha=args.overhang).with_max_n_frac(args.max_n_frac)
+    rc = not args.no_rc and not args.alphabet.startswith("ascii")  # (no reverse complement of plain text: forward only)
+    searcher = Searcher(args.alphabet, rc=rc, alpha=args.overhang).with_max_n_frac(args.max_n_frac)
     if args.cmd == "filter":
         return run_filter(args, searcher, [p for _, p in patterns], sys.stdout.buffer)
     out = sys.stdout

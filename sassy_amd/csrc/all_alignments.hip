@@ -41,11 +41,13 @@ __constant__ uint8_t kAaIupac[32] = {
 __device__ __forceinline__ bool aa_scan_eq(uint32_t pr, uint32_t p, uint32_t t) {
   if (pr == PROFILE_DNA) return ((p >> 1) & 3u) == ((t >> 1) & 3u);
   if (pr == PROFILE_IUPAC) return ((kAaIupac[p & 31u] & kAaIupac[t & 31u]) & 15u) != 0u;
+  if (pr == PROFILE_ASCII_CI) return fold_ascii(p) == fold_ascii(t);
   return p == t;
 }
 __device__ __forceinline__ bool aa_is_match(uint32_t pr, uint32_t p, uint32_t t) {
   if (pr == PROFILE_DNA) return (p | 0x20u) == (t | 0x20u);
   if (pr == PROFILE_IUPAC) return (kAaIupac[p & 31u] & kAaIupac[t & 31u]) != 0u;
+  if (pr == PROFILE_ASCII_CI) return fold_ascii(p) == fold_ascii(t);
   return p == t;
 }
 
@@ -347,6 +349,7 @@ int sassy_hip_search_all_alignments(sassy_SearcherType* s, const uint8_t* patter
                                     sassy_hip_Result** out) {
   if (!s || !pattern || (!text && text_len) || !out)
     return fail(SASSY_HIP_EINVAL, "Pointers in search_all_alignments() must not be null");
+  SASSY_NO_LINE_SPANS(flags);
   if (flags & ~(uint32_t)(SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_TEXT_UNCHANGED))
     return fail(SASSY_HIP_EINVAL, "search_all_alignments takes SASSY_HIP_TEXT_ON_DEVICE / SASSY_HIP_TEXT_UNCHANGED only");
   SASSY_NO_TICKETS(s);

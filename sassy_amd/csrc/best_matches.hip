@@ -169,16 +169,17 @@ int best_matches(sassy_SearcherType* s, const uint8_t* const* patterns, const si
                  const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags, sassy_hip_Result** out) {
   if (!s || !out || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!texts || !text_lens)))
     return fail(SASSY_HIP_EINVAL, "null argument");
+  SASSY_NO_LINE_SPANS(flags);
   if (flags & ~(SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_WITHOUT_TRACE))
     return fail(SASSY_HIP_EINVAL, "best_matches takes SASSY_HIP_TEXT_ON_DEVICE and SASSY_HIP_WITHOUT_TRACE only");
   if (k > 254) return fail(SASSY_HIP_EINVAL, "best_matches: k must be <= 254 (as best_pattern: costs are bytes, 255 = no match)");
   SASSY_NO_TICKETS(s);
-  if (s->rc && s->profile == PROFILE_ASCII && n_patterns && n_texts)
+  if (s->rc && is_ascii(s->profile) && n_patterns && n_texts)
     return fail(SASSY_HIP_EUNSUPPORTED, "reverse complement is not defined for the ascii alphabet");
   const double t0 = now_ms();
   // ---- the device path: where best_pattern's device reduction takes the call, without the N filter, texts < 2^31 ----
   bool device = s->sw.best_match_device != 0 && n_texts >= 2 && n_patterns > 0 && !(flags & SASSY_HIP_TEXT_ON_DEVICE) &&
-                s->profile != PROFILE_ASCII && pattern_lens[0] <= 64 && 2 * k + 3 <= 64 && n_patterns < (1u << 24) &&
+                !is_ascii(s->profile) && pattern_lens[0] <= 64 && 2 * k + 3 <= 64 && n_patterns < (1u << 24) &&
                 std::isnan(s->max_n_frac);
   for (size_t pi = 1; device && pi < n_patterns; ++pi) device = pattern_lens[pi] == pattern_lens[0];
   for (size_t ti = 0; device && ti < n_texts; ++ti) device = text_lens[ti] < (1ull << 31) - 128;  // (the end position: 31 bits, virtual columns included)

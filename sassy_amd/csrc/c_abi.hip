@@ -50,13 +50,14 @@ const char* switch_table() {
   return table.c_str();
 }
 
-// "ascii" | "dna" | "iupac" (reference: src/c.rs:52-70)
+// "ascii" | "dna" | "iupac" (reference: src/c.rs:52-70) | "ascii_ci" (the reference's CaseInsensitiveAscii, src/profiles.rs:5)
 bool parse_alphabet(const char* alphabet, Profile& pr) {
   std::string a(alphabet ? alphabet : "");
   for (char& c : a) c = (char)tolower((unsigned char)c);
   if (a == "dna") pr = PROFILE_DNA;
   else if (a == "iupac") pr = PROFILE_IUPAC;
   else if (a == "ascii") pr = PROFILE_ASCII;
+  else if (a == "ascii_ci") pr = PROFILE_ASCII_CI;
   else return false;
   return true;
 }
@@ -247,6 +248,7 @@ int sassy_hip_search_with_fn(sassy_SearcherType* s, const uint8_t* pattern, size
                              const uint8_t* text, size_t text_len, size_t k, uint32_t flags,
                              sassy_hip_end_filter fn, void* user, sassy_hip_Result** out) {
   if (!s || !pattern || (!text && text_len) || !out || !fn) return fail(SASSY_HIP_EINVAL, "Pointers in search() must not be null");
+  SASSY_NO_LINE_SPANS(flags);
   SASSY_NO_TICKETS(s);
   DeviceGuard on_device(s);
   if (flags & SASSY_HIP_TEXT_ON_DEVICE) return fail(SASSY_HIP_EINVAL, "search_with_fn needs the text in host memory");
@@ -269,9 +271,10 @@ int sassy_hip_search_many(sassy_SearcherType* s, const uint8_t* const* patterns,
                           size_t k, uint32_t flags, sassy_hip_Result** out) {
   if (!s || !out || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!texts || !text_lens)))
     return fail(SASSY_HIP_EINVAL, "null argument");
+  SASSY_NO_LINE_SPANS(flags);
   SASSY_NO_TICKETS(s);
   DeviceGuard on_device(s);
-  if (s->rc && s->profile == PROFILE_ASCII && n_patterns && n_texts)  // as in search_text: the reference panics here
+  if (s->rc && is_ascii(s->profile) && n_patterns && n_texts)  // as in search_text: the reference panics here
     return fail(SASSY_HIP_EUNSUPPORTED, "reverse complement is not defined for the ascii alphabet");
   const double t0 = now_ms();
   reset_stats(s);
@@ -408,12 +411,28 @@ int sassy_hip_search(sassy_SearcherType* s, const uint8_t* pattern, size_t patte
                      sassy_hip_Result** out) {
   if (!s || !pattern || (!text && text_len) || !out) return fail(SASSY_HIP_EINVAL, "Pointers in search() must not be null");
   SASSY_NO_TICKETS(s);
+  const bool want_lines = (flags & SASSY_HIP_LINE_SPANS) != 0;
+  if (want_lines && (flags & SASSY_HIP_WITHOUT_TRACE))
+    return fail(SASSY_HIP_EUNSUPPORTED, "SASSY_HIP_LINE_SPANS needs traced matches (a match without trace has no start)");
   DeviceGuard on_device(s);
   const double t0 = now_ms();
   reset_stats(s);
   sassy_hip_Result* R = new sassy_hip_Result();
   if (int rc = search_text(s, pattern, pattern_len, text, text_len, k, flags, 0, true, s->rc, R)) { delete R; return rc; }
   if (R->pool.empty()) R->pool.push_back('\0');
+  if (want_lines) {  // the text is still resident: the caller's buffer, or the copy the search uploaded
+    const size_t n = R->size();
+    const sassy_hip_Match* rows = R->data();
+    std::vector<uint64_t> ends(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+      ends[i] = rows[i].text_start;
+      ends[n + i] = std::max(rows[i].text_start, rows[i].text_end - (rows[i].text_end ? 1 : 0));
+    }
+    R->line_spans.resize(n);
+    R->has_line_spans = true;
+    const uint8_t* d_text = (flags & SASSY_HIP_TEXT_ON_DEVICE) ? text : s->d_text.p;
+    if (int rc = line_spans_on_device(s, d_text, text_len, ends.data(), ends.data() + n, n, R->line_spans.data())) { delete R; return rc; }
+  }
   s->stats.total_ms = now_ms() - t0;
   s->stats.host_post_ms = s->stats.total_ms - s->stats.host_enqueue_ms - s->stats.host_wait_ms;
   *out = R;
@@ -433,6 +452,7 @@ int sassy_hip_search_shard(sassy_SearcherType* s, const uint8_t* pattern, size_t
                            uint64_t global_offset, uint64_t total_len, size_t k, uint32_t flags,
                            sassy_hip_Result** out) {
   if (!s || !pattern || !d_text || !out) return fail(SASSY_HIP_EINVAL, "null argument");
+  SASSY_NO_LINE_SPANS(flags);
   SASSY_NO_TICKETS(s);
   DeviceGuard on_device(s);
   if (halo_len % 64 || global_offset % 64) return fail(SASSY_HIP_EINVAL, "halo_len and global_offset must be multiples of 64");
@@ -625,6 +645,7 @@ int sassy_hip_search_shard_begin(sassy_SearcherType* s, const uint8_t* pattern, 
                                  uint64_t global_offset, uint64_t total_len, size_t k, uint32_t flags,
                                  sassy_hip_Ticket** out) {
   if (!s || !pattern || !d_text || !out) return fail(SASSY_HIP_EINVAL, "null argument");
+  SASSY_NO_LINE_SPANS(flags);
   DeviceGuard on_device(s);
   if (halo_len % 64 || global_offset % 64) return fail(SASSY_HIP_EINVAL, "halo_len and global_offset must be multiples of 64");
   if (global_offset < halo_len) return fail(SASSY_HIP_EINVAL, "halo reaches left of the text start");
@@ -732,6 +753,9 @@ int sassy_hip_search_finish(sassy_SearcherType* s, sassy_hip_Ticket* t, sassy_hi
 
 size_t sassy_hip_result_len(const sassy_hip_Result* r) { return r ? r->size() : 0; }
 const sassy_hip_Match* sassy_hip_result_matches(const sassy_hip_Result* r) { return r ? r->data() : nullptr; }
+const sassy_hip_LineSpan* sassy_hip_result_line_spans(const sassy_hip_Result* r) {
+  return r && r->has_line_spans ? r->line_spans.data() : nullptr;
+}
 const char* sassy_hip_result_cigars(const sassy_hip_Result* r) { return r ? r->pool_data() : nullptr; }
 size_t sassy_hip_result_cigars_len(const sassy_hip_Result* r) { return r ? r->pool_size() : 0; }
 
@@ -793,10 +817,10 @@ uintptr_t search(sassy_SearcherType* searcher, const uint8_t* pattern, uintptr_t
   sassy_hip_Result* R = nullptr;
   const std::vector<int> devs = searcher->sw.devices.empty() ? std::vector<int>() : drop_in_devices(searcher->sw.devices);
   const bool plain_modes = std::isnan(searcher->alpha) && std::isnan(searcher->max_n_frac) && !searcher->only_best &&
-                           searcher->ref_lanes == 0 && !(searcher->rc && searcher->profile == PROFILE_ASCII);
+                           searcher->ref_lanes == 0 && !(searcher->rc && is_ascii(searcher->profile));
   if (!devs.empty() && plain_modes && text_len >= devs.size() * (size_t)(4u << 20)) {
     if (!searcher->multi) {
-      const char* names[] = {"ascii", "dna", "iupac"};
+      const char* names[] = {"ascii", "dna", "iupac", nullptr, "ascii_ci"};  // by Profile value
       sassy_hip_Multi* mm = sassy_hip_multi_new(names[(int)searcher->profile], NAN, devs.data(), devs.size());
       if (!mm) die(g_err.c_str());
       if (sassy_hip_multi_set_rc(mm, searcher->rc ? 1 : 0) != 0) die(g_err.c_str());
@@ -840,7 +864,7 @@ sassy_hip_Encoded* sassy_hip_encode_patterns(sassy_SearcherType* s, const uint8_
     fail(SASSY_HIP_EINVAL, "Invalid pattern length (must be 1..=64)");
     return nullptr;
   }
-  if (s->rc && s->profile == PROFILE_ASCII) {
+  if (s->rc && is_ascii(s->profile)) {
     fail(SASSY_HIP_EUNSUPPORTED, "reverse complement is not defined for the ascii alphabet");
     return nullptr;
   }
@@ -864,6 +888,7 @@ void sassy_hip_encoded_free(sassy_hip_Encoded* e) { delete e; }
 int sassy_hip_search_encoded(sassy_SearcherType* s, const sassy_hip_Encoded* e, const uint8_t* text,
                              size_t text_len, size_t k, uint32_t flags, sassy_hip_Result** out) {
   if (!s || !e || (!text && text_len) || !out) return fail(SASSY_HIP_EINVAL, "null argument");
+  SASSY_NO_LINE_SPANS(flags);
   SASSY_NO_TICKETS(s);
   DeviceGuard on_device(s);
   const double t0 = now_ms();
@@ -936,7 +961,7 @@ int sassy_hip_search_encoded(sassy_SearcherType* s, const sassy_hip_Encoded* e, 
     // 7.8e-14 s per text byte behind the multi-pattern prefilter (long plain-ACGT texts), or 60 us + 5.5e-13 s
     // per byte with its own filter pass (texts with other letters).  SASSY_HIP_TILED=0 / 1 forces the choice.
     const int env_tiled = (int)s->sw.tiled;
-    const bool tiled_ok = s->profile != PROFILE_ASCII && std::isnan(s->alpha) && 2 * k + 3 <= 64 &&
+    const bool tiled_ok = !is_ascii(s->profile) && std::isnan(s->alpha) && 2 * k + 3 <= 64 &&
                           e->patterns.size() < (1u << 24) && text_len < (1ull << 40);
     const uint64_t tiled_groups = (e->patterns.size() + 63) / 64;
     const double est_tiled = (double)text_len * (double)tiled_groups / 3.8e10 + 1e-4;

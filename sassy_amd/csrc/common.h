@@ -5,11 +5,17 @@
 
 namespace sassy_hip {
 
-enum Profile : uint32_t { PROFILE_ASCII = 0, PROFILE_DNA = 1, PROFILE_IUPAC = 2 };
+// PROFILE_ASCII_CI: Ascii where A-Z and a-z fold onto each other (the reference's Ascii<false>::is_match,
+// u8::eq_ignore_ascii_case); every other byte matches only itself.  It takes every route PROFILE_ASCII takes (is_ascii).
+enum Profile : uint32_t { PROFILE_ASCII = 0, PROFILE_DNA = 1, PROFILE_IUPAC = 2, PROFILE_ASCII_CI = 4 };
+constexpr bool is_ascii(Profile pr) { return pr == PROFILE_ASCII || pr == PROFILE_ASCII_CI; }
 // Kernel-side only (ScanParams::profile, template argument): Ascii patterns with more than kMaxSlots distinct bytes.
 // No mask per distinct byte: the block's 8 bit planes are the "slots", a row's Eq word is computed from them and the
 // row's pattern byte (the row table then holds the bytes themselves): 16 VALU more per row, any pattern.
 constexpr uint32_t PROFILE_ASCII_BYTES = 3;
+constexpr uint32_t PROFILE_ASCII_CI_BYTES = 5;  // the same under PROFILE_ASCII_CI: the row table holds the folded bytes
+// The fold of PROFILE_ASCII_CI (u8::to_ascii_lowercase): pattern bytes are folded by the host, text bytes by the kernels.
+__host__ __device__ constexpr uint32_t fold_ascii(uint32_t c) { return (c | 0x20u) - 'a' < 26u ? (c | 0x20u) : c; }
 
 constexpr int kWave = 64;              // gfx950 wavefront
 constexpr int kWavesPerGroup = 4;      // 256-thread workgroups, every wave works alone

@@ -36,6 +36,7 @@ namespace sassy_hip {
 hipError_t launch_scan_dna(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_scan_iupac(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_scan_ascii(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
+hipError_t launch_scan_ascii_ci(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_filter_dna(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_filter_group(const ScanParams& P, uint32_t grid, hipStream_t stream);  // (two searches, one pass)
 hipError_t launch_filter_table(const ScanParams& P, uint32_t grid, hipStream_t stream);
@@ -48,9 +49,11 @@ hipError_t launch_reverse_texts(const uint8_t* d_src, uint8_t* d_dst, uint64_t n
                                 const uint64_t* d_start, const uint64_t* d_len, uint32_t pad, hipStream_t stream);
 hipError_t launch_filter_iupac(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_filter_ascii(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
+hipError_t launch_filter_ascii_ci(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_list_dna(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_list_iupac(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_list_ascii(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
+hipError_t launch_list_ascii_ci(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_build_chunks(const unsigned long long* d_hit, uint64_t n_words, uint64_t n_blocks,
                                uint64_t first_owned, uint32_t wb, uint32_t L, uint32_t maxlen,
                                ChunkDesc* d_desc, uint32_t* d_desc_count, uint32_t desc_cap,
@@ -265,6 +268,9 @@ struct sassy_hip_Result {
   size_t ext_n = 0;
   const char* ext_pool = nullptr;
   size_t ext_pool_len = 0;
+  // SASSY_HIP_LINE_SPANS: one span per record, in record order
+  bool has_line_spans = false;
+  std::vector<sassy_hip_LineSpan> line_spans;
   size_t size() const { return pin.h ? ext_n : matches.size(); }
   const sassy_hip_Match* data() const { return pin.h ? ext_matches : matches.data(); }
   const char* pool_data() const { return pin.h ? ext_pool : pool.c_str(); }
@@ -651,6 +657,14 @@ struct sassy_SearcherType {
   DevBuf<Candidate> d_zone_list;
   hipEvent_t ev_multi = nullptr, ev_multi_a = nullptr;
   hipEvent_t ev_a_multi() { return ev_multi_a; }
+  // line resolution (line_index.hip): tile offsets | super-tile counts, the super-tile prefix, the spans' ends, the spans;
+  // the HIP-event times of the last call's index and resolve passes (timing level 2)
+  DevBuf<uint32_t> d_line_tiles;
+  DevBuf<unsigned long long> d_line_prefix;
+  DevBuf<uint64_t> d_line_pos;
+  DevBuf<sassy_hip_LineSpan> d_line_out;
+  double line_index_ms = 0, line_resolve_ms = 0;
+  hipEvent_t ev_line[4] = {nullptr, nullptr, nullptr, nullptr};  // index pass begin / end, resolve pass begin / end
   DevBuf<uint64_t> d_range;      // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
@@ -671,6 +685,7 @@ struct sassy_SearcherType {
     for (sassy_hip_Ticket*& t : lane_ticket) { delete t; t = nullptr; }
     d_text.release(); d_rev.release(); d_rc_bitmap.release();
     free_stage();
+    d_line_tiles.release(); d_line_prefix.release(); d_line_pos.release(); d_line_out.release();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();
@@ -680,6 +695,8 @@ struct sassy_SearcherType {
     d_zone_u64.release(); d_zone_tab.release(); d_zone_peq.release(); d_zone_text.release(); d_zone_list.release();
     if (ev_multi) (void)hipEventDestroy(ev_multi);
     if (ev_multi_a) (void)hipEventDestroy(ev_multi_a);
+    for (hipEvent_t e : ev_line)
+      if (e) (void)hipEventDestroy(e);
     for (ScanLane& l : lanes) l.destroy();
     if (ev_inputs) (void)hipEventDestroy(ev_inputs);
   }
@@ -699,6 +716,7 @@ struct sassy_SearcherType {
     HIP_TRY(hipEventCreateWithFlags(&ev_inputs, hipEventDisableTiming));
     HIP_TRY(hipEventCreate(&ev_multi));
     HIP_TRY(hipEventCreate(&ev_multi_a));
+    for (hipEvent_t& e : ev_line) HIP_TRY(hipEventCreate(&e));
     device_ready = true;
     return 0;
   }
@@ -1078,7 +1096,17 @@ struct DeviceGuard {
       return fail(SASSY_HIP_EINVAL, "searches are in flight on this searcher (sassy_hip_search_shard_begin): finish them first"); \
   } while (0)
 
+// SASSY_HIP_LINE_SPANS is sassy_hip_search's alone
+#define SASSY_NO_LINE_SPANS(flags)                                                                                       \
+  do {                                                                                                                   \
+    if ((flags) & SASSY_HIP_LINE_SPANS)                                                                                  \
+      return fail(SASSY_HIP_EUNSUPPORTED, "SASSY_HIP_LINE_SPANS is a flag of sassy_hip_search only");                    \
+  } while (0)
+
 // ---- functions one unit calls in another ----
+// line_index.hip
+int line_spans_on_device(sassy_SearcherType* S, const uint8_t* d_text, uint64_t text_len, const uint64_t* first, const uint64_t* last,
+                         size_t n, sassy_hip_LineSpan* out);
 struct TiledPerText;  // (many_patterns.hip)
 // c_abi.hip
 bool parse_alphabet(const char* alphabet, Profile& pr);

@@ -1243,7 +1243,7 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
                                size_t n_patterns, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts,
                                size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled, bool tiled_only) {
   handled = false;
-  if (n_texts < 2 || n_patterns == 0 || (flags & SASSY_HIP_TEXT_ON_DEVICE) || s->profile == PROFILE_ASCII) return 0;
+  if (n_texts < 2 || n_patterns == 0 || (flags & SASSY_HIP_TEXT_ON_DEVICE) || is_ascii(s->profile)) return 0;
   if (!std::isnan(s->alpha)) return 0;  // overhang gives every text its own special edges: pair by pair
   if (n_texts >= (1u << (32 - kCandTextShift))) return 0;
   size_t max_m = 0;
@@ -1540,7 +1540,7 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
     longest = std::max<uint64_t>(longest, text_lens[ti]);
   }
   if (longest > (1u << 20)) return 0;                      // a lane per text only pays for short texts
-  if (!overhang && s->profile != PROFILE_ASCII && filterable) return 0;  // search_many_batched takes it
+  if (!overhang && !is_ascii(s->profile) && filterable) return 0;  // search_many_batched takes it
   handled = true;
   if (int rc = s->ensure_device()) return rc;
   MinSinkDisarm disarm{s};
@@ -1773,9 +1773,8 @@ long sassy_hip_seed_layout(const char* alphabet, const uint8_t* const* patterns,
                            uint32_t* out_end, uint32_t* out_len) {
   if (!alphabet || !patterns || !out_end || !out_len || pattern_len == 0 || pattern_len > 64 || k > 7 || pattern_len / (k + 1) < 1)
     return -1;
-  const std::string a(alphabet);
-  const int profile = a == "dna" ? PROFILE_DNA : a == "iupac" ? PROFILE_IUPAC : a == "ascii" ? PROFILE_ASCII : -1;
-  if (profile < 0) return -1;
+  Profile profile;
+  if (!parse_alphabet(alphabet, profile)) return -1;  // (the searchers' parser: any letter case)
   seed_layout(true, profile, patterns, n_patterns, (uint32_t)pattern_len, (uint32_t)k, out_end, out_len);
   return (long)(k + 1);
 }

@@ -140,6 +140,7 @@ int best_costs(sassy_SearcherType* s, const uint8_t* const* patterns, const size
                uint8_t* out_cost, uint32_t* out_pattern, uint8_t* out_strand) {
   if (!s || !out_cost || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!texts || !text_lens)))
     return fail(SASSY_HIP_EINVAL, "null argument");
+  SASSY_NO_LINE_SPANS(flags);
   if (flags & ~SASSY_HIP_TEXT_ON_DEVICE) return fail(SASSY_HIP_EINVAL, "best-cost search takes SASSY_HIP_TEXT_ON_DEVICE only");
   if (k > 254) return fail(SASSY_HIP_EINVAL, "best-cost search: k must be <= 254 (costs are bytes, 255 = no match)");
   SASSY_NO_TICKETS(s);
@@ -147,7 +148,7 @@ int best_costs(sassy_SearcherType* s, const uint8_t* const* patterns, const size
   const size_t n_out = per_text ? n_texts : n_patterns * n_texts;
   // ---- the device path: a batch of host texts, patterns of one length (what the one-pass paths of search_many take) ----
   bool device = s->sw.min_cost_device != 0 && n_texts >= 2 && n_patterns > 0 && !(flags & SASSY_HIP_TEXT_ON_DEVICE) &&
-                s->profile != PROFILE_ASCII && pattern_lens[0] <= 64 && 2 * k + 3 <= 64 &&
+                !is_ascii(s->profile) && pattern_lens[0] <= 64 && 2 * k + 3 <= 64 &&
                 (per_text ? n_patterns < (1u << 24) : (uint64_t)n_patterns * n_texts <= 0xFFFFFF00ull);
   for (size_t pi = 1; device && pi < n_patterns; ++pi) device = pattern_lens[pi] == pattern_lens[0];
   MinSink sink;

@@ -279,7 +279,7 @@ int sassy_hip_multi_set_rc(sassy_hip_Multi* m, int rc) {
   if (!m) return fail(SASSY_HIP_EINVAL, "null argument");
   SASSY_MULTI_NO_TICKETS(m);
   Profile pr;
-  if (rc && parse_alphabet(m->alphabet.c_str(), pr) && pr == PROFILE_ASCII)
+  if (rc && parse_alphabet(m->alphabet.c_str(), pr) && is_ascii(pr))
     return fail(SASSY_HIP_EUNSUPPORTED, "reverse complement is not defined for the ascii alphabet");
   m->rc = rc != 0;
   return 0;
@@ -404,6 +404,7 @@ int sassy_hip_multi_search(sassy_hip_Multi* m, const uint8_t* pattern, size_t pa
                            sassy_hip_Result** out) {
   std::vector<uint8_t> cp;
   if (int rc = multi_check_search(m, pattern, pattern_len, k, out, cp)) return rc;
+  SASSY_NO_LINE_SPANS(flags);
   SASSY_MULTI_NO_TICKETS(m);
   const uint32_t f = flags & (SASSY_HIP_ALL_MINIMA | SASSY_HIP_WITHOUT_TRACE);
   const int rc = m->on_all([&](sassy_hip_Multi::Part& p) -> int {
@@ -443,6 +444,7 @@ int sassy_hip_multi_search_begin(sassy_hip_Multi* m, const uint8_t* pattern, siz
                                  sassy_hip_MultiTicket** out) {
   std::unique_ptr<sassy_hip_MultiTicket> T(new sassy_hip_MultiTicket());
   if (int rc = multi_check_search(m, pattern, pattern_len, k, out, T->cpat)) return rc;
+  SASSY_NO_LINE_SPANS(flags);
   for (sassy_hip_Multi::Part& p : m->parts)
     if (p.open_tickets >= m->pipe_depth) return fail(SASSY_HIP_EINVAL, "too many searches in flight: finish one first (sassy_hip_multi_set_pipe_depth)");
   T->owner = m;
@@ -557,6 +559,7 @@ long sassy_hip_multi_layout(uint64_t len, size_t n_parts, size_t max_pattern_len
 int sassy_hip_multi_search_encoded(sassy_hip_Multi* m, const uint8_t* patterns, size_t n_patterns, size_t pattern_len, size_t k,
                                    uint32_t flags, sassy_hip_Result** out) {
   if (!m || !patterns || !out) return fail(SASSY_HIP_EINVAL, "null argument");
+  SASSY_NO_LINE_SPANS(flags);
   SASSY_MULTI_NO_TICKETS(m);
   if (!m->have_text || !m->replicate)
     return fail(SASSY_HIP_EINVAL, "search_encoded over several devices shards the patterns: every device needs the whole text "
@@ -613,6 +616,7 @@ int sassy_hip_multi_search_many(sassy_hip_Multi* m, const uint8_t* const* patter
                                 const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
                                 sassy_hip_Result** out) {
   if (!m || !out || (!patterns && n_patterns) || (!texts && n_texts)) return fail(SASSY_HIP_EINVAL, "null argument");
+  SASSY_NO_LINE_SPANS(flags);
   SASSY_MULTI_NO_TICKETS(m);
   const size_t G = m->parts.size();
   const uint32_t f = flags & (SASSY_HIP_ALL_MINIMA | SASSY_HIP_WITHOUT_TRACE);

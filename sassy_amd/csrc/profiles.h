@@ -6,6 +6,9 @@
 //   Dna   : reference src/profiles/dna.rs:14-138
 //   Iupac : reference src/profiles/iupac.rs:13-344
 //   Ascii : reference src/profiles/ascii.rs:13-73 (case sensitive, what src/c.rs:64 instantiates)
+//   Ascii, case-insensitive (PROFILE_ASCII_CI): Ascii<false>::is_match, ascii.rs:44-51, for the scan and the traceback
+//           alike -- not the reference's own case-insensitive scan profile, which cannot match '_', '@', '[' or '\n'
+//           with themselves
 #pragma once
 #include <cstdint>
 #include <string>
@@ -32,6 +35,7 @@ inline bool scan_eq(Profile pr, uint8_t p, uint8_t t) {
   switch (pr) {
     case PROFILE_DNA: return ((p >> 1) & 3) == ((t >> 1) & 3);
     case PROFILE_IUPAC: return ((iupac_code(p) & iupac_code(t)) & 0x0F) != 0;
+    case PROFILE_ASCII_CI: return fold_ascii(p) == fold_ascii(t);
     default: return p == t;
   }
 }
@@ -40,6 +44,7 @@ inline bool trace_is_match(Profile pr, uint8_t p, uint8_t t) {
   switch (pr) {
     case PROFILE_DNA: return (p | 0x20) == (t | 0x20);
     case PROFILE_IUPAC: return (iupac_code(p) & iupac_code(t)) > 0;
+    case PROFILE_ASCII_CI: return fold_ascii(p) == fold_ascii(t);
     default: return p == t;
   }
 }
@@ -79,10 +84,10 @@ struct PatternPlan {
   uint32_t m = 0;
   uint32_t nslots = 0;
   uint32_t nwords = 0;               // ceil(m / 32)
-  uint8_t slot_val[kMaxSlots] = {};  // Dna: 2-bit code; Iupac: base-set nibble; Ascii: byte
+  uint8_t slot_val[kMaxSlots] = {};  // Dna: 2-bit code; Iupac: base-set nibble; Ascii: byte (PROFILE_ASCII_CI: folded)
   std::vector<uint32_t> row_tab;     // one byte per row = 2 * its profile slot, 4 rows per word,
                                      // 8 words per 32 rows (padded with slot 0)
-  bool bytes = false;                // Ascii with more than kMaxSlots distinct bytes (PROFILE_ASCII_BYTES): nslots = 8
+  bool bytes = false;                // Ascii with more than kMaxSlots distinct (folded) bytes (PROFILE_ASCII_BYTES): nslots = 8
                                      // (the bit planes), the row table holds the pattern bytes themselves
 };
 
@@ -110,7 +115,8 @@ inline bool make_plan(Profile pr, const uint8_t* pat, size_t m, PatternPlan& pla
     letters = {'A', 'C', 'T', 'G'};
   }
   for (size_t j = 0; j < m; ++j) {
-    const uint8_t c = pr == PROFILE_IUPAC ? (uint8_t)(pat[j] & ~0x20) : pat[j];
+    // (PROFILE_ASCII_CI: one slot per folded byte -- 'l' and 'L' share it)
+    const uint8_t c = pr == PROFILE_IUPAC ? (uint8_t)(pat[j] & ~0x20) : pr == PROFILE_ASCII_CI ? (uint8_t)fold_ascii(pat[j]) : pat[j];
     size_t s = 0;
     while (s < letters.size() && letters[s] != c) ++s;
     if (s == letters.size()) letters.push_back(c);
@@ -128,7 +134,8 @@ inline bool make_plan(Profile pr, const uint8_t* pat, size_t m, PatternPlan& pla
     plan.bytes = true;
     plan.nslots = 8;
     plan.row_tab.assign((size_t)plan.nwords * 8, 0u);
-    for (size_t j = 0; j < m; ++j) plan.row_tab[j >> 2] |= (uint32_t)pat[j] << (8 * (j & 3));
+    for (size_t j = 0; j < m; ++j)
+      plan.row_tab[j >> 2] |= (pr == PROFILE_ASCII_CI ? fold_ascii(pat[j]) : (uint32_t)pat[j]) << (8 * (j & 3));
     return true;
   }
   plan.nslots = (uint32_t)letters.size();

@@ -153,6 +153,7 @@ static hipError_t launch_scan_any(Profile pr, const ScanParams& P, uint32_t grid
   switch (pr) {
     case PROFILE_DNA: return launch_scan_dna(P, grid, smem, st);
     case PROFILE_IUPAC: return launch_scan_iupac(P, grid, smem, st);
+    case PROFILE_ASCII_CI: return launch_scan_ascii_ci(P, grid, smem, st);
     default: return launch_scan_ascii(P, grid, smem, st);
   }
 }
@@ -160,6 +161,7 @@ static hipError_t launch_filter_any(Profile pr, const ScanParams& P, uint32_t gr
   switch (pr) {
     case PROFILE_DNA: return launch_filter_dna(P, grid, smem, st);
     case PROFILE_IUPAC: return launch_filter_iupac(P, grid, smem, st);
+    case PROFILE_ASCII_CI: return launch_filter_ascii_ci(P, grid, smem, st);
     default: return launch_filter_ascii(P, grid, smem, st);
   }
 }
@@ -167,6 +169,7 @@ static hipError_t launch_list_any(Profile pr, const ScanParams& P, uint32_t grid
   switch (pr) {
     case PROFILE_DNA: return launch_list_dna(P, grid, smem, st);
     case PROFILE_IUPAC: return launch_list_iupac(P, grid, smem, st);
+    case PROFILE_ASCII_CI: return launch_list_ascii_ci(P, grid, smem, st);
     default: return launch_list_ascii(P, grid, smem, st);
   }
 }
@@ -238,7 +241,7 @@ int ScanJob::prepare() {
   P.k = k;
   P.nwords = plan.nwords;
   P.nslots = plan.nslots;
-  P.profile = plan.bytes ? PROFILE_ASCII_BYTES : (uint32_t)S->profile;
+  P.profile = !plan.bytes ? (uint32_t)S->profile : S->profile == PROFILE_ASCII_CI ? PROFILE_ASCII_CI_BYTES : PROFILE_ASCII_BYTES;
   P.wb = warmup_blocks(plan.m, k);
   P.flags = (all_minima ? kScanAllMinima : 0u) | (sh.text_start ? kScanTextStart : 0u) |
             (sh.text_end ? kScanTextEnd : 0u) | (overhang ? kScanOverhang : 0u);
@@ -318,7 +321,7 @@ int ScanJob::prepare() {
   // hit blocks of the k+1 pieces, except where the cheaper bit-plane kernel applies (one strand: both
   // strands in one pass cost the bit-plane kernel 8 pieces, 0.85 ms per 3 GB, the counting kernel nothing extra).
   count_r = 0;
-  if (!overhang && !ext_bitmap && !ext_desc && S->profile != PROFILE_ASCII && env_pre != 0 &&
+  if (!overhang && !ext_bitmap && !ext_desc && !is_ascii(S->profile) && env_pre != 0 &&
       (env_kind == 0 || env_kind == kFilterCount) && !(can_planes && env_kind == 0 && rc_bitmap == nullptr) &&
       !(pair_ok && env_pair != 2)) {
     // two positions per lookup first (half the LDS traffic of (7,1)); the 7-gram variant only where
@@ -394,7 +397,7 @@ int ScanJob::prepare() {
   }
   filtered = q > 0;
   if (filtered && !ext_bitmap && !ext_desc && fkind != kFilterCount) {
-    const bool can_table = S->profile != PROFILE_ASCII && q >= 7;
+    const bool can_table = !is_ascii(S->profile) && q >= 7;
     const bool can_generic = (uint64_t)pieces * q <= 255;   // its term table holds 256 piece rows
     if (can_planes && (env_kind == 0 || env_kind == kFilterPlanes)) fkind = kFilterPlanes;
     else if (can_table && (env_kind == 0 || env_kind == kFilterTable || !can_generic)) fkind = kFilterTable;
@@ -1837,7 +1840,7 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
   std::string err;
   if (!make_plan(S->profile, pattern, plen, plan, err)) return fail(SASSY_HIP_EINVAL, err);
   if (k > 0x7FFFFFFFu) return fail(SASSY_HIP_EINVAL, "k too large");
-  if (rc_strand && S->profile == PROFILE_ASCII)
+  if (rc_strand && is_ascii(S->profile))
     // the reference constructs such a searcher and panics at its first search: Profile::complement is
     // unimplemented for Ascii (the trait default, src/profiles.rs:57-60), reached from src/search.rs:813-820
     return fail(SASSY_HIP_EUNSUPPORTED, "reverse complement is not defined for the ascii alphabet");
@@ -1881,7 +1884,7 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
   const bool pair_strands = env_pair_rc != 0 && S->fuse && !wo && k <= 0xFFFFu &&
                             pair_eligible(S, pattern, plan.m, (uint32_t)k, &ps_, &pq_);
   const bool can_fuse = fwd_strand && rc_strand && env_fuse != 0 && !ef.fn && std::isnan(S->max_n_frac) &&
-                        std::isnan(S->alpha) && S->profile != PROFILE_ASCII && ref_lanes == 0 && !pair_strands;
+                        std::isnan(S->alpha) && !is_ascii(S->profile) && ref_lanes == 0 && !pair_strands;
   bool rc_by_bitmap = false;
 
   // Two searches, one per strand (the Rc strand's on the reversed copy) -- the paired filter's shapes, searchers with an
@@ -1890,7 +1893,7 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
   // SASSY_HIP_STRANDS_IN_FLIGHT=0: one after the other.
   const bool env_two = S->sw.strands_in_flight != 0;
   if (fwd_strand && rc_strand && !can_fuse && env_two && ref_lanes == 0 && !ef.fn && std::isnan(S->alpha) &&
-      S->profile != PROFILE_ASCII) {
+      !is_ascii(S->profile)) {
     const bool reuse = on_dev && (flags & SASSY_HIP_TEXT_UNCHANGED) && S->rev_src == d_fwd && S->rev_len == tlen &&
                        S->d_rev.p != nullptr;
     if (!reuse) {

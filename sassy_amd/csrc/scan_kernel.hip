@@ -472,6 +472,23 @@ __device__ __forceinline__ uint32_t iupac_base_plane(uint32_t b0, uint32_t b1, u
   return mux(b4, mux(b3, g0, g1), mux(b3, g2, g3));
 }
 
+// Byte mode (common.h: PROFILE_ASCII_BYTES), case-sensitive or folded.
+__host__ __device__ constexpr bool bytes_profile(int profile) {
+  return profile == (int)PROFILE_ASCII_BYTES || profile == (int)PROFILE_ASCII_CI_BYTES;
+}
+// PROFILE_ASCII_CI: plane 5 of the block's text with the upper-case letters folded onto the lower-case ones (the host
+// folds the pattern the same way, profiles.h: make_plan).  A byte is an upper-case letter iff planes 7..5 read 010 and
+// its low five bits are 1 .. 26: not 0 and not 27 .. 31 (11011, 111xx).  20 VALU per block, whatever the slot count.
+__device__ __forceinline__ uint2 folded_plane5(const uint2 (&pl)[8]) {
+  auto upper = [](uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, uint32_t p4, uint32_t p5, uint32_t p6, uint32_t p7) {
+    const uint32_t any = p0 | p1 | p2 | p3 | p4;
+    const uint32_t high = p4 & p3 & (p2 | (p1 & p0));
+    return p6 & ~(p7 | p5) & any & ~high;
+  };
+  return make_uint2(pl[5].x | upper(pl[0].x, pl[1].x, pl[2].x, pl[3].x, pl[4].x, pl[5].x, pl[6].x, pl[7].x),
+                    pl[5].y | upper(pl[0].y, pl[1].y, pl[2].y, pl[3].y, pl[4].y, pl[5].y, pl[6].y, pl[7].y));
+}
+
 // Slot masks of one block from the lane's 64 text bytes.  m[s] = mask of slot s (lo, hi).
 template <int PROFILE, int NS>
 __device__ __forceinline__ void build_masks(const uint32_t (&x)[16], const ScanParams& P, uint2 (&m)[NS]) {
@@ -504,16 +521,18 @@ __device__ __forceinline__ void build_masks(const uint32_t (&x)[16], const ScanP
       }
       m[s] = r;
     }
-  } else if constexpr (PROFILE == (int)PROFILE_ASCII_BYTES) {
+  } else if constexpr (bytes_profile(PROFILE)) {
     // byte mode: the eight bit planes themselves (dp_word compares them with the row's pattern byte)
     static_assert(NS == 8, "byte mode keeps eight planes");
     m[0] = bit_plane<0>(x); m[1] = bit_plane<1>(x); m[2] = bit_plane<2>(x); m[3] = bit_plane<3>(x);
     m[4] = bit_plane<4>(x); m[5] = bit_plane<5>(x); m[6] = bit_plane<6>(x); m[7] = bit_plane<7>(x);
+    if constexpr (PROFILE == (int)PROFILE_ASCII_CI_BYTES) m[5] = folded_plane5(m);
   } else {
     // Ascii: byte equality with the slot's pattern byte (reference: src/profiles/ascii.rs:75-90)
     uint2 pl[8];
     pl[0] = bit_plane<0>(x); pl[1] = bit_plane<1>(x); pl[2] = bit_plane<2>(x); pl[3] = bit_plane<3>(x);
     pl[4] = bit_plane<4>(x); pl[5] = bit_plane<5>(x); pl[6] = bit_plane<6>(x); pl[7] = bit_plane<7>(x);
+    if constexpr (PROFILE == (int)PROFILE_ASCII_CI) pl[5] = folded_plane5(pl);  // (the slots hold folded bytes)
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
       const uint32_t sv = P.slot_val[s];
@@ -883,7 +902,7 @@ __global__ __launch_bounds__(256) void scan_kernel(const ScanParams P) {
     if ((it & 7u) == 7u && first_rows > 8u && first_rows <= m) first_rows -= 4u;  // now and then try an earlier row again
     DpWord V;
     int ds;  // cost at the block's left edge in the last row
-    const bool ran_through = dp_block<PROFILE == (int)PROFILE_ASCII_BYTES, GC>(V, ds, my_masks, carry, lane, row_tab, pkw0, nwords, last_rows, last_word_init, k,
+    const bool ran_through = dp_block<bytes_profile(PROFILE), GC>(V, ds, my_masks, carry, lane, row_tab, pkw0, nwords, last_rows, last_word_init, k,
                                       !active, first_rows, minus_total, m, P.counters != nullptr && active, cnt_rows);
 
     // ---- last row of the block: anything <= k ? ----
@@ -1523,7 +1542,7 @@ __device__ __forceinline__ void list_lanes(const ScanParams& P, unsigned char* m
       if ((it & 7u) == 7u && first_rows > 8u && first_rows <= m) first_rows -= 4u;
       DpWord V;
       int ds;
-      const bool ran_through = dp_block<PROFILE == (int)PROFILE_ASCII_BYTES, GC>(V, ds, my_masks, carry, lane, row_tab, pkw0, nwords, last_rows, last_word_init, k,
+      const bool ran_through = dp_block<bytes_profile(PROFILE), GC>(V, ds, my_masks, carry, lane, row_tab, pkw0, nwords, last_rows, last_word_init, k,
                                         !active, first_rows, minus_total, m, P.counters != nullptr && active, cnt_rows);
       rep4 rr = make_rep4(0u, 0u, 0u, 0u);
       const uint64_t vp = ((uint64_t)V.vph << 32) | V.vpl, vm = ((uint64_t)V.vmh << 32) | V.vml;
@@ -2501,7 +2520,7 @@ __global__ __launch_bounds__(256) void list_words_kernel(const ScanParams P) {
     if (w == 0) { V.vpl = V.vph = V.vml = V.vmh = 0; ds = 0; }
     ds += __popc(ohp) - __popc(ohm);
     uint32_t nhp, nhm;
-    dp_word<false, false, PROFILE == (int)PROFILE_ASCII_BYTES>(V, my_masks, ohp, ohm, pkw, rows, nhp, nhm);
+    dp_word<false, false, bytes_profile(PROFILE)>(V, my_masks, ohp, ohm, pkw, rows, nhp, nhm);
     rep4 rr = make_rep4(0u, 0u, 0u, 0u);
     const uint64_t vp = ((uint64_t)V.vph << 32) | V.vpl, vm = ((uint64_t)V.vmh << 32) | V.vml;
     const bool live = active && last_word && row_maybe_live(ds, V, k);
@@ -2823,7 +2842,7 @@ static hipError_t launch_list_one(const ScanParams& P, uint32_t grid, size_t sme
 }
 
 #ifndef SASSY_SCAN_PROFILE
-#error "compile with -DSASSY_SCAN_PROFILE=<0|1|2> (one translation unit per profile)"
+#error "compile with -DSASSY_SCAN_PROFILE=<0|1|2|4> (one translation unit per profile, by its Profile value)"
 #endif
 
 #if SASSY_SCAN_PROFILE == 1
@@ -2957,20 +2976,32 @@ hipError_t launch_filter_group(const ScanParams& P, uint32_t grid, hipStream_t s
   }
 }
 #else
+// Ascii and its case-insensitive twin (one translation unit each): the same launchers over their own instantiations
+#if SASSY_SCAN_PROFILE == 4
+#define SASSY_SCAN_ASCII_UNIT 1
+#define SASSY_ASCII_FN(stem) stem##_ascii_ci
+constexpr int kAsciiProfile = PROFILE_ASCII_CI, kAsciiBytesProfile = (int)PROFILE_ASCII_CI_BYTES;
+#elif SASSY_SCAN_PROFILE == 0
+#define SASSY_SCAN_ASCII_UNIT 1
+#define SASSY_ASCII_FN(stem) stem##_ascii
+constexpr int kAsciiProfile = PROFILE_ASCII, kAsciiBytesProfile = (int)PROFILE_ASCII_BYTES;
+#else
+#define SASSY_SCAN_ASCII_UNIT 0
+#endif
 #if SASSY_SCAN_PROFILE == 2
 hipError_t launch_scan_iupac(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
   constexpr int PR = PROFILE_IUPAC;
 #else
-hipError_t launch_scan_ascii(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
-  constexpr int PR = PROFILE_ASCII;
+hipError_t SASSY_ASCII_FN(launch_scan)(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
+  constexpr int PR = kAsciiProfile;
 #endif
-#if SASSY_SCAN_PROFILE == 0
-  if (P.profile == PROFILE_ASCII_BYTES) return launch_one<(int)PROFILE_ASCII_BYTES, 8>(P, grid, smem, stream);
+#if SASSY_SCAN_ASCII_UNIT
+  if (P.profile == (uint32_t)kAsciiBytesProfile) return launch_one<kAsciiBytesProfile, 8>(P, grid, smem, stream);
 #endif
   if (P.nslots <= 4) return launch_one<PR, 4>(P, grid, smem, stream);
   if (P.nslots <= 8) return launch_one<PR, 8>(P, grid, smem, stream);
   if (P.nslots <= 16) return launch_one<PR, 16>(P, grid, smem, stream);
-#if SASSY_SCAN_PROFILE == 0
+#if SASSY_SCAN_ASCII_UNIT
   // Ascii patterns with many distinct bytes (the reference's Ascii profile has 256 slots)
   if (P.nslots <= 32) return launch_one<PR, 32>(P, grid, smem, stream);
   if (P.nslots <= 64) return launch_one<PR, 64>(P, grid, smem, stream);
@@ -3034,8 +3065,8 @@ hipError_t launch_filter_iupac(const ScanParams& P, uint32_t grid, size_t smem, 
   constexpr int PR2 = PROFILE_IUPAC;
   if (P.piece_planes) return P.fused ? launch_filter_planes_iupac(P, grid, stream) : hipErrorInvalidValue;
 #else
-hipError_t launch_filter_ascii(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
-  constexpr int PR2 = PROFILE_ASCII;
+hipError_t SASSY_ASCII_FN(launch_filter)(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
+  constexpr int PR2 = kAsciiProfile;
 #endif
   if (P.nslots <= 4) return launch_filter_one<PR2, 4>(P, grid, smem, stream);
   if (P.nslots <= 8) return launch_filter_one<PR2, 8>(P, grid, smem, stream);
@@ -3046,16 +3077,16 @@ hipError_t launch_filter_ascii(const ScanParams& P, uint32_t grid, size_t smem, 
 hipError_t launch_list_iupac(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
   constexpr int PR3 = PROFILE_IUPAC;
 #else
-hipError_t launch_list_ascii(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
-  constexpr int PR3 = PROFILE_ASCII;
+hipError_t SASSY_ASCII_FN(launch_list)(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
+  constexpr int PR3 = kAsciiProfile;
 #endif
-#if SASSY_SCAN_PROFILE == 0
-  if (P.profile == PROFILE_ASCII_BYTES) return launch_list_one<(int)PROFILE_ASCII_BYTES, 8>(P, grid, smem, stream);
+#if SASSY_SCAN_ASCII_UNIT
+  if (P.profile == (uint32_t)kAsciiBytesProfile) return launch_list_one<kAsciiBytesProfile, 8>(P, grid, smem, stream);
 #endif
   if (P.nslots <= 4) return launch_list_one<PR3, 4>(P, grid, smem, stream);
   if (P.nslots <= 8) return launch_list_one<PR3, 8>(P, grid, smem, stream);
   if (P.nslots <= 16) return launch_list_one<PR3, 16>(P, grid, smem, stream);
-#if SASSY_SCAN_PROFILE == 0
+#if SASSY_SCAN_ASCII_UNIT
   if (P.nslots <= 32) return launch_list_one<PR3, 32>(P, grid, smem, stream);
   if (P.nslots <= 64) return launch_list_one<PR3, 64>(P, grid, smem, stream);
 #endif

@@ -39,15 +39,22 @@ __constant__ uint8_t kIupacCode[32] = {
 //   display match   (Profile::is_match, '=' vs 'X') : ((X & mmask) != 0) == iupac
 // Dna: emask 6 ((c>>1)&3 codes, src/profiles/dna.rs:19-60), mmask 0xDF (case-insensitive byte);
 // Iupac: emask 15 (non-letters = 255 act as N in the scan), mmask 255; Ascii: both 255.
+// Case-insensitive Ascii (fold): s(c) = the folded byte, for pattern and text alike, then as Ascii.
 struct CharRule {
-  uint32_t iupac, emask, mmask;
+  uint32_t iupac, emask, mmask, fold;
 };
 __device__ __forceinline__ CharRule char_rule(uint32_t profile) {
   CharRule r;
   r.iupac = profile == PROFILE_IUPAC ? 1u : 0u;
   r.emask = profile == PROFILE_DNA ? 6u : profile == PROFILE_IUPAC ? 15u : 255u;
   r.mmask = profile == PROFILE_DNA ? 0xDFu : 255u;
+  r.fold = profile == PROFILE_ASCII_CI ? 1u : 0u;
   return r;
+}
+// the stored byte s(c)
+__device__ __forceinline__ uint32_t stored_char(const CharRule& r, uint32_t ch) {
+  if (r.iupac) return kIupacCode[ch & 31u];
+  return r.fold ? fold_ascii(ch) : ch;
 }
 __device__ __forceinline__ bool rule_hit(const CharRule& r, uint32_t p, uint32_t t, uint32_t mask) {
   const uint32_t x = r.iupac ? (p & t) : (p ^ t);
@@ -175,7 +182,7 @@ __global__ __launch_bounds__(64) void trace_kernel(const TraceParams P) {
   if (IN_LDS && !many) {
     for (uint32_t x = tid; x < P.m; x += 64) {
       const uint32_t ch = P.pattern[x];
-      spat[x] = (unsigned char)(rule.iupac ? kIupacCode[ch & 31u] : ch);
+      spat[x] = (unsigned char)stored_char(rule, ch);
     }
     __syncthreads();
   }
@@ -183,7 +190,7 @@ __global__ __launch_bounds__(64) void trace_kernel(const TraceParams P) {
   auto pat_at = [&](int j) -> uint32_t {
     if (IN_LDS && !many) return spat[j];
     const uint32_t ch = my_pat[j];
-    return rule.iupac ? kIupacCode[ch & 31u] : ch;
+    return stored_char(rule, ch);
   };
   unsigned char* slice = IN_LDS ? trace_smem + (size_t)tid * P.scratch_stride
                                 : P.scratch + ((uint64_t)blockIdx.x * 64 + tid) * P.scratch_stride;
@@ -214,8 +221,8 @@ __global__ __launch_bounds__(64) void trace_kernel(const TraceParams P) {
         win[wl - 1 - x] = a;
       }
     }
-    if (rule.iupac)
-      for (int x = 0; x < wl; ++x) win[x] = kIupacCode[win[x] & 31u];
+    if (rule.iupac | rule.fold)
+      for (int x = 0; x < wl; ++x) win[x] = (unsigned char)stored_char(rule, win[x]);
     auto text_at = [&](int i) -> uint32_t { return win[i]; };
 
     // overhang: the end cell may lie past the text (columns wl+1 .. iend are 'N')
@@ -412,7 +419,7 @@ __global__ __launch_bounds__(256) void trace_wave_kernel(const TraceParams P) {
   auto load_pattern = [&](const uint8_t* src) {
     for (uint32_t x = lane; x < P.m; x += 64u) {
       const uint32_t ch = src[x];
-      spat[x] = (unsigned char)(rule.iupac ? kIupacCode[ch & 31u] : ch);
+      spat[x] = (unsigned char)stored_char(rule, ch);
     }
     __builtin_amdgcn_wave_barrier();
   };
@@ -554,7 +561,7 @@ __global__ __launch_bounds__(256) void trace_wave_kernel(const TraceParams P) {
       const uint8_t* rsrc = P.text + (P.rev_n - 1 - (o - P.global_offset));  // reversed view: byte x = rsrc[-x]
       for (int x = (int)lane; x < iend; x += 64) {
         const uint32_t ch = x < wl ? ((have_wpre && x < 64) ? wpre : (P.rev_n ? rsrc[-(int64_t)x] : src[x])) : (uint32_t)'N';
-        win[x] = (unsigned char)(rule.iupac ? kIupacCode[ch & 31u] : ch);
+        win[x] = (unsigned char)stored_char(rule, ch);
       }
     }
     __builtin_amdgcn_wave_barrier();
