@@ -5,7 +5,7 @@
 //! SOURCE ONLY: the image this repository is built in has no `rustc` / `cargo`; nothing in the test
 //! suite compiles this file.  Every `extern "C"` item below is a declaration of `include/sassy_hip.h`;
 //! the C client `tests/c/dropin_client.c` and the Python `ctypes` layer exercise the same symbols.
-use std::ffi::{c_char, c_int, CStr, CString};
+use std::ffi::{c_char, c_int, c_long, CStr, CString};
 use std::marker::PhantomData;
 
 #[repr(C)]
@@ -56,6 +56,10 @@ extern "C" {
     fn sassy_hip_last_error() -> *const c_char;
     fn sassy_hip_search(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, text: *const u8,
                         text_len: usize, k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
+    // character-class patterns (include/sassy_hip.h): 32 bytes per position, byte c at bit c & 7 of sets[32 j + (c >> 3)]
+    fn sassy_hip_search_classes(s: *mut RawSearcher, sets: *const u8, m: usize, text: *const u8, text_len: usize,
+                                k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
+    fn sassy_hip_class_cover(set: *const u8, value: *mut u8, care: *mut u8, cap: usize, complemented: *mut c_int) -> c_long;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

@@ -198,6 +198,29 @@ int sassy_hip_search(sassy_SearcherType *s, const uint8_t *pattern, size_t patte
                      const uint8_t *text, size_t text_len, size_t k, uint32_t flags,
                      sassy_hip_Result **out);
 
+/* Character-class patterns: position j of the pattern is a SET of byte values, 32 bytes per position -- byte value c belongs
+ * to position j iff bit (c & 7) of sets[32 j + (c >> 3)] is set.  Cost is edit distance under "text byte is a member of
+ * the row's set"; in the cigar '=' is a member and 'X' a non-member; an empty set is legal and matches nothing.  Flags,
+ * records, cigar pool and report rule are those of sassy_hip_search (SASSY_HIP_ALL_MINIMA, _WITHOUT_TRACE,
+ * _TEXT_ON_DEVICE, _TEXT_UNCHANGED, _LINE_SPANS).
+ *  - the searcher's alphabet is "ascii" or "ascii_ci"; under ascii_ci every set is closed under the A-Z / a-z twin first;
+ *  - a dna / iupac searcher, rc = true and an overhang searcher (alpha): SASSY_HIP_EUNSUPPORTED;
+ *  - distinct sets are the pattern's profile slots: more than 64 distinct sets is SASSY_HIP_EINVAL;
+ *  - every slot is covered by cubes (value, care) -- byte c is in a cube iff ((c ^ value) & care) == 0 --, each run of
+ *    consecutive byte values by at most 14 aligned power-of-two cubes, the set or (complement flag) whichever of the
+ *    set and its complement takes fewer: at most 128 per set.  The device builds a slot's match mask per 64-byte text
+ *    block from its cubes, about 32 vector instructions per cube against 25 per pattern row; a pattern whose slots
+ *    need more than SASSY_HIP_CLASS_MAX_CUBES cubes together is refused with SASSY_HIP_EINVAL rather than run slowly;
+ *  - the search is the streaming DP over the whole text (no prefilter: their exactness rests on byte equality).
+ * Not available for class patterns: search_all_alignments, search_many, min_costs, best_pattern, best_matches, encoded
+ * patterns, shards / multi-device, search_with_fn -- those entry points take byte patterns only. */
+#define SASSY_HIP_CLASS_MAX_CUBES 256
+int sassy_hip_search_classes(sassy_SearcherType *s, const uint8_t *sets, size_t m, const void *text, size_t text_len, size_t k,
+                             uint32_t flags, sassy_hip_Result **out);
+/* The cover sassy_hip_search_classes gives one set (host only, no device needed): writes the first `cap` cubes to value[] /
+ * care[], *complemented = 1 if they cover the set's complement, and returns the number of cubes (<= 128). */
+long sassy_hip_class_cover(const uint8_t set[32], uint8_t *value, uint8_t *care, size_t cap, int *complemented);
+
 /* Line resolution on the device (sassy_amd/csrc/line_index.hip): out[i] = the span of [first[i], last[i]] in the text, for
  * n spans with first[i] <= last[i] <= text_len (anything else: SASSY_HIP_EINVAL; last == text_len is the empty position
  * behind the text).  A match [text_start, text_end) is the span first = text_start, last = max(text_start, text_end - 1).

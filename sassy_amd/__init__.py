@@ -34,6 +34,7 @@ WITHOUT_TRACE = 2
 TEXT_ON_DEVICE = 4
 NO_MATCH = 255  # min_costs / best_pattern: no match of cost <= k
 TEXT_UNCHANGED = 8
+CLASS_MAX_CUBES = 256  # SASSY_HIP_CLASS_MAX_CUBES: cubes of one class pattern, all distinct sets together
 LINE_SPANS = 16  # sassy_hip_search only: resolve the matches to their lines (Result.line_spans)
 UINT64_MAX = (1 << 64) - 1
 
@@ -150,6 +151,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_generate_dna", "sassy_hip_generate_genome_like", "sassy_hip_plant",
     "sassy_hip_malloc", "sassy_hip_free", "sassy_hip_memcpy_h2d", "sassy_hip_memcpy_d2h",
     "sassy_hip_line_spans", "sassy_hip_result_line_spans", "sassy_hip_line_tile", "sassy_hip_line_span_times",
+    "sassy_hip_search_classes", "sassy_hip_class_cover",
 ]
 
 _lib = None
@@ -278,6 +280,10 @@ def lib():
                                            END_FILTER, vp, C.POINTER(vp)]
     L.sassy_hip_search.restype = C.c_int
     L.sassy_hip_search.argtypes = [vp, u8p, sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
+    L.sassy_hip_search_classes.restype = C.c_int
+    L.sassy_hip_search_classes.argtypes = [vp, u8p, sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
+    L.sassy_hip_class_cover.restype = C.c_long
+    L.sassy_hip_class_cover.argtypes = [u8p, vp, vp, sz, C.POINTER(C.c_int)]
     L.sassy_hip_search_all_alignments.restype = C.c_int
     L.sassy_hip_search_all_alignments.argtypes = [vp, u8p, sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
     L.sassy_hip_search_shard.restype = C.c_int
@@ -610,6 +616,170 @@ class EncodedPatterns:
             self._h = None
 
 
+class ClassPattern:
+    """A character-class pattern: m positions, each a set of byte values.  `sets` holds 32 bytes per position -- byte value
+    c belongs to position j iff bit c & 7 of sets[32 j + (c >> 3)] is set (the layout sassy_hip_search_classes takes)."""
+
+    def __init__(self, sets: bytes):
+        sets = bytes(sets)
+        if len(sets) % 32:
+            raise SassyHipError("ClassPattern: 32 bytes per position")
+        self.sets = sets
+        self.m = len(sets) // 32
+
+    @classmethod
+    def from_sets(cls, sets) -> "ClassPattern":
+        """One iterable of byte values (ints, or a bytes object) per position."""
+        out = bytearray()
+        for members in sets:
+            out += _set_bytes(members)
+        return cls(bytes(out))
+
+    def members(self, j: int) -> List[int]:
+        return [c for c in range(256) if (self.sets[32 * j + (c >> 3)] >> (c & 7)) & 1]
+
+    def __len__(self):
+        return self.m
+
+    def __eq__(self, other):
+        return isinstance(other, ClassPattern) and self.sets == other.sets
+
+    def __repr__(self):
+        return "ClassPattern(m=%d)" % self.m
+
+
+def _set_bytes(members) -> bytearray:
+    b = bytearray(32)
+    for c in members:
+        c = int(c)
+        if not 0 <= c < 256:
+            raise SassyHipError("a class holds byte values 0 .. 255, got %d" % c)
+        b[c >> 3] |= 1 << (c & 7)
+    return b
+
+
+_CLASS_ESCAPES = {
+    ord("d"): frozenset(range(ord("0"), ord("9") + 1)),
+    ord("w"): frozenset(list(range(ord("0"), ord("9") + 1)) + list(range(ord("A"), ord("Z") + 1)) +
+                        list(range(ord("a"), ord("z") + 1)) + [ord("_")]),
+    ord("s"): frozenset(b" \t\n\r\f\v"),
+}
+_ALL_BYTES = frozenset(range(256))
+
+
+def parse_classes(expr: bytes) -> ClassPattern:
+    """The class pattern of an expression, one element per position: a literal byte; `.` (every byte but '\\n');
+    `[...]` with ranges and a leading `^` (the complement over all 256 byte values; a `]` right behind `[` or `[^` is a
+    member); the escapes \\d \\D \\w \\W \\s \\S (also inside brackets), \\n \\t \\xHH and an escaped . [ ] \\ ^ -.  No
+    quantifiers, alternation or anchors.  Raises SassyHipError with the offset of what it cannot read."""
+    if isinstance(expr, str):
+        expr = expr.encode()
+    expr = bytes(expr)
+    n = len(expr)
+    if n == 0:
+        raise SassyHipError("empty class expression (offset 0)")
+
+    def escape(i):
+        """The escape whose backslash sits at i: (set of members, next offset)."""
+        if i + 1 >= n:
+            raise SassyHipError("trailing backslash at offset %d" % i)
+        c = expr[i + 1]
+        if c in b"dDwWsS":
+            base = _CLASS_ESCAPES[c | 0x20]
+            return (base if c & 0x20 else _ALL_BYTES - base), i + 2
+        if c == ord("n"):
+            return frozenset([10]), i + 2
+        if c == ord("t"):
+            return frozenset([9]), i + 2
+        if c == ord("x"):
+            hx = expr[i + 2:i + 4]
+            try:
+                if len(hx) != 2:
+                    raise ValueError
+                return frozenset([int(hx.decode("ascii"), 16)]), i + 4
+            except ValueError:
+                raise SassyHipError("\\x needs two hex digits at offset %d" % i) from None
+        if c in b".[]\\^-":
+            return frozenset([c]), i + 2
+        raise SassyHipError("unknown escape \\%s at offset %d" % (chr(c), i))
+
+    sets = []
+    i = 0
+    while i < n:
+        c = expr[i]
+        if c == ord("\\"):
+            members, i = escape(i)
+        elif c == ord("."):
+            members, i = _ALL_BYTES - {10}, i + 1
+        elif c == ord("["):
+            start = i
+            i += 1
+            negate = i < n and expr[i] == ord("^")
+            if negate:
+                i += 1
+            members = set()
+            first = True
+            while True:
+                if i >= n:
+                    raise SassyHipError("unterminated class opened at offset %d" % start)
+                c = expr[i]
+                if c == ord("]") and not first:
+                    i += 1
+                    break
+                first = False
+                if c == ord("\\"):
+                    lo_set, nxt = escape(i)
+                    if len(lo_set) != 1:  # \d and its kin: no range ends
+                        members |= lo_set
+                        i = nxt
+                        continue
+                    lo = next(iter(lo_set))
+                else:
+                    lo, nxt = c, i + 1
+                # a range lo-hi ('-' right in front of the closing bracket is a member)
+                if nxt + 1 < n and expr[nxt] == ord("-") and expr[nxt + 1] != ord("]"):
+                    at = nxt + 1
+                    if expr[at] == ord("\\"):
+                        hi_set, nxt2 = escape(at)
+                        if len(hi_set) != 1:
+                            raise SassyHipError("a range cannot end in a class escape at offset %d" % at)
+                        hi = next(iter(hi_set))
+                    else:
+                        hi, nxt2 = expr[at], at + 1
+                    if hi < lo:
+                        raise SassyHipError("reversed range at offset %d" % i)
+                    members |= set(range(lo, hi + 1))
+                    i = nxt2
+                else:
+                    members.add(lo)
+                    i = nxt
+            if negate:
+                members = _ALL_BYTES - members
+        else:
+            members, i = frozenset([c]), i + 1
+        sets.append(members)
+    return ClassPattern.from_sets(sets)
+
+
+def class_cover(members):
+    """The cube cover the library gives one set (sassy_hip_class_cover; host only): (cubes, complemented) with cubes a
+    list of (value, care) -- byte c is in a cube iff (c ^ value) & care == 0; complemented: they cover the complement."""
+    st = bytes(_set_bytes(members))
+    value = (C.c_uint8 * 128)()
+    care = (C.c_uint8 * 128)()
+    inv = C.c_int(0)
+    n = lib().sassy_hip_class_cover(st, value, care, 128, C.byref(inv))
+    if n < 0:
+        raise SassyHipError(lib().sassy_hip_last_error().decode())
+    return [(value[i], care[i]) for i in range(n)], bool(inv.value)
+
+
+def _byte_pattern(pattern) -> bytes:
+    if isinstance(pattern, ClassPattern):
+        raise SassyHipError("this call takes byte patterns only: a class pattern runs through Searcher.search_classes")
+    return bytes(pattern)
+
+
 class Searcher:
     """Mirror of sassy.Searcher (src/python.rs:26-64) / Searcher::<P>::new (src/search.rs:486-503).
 
@@ -665,12 +835,30 @@ class Searcher:
         r = self._search(pattern, text, k, LINE_SPANS | (ALL_MINIMA if all_minima else 0))
         return r.matches, r.line_spans
 
+    def search_classes(self, pattern, text, k: int, all_minima: bool = False, without_trace: bool = False, lines: bool = False):
+        """`search` / `search_all` / `search_without_trace` for a character-class pattern (sassy_hip_search_classes): a
+        ClassPattern, or an expression for `parse_classes`.  Row j matches text byte c iff c is in set j; '=' in the cigar
+        is a member, 'X' a non-member.  The searcher's alphabet is "ascii" or "ascii_ci" (every set is then closed under
+        the case twin), rc=False, no alpha.  lines=True: (matches, spans) as `search_lines`.  `text` as for `search`."""
+        if not isinstance(pattern, ClassPattern):
+            pattern = parse_classes(pattern)
+        flags = (ALL_MINIMA if all_minima else 0) | (WITHOUT_TRACE if without_trace else 0) | (LINE_SPANS if lines else 0)
+        addr, n, keep, on_dev = _ptr_len(text)
+        if on_dev:
+            flags |= TEXT_ON_DEVICE
+            if getattr(self, "_text_unchanged", False):
+                flags |= TEXT_UNCHANGED
+        out = C.c_void_p()
+        _check(lib().sassy_hip_search_classes(self._h, pattern.sets, pattern.m, addr, n, k, flags, C.byref(out)))
+        r = Result(out, flags)
+        return (r.matches, r.line_spans) if lines else r.matches
+
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k
         at every end position of search_all, grouped: one list per (strand, anchor) -- the anchor is text_end for
         Fwd matches and text_start for Rc matches --, Fwd groups by ascending text_end, then Rc groups by descending
         text_start, alignments in DFS order inside a group.  `text` as for `search` (bytes or a device tensor)."""
-        pattern = bytes(pattern)
+        pattern = _byte_pattern(pattern)
         addr, n, keep, on_dev = _ptr_len(text)
         flags = 0
         if on_dev:
@@ -692,7 +880,7 @@ class Searcher:
     def search_with_fn(self, pattern: bytes, text: bytes, k: int, all_minima: bool, filter_fn) -> List[Match]:
         """Searcher::search_with_fn (src/search.rs:767-784): keep the end positions for which
         filter_fn(pattern_of_strand: bytes, text_till_end: bytes, strand: '+'|'-') is true."""
-        pattern, text = bytes(pattern), bytes(text)
+        pattern, text = _byte_pattern(pattern), bytes(text)
 
         def tramp(p, plen, t, end, strand, _user):
             return 1 if filter_fn(C.string_at(p, plen), C.string_at(t, end), "-" if strand else "+") else 0
@@ -709,7 +897,7 @@ class Searcher:
         """(pattern pointers, pattern lengths, n_patterns, text pointers, text lengths, n_texts, texts on the device, what
         must stay alive during the call) for the many-pattern calls; `texts` a list or a TextBatch."""
         held = None
-        patterns = [bytes(p) for p in patterns]
+        patterns = [_byte_pattern(p) for p in patterns]
         pp = (C.c_char_p * len(patterns))(*patterns)
         pl = (C.c_size_t * len(patterns))(*[len(p) for p in patterns])
         if isinstance(texts, TextBatch):
@@ -796,7 +984,7 @@ class Searcher:
 
     def search_patterns(self, patterns: Sequence[bytes], text, k: int) -> List[Match]:
         """Searcher::search_patterns (src/search.rs:648-678): equal-length patterns in one text."""
-        patterns = [bytes(p) for p in patterns]
+        patterns = [_byte_pattern(p) for p in patterns]
         if patterns and any(len(p) != len(patterns[0]) for p in patterns):
             raise SassyHipError("All patterns passed to search_patterns must have the same length")
         return self.search_many(patterns, [text], k)
@@ -841,7 +1029,7 @@ class Searcher:
         return self
 
     def encode_patterns(self, patterns: Sequence[bytes]) -> EncodedPatterns:
-        patterns = [bytes(p) for p in patterns]
+        patterns = [_byte_pattern(p) for p in patterns]
         if not patterns:
             raise SassyHipError("No queries provided")
         plen = len(patterns[0])
@@ -870,7 +1058,7 @@ class Searcher:
     def search_shard(self, pattern: bytes, d_text_ptr: int, halo_len: int, shard_len: int,
                      global_offset: int, total_len: int, k: int, flags: int = 0) -> Result:
         out = C.c_void_p()
-        pattern = bytes(pattern)
+        pattern = _byte_pattern(pattern)
         _check(lib().sassy_hip_search_shard(self._h, pattern, len(pattern), d_text_ptr, halo_len,
                                             shard_len, global_offset, total_len, k, flags,
                                             C.byref(out)))
@@ -881,7 +1069,7 @@ class Searcher:
         """Queue one search of a resident shard and return a ticket at once (sassy_hip_search_shard_begin);
         up to 2 may be in flight.  search_finish(ticket) waits for it and returns its Result."""
         out = C.c_void_p()
-        pattern = bytes(pattern)
+        pattern = _byte_pattern(pattern)
         _check(lib().sassy_hip_search_shard_begin(self._h, pattern, len(pattern), d_text_ptr, halo_len, shard_len,
                                                   global_offset, total_len, k, flags, C.byref(out)))
         return out.value
@@ -956,7 +1144,7 @@ class Searcher:
         return self
 
     def _search(self, pattern: bytes, text, k: int, flags: int) -> Result:
-        pattern = bytes(pattern)
+        pattern = _byte_pattern(pattern)
         addr, n, keep, on_dev = _ptr_len(text)
         if on_dev:
             flags |= TEXT_ON_DEVICE
@@ -1019,13 +1207,13 @@ class MultiSearcher:
 
     def plant(self, seed: int, pattern: bytes, k: int, stride: int = 1 << 20) -> int:
         cnt = C.c_uint64()
-        pattern = bytes(pattern)
+        pattern = _byte_pattern(pattern)
         _check(lib().sassy_hip_multi_plant(self._h, seed, pattern, len(pattern), k, stride, C.byref(cnt)))
         return cnt.value
 
     def search(self, pattern: bytes, k: int, flags: int = 0) -> "Result":
         out = C.c_void_p()
-        pattern = bytes(pattern)
+        pattern = _byte_pattern(pattern)
         _check(lib().sassy_hip_multi_search(self._h, pattern, len(pattern), k, flags, C.byref(out)))
         return Result(out)
 
@@ -1054,7 +1242,7 @@ class MultiSearcher:
 
     def search_begin(self, pattern: bytes, k: int, flags: int = 0) -> int:
         """Queues one search on every device and returns a ticket (sassy_hip_multi_search_begin)."""
-        pattern = bytes(pattern)
+        pattern = _byte_pattern(pattern)
         t = C.c_void_p()
         _check(lib().sassy_hip_multi_search_begin(self._h, pattern, len(pattern), k, flags, C.byref(t)))
         return t.value
@@ -1065,7 +1253,7 @@ class MultiSearcher:
         return Result(out)
 
     def search_encoded(self, patterns: Sequence[bytes], k: int, flags: int = 0) -> "Result":
-        patterns = [bytes(p) for p in patterns]
+        patterns = [_byte_pattern(p) for p in patterns]
         if not patterns:
             raise SassyHipError("No queries provided")
         plen = len(patterns[0])
@@ -1076,7 +1264,7 @@ class MultiSearcher:
         return Result(out)
 
     def search_many(self, patterns: Sequence[bytes], texts: Sequence[bytes], k: int, flags: int = 0) -> "Result":
-        patterns = [bytes(p) for p in patterns]
+        patterns = [_byte_pattern(p) for p in patterns]
         texts = [bytes(t) for t in texts]
         pp = (C.c_char_p * len(patterns))(*patterns)
         pl = (C.c_size_t * len(patterns))(*[len(p) for p in patterns])
@@ -1098,7 +1286,7 @@ def multi_layout(length: int, n_parts: int, max_pattern_len: int, max_k: int):
 def seed_layout(alphabet: str, patterns: Sequence[bytes], k: int):
     """[(first row, rows)] of the k + 1 seeds the seeded search of search_encoded_patterns would use for these patterns
     (sassy_hip_seed_layout: host arithmetic, no device needed)."""
-    patterns = [bytes(p) for p in patterns]
+    patterns = [_byte_pattern(p) for p in patterns]
     if not patterns or any(len(p) != len(patterns[0]) for p in patterns):
         raise SassyHipError("seed_layout: patterns of one length, at least one")
     pp = (C.c_char_p * len(patterns))(*patterns)
@@ -1140,7 +1328,7 @@ def generate_genome_like(d_ptr: int, n: int, seed: int, first: int = 0, with_n: 
 def plant(d_ptr: int, n: int, first: int, total_n: int, seed: int, pattern: bytes, k: int,
           stride: int = 1 << 20, stream: int = 0, phase: int = 0) -> int:
     cnt = C.c_uint64()
-    pattern = bytes(pattern)
+    pattern = _byte_pattern(pattern)
     _check(lib().sassy_hip_plant_phase(d_ptr, n, first, total_n, seed, pattern, len(pattern), k, stride, phase,
                                        stream or None, C.byref(cnt)))
     return cnt.value

@@ -28,6 +28,7 @@ UNITS = [
     ("scan_kernel.hip", "scan_dna.o", ["-DSASSY_SCAN_PROFILE=1"]),
     ("scan_kernel.hip", "scan_iupac.o", ["-DSASSY_SCAN_PROFILE=2"]),
     ("scan_kernel.hip", "scan_ascii_ci.o", ["-DSASSY_SCAN_PROFILE=4"]),
+    ("scan_kernel.hip", "scan_classes.o", ["-DSASSY_SCAN_PROFILE=6"]),
     ("count_filter.hip", "count_filter.o", []),
     ("aux_kernels.hip", "aux_kernels.o", []),
     ("sort_kernels.hip", "sort_kernels.o", []),

@@ -23,6 +23,8 @@ files"): every file (no path or `-`: stdin) is read whole and searched forward w
 one block per match, sorted by (start, end): `PATH:LINE:COL:COST:` and the line(s) the match lies in -- LINE and the line's
 bounds come from the device (`Searcher.search_lines`), COL is the 1-based byte column of the match's start.  `-C N` adds up to
 N lines of context as `PATH-LINE-` rows, `--` between blocks that do not touch.  The per-cost histogram goes to stderr.
+`-E / --classes` reads PATTERN as a class expression (`gr[ae]y`, `\\d\\d\\d\\d-\\d\\d-\\d\\d`, `.`, `[^ ]`; one element per
+position, `sassy_amd.parse_classes`) and searches it through `Searcher.search_classes`; with `-i` the sets are closed under case.
 Exit status 0: something matched, 1: nothing did, 2: error.
 
 Not mirrored: coloured output, --v2, threads.
@@ -33,7 +35,7 @@ import argparse
 import sys
 from typing import List, Tuple
 
-from . import NO_MATCH, SassyHipError, Searcher
+from . import NO_MATCH, ClassPattern, SassyHipError, Searcher, parse_classes
 
 BATCH_BYTES = 64 << 20  # input bytes per search_many call (a longer record is a batch of its own; the reader reuses its buffers)
 
@@ -173,6 +175,9 @@ def agrep_parser(sub=None):
     ap = sub.add_parser("agrep", help=doc) if sub is not None else argparse.ArgumentParser(prog="python -m sassy_amd agrep", description=doc)
     ap.add_argument("-i", "--ignore-case", action="store_true", help="the ascii_ci profile: A-Z and a-z match each other")
     ap.add_argument("-C", "--context", type=int, default=0, metavar="N", help="lines of context around every match")
+    ap.add_argument("-E", "--classes", action="store_true",
+                    help="PATTERN is a class expression, one element per position: gr[ae]y, \\d\\d\\d\\d-\\d\\d, '.', [^ ] "
+                         "(sassy_amd.parse_classes; no quantifiers, alternation or anchors)")
     ap.add_argument("pattern")
     ap.add_argument("k", type=int)
     ap.add_argument("paths", nargs="*", help="files to search; none or '-': standard input")
@@ -189,6 +194,8 @@ def run_agrep(args, stdin=None, out=None, err=None) -> int:
     pattern = args.pattern.encode()
     hist = [0] * (args.k + 1)
     try:
+        if getattr(args, "classes", False):
+            pattern = parse_classes(pattern)
         searcher = Searcher("ascii_ci" if args.ignore_case else "ascii", rc=False)
         for path in args.paths or ["-"]:
             if path == "-":
@@ -197,7 +204,10 @@ def run_agrep(args, stdin=None, out=None, err=None) -> int:
                 name = path
                 with open(path, "rb") as fh:
                     text = fh.read()
-            matches, spans = searcher.search_lines(pattern, text, args.k)
+            if isinstance(pattern, ClassPattern):
+                matches, spans = searcher.search_classes(pattern, text, args.k, lines=True)
+            else:
+                matches, spans = searcher.search_lines(pattern, text, args.k)
             for m in matches:
                 hist[m.cost] += 1
             out.write(format_agrep(name, text, matches, spans, args.context))

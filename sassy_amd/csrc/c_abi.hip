@@ -406,10 +406,9 @@ long sassy_hip_format_tsv(const sassy_SearcherType* s, const sassy_hip_Match* mp
   return (long)row.size();
 }
 
-int sassy_hip_search(sassy_SearcherType* s, const uint8_t* pattern, size_t pattern_len,
-                     const uint8_t* text, size_t text_len, size_t k, uint32_t flags,
-                     sassy_hip_Result** out) {
-  if (!s || !pattern || (!text && text_len) || !out) return fail(SASSY_HIP_EINVAL, "Pointers in search() must not be null");
+// sassy_hip_search and sassy_hip_search_classes (class_plan != nullptr: `pattern` holds the rows' slot indices)
+static int search_entry(sassy_SearcherType* s, const uint8_t* pattern, size_t pattern_len, const uint8_t* text, size_t text_len,
+                        size_t k, uint32_t flags, sassy_hip_Result** out, const PatternPlan* class_plan) {
   SASSY_NO_TICKETS(s);
   const bool want_lines = (flags & SASSY_HIP_LINE_SPANS) != 0;
   if (want_lines && (flags & SASSY_HIP_WITHOUT_TRACE))
@@ -418,7 +417,7 @@ int sassy_hip_search(sassy_SearcherType* s, const uint8_t* pattern, size_t patte
   const double t0 = now_ms();
   reset_stats(s);
   sassy_hip_Result* R = new sassy_hip_Result();
-  if (int rc = search_text(s, pattern, pattern_len, text, text_len, k, flags, 0, true, s->rc, R)) { delete R; return rc; }
+  if (int rc = search_text(s, pattern, pattern_len, text, text_len, k, flags, 0, true, s->rc, R, EndFilter(), false, class_plan)) { delete R; return rc; }
   if (R->pool.empty()) R->pool.push_back('\0');
   if (want_lines) {  // the text is still resident: the caller's buffer, or the copy the search uploaded
     const size_t n = R->size();
@@ -437,6 +436,36 @@ int sassy_hip_search(sassy_SearcherType* s, const uint8_t* pattern, size_t patte
   s->stats.host_post_ms = s->stats.total_ms - s->stats.host_enqueue_ms - s->stats.host_wait_ms;
   *out = R;
   return 0;
+}
+
+int sassy_hip_search(sassy_SearcherType* s, const uint8_t* pattern, size_t pattern_len,
+                     const uint8_t* text, size_t text_len, size_t k, uint32_t flags,
+                     sassy_hip_Result** out) {
+  if (!s || !pattern || (!text && text_len) || !out) return fail(SASSY_HIP_EINVAL, "Pointers in search() must not be null");
+  return search_entry(s, pattern, pattern_len, text, text_len, k, flags, out, nullptr);
+}
+
+static_assert(SASSY_HIP_CLASS_MAX_CUBES == kMaxClassCubes, "the header documents the cube cap");
+long sassy_hip_class_cover(const uint8_t set[32], uint8_t* value, uint8_t* care, size_t cap, int* complemented) {
+  if (!set || (cap && (!value || !care))) return fail(SASSY_HIP_EINVAL, "Pointers in class_cover() must not be null");
+  return (long)class_cover(set, cap ? value : nullptr, care, cap, complemented);
+}
+
+int sassy_hip_search_classes(sassy_SearcherType* s, const uint8_t* sets, size_t m, const void* text, size_t text_len, size_t k,
+                             uint32_t flags, sassy_hip_Result** out) {
+  if (!s || !sets || (!text && text_len) || !out) return fail(SASSY_HIP_EINVAL, "Pointers in search_classes() must not be null");
+  if (!is_ascii(s->profile))
+    return fail(SASSY_HIP_EUNSUPPORTED, "class patterns need an ascii or ascii_ci searcher (Iupac letters are the dna alphabets' classes)");
+  if (s->rc) return fail(SASSY_HIP_EUNSUPPORTED, "reverse complement is not defined for the ascii alphabet");
+  if (!std::isnan(s->alpha)) return fail(SASSY_HIP_EUNSUPPORTED, "class patterns do not take overhang (alpha)");
+  if (flags & ~(uint32_t)(SASSY_HIP_ALL_MINIMA | SASSY_HIP_WITHOUT_TRACE | SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_TEXT_UNCHANGED |
+                          SASSY_HIP_LINE_SPANS))
+    return fail(SASSY_HIP_EINVAL, "unknown flag in search_classes()");
+  PatternPlan plan;
+  std::vector<uint8_t> rows;
+  std::string err;
+  if (!make_class_plan(s->profile, sets, m, plan, rows, err)) return fail(SASSY_HIP_EINVAL, err);
+  return search_entry(s, rows.data(), m, static_cast<const uint8_t*>(text), text_len, k, flags, out, &plan);
 }
 
 uint64_t sassy_hip_required_halo(size_t pattern_len, size_t k) {

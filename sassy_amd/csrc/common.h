@@ -14,6 +14,12 @@ constexpr bool is_ascii(Profile pr) { return pr == PROFILE_ASCII || pr == PROFIL
 // row's pattern byte (the row table then holds the bytes themselves): 16 VALU more per row, any pattern.
 constexpr uint32_t PROFILE_ASCII_BYTES = 3;
 constexpr uint32_t PROFILE_ASCII_CI_BYTES = 5;  // the same under PROFILE_ASCII_CI: the row table holds the folded bytes
+// Kernel-side only: character-class patterns (sassy_hip_search_classes) of an Ascii searcher.  A slot is a SET of byte
+// values, covered by cubes (value, care): byte c is in a cube iff ((c ^ value) & care) == 0; the slot's mask is the OR of
+// its cubes' masks, inverted when the slot is stored as its complement (ScanParams::class_tab).  The traceback reads the
+// slots' 256-bit bitmaps instead (TraceParams::class_bits); its pattern "characters" are the rows' slot indices.
+constexpr uint32_t PROFILE_CLASSES = 6;
+constexpr uint32_t kMaxClassCubes = 256;      // cubes of one class pattern, all slots together (32 VALU per cube and block)
 // The fold of PROFILE_ASCII_CI (u8::to_ascii_lowercase): pattern bytes are folded by the host, text bytes by the kernels.
 __host__ __device__ constexpr uint32_t fold_ascii(uint32_t c) { return (c | 0x20u) - 'a' < 26u ? (c | 0x20u) : c; }
 
@@ -27,6 +33,10 @@ constexpr uint32_t kHalfTileBytes = 64 * 64;  // 1 block (half a line), (owner>>
 constexpr uint32_t kRegionSlots = 16;  // chunk descriptors a wave of the counting filter can file (count_direct)
 constexpr int kMaxSlots = 64;          // profile slots (distinct pattern letters) per search: Dna 4, Iupac <= 16,
                                        // Ascii <= 64 distinct pattern bytes
+// class patterns' device table (ScanParams::class_tab): word s < kMaxSlots = the header of slot s -- index of its first cube
+// (bits 0..15), number of cubes (bits 16..30), complement flag (bit 31) --, then the cubes: value | care << 8
+constexpr uint32_t kClassTabWords = kMaxSlots + kMaxClassCubes;
+constexpr uint32_t kClassBitsBytes = 256 * 32;  // TraceParams::class_bits: 32 bytes per slot, room for any byte as a "slot"
 
 // Control block (64 bytes, device): u32 [0] reports, [1] chunk descriptors | bytes 16..47: u64
 // counters | words 12..15 (tail): the chunk that ends the buffer -- own_lo, exit state, descriptor
@@ -231,6 +241,7 @@ struct ScanParams {
     uint32_t m, k, nwords, wb, flags, cand_cap, stash_cap, pad_;
   } member1;
   uint32_t piece_member;
+  const uint32_t* class_tab;  // PROFILE_CLASSES: device, kClassTabWords words (read through scalar loads)
 };
 constexpr uint32_t kFuseGroupMaxWords = 4;  // grouped pass: pattern words per member (the carries leave the tile's upper half free)
 
@@ -402,6 +413,9 @@ struct TraceParams {
   // many patterns over a multi-text buffer (pattern_stride != 0 and texts.n != 0): the flags name the pattern, the
   // text of report c is report_text[c]
   const uint32_t* report_text;
+  // PROFILE_CLASSES: device, 32 bytes per slot -- bit (t & 7) of byte 32 s + (t >> 3) = text byte t is in slot s's set;
+  // `pattern` then holds the rows' slot indices
+  const uint8_t* class_bits;
 };
 constexpr uint32_t kTraceWaveDummy = 128;  // trace_wave_kernel: bytes at the end of a wave's slice that nothing reads
 // MatchOut::pad_[0] of a record whose traceback found no ancestor / exceeded the scanned cost

@@ -37,6 +37,7 @@ hipError_t launch_scan_dna(const ScanParams& P, uint32_t grid, size_t smem, hipS
 hipError_t launch_scan_iupac(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_scan_ascii(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_scan_ascii_ci(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
+hipError_t launch_scan_classes(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);  // (PROFILE_CLASSES)
 hipError_t launch_filter_dna(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_filter_group(const ScanParams& P, uint32_t grid, hipStream_t stream);  // (two searches, one pass)
 hipError_t launch_filter_table(const ScanParams& P, uint32_t grid, hipStream_t stream);
@@ -350,8 +351,10 @@ struct ScanLane {
   DevBuf<TextStash> d_stash;   // fused filter: the text under the reports, for the traceback
   DevBuf<unsigned long long> d_probe;  // SASSY_HIP_TRACE_PROBE
   DevBuf<uint32_t> d_rowoff, d_ovtab;
-  std::vector<uint8_t> up_pattern, h_table, table_pattern;
-  std::vector<uint32_t> up_rowtab, up_ovtab;
+  DevBuf<uint32_t> d_classtab;   // class patterns: the cube table of the scan, the slot bitmaps of the traceback
+  DevBuf<uint8_t> d_classbits;
+  std::vector<uint8_t> up_pattern, h_table, table_pattern, up_classbits;
+  std::vector<uint32_t> up_rowtab, up_ovtab, up_classtab;
   int up_profile = -1, table_profile = -1;
   uint32_t table_q = 0, table_k = 0, table_r = 0;   // table_r: 0 = piece bit table, else the counting table's R
   bool table_rc = false;                            // the counting table also holds the Rc strand's q-grams
@@ -488,6 +491,7 @@ struct ScanLane {
     for (unsigned char*& b : h_bulk) { if (b) (void)hipHostFree(b); b = nullptr; }
     d_cand.release(); d_sorted.release(); d_trace.release(); d_desc.release(); d_regions.release(); d_region_count.release(); d_carry.release();
     d_pattern.release(); d_table.release(); d_rowoff.release(); d_ovtab.release(); d_stash.release();
+    d_classtab.release(); d_classbits.release();
     if (h_pin) g_pin_pool.give(PinBlock{h_pin, h_pin_dev, h_pin_cap, h_pin_device});
     h_pin = nullptr;
     for (hipEvent_t e : {ev_a, ev_b, ev_c, ev_f, ev_filter_done, ev_done, ev_group})
@@ -1149,7 +1153,7 @@ void layout_texts(uint8_t* dst, const uint8_t* const* texts, const size_t* lens,
 int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, const uint8_t* text,
                        size_t tlen, size_t k, uint32_t flags, uint64_t pattern_idx, bool fwd_strand,
                        bool rc_strand, sassy_hip_Result* R, const EndFilter& ef = EndFilter(),
-                       bool already_uploaded = false);
+                       bool already_uploaded = false, const PatternPlan* class_plan = nullptr);
 int run_scan(sassy_SearcherType* S, const ShardView& sh, const PatternPlan& plan, uint32_t k,
                     bool all_minima, const uint8_t* pat, bool do_trace, uint64_t total_len, ScanOut& out);
 int run_scan_ref_lanes(sassy_SearcherType* S, const uint8_t* d_text, uint64_t n, const PatternPlan& plan, uint32_t k,

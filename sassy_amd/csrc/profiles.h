@@ -11,6 +11,7 @@
 //           with themselves
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -89,6 +90,10 @@ struct PatternPlan {
                                      // 8 words per 32 rows (padded with slot 0)
   bool bytes = false;                // Ascii with more than kMaxSlots distinct (folded) bytes (PROFILE_ASCII_BYTES): nslots = 8
                                      // (the bit planes), the row table holds the pattern bytes themselves
+  // class patterns (make_class_plan; PROFILE_CLASSES): a slot is a set of byte values
+  bool classes = false;
+  std::vector<uint32_t> class_tab;   // kClassTabWords words: slot headers, then the cubes (common.h)
+  std::vector<uint8_t> class_bits;   // 32 bytes per slot: the set itself, for the traceback
 };
 
 // Profile::encode_pattern (dna.rs:19-23, iupac.rs:18-36, ascii.rs:18-29).
@@ -141,6 +146,95 @@ inline bool make_plan(Profile pr, const uint8_t* pat, size_t m, PatternPlan& pla
   plan.nslots = (uint32_t)letters.size();
   for (size_t s = 0; s < letters.size(); ++s)
     plan.slot_val[s] = pr == PROFILE_IUPAC ? (uint8_t)(iupac_code(letters[s]) & 0x0F) : letters[s];
+  return true;
+}
+
+// ---- character classes: a pattern position is a set of byte values (256 bits: byte c at bit c & 7 of set[c >> 3]) ----
+inline bool class_has(const uint8_t* set, uint32_t c) { return (set[c >> 3] >> (c & 7)) & 1u; }
+
+// The runs of consecutive members of `set` (inverted: of its complement), each split into aligned power-of-two cubes --
+// at most 14 per run (7 growing, 7 shrinking).  Cube i = (value[i], care[i]): byte c is in it iff ((c ^ value) & care) == 0.
+// Writes the first `cap` cubes (value == nullptr: none) and returns how many there are.
+inline size_t class_run_cubes(const uint8_t* set, bool inverted, uint8_t* value, uint8_t* care, size_t cap) {
+  size_t n = 0;
+  uint32_t c = 0;
+  while (c < 256) {
+    if (class_has(set, c) == inverted) { ++c; continue; }
+    uint32_t hi = c;
+    while (hi + 1 < 256 && class_has(set, hi + 1) != inverted) ++hi;
+    uint32_t a = c;
+    while (a <= hi) {
+      uint32_t size = 1;
+      while (2 * size <= 256 && (a & (2 * size - 1)) == 0 && a + 2 * size - 1 <= hi) size *= 2;
+      if (value && n < cap) { value[n] = (uint8_t)a; care[n] = (uint8_t)(~(size - 1) & 0xFFu); }
+      ++n;
+      a += size;
+    }
+    c = hi + 1;
+  }
+  return n;
+}
+// The cover of one set: its own runs, or -- where that takes fewer cubes -- the runs of its complement (*complemented = 1:
+// a byte is a member iff NO cube holds it).  Never more than 128 cubes: a set of n bytes takes at most n, its complement
+// at most 256 - n.
+inline size_t class_cover(const uint8_t* set, uint8_t* value, uint8_t* care, size_t cap, int* complemented) {
+  const size_t plain = class_run_cubes(set, false, nullptr, nullptr, 0);
+  const size_t inv = class_run_cubes(set, true, nullptr, nullptr, 0);
+  const bool use_inv = inv < plain;
+  if (complemented) *complemented = use_inv ? 1 : 0;
+  return class_run_cubes(set, use_inv, value, care, cap);
+}
+
+// The plan of a class pattern: `sets` holds m sets of 32 bytes.  Distinct sets become slots (PROFILE_ASCII_CI: after
+// closing every set under the A-Z / a-z twin); `rows` receives the slot of every row -- the "pattern" the traceback sees.
+inline bool make_class_plan(Profile pr, const uint8_t* sets, size_t m, PatternPlan& plan, std::vector<uint8_t>& rows, std::string& err) {
+  if (m == 0) { err = "empty pattern"; return false; }
+  if (m > (1u << 20)) { err = "pattern longer than 2^20 is not supported"; return false; }
+  plan = PatternPlan{};
+  plan.classes = true;
+  plan.m = (uint32_t)m;
+  plan.nwords = (uint32_t)((m + 31) / 32);
+  plan.row_tab.assign((size_t)plan.nwords * 8, 0u);
+  rows.assign(m, 0);
+  std::vector<uint8_t> slots;  // 32 bytes each
+  for (size_t j = 0; j < m; ++j) {
+    uint8_t set[32];
+    memcpy(set, sets + 32 * j, 32);
+    if (pr == PROFILE_ASCII_CI)
+      for (uint32_t c = 'A'; c <= 'Z'; ++c)
+        if (class_has(set, c) || class_has(set, c | 0x20u)) {
+          set[c >> 3] |= (uint8_t)(1u << (c & 7));
+          set[(c | 0x20u) >> 3] |= (uint8_t)(1u << ((c | 0x20u) & 7));
+        }
+    size_t s = 0;
+    const size_t ns = slots.size() / 32;
+    while (s < ns && memcmp(slots.data() + 32 * s, set, 32) != 0) ++s;
+    if (s == ns) {
+      if (ns == (size_t)kMaxSlots) {
+        err = "class pattern uses more than " + std::to_string(kMaxSlots) + " distinct sets";
+        return false;
+      }
+      slots.insert(slots.end(), set, set + 32);
+    }
+    rows[j] = (uint8_t)s;
+    plan.row_tab[j >> 2] |= (2u * (uint32_t)s) << (8 * (j & 3));
+  }
+  plan.nslots = (uint32_t)(slots.size() / 32);
+  plan.class_bits = slots;
+  plan.class_tab.assign(kClassTabWords, 0u);
+  uint32_t total = 0;
+  for (uint32_t s = 0; s < plan.nslots; ++s) {
+    uint8_t value[128], care[128];
+    int inv = 0;
+    const uint32_t n = (uint32_t)class_cover(slots.data() + 32 * s, value, care, 128, &inv);
+    if (total + n > kMaxClassCubes) {
+      err = "class pattern needs more than " + std::to_string(kMaxClassCubes) + " cubes (SASSY_HIP_CLASS_MAX_CUBES)";
+      return false;
+    }
+    plan.class_tab[s] = total | (n << 16) | (inv ? 0x80000000u : 0u);
+    for (uint32_t i = 0; i < n; ++i) plan.class_tab[kMaxSlots + total + i] = (uint32_t)value[i] | ((uint32_t)care[i] << 8);
+    total += n;
+  }
   return true;
 }
 

@@ -150,6 +150,7 @@ static double clumped_tail(double lambda, uint32_t t) {
 }
 
 static hipError_t launch_scan_any(Profile pr, const ScanParams& P, uint32_t grid, size_t smem, hipStream_t st) {
+  if (P.profile == PROFILE_CLASSES) return launch_scan_classes(P, grid, smem, st);
   switch (pr) {
     case PROFILE_DNA: return launch_scan_dna(P, grid, smem, st);
     case PROFILE_IUPAC: return launch_scan_iupac(P, grid, smem, st);
@@ -242,6 +243,12 @@ int ScanJob::prepare() {
   P.nwords = plan.nwords;
   P.nslots = plan.nslots;
   P.profile = !plan.bytes ? (uint32_t)S->profile : S->profile == PROFILE_ASCII_CI ? PROFILE_ASCII_CI_BYTES : PROFILE_ASCII_BYTES;
+  if (plan.classes) {
+    // class patterns exist on the streaming DP only: every filter's exactness rests on byte equality
+    if (!is_ascii(S->profile) || overhang || ext_bitmap || ext_desc || rc_bitmap || rev_n || texts.n)
+      return fail(SASSY_HIP_EUNSUPPORTED, "internal: a class pattern runs as one streaming search of an ascii searcher");
+    P.profile = PROFILE_CLASSES;
+  }
   P.wb = warmup_blocks(plan.m, k);
   P.flags = (all_minima ? kScanAllMinima : 0u) | (sh.text_start ? kScanTextStart : 0u) |
             (sh.text_end ? kScanTextEnd : 0u) | (overhang ? kScanOverhang : 0u);
@@ -258,7 +265,7 @@ int ScanJob::prepare() {
   if (overhang) q = 0;
   // Ascii patterns with more than 16 distinct bytes: only the DP kernels carry that many slot masks (or, byte mode,
   // compare bytes instead of looking slots up)
-  if (plan.nslots > 16 || plan.bytes) q = 0;
+  if (plan.nslots > 16 || plan.bytes || plan.classes) q = 0;
   if (ext_bitmap) q = ext_q;
   if (ext_desc) q = 1;  // list mode without a filter
   // which prefilter kernel (SASSY_HIP_FILTER_KIND=1|2|3|4 forces one where it applies)
@@ -437,6 +444,21 @@ int ScanJob::prepare() {
       if (int rc = L.upload(L.d_pattern.p, L.up_pattern.data(), plan.m)) return rc;
     }
   }
+  if (plan.classes) {
+    if (int rc = L.d_classtab.reserve(kClassTabWords)) return rc;
+    // (the traceback's unrolled fill reads a row ahead of the pattern and beside the window, values it then drops: the
+    // bitmap area holds 256 "slots", so that any byte pair indexes inside it)
+    if (int rc = L.d_classbits.reserve(kClassBitsBytes)) return rc;
+    std::vector<uint8_t> bits(plan.class_bits);
+    bits.resize(kClassBitsBytes, 0);
+    if (L.up_classtab != plan.class_tab || L.up_classbits != bits) {
+      L.up_classtab = plan.class_tab;
+      L.up_classbits.swap(bits);
+      if (int rc = L.upload(L.d_classtab.p, L.up_classtab.data(), L.up_classtab.size() * sizeof(uint32_t))) return rc;
+      if (int rc = L.upload(L.d_classbits.p, L.up_classbits.data(), L.up_classbits.size())) return rc;
+    }
+    P.class_tab = L.d_classtab.p;
+  }
   if (overhang) {
     // left-edge vertical deltas at the text start: floor((i+1) alpha) - floor(i alpha) for the first
     // min(m, max_overhang) rows, 1 below (reference: src/search.rs:1713-1731); row r of word w at bit 31-r
@@ -523,7 +545,8 @@ int ScanJob::prepare() {
     T.cand_count = d_counts;
     T.m = plan.m;
     T.k = k;
-    T.profile = (uint32_t)S->profile;
+    T.profile = plan.classes ? PROFILE_CLASSES : (uint32_t)S->profile;
+    T.class_bits = plan.classes ? L.d_classbits.p : nullptr;
     T.pattern = L.d_pattern.p;
     T.scratch = L.d_scratch.p;
     T.scratch_stride = (uint32_t)stride;
@@ -1835,10 +1858,12 @@ int post_filter(sassy_SearcherType* S, ScanOut& so, const PatternPlan& plan, con
 int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, const uint8_t* text,
                        size_t tlen, size_t k, uint32_t flags, uint64_t pattern_idx, bool fwd_strand,
                        bool rc_strand, sassy_hip_Result* R, const EndFilter& ef,
-                       bool already_uploaded) {
+                       bool already_uploaded, const PatternPlan* class_plan) {
   PatternPlan plan;
   std::string err;
-  if (!make_plan(S->profile, pattern, plen, plan, err)) return fail(SASSY_HIP_EINVAL, err);
+  // (a class pattern comes with its plan: `pattern` then holds the rows' slot indices)
+  if (class_plan) plan = *class_plan;
+  else if (!make_plan(S->profile, pattern, plen, plan, err)) return fail(SASSY_HIP_EINVAL, err);
   if (k > 0x7FFFFFFFu) return fail(SASSY_HIP_EINVAL, "k too large");
   if (rc_strand && is_ascii(S->profile))
     // the reference constructs such a searcher and panics at its first search: Profile::complement is
@@ -1875,7 +1900,7 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
   // that can do it (bit-plane / counting) and no option that wants the reversed text as such.
   const int env_fuse = (int)S->sw.rc_fused;
   // the reference's lane reports (run_scan_ref_lanes): single texts, no overhang; each strand lane by lane
-  const uint32_t ref_lanes = (S->ref_lanes == 4 || S->ref_lanes == 8) && std::isnan(S->alpha) ? S->ref_lanes : 0u;
+  const uint32_t ref_lanes = (S->ref_lanes == 4 || S->ref_lanes == 8) && std::isnan(S->alpha) && !class_plan ? S->ref_lanes : 0u;
   // Shapes of the paired filter: it exists as the fused launch of ONE strand only, and two of them (the Rc strand's on the
   // reversed copy) beat the forward strand's streaming DP with the Rc marks in it (m = 23, k = 3: 1.4 against 1.8 ms).
   // SASSY_HIP_PAIR_RC=0: as before.

@@ -489,6 +489,8 @@ __device__ __forceinline__ uint2 folded_plane5(const uint2 (&pl)[8]) {
                     pl[5].y | upper(pl[0].y, pl[1].y, pl[2].y, pl[3].y, pl[4].y, pl[5].y, pl[6].y, pl[7].y));
 }
 
+typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;  // scalar (s_load) reads
+
 // Slot masks of one block from the lane's 64 text bytes.  m[s] = mask of slot s (lo, hi).
 template <int PROFILE, int NS>
 __device__ __forceinline__ void build_masks(const uint32_t (&x)[16], const ScanParams& P, uint2 (&m)[NS]) {
@@ -548,6 +550,41 @@ __device__ __forceinline__ void build_masks(const uint32_t (&x)[16], const ScanP
   }
 }
 
+// Character classes (common.h: PROFILE_CLASSES): a slot is a set of byte values, covered by cubes.  The mask of a cube is
+// the Ascii slot build above with a don't-care term -- AND over the bits b of ((plane b XNOR value bit b) | ~care bit b) --,
+// the slot's mask the OR over its cubes, inverted where the slot is stored as its complement.  The table comes through
+// scalar loads: headers, cubes and both loop bounds are wave-uniform.  Unused slots have a zero header: an empty mask.
+// Every mask goes to LDS (`dst`: the lane's 8 bytes of slot 0, slots 512 bytes apart) as soon as it is made: the cube
+// loops have run-time bounds, and 64 masks kept until the end would cost 128 VGPRs.
+template <int NS>
+__device__ __forceinline__ void build_class_masks(const uint32_t (&x)[16], const ScanParams& P, unsigned char* dst) {
+  uint2 pl[8];
+  pl[0] = bit_plane<0>(x); pl[1] = bit_plane<1>(x); pl[2] = bit_plane<2>(x); pl[3] = bit_plane<3>(x);
+  pl[4] = bit_plane<4>(x); pl[5] = bit_plane<5>(x); pl[6] = bit_plane<6>(x); pl[7] = bit_plane<7>(x);
+  const_u32_ptr tab = (const_u32_ptr)(P.class_tab);
+#pragma unroll 4
+  for (int s = 0; s < NS; ++s) {
+    const uint32_t hdr = tab[s];
+    const uint32_t first = (uint32_t)kMaxSlots + (hdr & 0xFFFFu), n = (hdr >> 16) & 0x7FFFu;
+    uint2 r = make_uint2(0u, 0u);
+    for (uint32_t c = 0; c < n; ++c) {
+      const uint32_t cube = tab[first + c];  // value | care << 8
+      uint2 t = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        const uint32_t inv = ~(uint32_t)__builtin_amdgcn_sbfe((int)cube, b, 1);       // all ones iff the value's bit is 0
+        const uint32_t free_ = ~(uint32_t)__builtin_amdgcn_sbfe((int)cube, 8 + b, 1);  // all ones iff the bit is don't-care
+        t.x &= bitop3<0xBE>(pl[b].x, inv, free_);  // (a ^ b) | c
+        t.y &= bitop3<0xBE>(pl[b].y, inv, free_);
+      }
+      r.x |= t.x;
+      r.y |= t.y;
+    }
+    const uint32_t flip = (uint32_t)((int)hdr >> 31);  // all ones: the cubes cover the complement
+    *reinterpret_cast<uint2*>(dst + s * 512) = make_uint2(r.x ^ flip, r.y ^ flip);
+  }
+}
+
 // first block a chunk touches: its first owned block minus `back` = the warm-up plus the parity
 // that makes it even (a staged pair of blocks is then one aligned 128-byte line; bpl is even),
 // clipped at the buffer start (only the very first chunk of a text clips).
@@ -555,8 +592,6 @@ __device__ __forceinline__ uint64_t chunk_blk0(uint64_t first_owned, uint32_t bp
   const uint64_t start = first_owned + chunk * (uint64_t)bpl;
   return start > back ? start - back : 0;
 }
-
-typedef const uint32_t __attribute__((address_space(4)))* const_u32_ptr;  // scalar (s_load) reads
 
 // Row -> LDS offset of its slot mask, from the packed row table: one byte per row holding
 // slot*2, so that (byte << 8) = slot * 512.  Scalar extraction (s_bfe) + one VALU add.
@@ -888,11 +923,15 @@ __global__ __launch_bounds__(256) void scan_kernel(const ScanParams P) {
         const uint4 v = *reinterpret_cast<const uint4*>(tile + rc[c]);
         x[4 * c] = v.x; x[4 * c + 1] = v.y; x[4 * c + 2] = v.z; x[4 * c + 3] = v.w;
       }
-      uint2 msk[NS];
-      build_masks<PROFILE, NS>(x, P, msk);
+      if constexpr (PROFILE == (int)PROFILE_CLASSES) {
+        build_class_masks<NS>(x, P, mask_bytes + lane * 8);
+      } else {
+        uint2 msk[NS];
+        build_masks<PROFILE, NS>(x, P, msk);
 #pragma unroll
-      for (int s = 0; s < NS; ++s)
-        *reinterpret_cast<uint2*>(mask_bytes + s * 512 + lane * 8) = msk[s];
+        for (int s = 0; s < NS; ++s)
+          *reinterpret_cast<uint2*>(mask_bytes + s * 512 + lane * 8) = msk[s];
+      }
     }
 
     // ---- the DP rows of this block (bounded: the wave stops at the first row below which no lane can
@@ -2842,7 +2881,7 @@ static hipError_t launch_list_one(const ScanParams& P, uint32_t grid, size_t sme
 }
 
 #ifndef SASSY_SCAN_PROFILE
-#error "compile with -DSASSY_SCAN_PROFILE=<0|1|2|4> (one translation unit per profile, by its Profile value)"
+#error "compile with -DSASSY_SCAN_PROFILE=<0|1|2|4|6> (one translation unit per profile, by its Profile value)"
 #endif
 
 #if SASSY_SCAN_PROFILE == 1
@@ -2974,6 +3013,18 @@ hipError_t launch_filter_group(const ScanParams& P, uint32_t grid, hipStream_t s
     case 12: return launch_filter_group_q<12>(P, grid, stream);
     default: return hipErrorInvalidValue;
   }
+}
+#elif SASSY_SCAN_PROFILE == 6
+// Character classes (sassy_hip_search_classes): the streaming DP only -- no prefilter and no chunk list build their masks.
+hipError_t launch_scan_classes(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream) {
+  constexpr int PR = (int)PROFILE_CLASSES;
+  if (P.profile != PROFILE_CLASSES || P.class_tab == nullptr) return hipErrorInvalidValue;
+  if (P.nslots <= 4) return launch_one<PR, 4>(P, grid, smem, stream);
+  if (P.nslots <= 8) return launch_one<PR, 8>(P, grid, smem, stream);
+  if (P.nslots <= 16) return launch_one<PR, 16>(P, grid, smem, stream);
+  if (P.nslots <= 32) return launch_one<PR, 32>(P, grid, smem, stream);
+  if (P.nslots <= 64) return launch_one<PR, 64>(P, grid, smem, stream);
+  return hipErrorInvalidValue;
 }
 #else
 // Ascii and its case-insensitive twin (one translation unit each): the same launchers over their own instantiations

@@ -40,11 +40,18 @@ __constant__ uint8_t kIupacCode[32] = {
 // Dna: emask 6 ((c>>1)&3 codes, src/profiles/dna.rs:19-60), mmask 0xDF (case-insensitive byte);
 // Iupac: emask 15 (non-letters = 255 act as N in the scan), mmask 255; Ascii: both 255.
 // Case-insensitive Ascii (fold): s(c) = the folded byte, for pattern and text alike, then as Ascii.
+// Character classes (cls != nullptr; PROFILE_CLASSES): the stored pattern "character" of a row is its slot index, the text
+// byte stays raw, and a hit -- scan equality and display match alike -- is bit t of that slot's 256-bit set.
 struct CharRule {
   uint32_t iupac, emask, mmask, fold;
+  const uint8_t* cls;
 };
-__device__ __forceinline__ CharRule char_rule(uint32_t profile) {
+__device__ __forceinline__ bool class_hit(const uint8_t* cls, uint32_t slot, uint32_t t) {
+  return (((uint32_t)cls[slot * 32u + (t >> 3)] >> (t & 7u)) & 1u) != 0u;
+}
+__device__ __forceinline__ CharRule char_rule(uint32_t profile, const uint8_t* class_bits) {
   CharRule r;
+  r.cls = profile == PROFILE_CLASSES ? class_bits : nullptr;
   r.iupac = profile == PROFILE_IUPAC ? 1u : 0u;
   r.emask = profile == PROFILE_DNA ? 6u : profile == PROFILE_IUPAC ? 15u : 255u;
   r.mmask = profile == PROFILE_DNA ? 0xDFu : 255u;
@@ -57,6 +64,7 @@ __device__ __forceinline__ uint32_t stored_char(const CharRule& r, uint32_t ch) 
   return r.fold ? fold_ascii(ch) : ch;
 }
 __device__ __forceinline__ bool rule_hit(const CharRule& r, uint32_t p, uint32_t t, uint32_t mask) {
+  if (r.cls) return class_hit(r.cls, p, t);
   const uint32_t x = r.iupac ? (p & t) : (p ^ t);
   return ((x & mask) != 0u) == (r.iupac != 0u);
 }
@@ -175,7 +183,7 @@ __global__ __launch_bounds__(64) void trace_kernel(const TraceParams P) {
   const uint32_t tid = threadIdx.x;
   // block-shared pattern copy behind the 64 slices (LDS mode)
   unsigned char* spat = trace_smem + (size_t)64 * P.scratch_stride;
-  const CharRule rule = char_rule(P.profile);
+  const CharRule rule = char_rule(P.profile, P.class_bits);
   // (pattern_stride != 0: many patterns -- a report brings its own, named in its flags' upper bits; the threads of a
   // workgroup then read their rows from the patterns' array, a few KB that stay in L1 / L2)
   const bool many = P.pattern_stride != 0;
@@ -411,7 +419,7 @@ __global__ __launch_bounds__(256) void trace_wave_kernel(const TraceParams P) {
   const int bw = 2 * k + 3;  // <= 64
   const int inf = k + 1;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const CharRule rule = char_rule(P.profile);
+  const CharRule rule = char_rule(P.profile, P.class_bits);
   // LDS: per wave: pattern codes | then per wave: band rows | window | ops.  With many patterns
   // (pattern_stride != 0: the pattern-tiled search) a report brings its own pattern, loaded per report.
   const uint32_t pat_bytes = (P.m + 15u) & ~15u;
@@ -618,8 +626,9 @@ __global__ __launch_bounds__(256) void trace_wave_kernel(const TraceParams P) {
       // |dlo + b| stays below either size) and is overwritten.
       const unsigned char* wp = win + (dlo + b);
       const int dlo_u = __builtin_amdgcn_readfirstlane(dlo);  // (the report is the wave's: the compiler cannot know)
-      auto rows = [&](auto iupac_tag, auto width_tag) {
-        constexpr bool IUPAC = decltype(iupac_tag)::value;
+      auto rows = [&](auto mode_tag, auto width_tag) {
+        constexpr int MODE = decltype(mode_tag)::value;  // 0: byte compare, 1: Iupac base sets, 2: character classes
+        constexpr bool IUPAC = MODE == 1;
         constexpr int WIDTH = decltype(width_tag)::value;  // lanes the band may reach: 16 / 32 / 64
         int prevq = prev - b;
         // lanes outside the band store into a cell of their own at the end of the slice (kTraceWaveDummy bytes nothing
@@ -637,6 +646,7 @@ __global__ __launch_bounds__(256) void trace_wave_kernel(const TraceParams P) {
           const int uq = __builtin_amdgcn_update_dpp(0, prevq, 0x130, 0xF, 0xF, true) + 2;  // wave_shl:1
           int dgq;
           if constexpr (IUPAC) dgq = prevq + ((pc & tc) == 0u ? 1 : 0);  // (pattern letters are base sets <= 15: no mask)
+          else if constexpr (MODE == 2) dgq = prevq + (class_hit(rule.cls, pc, tc) ? 0 : 1);
           else dgq = prevq + (((pc ^ tc) & rule.emask) != 0u ? 1 : 0);
           int xq = dgq < uq ? dgq : uq;
           bool valid = true;
@@ -692,10 +702,15 @@ __global__ __launch_bounds__(256) void trace_wave_kernel(const TraceParams P) {
           run(mid1 + 1, m, std::false_type{});
         }
       };
-      const bool iu = rule.iupac != 0u;  // wave-uniform, like bw
-      if (bw <= 16) { if (iu) rows(std::true_type{}, std::integral_constant<int, 16>{}); else rows(std::false_type{}, std::integral_constant<int, 16>{}); }
-      else if (bw <= 32) { if (iu) rows(std::true_type{}, std::integral_constant<int, 32>{}); else rows(std::false_type{}, std::integral_constant<int, 32>{}); }
-      else { if (iu) rows(std::true_type{}, std::integral_constant<int, 64>{}); else rows(std::false_type{}, std::integral_constant<int, 64>{}); }
+      const int mode = rule.cls ? 2 : rule.iupac != 0u ? 1 : 0;  // wave-uniform, like bw
+      auto rows_of = [&](auto width_tag) {
+        if (mode == 2) rows(std::integral_constant<int, 2>{}, width_tag);
+        else if (mode == 1) rows(std::integral_constant<int, 1>{}, width_tag);
+        else rows(std::integral_constant<int, 0>{}, width_tag);
+      };
+      if (bw <= 16) rows_of(std::integral_constant<int, 16>{});
+      else if (bw <= 32) rows_of(std::integral_constant<int, 32>{});
+      else rows_of(std::integral_constant<int, 64>{});
     }
     // make the band and the window visible to every lane (same wave: LDS ops are in order, this
     // only keeps the compiler from reordering)
