@@ -60,6 +60,9 @@ extern "C" {
     fn sassy_hip_search_classes(s: *mut RawSearcher, sets: *const u8, m: usize, text: *const u8, text_len: usize,
                                 k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
     fn sassy_hip_class_cover(set: *const u8, value: *mut u8, care: *mut u8, cap: usize, complemented: *mut c_int) -> c_long;
+    // Hamming search (include/sassy_hip.h): every start with at most k mismatches of every pattern, one text
+    fn sassy_hip_search_hamming(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                text: *const u8, text_len: usize, k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

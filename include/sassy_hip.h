@@ -92,7 +92,8 @@ typedef struct sassy_hip_Stats {
                             DP on the listed chunks; 2: the same with the Dna bit-plane prefilter (filter_dna_kernel);
                             3: q-gram piece table (filter_table_kernel); 4: q-gram counting (filter_count_kernel);
                             5: the pattern-tiled scan of search_encoded (tiled_kernel: all patterns in one pass);
-                            6: the seeded search of search_encoded (seed_kernels: seed table lookups, one lane per hit) */
+                            6: the seeded search of search_encoded (seed_kernels: seed table lookups, one lane per hit);
+                            7: the Hamming scan of sassy_hip_search_hamming (hamming.hip: no DP) */
   double filter_ms;      /* HIP-event time of the prefilter kernel (part of scan_ms); a search in flight whose text pass
                             was served by several launches (see pass_patterns): the sum of their durations */
   uint64_t hit_blocks;   /* text blocks in which an exact pattern piece ends */
@@ -346,6 +347,31 @@ int sassy_hip_best_pattern(sassy_SearcherType *s, const uint8_t *const *patterns
 int sassy_hip_best_matches(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
                            size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
                            size_t k, uint32_t flags, sassy_hip_Result **out);
+
+/* Hamming search: every start s with at most k MISMATCHES -- substitutions only, no insertions or deletions -- of each
+ * pattern in one text (sassy_amd/csrc/hamming.hip).  With match(p, t) the searcher's profile relation (Dna:
+ * equal 2-bit codes (c >> 1) & 3; Iupac: intersecting base sets; Ascii: byte equality; ascii_ci: eq_ignore_ascii_case),
+ * H(s) = #{ j < m : !match(P[j], T[s + j]) } for 0 <= s <= n - m; a hit is EVERY s with H(s) <= k (no local-minimum rule;
+ * k >= m: every start; n < m: nothing).  One record per hit: text_start = s, text_end = s + m, pattern_start = 0,
+ * pattern_end = m, cost = H(s), a cigar of run-length encoded '=' / 'X'.  A searcher with rc (Dna / Iupac) also searches
+ * reverse_complement(P) on the forward text: those records carry strand 1 and forward-text coordinates, their cigar runs in
+ * pattern direction (op j = match(complement(P[j]), T[s + m - 1 - j])), as sassy_hip_search's Rc records do.  max_n_frac
+ * set: a hit is kept iff float(N in its span) / float(m) <= max_n_frac, decided on the device before the hit takes any
+ * list space.  Order: (pattern_idx, Fwd before Rc, text_start) ascending -- part of the contract.
+ *  - one text, n_patterns >= 1 patterns of any (mixed) lengths; the patterns of a launch share one pass over the text;
+ *  - flags: SASSY_HIP_WITHOUT_TRACE (the same records without cigar), SASSY_HIP_TEXT_ON_DEVICE, SASSY_HIP_TEXT_UNCHANGED
+ *    (accepted, nothing is cached); anything else SASSY_HIP_EINVAL;
+ *  - refused before any device work: overhang searchers and only_best_match (SASSY_HIP_EUNSUPPORTED), Ascii with rc (as
+ *    everywhere), an empty pattern or list, an invalid Iupac pattern, k > 0x7FFFFFFF (SASSY_HIP_EINVAL), a pattern of more
+ *    than SASSY_HIP_HAMMING_MAX_ROWS rows, an Ascii pattern with more than 64 distinct (folded) bytes
+ *    (SASSY_HIP_EUNSUPPORTED); Ascii pattern sets whose distinct bytes exceed 64 together are split over launches;
+ *  - result limits: 2^32 records, 4 GiB of cigar text (SASSY_HIP_ENOMEM); texts of up to 2^32 - 17 blocks of 64 bytes;
+ *  - sassy_hip_get_stats afterwards: scan_ms = the scan kernel's HIP-event time over all launches (timing level >= 1),
+ *    scan_launches, candidates = hits, hit_blocks = 16-byte items, filtered = 7. */
+#define SASSY_HIP_HAMMING_MAX_ROWS 1024
+int sassy_hip_search_hamming(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                             size_t n_patterns, const void *text, size_t text_len, size_t k, uint32_t flags,
+                             sassy_hip_Result **out);
 
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar

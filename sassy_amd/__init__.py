@@ -152,6 +152,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_malloc", "sassy_hip_free", "sassy_hip_memcpy_h2d", "sassy_hip_memcpy_d2h",
     "sassy_hip_line_spans", "sassy_hip_result_line_spans", "sassy_hip_line_tile", "sassy_hip_line_span_times",
     "sassy_hip_search_classes", "sassy_hip_class_cover",
+    "sassy_hip_search_hamming",
 ]
 
 _lib = None
@@ -282,6 +283,8 @@ def lib():
     L.sassy_hip_search.argtypes = [vp, u8p, sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
     L.sassy_hip_search_classes.restype = C.c_int
     L.sassy_hip_search_classes.argtypes = [vp, u8p, sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
+    L.sassy_hip_search_hamming.restype = C.c_int
+    L.sassy_hip_search_hamming.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
     L.sassy_hip_class_cover.restype = C.c_long
     L.sassy_hip_class_cover.argtypes = [u8p, vp, vp, sz, C.POINTER(C.c_int)]
     L.sassy_hip_search_all_alignments.restype = C.c_int
@@ -852,6 +855,32 @@ class Searcher:
         _check(lib().sassy_hip_search_classes(self._h, pattern.sets, pattern.m, addr, n, k, flags, C.byref(out)))
         r = Result(out, flags)
         return (r.matches, r.line_spans) if lines else r.matches
+
+    def search_hamming(self, patterns, text, k: int, without_trace: bool = False, as_result: bool = False):
+        """Every start with at most k MISMATCHES (substitutions only) of every pattern in one text (sassy_hip_search_hamming):
+        one Match per hit -- text_start = s, text_end = s + m, cost = the number of mismatching rows under the searcher's
+        profile relation, a cigar of '=' / 'X' runs --, every hit (no local-minimum rule), ordered by (pattern_idx, '+'
+        before '-', text_start).  An rc searcher also reports reverse_complement(pattern) on the forward text as strand
+        '-', cigar in pattern direction.  `patterns`: bytes, or a sequence of bytes of any lengths -- they share one pass
+        over the text; `text` as for `search`.  without_trace: the same records without cigar.  as_result: the Result."""
+        if isinstance(patterns, ClassPattern) or (not isinstance(patterns, (bytes, bytearray, memoryview)) and
+                                                  any(isinstance(p, ClassPattern) for p in patterns)):
+            raise SassyHipError("search_hamming takes byte patterns only: a ClassPattern is not supported")
+        if isinstance(patterns, (bytes, bytearray, memoryview)):
+            patterns = [patterns]
+        patterns = [bytes(p) for p in patterns]
+        pp = (C.c_char_p * len(patterns))(*patterns)
+        pl = (C.c_size_t * len(patterns))(*[len(p) for p in patterns])
+        flags = WITHOUT_TRACE if without_trace else 0
+        addr, n, keep, on_dev = _ptr_len(text)
+        if on_dev:
+            flags |= TEXT_ON_DEVICE
+            if getattr(self, "_text_unchanged", False):
+                flags |= TEXT_UNCHANGED
+        out = C.c_void_p()
+        _check(lib().sassy_hip_search_hamming(self._h, pp, pl, len(patterns), addr, n, k, flags, C.byref(out)))
+        r = Result(out)
+        return r if as_result else r.matches
 
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k

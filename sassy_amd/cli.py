@@ -219,6 +219,12 @@ def run_agrep(args, stdin=None, out=None, err=None) -> int:
     return 0 if sum(hist) else 1
 
 
+def hamming_rows(searcher, patterns, text_id, where, matches, sam=False):
+    """The TSV rows of one record's Hamming hits (Searcher.search_hamming's order: pattern, strand, start); `where` is the
+    record's text as format_tsv takes it."""
+    return [searcher.format_tsv(m, patterns[m.pattern_idx][0], text_id, where, sam=sam) for m in matches]
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m sassy_amd", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -228,6 +234,9 @@ def main(argv=None) -> int:
     sp.add_argument("--sam", action="store_true")
     sp.add_argument("--best", action="store_true",
                     help="at most one row per record: its best match over all patterns and strands (Searcher.best_matches)")
+    sp.add_argument("--hamming", action="store_true",
+                    help="mismatches only (no insertions or deletions): every start with at most k mismatching positions "
+                         "(Searcher.search_hamming), all patterns in one call per record")
     sp.add_argument("paths", nargs="+")
     fp = sub.add_parser("filter", help="write the records that hold a match (-v: that hold none) to stdout")
     add_search_arguments(fp)
@@ -236,6 +245,8 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.cmd == "agrep":
         return run_agrep(args)
+    if args.cmd == "search" and args.hamming and (args.best or args.overhang is not None):
+        ap.error("--hamming takes neither --best nor --overhang")
 
     patterns = load_patterns(args)
     rc = not args.no_rc and not args.alphabet.startswith("ascii")  # (no reverse complement of plain text: forward only)
@@ -254,6 +265,13 @@ def main(argv=None) -> int:
     for path in args.paths:
         for batch in read_fastx_batches(path, BATCH_BYTES):
             if not len(batch):
+                continue
+            if args.hamming:  # one call per record with all patterns
+                base = int(batch.texts.buffer.ctypes.data)
+                for ti in range(len(batch)):
+                    lo, ln = int(batch.texts.starts[ti]), int(batch.texts.lens[ti])
+                    hits = searcher.search_hamming(pats, batch.texts.buffer[lo:lo + ln], args.k)
+                    out.writelines(hamming_rows(searcher, patterns, batch.id(ti), (base + lo, ln), hits, sam=args.sam))
                 continue
             if args.best:  # (one record per text at most, in text order already)
                 res = searcher.best_matches(pats, batch.texts, args.k, as_result=True)

@@ -1,0 +1,546 @@
+// hamming.hip -- sassy_hip_search_hamming: every start with at most k mismatches (substitutions only), counted on the device.
+//
+// No DP state: a block's answer depends on the text under it and on the W = ceil((m - 1) / 64) blocks to its right, so any
+// split of the text is exact -- no seams, no warm-up, no report rule.  Two kernels:
+//   ham_scan_kernel  a wavefront owns a tile of 64 consecutive blocks, a lane one block (64 starts).  The tile is staged
+//                    with coalesced loads, every lane builds its block's slot masks once (profile_masks.h) and puts them
+//                    into LDS as [slot][block] next to the masks of the tile's W halo blocks; then, per pattern of the
+//                    launch, a row is two LDS words, a funnel shift and a bit-sliced add (hamming_step.h).  A non-zero hit
+//                    mask leaves as one 16-byte item (pattern | strand, block, mask), one atomic per wavefront.
+//   ham_emit_kernel  the items sorted by (pattern | strand, block) and their popcount prefix give every hit its record
+//                    index: a lane per hit reads the m window bytes once for cost and cigar.
+#include "host_internal.h"
+#include "profile_masks.h"
+#include "hamming_step.h"
+
+namespace sassy_hip {
+namespace {
+
+static_assert(kHamMaxHalo == (kHamMaxRows - 1 + 63) / 64, "halo of the longest pattern");
+static_assert((uint32_t)PROFILE_DNA == kHamDna && (uint32_t)PROFILE_IUPAC == kHamIupac && (uint32_t)PROFILE_ASCII_CI == kHamAsciiCi,
+              "hamming_step.h names the profiles by value");
+
+constexpr uint32_t kHamStageBytes = kHamTileBlocks * 64;  // a tile's text
+constexpr uint32_t kHamLdsBudget = 160 * 1024;
+constexpr uint32_t kHamNoFilter = 0xFFFFFFFFu;
+
+// One item: the hits of one pattern in one block.  Laid out as a Candidate so that sort_kernels.hip sorts it by `key`.
+struct HamItem {
+  uint64_t key;   // launch-local pattern index (pattern and strand) << 32 | block
+  uint64_t mask;  // bit i: start 64 block + i is a hit
+};
+static_assert(sizeof(HamItem) == sizeof(Candidate) && offsetof(Candidate, pos) == 0, "items are sorted as candidates");
+
+// per pattern of a launch, kHamTabWords words: rows, offset of its row slots (words) in `rows`, offset of its bytes in `pats`,
+// N threshold (kHamNoFilter: none), pattern index of the call, strand
+constexpr uint32_t kHamTabWords = 8;
+
+struct HamParams {
+  const uint8_t* text;
+  uint64_t n;          // bytes
+  uint64_t n_blocks;   // ceil(n / 64): blocks that may be loaded
+  uint64_t tile0;      // this launch's tiles [tile0, tile0 + n_tiles)
+  uint64_t n_tiles;
+  uint32_t k, n_pat;
+  uint32_t halo;       // halo blocks of the launch's longest pattern
+  uint32_t nb;         // = 64 + halo: blocks per slot row in LDS
+  uint32_t n_filter;   // some pattern of the launch has an N threshold
+  uint32_t item_cap;
+  const uint32_t* tab;
+  const uint32_t* rows;
+  HamItem* items;
+  uint32_t* item_count;  // keeps counting past item_cap
+};
+
+// LDS of one wavefront: the staged tile, then (slots + 1) rows of nb masks -- the last row is the N mask --, whole 16 bytes
+__host__ __device__ constexpr uint32_t ham_lds_per_wave(uint32_t slots, uint32_t nb) {
+  return (kHamStageBytes + (slots + 1) * nb * 8u + 15u) & ~15u;
+}
+
+typedef const uint32_t __attribute__((address_space(4)))* ham_u32_ptr;  // scalar reads of wave-uniform tables
+
+__device__ __forceinline__ uint2 n_mask(const uint32_t (&x)[16]) {  // bit i: text byte i is 'N' / 'n'
+  uint32_t v[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const uint32_t d = (x[i] | 0x20202020u) ^ 0x6E6E6E6Eu;  // zero bytes are N
+    const uint32_t nz = ((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d;
+    v[i] = __builtin_amdgcn_udot4((~nz >> 7) & 0x01010101u, 0x08040201u, 0u, false);
+  }
+  uint2 r = make_uint2(0u, 0u);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    r.x |= v[i] << (4 * i);
+    r.y |= v[8 + i] << (4 * i);
+  }
+  return r;
+}
+
+template <int PROFILE, int NS, int P>
+__global__ __launch_bounds__(256) void ham_scan_kernel(const HamParams H, const ScanParams SP) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ham_lds[];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, wpg = blockDim.x >> 6;
+  const uint64_t t_rel = (uint64_t)blockIdx.x * wpg + wave;
+  if (t_rel >= H.n_tiles) return;  // (waves work alone: no workgroup barrier anywhere)
+  const uint64_t tile = H.tile0 + t_rel;
+  const uint32_t per_wave = ham_lds_per_wave((uint32_t)NS, H.nb);
+  unsigned char* stage = ham_lds + (size_t)wave * per_wave;
+  unsigned char* masks = stage + kHamStageBytes;  // [slot][block], slot NS = the N mask
+  const uint64_t block = tile * kHamTileBlocks + lane;
+
+  // the tile's text: 16-byte slot q (owner lane q >> 2, chunk q & 3) of the tile, loaded 1 KiB per instruction, kept at
+  // 4 owner + (chunk ^ ((owner >> 2) & 3)) so that the owners' 16-byte reads spread over the banks
+  const uint64_t tile_byte = tile * (uint64_t)kHamStageBytes, loadable = H.n_blocks * 64;
+#pragma unroll
+  for (uint32_t i = 0; i < 4; ++i) {
+    const uint32_t q = i * 64u + lane, owner = q >> 2, chunk = q & 3u;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (tile_byte + (uint64_t)q * 16 < loadable) v = *reinterpret_cast<const uint4*>(H.text + tile_byte + (uint64_t)q * 16);
+    *reinterpret_cast<uint4*>(stage + (4u * owner + (chunk ^ ((owner >> 2) & 3u))) * 16u) = v;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  // pass 0: every lane its own block; pass 1: lanes < halo the tile's halo blocks (never loaded behind the text's end)
+#pragma unroll 1
+  for (uint32_t pass = 0; pass < 2; ++pass) {
+    if (pass == 1 && H.halo == 0) break;
+    const bool on = pass == 0 || lane < H.halo;
+    uint32_t x[16];
+    if (pass == 0) {
+#pragma unroll
+      for (uint32_t c = 0; c < 4; ++c) {
+        const uint4 v = *reinterpret_cast<const uint4*>(stage + (4u * lane + (c ^ ((lane >> 2) & 3u))) * 16u);
+        x[4 * c] = v.x; x[4 * c + 1] = v.y; x[4 * c + 2] = v.z; x[4 * c + 3] = v.w;
+      }
+    } else {
+      const uint64_t hb = (tile + 1) * kHamTileBlocks + lane;
+      const bool load = on && hb < H.n_blocks;
+#pragma unroll
+      for (uint32_t c = 0; c < 4; ++c) {
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (load) v = *reinterpret_cast<const uint4*>(H.text + hb * 64 + c * 16u);
+        x[4 * c] = v.x; x[4 * c + 1] = v.y; x[4 * c + 2] = v.z; x[4 * c + 3] = v.w;
+      }
+    }
+    const uint64_t my_block = pass == 0 ? block : (tile + 1) * kHamTileBlocks + lane;
+    const bool inside = my_block < H.n_blocks;  // a block behind the text matches nothing
+    uint2 msk[NS];
+    build_masks<PROFILE, NS>(x, SP, msk);
+    const uint32_t col = pass * kHamTileBlocks + lane;
+    if (on) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+        *reinterpret_cast<uint2*>(masks + ((size_t)s * H.nb + col) * 8u) = inside ? msk[s] : make_uint2(0u, 0u);
+      if (H.n_filter) *reinterpret_cast<uint2*>(masks + ((size_t)NS * H.nb + col) * 8u) = inside ? n_mask(x) : make_uint2(0u, 0u);
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  const ham_u32_ptr tab = (ham_u32_ptr)H.tab;
+  const ham_u32_ptr rows = (ham_u32_ptr)H.rows;
+  const uint32_t nb = H.nb;
+  auto fetch = [&](uint32_t slot, uint32_t q) {
+    return *reinterpret_cast<const uint64_t*>(masks + ((size_t)slot * nb + lane + q) * 8u);
+  };
+  auto all_over = [](uint64_t over) { return __all(over == ~(uint64_t)0) != 0; };
+  for (uint32_t p = 0; p < H.n_pat; ++p) {
+    const uint32_t m = tab[kHamTabWords * p], roff = tab[kHamTabWords * p + 1], nmax = tab[kHamTabWords * p + 3];
+    auto row_word = [&](uint32_t w) { return rows[roff + w]; };
+    uint64_t hit = ham_hit_mask<P, true>(fetch, row_word, m, H.k, all_over) & ham_valid_mask(block, H.n, m);
+    // the N filter, before a hit takes list space -- and only where some block of the tile holds a hit
+    if (nmax != kHamNoFilter && __any(hit != 0)) {
+      auto n_word = [](uint32_t) { return (uint32_t)NS * 0x01010101u; };
+      hit &= ham_hit_mask<kHamNPlanes, false>(fetch, n_word, m, nmax, all_over);
+    }
+    const bool has = hit != 0;
+    const uint64_t bal = __ballot(has);
+    if (bal != 0) {
+      const uint32_t first = (uint32_t)__builtin_ctzll(bal);
+      uint32_t base = 0;
+      if (lane == first) base = atomicAdd(H.item_count, (uint32_t)__builtin_popcountll(bal));
+      base = __shfl(base, (int)first);
+      const uint32_t at = base + (uint32_t)__builtin_popcountll(bal & (((uint64_t)1 << lane) - 1));
+      if (has && at < H.item_cap) H.items[at] = HamItem{((uint64_t)p << 32) | (uint32_t)block, hit};
+    }
+  }
+}
+
+struct EmitParams {
+  const uint8_t* text;
+  const HamItem* items;      // sorted
+  const uint32_t* prefix;    // prefix[i] = hits of the items in front of item i
+  uint32_t n_items;
+  uint32_t first, count;     // this launch: hits [first, first + count) of the range
+  const uint32_t* tab;
+  const uint8_t* pats;       // the patterns as scanned
+  uint32_t profile;
+  uint32_t str_stride;       // 0: without trace
+  MatchOut* out;             // count records
+  char* strs;                // count * str_stride bytes
+};
+
+__global__ __launch_bounds__(256) void ham_emit_kernel(const EmitParams E) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= E.count) return;
+  const uint32_t r = E.first + t;
+  uint32_t lo = 0, hi = E.n_items;  // the last item whose prefix is <= r
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (E.prefix[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  const HamItem it = E.items[lo];
+  uint64_t mask = it.mask;
+  for (uint32_t skip = r - E.prefix[lo]; skip; --skip) mask &= mask - 1;
+  const uint64_t s = (it.key & 0xFFFFFFFFull) * 64 + (uint32_t)__builtin_ctzll(mask);
+  const uint32_t* row = E.tab + kHamTabWords * (uint32_t)(it.key >> 32);
+  const uint32_t m = row[0], strand = row[5];
+  const uint8_t* win = E.text + s;
+  uint32_t cost, n_count, cigar_len;
+  ham_emit_hit(E.profile, E.pats + row[2], m, [&](uint32_t i) { return (uint32_t)win[i]; }, strand != 0,
+               E.str_stride ? E.strs + (size_t)t * E.str_stride : nullptr, &cost, &n_count, &cigar_len);
+  MatchOut o{};
+  o.pattern_idx = row[4];
+  o.text_idx = 0;
+  o.text_start = s;
+  o.text_end = s + m;
+  o.pattern_start = 0;
+  o.pattern_end = m;
+  o.cost = (int32_t)cost;
+  o.strand = (uint8_t)strand;
+  o.cigar_off = t * E.str_stride;
+  o.cigar_len = cigar_len;
+  E.out[t] = o;
+}
+
+template <int PROFILE, int NS, int P>
+hipError_t launch_scan_k(const HamParams& H, const ScanParams& SP, uint32_t grid, uint32_t threads, size_t smem, hipStream_t st) {
+  static DeviceOnce attr_set;  // LDS beyond the 64 KiB default needs an explicit opt-in
+  if (attr_set.need()) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ham_scan_kernel<PROFILE, NS, P>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHamLdsBudget);
+    if (e != hipSuccess) return e;
+    attr_set.done();
+  }
+  hipLaunchKernelGGL((ham_scan_kernel<PROFILE, NS, P>), dim3(grid), dim3(threads), smem, st, H, SP);
+  return hipGetLastError();
+}
+
+template <int PROFILE, int NS>
+hipError_t launch_scan_p(const HamParams& H, const ScanParams& SP, uint32_t grid, uint32_t threads, size_t smem, hipStream_t st) {
+  switch (ham_planes(H.k)) {
+    case 2: return launch_scan_k<PROFILE, NS, 2>(H, SP, grid, threads, smem, st);
+    case 4: return launch_scan_k<PROFILE, NS, 4>(H, SP, grid, threads, smem, st);
+    case 8: return launch_scan_k<PROFILE, NS, 8>(H, SP, grid, threads, smem, st);
+    default: return launch_scan_k<PROFILE, NS, 11>(H, SP, grid, threads, smem, st);
+  }
+}
+
+hipError_t launch_scan(Profile pr, uint32_t ns, const HamParams& H, const ScanParams& SP, uint32_t grid, uint32_t threads, size_t smem,
+                       hipStream_t st) {
+  switch (pr) {
+    case PROFILE_DNA: return launch_scan_p<(int)PROFILE_DNA, 4>(H, SP, grid, threads, smem, st);
+    case PROFILE_IUPAC: return launch_scan_p<(int)PROFILE_IUPAC, 16>(H, SP, grid, threads, smem, st);
+    case PROFILE_ASCII_CI:
+      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII_CI, 16>(H, SP, grid, threads, smem, st)
+                      : launch_scan_p<(int)PROFILE_ASCII_CI, 64>(H, SP, grid, threads, smem, st);
+    default:
+      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII, 16>(H, SP, grid, threads, smem, st)
+                      : launch_scan_p<(int)PROFILE_ASCII, 64>(H, SP, grid, threads, smem, st);
+  }
+}
+
+// One pattern of the call on one strand, as it is scanned.
+struct HamPattern {
+  uint32_t idx, strand;
+  std::vector<uint8_t> bytes;  // strand 1: the reverse complement
+  uint32_t nmax;               // most N a hit's span may hold (kHamNoFilter: no filter)
+};
+
+uint32_t slot_byte(Profile pr, uint8_t c) {  // what a pattern byte's slot is keyed by
+  if (pr == PROFILE_DNA) return (c >> 1) & 3u;
+  if (pr == PROFILE_IUPAC) return iupac_code(c) & 0x0Fu;
+  return pr == PROFILE_ASCII_CI ? fold_ascii(c) : c;
+}
+
+}  // namespace
+
+// The search proper: refusals are the caller's; d_text is readable up to the next multiple of 64 bytes.
+int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                      const uint8_t* d_text, uint64_t n, uint32_t k, bool without_trace, sassy_hip_Result* R) {
+  const Profile pr = S->profile;
+  hipStream_t st = S->stream;
+  ScanLane& L = S->lanes[0];
+  const uint64_t n_blocks = (n + 63) / 64, n_tiles = (n_blocks + kHamTileBlocks - 1) / kHamTileBlocks;
+  if (n_blocks + kHamMaxHalo > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "text too long for the Hamming search (2^32 blocks)");
+  S->stats.filtered = 7;
+  S->stats.blocks_per_chunk = kHamTileBlocks;
+
+  // the patterns as scanned, in the contract's order: pattern, then + before -
+  std::vector<HamPattern> all;
+  for (size_t i = 0; i < n_patterns; ++i) {
+    const uint32_t m = (uint32_t)pattern_lens[i];
+    uint32_t nmax = kHamNoFilter;
+    if (!std::isnan(S->max_n_frac)) {
+      const int64_t c = ham_n_max(m, S->max_n_frac);
+      if (c < 0) continue;  // not even a span without N passes: the pattern has no hits
+      if (c < (int64_t)m) nmax = (uint32_t)c;
+    }
+    if (n < m) continue;
+    all.push_back(HamPattern{(uint32_t)i, 0, std::vector<uint8_t>(patterns[i], patterns[i] + m), nmax});
+    if (S->rc) {
+      HamPattern rc{(uint32_t)i, 1, {}, nmax};
+      for (size_t j = m; j-- > 0;) rc.bytes.push_back(complement_char(pr, patterns[i][j]));
+      all.push_back(std::move(rc));
+    }
+  }
+  const long batch_sw = S->sw.hamming_batch, items_sw = S->sw.hamming_items, records_sw = S->sw.hamming_records;
+  const size_t max_batch = batch_sw > 0 ? (size_t)batch_sw : 512;
+  const bool timed = S->timing >= 1;
+
+  size_t a0 = 0;
+  while (a0 < all.size()) {
+    // ---- a launch's patterns: as many as share the slots (Ascii: at most kMaxSlots distinct bytes) ----
+    ScanParams SP{};
+    uint32_t ns = pr == PROFILE_DNA ? 4u : pr == PROFILE_IUPAC ? 16u : 0u;
+    if (pr == PROFILE_IUPAC)
+      for (uint32_t s = 0; s < 16; ++s) SP.slot_val[s] = (uint8_t)s;  // a slot per base set
+    int slot_of[256];
+    std::fill(slot_of, slot_of + 256, -1);
+    if (!is_ascii(pr))
+      for (uint32_t s = 0; s < ns; ++s) slot_of[s] = (int)s;
+    size_t a1 = a0;
+    while (a1 < all.size() && a1 - a0 < max_batch) {
+      uint32_t add = 0;
+      bool seen[256] = {};
+      if (is_ascii(pr))
+        for (uint8_t c : all[a1].bytes) {
+          const uint32_t key = slot_byte(pr, c);
+          if (slot_of[key] < 0 && !seen[key]) { seen[key] = true; ++add; }
+        }
+      if (ns + add > (uint32_t)kMaxSlots) break;  // (a pattern alone always fits: the caller checked)
+      if (is_ascii(pr))
+        for (uint8_t c : all[a1].bytes) {
+          const uint32_t key = slot_byte(pr, c);
+          if (slot_of[key] < 0) { slot_of[key] = (int)ns; SP.slot_val[ns++] = (uint8_t)key; }
+        }
+      ++a1;
+    }
+    SP.nslots = ns;
+    SP.profile = (uint32_t)pr;
+    const uint32_t np = (uint32_t)(a1 - a0);
+    std::vector<uint32_t> tab((size_t)np * kHamTabWords, 0u), rows;
+    std::vector<uint8_t> pats;
+    uint32_t longest = 0;
+    bool n_filter = false;
+    for (uint32_t p = 0; p < np; ++p) {
+      const HamPattern& hp = all[a0 + p];
+      const uint32_t m = (uint32_t)hp.bytes.size();
+      longest = std::max(longest, m);
+      const uint32_t nmax = hp.nmax;
+      uint32_t* row = &tab[(size_t)p * kHamTabWords];
+      row[0] = m; row[1] = (uint32_t)rows.size(); row[2] = (uint32_t)pats.size(); row[3] = nmax; row[4] = hp.idx; row[5] = hp.strand;
+      n_filter = n_filter || nmax != kHamNoFilter;
+      rows.resize(rows.size() + (m + 3) / 4, 0u);
+      for (uint32_t j = 0; j < m; ++j) rows[row[1] + (j >> 2)] |= (uint32_t)slot_of[slot_byte(pr, hp.bytes[j])] << (8 * (j & 3));
+      pats.insert(pats.end(), hp.bytes.begin(), hp.bytes.end());
+    }
+    const uint32_t halo = ham_halo_blocks(longest), nb = kHamTileBlocks + halo;
+    const uint32_t ns_t = pr == PROFILE_DNA ? 4u : (pr == PROFILE_IUPAC || ns <= 16) ? 16u : 64u;
+    const uint32_t per_wave = ham_lds_per_wave(ns_t, nb);
+    const uint32_t wpg = std::min<uint32_t>(4, kHamLdsBudget / per_wave);
+    const size_t smem = (size_t)wpg * per_wave;
+
+    if (int rc = S->d_ham_tab.reserve(tab.size() + rows.size() + (pats.size() + 3) / 4 + 16)) return rc;
+    uint32_t* d_tab = S->d_ham_tab.p;
+    uint32_t* d_rows = d_tab + tab.size();
+    uint8_t* d_pats = reinterpret_cast<uint8_t*>(d_rows + rows.size());
+    if (int rc = S->d_ham_count.reserve(16)) return rc;
+    L.h_up_used = 0;
+    if (int rc = L.upload(d_tab, tab.data(), tab.size() * 4)) return rc;
+    if (int rc = L.upload(d_rows, rows.data(), rows.size() * 4)) return rc;
+    if (int rc = L.upload(d_pats, pats.data(), pats.size())) return rc;
+
+    // ---- the text in ranges of tiles: a range whose items overflow the list is cut down and launched again ----
+    const uint64_t min_cap = (uint64_t)np * kHamTileBlocks;  // one tile always fits
+    uint64_t item_cap = std::max<uint64_t>(items_sw > 0 ? (uint64_t)items_sw : (1u << 16), min_cap);
+    const uint64_t max_cap = items_sw > 0 ? item_cap : std::max<uint64_t>(min_cap, 1u << 22);
+    const uint64_t rec_cap = records_sw > 0 ? (uint64_t)records_sw : (1u << 20);
+    const uint64_t span_max = std::max<uint64_t>(1, (0x7FFFFFFFull / kHamTileBlocks) / np);  // the counter cannot wrap
+    uint64_t tile0 = 0, span = std::min(n_tiles, span_max);
+    size_t first_row = R->matches.size();
+    uint32_t ranges = 0;
+    while (tile0 < n_tiles) {
+      span = std::min(span, n_tiles - tile0);
+      if (int rc = S->d_ham_items.reserve(item_cap)) return rc;
+      HamParams H{};
+      H.text = d_text; H.n = n; H.n_blocks = n_blocks; H.tile0 = tile0; H.n_tiles = span;
+      H.k = k; H.n_pat = np; H.halo = halo; H.nb = nb; H.n_filter = n_filter ? 1u : 0u; H.item_cap = (uint32_t)item_cap;
+      H.tab = d_tab; H.rows = d_rows; H.items = reinterpret_cast<HamItem*>(S->d_ham_items.p); H.item_count = S->d_ham_count.p;
+      HIP_TRY(hipMemsetAsync(S->d_ham_count.p, 0, 4, st));
+      if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
+      const uint32_t grid = (uint32_t)((span + wpg - 1) / wpg);
+      HIP_TRY(launch_scan(pr, ns, H, SP, grid, wpg * 64, smem, st));
+      if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
+      uint32_t count = 0;
+      HIP_TRY(hipMemcpyAsync(&count, S->d_ham_count.p, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if (timed) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, L.ev_a, L.ev_b) == hipSuccess) S->stats.scan_ms += ms;
+      }
+      S->stats.scan_launches += 1;
+      S->stats.grid = grid;
+      if (count > item_cap) {  // nothing of this launch is used: a larger list, or a shorter range
+        if (item_cap < max_cap && (uint64_t)count <= max_cap) item_cap = std::min<uint64_t>(max_cap, (uint64_t)count + count / 4);
+        else if (item_cap < max_cap) item_cap = max_cap;
+        if (count > item_cap) span = std::max<uint64_t>(1, std::min<uint64_t>(span - 1, span * item_cap / count));
+        continue;
+      }
+      ++ranges;
+      S->stats.blocks += std::min<uint64_t>(span * kHamTileBlocks, n_blocks - tile0 * kHamTileBlocks);
+      S->stats.hit_blocks += count;
+      if (count) {
+        // items by (pattern | strand, block), then their popcount prefix
+        if (int rc = S->d_ham_sorted.reserve(count)) return rc;
+        const size_t sb = sort_scratch_bytes(count);
+        if (int rc = S->d_ham_sort.reserve(sb)) return rc;
+        int key_bits = 33;
+        while (key_bits < 64 && ((uint64_t)(np - 1) >> (key_bits - 32)) != 0) ++key_bits;
+        HIP_TRY(launch_sort_candidates(S->d_ham_items.p, S->d_ham_sorted.p, count, S->d_ham_sort.p, S->d_ham_sort.cap, st, 0, key_bits));
+        std::vector<HamItem> items(count);
+        HIP_TRY(hipMemcpyAsync(items.data(), S->d_ham_sorted.p, (size_t)count * sizeof(HamItem), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<uint32_t> prefix(count);
+        uint64_t hits = 0;
+        for (uint32_t i = 0; i < count; ++i) {
+          prefix[i] = (uint32_t)hits;
+          hits += (uint64_t)__builtin_popcountll(items[i].mask);
+        }
+        if (hits > 0xFFFFFFFFull || R->matches.size() + hits > 0xFFFFFFFFull)
+          return fail(SASSY_HIP_ENOMEM, "Hamming search: more than 2^32 records (" + std::to_string(R->matches.size() + hits) + ")");
+        if (int rc = S->d_ham_prefix.reserve(count)) return rc;
+        HIP_TRY(hipMemcpyAsync(S->d_ham_prefix.p, prefix.data(), (size_t)count * 4, hipMemcpyHostToDevice, st));
+        // records in batches of the record block
+        const uint32_t stride = without_trace ? 0u : 2u * longest + 8u;
+        const uint64_t batch = std::min<uint64_t>(hits, rec_cap);
+        if (int rc = L.d_trace.reserve(batch)) return rc;
+        if (stride)
+          if (int rc = L.d_str.reserve(batch * stride)) return rc;
+        std::vector<MatchOut> rows_h;
+        std::vector<char> strs_h;
+        for (uint64_t r0 = 0; r0 < hits; r0 += batch) {
+          const uint32_t cnt = (uint32_t)std::min<uint64_t>(batch, hits - r0);
+          EmitParams E{};
+          E.text = d_text; E.items = reinterpret_cast<const HamItem*>(S->d_ham_sorted.p); E.prefix = S->d_ham_prefix.p; E.n_items = count;
+          E.first = (uint32_t)r0; E.count = cnt; E.tab = d_tab; E.pats = d_pats; E.profile = (uint32_t)pr; E.str_stride = stride;
+          E.out = L.d_trace.p; E.strs = reinterpret_cast<char*>(L.d_str.p);
+          hipLaunchKernelGGL(ham_emit_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, E);
+          HIP_TRY(hipGetLastError());
+          rows_h.resize(cnt);
+          if (int rc = L.download(rows_h.data(), L.d_trace.p, (size_t)cnt * sizeof(MatchOut))) return rc;
+          if (stride) {
+            strs_h.resize((size_t)cnt * stride);
+            if (int rc = L.download(strs_h.data(), L.d_str.p, strs_h.size())) return rc;
+          }
+          HIP_TRY(hipStreamSynchronize(st));
+          for (uint32_t i = 0; i < cnt; ++i) {
+            sassy_hip_Match mo;
+            memcpy(&mo, &rows_h[i], sizeof(mo));
+            if (R->pool.size() + mo.cigar_len + 1 > 0xFFFFFFFFull)
+              return fail(SASSY_HIP_ENOMEM, "Hamming search: more than 4 GiB of cigar text");
+            const uint32_t off = (uint32_t)R->pool.size();
+            if (stride) R->pool.append(strs_h.data() + (size_t)i * stride, mo.cigar_len);
+            R->pool.push_back('\0');
+            mo.cigar_off = off;
+            R->matches.push_back(mo);
+          }
+        }
+        S->stats.candidates += hits;
+      }
+      tile0 += span;
+      span = std::min(n_tiles, span_max);  // the next range tries everything that is left
+    }
+    // several ranges: each came sorted by (pattern, strand, start); the ranges ascend, so a stable sort restores the order
+    if (ranges > 1)
+      std::stable_sort(R->matches.begin() + (long)first_row, R->matches.end(), [](const sassy_hip_Match& a, const sassy_hip_Match& b) {
+        return a.pattern_idx != b.pattern_idx ? a.pattern_idx < b.pattern_idx : a.strand < b.strand;
+      });
+    S->stats.text_bytes += n;
+    a0 = a1;
+  }
+  S->stats.chunks = n_tiles;
+  return 0;
+}
+
+}  // namespace sassy_hip
+
+using namespace sassy_hip;
+
+extern "C" {
+
+int sassy_hip_search_hamming(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                             const void* text, size_t text_len, size_t k, uint32_t flags, sassy_hip_Result** out) {
+  if (!s || !out || (n_patterns && (!patterns || !pattern_lens)) || (!text && text_len))
+    return fail(SASSY_HIP_EINVAL, "Pointers in search_hamming() must not be null");
+  if (flags & ~(uint32_t)(SASSY_HIP_WITHOUT_TRACE | SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_TEXT_UNCHANGED))
+    return fail(SASSY_HIP_EINVAL, "search_hamming takes SASSY_HIP_WITHOUT_TRACE, _TEXT_ON_DEVICE and _TEXT_UNCHANGED only");
+  if (!std::isnan(s->alpha) || s->max_overhang >= 0)
+    return fail(SASSY_HIP_EUNSUPPORTED, "the Hamming search does not take overhang (alpha): a hit spans the whole pattern");
+  if (s->only_best) return fail(SASSY_HIP_EUNSUPPORTED, "the Hamming search reports every hit: only_best_match is not supported");
+  if (is_ascii(s->profile) && s->rc) return fail(SASSY_HIP_EUNSUPPORTED, "reverse complement is not defined for the ascii alphabet");
+  if (n_patterns == 0) return fail(SASSY_HIP_EINVAL, "search_hamming needs at least one pattern");
+  for (size_t i = 0; i < n_patterns; ++i) {
+    if (!patterns[i] || pattern_lens[i] == 0) return fail(SASSY_HIP_EINVAL, "empty pattern (pattern " + std::to_string(i) + ")");
+    if (!valid_pattern(s->profile, patterns[i], pattern_lens[i])) return fail(SASSY_HIP_EINVAL, "Pattern is not valid IUPAC");
+  }
+  if (k > 0x7FFFFFFFull) return fail(SASSY_HIP_EINVAL, "k is larger than 2^31 - 1");
+  for (size_t i = 0; i < n_patterns; ++i) {
+    if (pattern_lens[i] > kHamMaxRows)
+      return fail(SASSY_HIP_EUNSUPPORTED, "the Hamming search takes patterns of at most " + std::to_string(kHamMaxRows) + " rows (pattern " +
+                                              std::to_string(i) + " has " + std::to_string(pattern_lens[i]) + ")");
+    if (is_ascii(s->profile)) {
+      bool seen[256] = {};
+      size_t distinct = 0;
+      for (size_t j = 0; j < pattern_lens[i]; ++j) {
+        const uint32_t c = s->profile == PROFILE_ASCII_CI ? fold_ascii(patterns[i][j]) : patterns[i][j];
+        if (!seen[c]) { seen[c] = true; ++distinct; }
+      }
+      if (distinct > (size_t)kMaxSlots)
+        return fail(SASSY_HIP_EUNSUPPORTED, "the Hamming search takes Ascii patterns of at most " + std::to_string(kMaxSlots) +
+                                                " distinct bytes (pattern " + std::to_string(i) + " has " + std::to_string(distinct) + ")");
+    }
+  }
+  SASSY_NO_TICKETS(s);
+  DeviceGuard on_device(s);
+  const double t0 = now_ms();
+  reset_stats(s);
+  if (int rc = s->ensure_device()) return rc;
+  const uint8_t* d_text = static_cast<const uint8_t*>(text);
+  if (flags & SASSY_HIP_TEXT_ON_DEVICE) {
+    if (((uintptr_t)text & 15) != 0) return fail(SASSY_HIP_EINVAL, "device text pointer must be 16-byte aligned");
+  } else if (text_len) {
+    if (int rc = s->d_text.reserve(text_len + 64)) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_text.p, text, text_len, hipMemcpyHostToDevice, s->stream));
+    d_text = s->d_text.p;
+  }
+  sassy_hip_Result* R = new sassy_hip_Result();
+  size_t longest = 0;
+  for (size_t i = 0; i < n_patterns; ++i) longest = std::max(longest, pattern_lens[i]);
+  const uint32_t kk = (uint32_t)std::min<size_t>(k, longest);  // k >= m reports every start
+  if (int rc = hamming_on_device(s, patterns, pattern_lens, n_patterns, d_text, text_len, kk, (flags & SASSY_HIP_WITHOUT_TRACE) != 0, R)) {
+    (void)hipStreamSynchronize(s->stream);
+    delete R;
+    return rc;
+  }
+  if (R->pool.empty()) R->pool.push_back('\0');
+  s->stats.total_ms = now_ms() - t0;
+  *out = R;
+  return 0;
+}
+
+}  // extern "C"

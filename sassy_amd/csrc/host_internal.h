@@ -3,6 +3,7 @@
 //   scan_driver.hip   one pattern over one buffer: ScanJob (prepare / enqueue / finish), strands, search_text
 //   many_patterns.hip search_encoded / search_many: pattern-tiled scan, seeded search, lists -> reports -> records
 //   multi_device.hip  sassy_hip_multi_*: one text over several devices inside one process
+//   hamming.hip       sassy_hip_search_hamming: the Hamming scan and emit kernels with their driver and entry point
 //   c_abi.hip         the C-ABI of include/sassy.h + sassy_hip.h, the switch table, synthetic inputs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -669,6 +670,11 @@ struct sassy_SearcherType {
   DevBuf<sassy_hip_LineSpan> d_line_out;
   double line_index_ms = 0, line_resolve_ms = 0;
   hipEvent_t ev_line[4] = {nullptr, nullptr, nullptr, nullptr};  // index pass begin / end, resolve pass begin / end
+  // Hamming search (hamming.hip): the pattern tables of a launch, the item counter, the items as written and sorted (laid
+  // out as candidates for the sort), the sort's scratch, the items' popcount prefix
+  DevBuf<uint32_t> d_ham_tab, d_ham_count, d_ham_prefix;
+  DevBuf<Candidate> d_ham_items, d_ham_sorted;
+  DevBuf<uint8_t> d_ham_sort;
   DevBuf<uint64_t> d_range;      // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
@@ -690,6 +696,7 @@ struct sassy_SearcherType {
     d_text.release(); d_rev.release(); d_rc_bitmap.release();
     free_stage();
     d_line_tiles.release(); d_line_prefix.release(); d_line_pos.release(); d_line_out.release();
+    d_ham_tab.release(); d_ham_count.release(); d_ham_prefix.release(); d_ham_items.release(); d_ham_sorted.release(); d_ham_sort.release();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();

@@ -56,7 +56,10 @@ namespace sassy_hip {
   X(shared_pass, 1, "searches in flight over one buffer share text passes, two per fused bit-plane launch: 1 staggered in halves of the grid (a begin launches the previous search's second half with this one's first; a search with no partner and no pass streaming goes whole); 4: as 1, but a search without a partner always keeps its second half back; 0: a pass per search; 3: whole passes, a groupable search always waits for a partner; 2: as 3 while a pass streams, and a waiting search is launched before a finish that has to wait") \
   X(aa_batch, 0, "search_all_alignments: at most this many alignments per emit batch (0: 32 MiB of rows / cigar text)") \
   X(min_cost_device, 1, "min_costs / best_pattern: 0: never the device reduction of the scan's list (search_many's records reduced by the host)") \
-  X(best_match_device, 1, "best_matches: 0: never the device path (locating reduction of the scan's list, one traceback per text); search_many's records reduced by the host")
+  X(best_match_device, 1, "best_matches: 0: never the device path (locating reduction of the scan's list, one traceback per text); search_many's records reduced by the host") \
+  X(hamming_items, 0, "search_hamming: > 0: the item list holds exactly this many 16-byte items (at least one tile's worth) and never grows -- a text range whose items overflow it is cut down and launched again (0: 65536, grown up to 4 Mi items before ranges are cut)") \
+  X(hamming_records, 0, "search_hamming: > 0: records are emitted at most this many per launch of the emit kernel (0: 1 Mi)") \
+  X(hamming_batch, 0, "search_hamming: > 0: at most this many scanned patterns (a strand counts as one) share a launch of the scan kernel (0: 512)")
 
 struct Switches {
 #define SASSY_HIP_SWITCH_FIELD(name, dflt, doc) long name = (dflt);
