@@ -28,6 +28,7 @@
 #include "profiles.h"
 #include "switches.h"
 #include "pass_planner.h"
+#include "scan_route.h"
 
 namespace sassy_hip {
 // (thread_local LaunchEvents g_launch_events: defined in scan_driver.hip, declared in common.h)
@@ -825,14 +826,6 @@ inline TraceShape trace_shape(uint32_t m, uint32_t k) {
   s.thread_count = std::min<uint64_t>(256ull * 64ull * std::max<uint64_t>(1, (160ull * 1024) / wg_bytes), 131072);
   return s;
 }
-
-// The three prefilter kernels (scan_kernel.hip): which one evaluates the pieces.
-enum FilterKind : uint32_t {
-  kFilterGeneric = 1,  // filter_kernel: slot masks in LDS, any profile, <= 255 piece rows
-  kFilterPlanes = 2,   // filter_dna_kernel: Dna, <= 8 pieces
-  kFilterTable = 3,    // filter_table_kernel: q-gram bit table, Dna / Iupac, 7 <= q <= 9
-  kFilterCount = 4,    // filter_count_kernel: q-gram lemma (count the pattern's q-grams per window), Dna / Iupac
-};
 
 // One scan of one buffer (a whole text or a shard) on one lane, in three phases so that several can be
 // in flight: prepare() sizes everything and uploads what the pattern needs, enqueue() queues the

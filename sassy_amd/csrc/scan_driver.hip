@@ -8,147 +8,6 @@ PinPool g_pin_pool;
 namespace sassy_hip {
 thread_local LaunchEvents g_launch_events;
 
-// Prefilter geometry: k+1 disjoint pattern pieces of q rows.  Enabled when the pieces are long
-// enough to be selective (expected hit blocks on random DNA: 64*(k+1)/4^q of all blocks).
-// mode: the searcher's own setting (sassy_hip_set_prefilter), -1 = the process default (SASSY_HIP_PREFILTER)
-static int prefilter_mode(const sassy_SearcherType* S) {
-  return S->prefilter >= 0 ? S->prefilter : (int)S->sw.prefilter;
-}
-static uint32_t filter_piece_len(const PatternPlan& plan, uint32_t k, const sassy_SearcherType* S) {
-  const int env = prefilter_mode(S);
-  if (env == 0) return 0;
-  const uint64_t pieces = (uint64_t)k + 1;
-  uint64_t q = plan.m / pieces;
-  if (q > 12) q = 12;
-  if (q < (env == 1 ? 2u : 7u)) return 0;    // too unselective: stream the full DP instead
-  return (uint32_t)q;
-}
-
-// The paired filter's geometry for a shape (filter_dna_kernel<.., PAIR>): S = ceil((k+1)/2) super-pieces of two sub-pieces
-// of Q = m / (2 S) rows each.  Taken where the k+1 pigeonhole pieces are shorter than 7 rows and Q is 5 or 6 (m = 23, k = 3;
-// m = 32, k = 4, 5; m = 12, k = 1; ...).  False: the shape is not one of them.
-static bool pair_geometry(uint32_t m, uint32_t k, uint32_t* s_out, uint32_t* q_out) {
-  if (k < 1 || m / (k + 1) >= 7) return false;
-  const uint32_t s = (k + 2) / 2;
-  if (s > 4) return false;
-  const uint32_t q = m / (2 * s);
-  if (q != 5 && q != 6) return false;
-  *s_out = s;
-  *q_out = q;
-  return true;
-}
-// rows of the pattern, from row 0 on, that are plain bases
-static size_t plain_prefix(const uint8_t* pat, size_t m) {
-  size_t j = 0;
-  for (; j < m; ++j) {
-    const uint8_t u = pat[j] & 0xDFu;
-    if (u != 'A' && u != 'C' && u != 'G' && u != 'T') break;
-  }
-  return j;
-}
-static bool plain_acgt(const uint8_t* pat, size_t m) { return plain_prefix(pat, m) == m; }
-// May this searcher take the paired filter for this pattern and k, and with which S and Q?  The part of the answer that
-// ScanJob::prepare() (one job's route) and search_text() (two strands as two searches) share; each adds what only it knows.
-// An Iupac searcher: the filter's 2 S Q rows are plain bases -- the rows behind them may hold ambiguity letters, a guide's NGG.
-static bool pair_eligible(const sassy_SearcherType* S, const uint8_t* pat, uint32_t m, uint32_t k, uint32_t* s_out, uint32_t* q_out) {
-  if (S->sw.pair == 0 || prefilter_mode(S) >= 0 || !pair_geometry(m, k, s_out, q_out)) return false;
-  if (S->profile == PROFILE_DNA) return true;
-  return S->profile == PROFILE_IUPAC && *s_out <= 3 && plain_prefix(pat, m) >= (size_t)2 * *s_out * *q_out;
-}
-
-
-// Bit table of every q-gram (2 bits per char, first piece row most significant; codes A0 C1 T2 G3)
-// that some piece accepts; rows with ambiguity letters are expanded.  False if that takes more
-// than `limit` q-grams (then the table says nothing useful anyway).
-static bool build_qgram_table(Profile pr, const uint8_t* pat, uint32_t q, uint32_t pieces, std::vector<uint8_t>& tab) {
-  const size_t limit = 1u << 16;
-  tab.assign((size_t)1 << (2 * q - 3), 0);
-  const uint32_t low_bits = 2 * q - 3;
-  std::vector<uint32_t> cur, nxt;
-  size_t total = 0;
-  for (uint32_t p = 0; p < pieces; ++p) {
-    cur.assign(1, 0u);
-    for (uint32_t j = 0; j < q && !cur.empty(); ++j) {
-      const uint8_t c = pat[p * q + j];
-      // base set of the row as a nibble whose bit index is the 2-bit text code
-      const uint32_t set = pr == PROFILE_IUPAC ? (iupac_code(c) & 15u) : (1u << ((c >> 1) & 3u));
-      nxt.clear();
-      for (uint32_t code : cur)
-        for (uint32_t b = 0; b < 4; ++b)
-          if ((set >> b) & 1u) nxt.push_back((code << 2) | b);
-      if (nxt.size() + total > limit) return false;
-      cur.swap(nxt);
-    }
-    total += cur.size();
-    for (uint32_t code : cur) tab[code & ((1u << low_bits) - 1u)] |= (uint8_t)(1u << (code >> low_bits));
-  }
-  return true;
-}
-
-// The counting filter's table (count_filter.hip): H = every Q-gram some Q consecutive pattern rows
-// accept (2 bits per letter, first row most significant, codes A0 C1 T2 G3; ambiguous rows are
-// expanded); entry w of the table, w a (Q+R-1)-gram, = how many of the R Q-grams w ends with are
-// in H.  density = |H| / 4^Q, the chance that a random position counts.  False if the expansion
-// takes more than `limit` Q-grams.
-static bool build_count_table(Profile pr, const uint8_t* pat, const uint8_t* pat2, uint32_t m, uint32_t Q, uint32_t R,
-                              std::vector<uint8_t>& tab, double* density) {
-  const size_t limit = 1u << 20;
-  const uint32_t nq = 1u << (2 * Q);
-  std::vector<uint8_t> H(nq, 0);
-  std::vector<uint32_t> cur, nxt;
-  size_t total = 0;
-  // pat2: a second pattern whose q-grams also count (the Rc strand's, in forward orientation)
-  for (uint32_t o = 0; o + Q <= (pat2 ? 2 * m : m); ++o) {
-    if (o + Q > m && o < m) continue;  // no q-gram across the two patterns
-    cur.assign(1, 0u);
-    for (uint32_t j = 0; j < Q; ++j) {
-      const uint8_t c = o < m ? pat[o + j] : pat2[o - m + j];
-      const uint32_t set = pr == PROFILE_IUPAC ? (iupac_code(c) & 15u) : (1u << ((c >> 1) & 3u));
-      nxt.clear();
-      for (uint32_t code : cur)
-        for (uint32_t b = 0; b < 4; ++b)
-          if ((set >> b) & 1u) nxt.push_back((code << 2) | b);
-      if (nxt.size() + total > limit) return false;
-      cur.swap(nxt);
-    }
-    total += cur.size();
-    for (uint32_t code : cur) H[code] = 1;
-  }
-  size_t set_bits = 0;
-  for (uint8_t v : H) set_bits += v;
-  *density = (double)set_bits / (double)nq;
-  const uint32_t nw = 1u << (2 * (Q + R - 1));
-  tab.assign(nw, 0);
-  for (uint32_t w = 0; w < nw; ++w) {
-    uint32_t c = 0;
-    for (uint32_t r = 0; r < R; ++r) c += H[(w >> (2 * r)) & (nq - 1)];
-    tab[w] = (uint8_t)c;
-  }
-  return true;
-}
-
-// How often a window of random text reaches the threshold t when it holds lambda q-gram hits on
-// average.  Hits come in clumps (a text stretch that equals L >= Q pattern rows gives L - Q + 1 of
-// them): clumps arrive Poisson(lambda (1 - r)) with geometric sizes, P(j) = (1 - r) r^(j-1), r = 1/4
-// the chance that the next letter extends the stretch.  P(S >= t) by Panjer's recursion.
-static double clumped_tail(double lambda, uint32_t t) {
-  if (t == 0) return 1.0;
-  if (lambda <= 0) return 0.0;
-  if (lambda >= (double)t) return 1.0;  // at or above the mean: no filter
-  const double r = 0.25, lc = lambda * (1.0 - r);
-  std::vector<double> p(t, 0.0);
-  p[0] = std::exp(-lc);
-  if (p[0] <= 0) return 1.0;
-  double below = p[0];
-  for (uint32_t s = 1; s < t; ++s) {
-    double acc = 0, g = 1.0 - r;  // g = P(size j)
-    for (uint32_t j = 1; j <= s && j <= 48; ++j, g *= r) acc += (double)j * g * p[s - j];
-    p[s] = lc / (double)s * acc;
-    below += p[s];
-  }
-  return std::min(1.0, std::max(0.0, 1.0 - below));
-}
-
 static hipError_t launch_scan_any(Profile pr, const ScanParams& P, uint32_t grid, size_t smem, hipStream_t st) {
   if (P.profile == PROFILE_CLASSES) return launch_scan_classes(P, grid, smem, st);
   switch (pr) {
@@ -259,175 +118,39 @@ int ScanJob::prepare() {
   P.rev_n = rev_n;
   bucket = plan.nslots <= 4 ? 4 : plan.nslots <= 8 ? 8 : plan.nslots <= 16 ? 16 : plan.nslots <= 32 ? 32 : 64;
   for (int s = 0; s < kMaxSlots; ++s) P.slot_val[s] = plan.slot_val[s];
-  q = filter_piece_len(plan, k, S);
-  // a match that hangs over an end of the text contains only part of the pattern: the pigeonhole
-  // argument of the prefilter does not cover it, so overhang searches stream the full DP
-  if (overhang) q = 0;
-  // Ascii patterns with more than 16 distinct bytes: only the DP kernels carry that many slot masks (or, byte mode,
-  // compare bytes instead of looking slots up)
-  if (plan.nslots > 16 || plan.bytes || plan.classes) q = 0;
-  if (ext_bitmap) q = ext_q;
-  if (ext_desc) q = 1;  // list mode without a filter
-  // which prefilter kernel (SASSY_HIP_FILTER_KIND=1|2|3|4 forces one where it applies)
-  const int env_kind = (int)sw.filter_kind;
-  const int env_pre = prefilter_mode(S);
-  fkind = kFilterGeneric;
-  if (ext_bitmap || ext_desc) fkind = kFilterPlanes;  // (ext_bitmap: marked like filter_dna_kernel does)
   if (ext_desc) {
     P.flags |= kScanPerText;
     P.texts_start = texts.start;
     P.texts_len = texts.len;
   }
-  const uint32_t pieces = k + 1;
-  // The fused launch (filter + chunk DP in one kernel, see below) takes one strand of one text whose reports the
-  // traceback waves rank themselves: the wave-per-report traceback must be this job's (use_wave).
+  // the route (scan_route.h): filter kind and piece length, paired / fused / direct launch, traceback shape, the table
   const TraceShape ts = trace_shape(plan.m, k);
-  use_wave = do_trace && sw.trace_wave != 0 && ts.wave_fits;
-  const bool fuse_ok = !ext_bitmap && !ext_desc && rc_bitmap == nullptr && rev_n == 0 && S->fuse && !no_fuse &&
-                       L.fuse_backoff == 0 && sw.self_rank != 0 && use_wave &&
-                       texts.n == 0 && plan.nwords <= 8 && n_blocks < 0x7FFFFFFFull && !S->want_counters;
-  // Iupac searcher, pattern of plain A C G T, <= 4 pieces: the Dna bit-plane filter with a check of the text
-  // (filter_dna_kernel, CHECK) -- as the fused launch only.  Where the text holds other letters (N runs, ambiguity codes,
-  // anything) the lane that owns the block queues the columns a match touching them can end in, like a piece
-  // occurrence, and the chunk DP of such a launch builds the Iupac profile's masks: exact on any text.
-  const int env_iupac_planes = (int)sw.iupac_planes;
-  bool plain_pattern = S->profile == PROFILE_IUPAC && env_iupac_planes != 0 && !overhang;
-  for (uint32_t j = 0; plain_pattern && j < plan.m; ++j) {
-    const uint8_t u = pat[j] & 0xDFu;
-    plain_pattern = u == 'A' || u == 'C' || u == 'G' || u == 'T';
+  const RouteInput ri{S->profile, plan.m, plan.nwords, plan.nslots, plan.bytes, plan.classes, pat, rc_bitmap ? rc_pat : nullptr, k, sw,
+                      S->prefilter, S->fuse, S->want_counters, overhang, do_trace, ts.wave_fits, ext_bitmap != nullptr, ext_q,
+                      ext_desc != nullptr, rc_bitmap != nullptr, rev_n != 0, texts.n != 0, no_fuse, n_blocks, L.fuse_backoff,
+                      L.table_q, L.table_r, L.table_k, L.table_profile, L.table_rc, L.table_pattern, L.table_density};
+  Route route;
+  choose_route(ri, route, L.h_table);
+  if (route.table_dropped) L.table_q = 0;
+  if (route.table != kTableNone && !route.table_cached) {
+    if (int rc = L.d_table.reserve(L.h_table.size())) return rc;
+    if (int rc = L.upload(L.d_table.p, L.h_table.data(), L.h_table.size())) return rc;
+    L.table_q = route.table_q; L.table_r = route.table_r; L.table_k = k; L.table_profile = (int)S->profile;
+    if (route.table == kTableCount) { L.table_rc = route.rc_marked; L.table_density = route.table_density; }
+    L.table_pattern.assign(pat, pat + plan.m);
   }
-  bool iupac_planes = plain_pattern && fuse_ok && q >= 6 && q <= 12 && pieces <= 4 && plan.nslots <= 4;
-  bool can_planes = q > 0 && pieces <= 8 && (S->profile == PROFILE_DNA || iupac_planes);
-  // Pieces of 6 rows, at most four of them, where the q-gram counting filter below finds nothing selective (m = 24, k = 3;
-  // m = 18, k = 2; m = 12, k = 1): a window chunk in every sixteenth block is still less work for the fused launch than
-  // the streaming DP over every block -- 0.85 against 1.03 ms per 3 GB (Iupac searcher: 0.94 against 1.29), m = 12, k = 1 with
-  // its 13 764 matches 0.99 against 1.21.  Where the counting filter applies it stays (a 20-mer with k = 2: 0.76 against 0.79;
-  // m = 27, k = 3: 0.72 against 0.87); five pieces, or pieces of 5 rows, lose against the streaming DP
-  // (tools/probe_short_pieces.py).  SASSY_HIP_SHORT_PIECES=0: never.
-  const bool env_short = sw.short_pieces != 0;
-  const bool short_ok = q == 0 && env_pre < 0 && env_short && fuse_ok && !overhang && !ext_bitmap && !ext_desc && plan.nslots <= 16 &&
-                        !plan.bytes && (S->profile == PROFILE_DNA || plain_pattern) && pieces <= 4 && plan.m / pieces == 6;
-  // (5-row pieces lose everywhere: m = 11, k = 1 takes 2.6 ms against 1.7 on the streaming DP, m = 15, k = 2 2.2 against 1.2)
-  // The paired filter (filter_dna_kernel<.., PAIR>): S = ceil((k+1)/2) super-pieces of 2 Q rows, each with at most one of
-  // the k edits -- one half exact, the other half with <= 1 edit right next to it, tested on the bit planes the lane
-  // holds.  For the shapes whose k+1 pigeonhole pieces are 5 or 6 rows (m = 23, k = 3; m = 32, k = 4, 5; ...): the fused
-  // launch, and only it (what it cannot finish goes to the paths below, as before).  SASSY_HIP_PAIR=0: never; 2: the
-  // q-gram counting filter keeps the shapes it is selective for.
-  const int env_pair = (int)sw.pair;
-  uint32_t pair_s = 0, pair_q = 0;
-  // (this side only, search_text() does not ask: an Iupac searcher's launch is the bit-plane launch with the text check
-  // (switch iupac_planes), and its chunk DP builds up to eight slot masks for the rows behind the plain prefix)
-  const bool pair_iupac_dp_ok = S->profile != PROFILE_IUPAC ||
-                                (env_iupac_planes != 0 && (plan.nslots <= 4 || (plan.nslots <= 8 && plan.nwords <= 4)));
-  const bool pair_ok = pair_eligible(S, pat, plan.m, k, &pair_s, &pair_q) && pair_iupac_dp_ok && q == 0 && fuse_ok && !overhang &&
-                       !ext_bitmap && !ext_desc && !plan.bytes && (env_kind == 0 || env_kind == kFilterPlanes);
-  pair = 0;
-  // q-gram counting (count_filter.hip): per (Q, R) variant the threshold t = m + 1 - (k+1) Q, the
-  // window W, and how often a window of random text reaches t by chance (the pattern's q-grams,
-  // ambiguity letters expanded, against 4^Q; Poisson tail).  Taken when that beats the expected
-  // hit blocks of the k+1 pieces, except where the cheaper bit-plane kernel applies (one strand: both
-  // strands in one pass cost the bit-plane kernel 8 pieces, 0.85 ms per 3 GB, the counting kernel nothing extra).
-  count_r = 0;
-  if (!overhang && !ext_bitmap && !ext_desc && !is_ascii(S->profile) && env_pre != 0 &&
-      (env_kind == 0 || env_kind == kFilterCount) && !(can_planes && env_kind == 0 && rc_bitmap == nullptr) &&
-      !(pair_ok && env_pair != 2)) {
-    // two positions per lookup first (half the LDS traffic of (7,1)); the 7-gram variant only where
-    // the shorter q-grams are not selective enough
-    static const uint32_t variants[][2] = {{6, 2}, {5, 2}, {7, 1}};
-    double best = 1.0;
-    uint32_t bq = 0, br = 0;
-    // the same pattern as in the last call on this lane: the decision and the table are still there
-    const bool with_rc = rc_bitmap != nullptr;
-    std::vector<uint8_t> rc_fwd;  // the Rc strand's pattern as it reads on the forward text: reversed
-    if (with_rc) rc_fwd.assign(std::reverse_iterator<const uint8_t*>(rc_pat + plan.m), std::reverse_iterator<const uint8_t*>(rc_pat));
-    const bool same_as_last = L.table_r != 0 && L.table_k == k && L.table_profile == (int)S->profile && L.table_rc == with_rc &&
-                              L.table_pattern.size() == plan.m && memcmp(L.table_pattern.data(), pat, plan.m) == 0;
-    if (same_as_last) { bq = L.table_q; br = L.table_r; best = 0.0; }
-    for (const auto& v : variants) {
-      if (same_as_last) break;
-      const uint32_t Q = v[0];
-      if (v[1] == 1 && best < 1e-3) break;
-      if ((uint64_t)pieces * Q > plan.m) continue;  // t >= 1
-      const uint32_t t = plan.m + 1 - pieces * Q;
-      const uint32_t W = (plan.m + k - Q + 63) / 64 + 1;
-      if (W > 64) continue;
-      double grams = 0;  // expected size of H: the product of the rows' base-set sizes, per q-gram
-      for (uint32_t o = 0; o + Q <= plan.m; ++o) {
-        double e = 1;
-        for (uint32_t j = 0; j < Q; ++j)
-          e *= S->profile == PROFILE_IUPAC ? (double)__builtin_popcount(iupac_code(pat[o + j]) & 15u) : 1.0;
-        grams += e;
-      }
-      const double dens = std::min(1.0, (with_rc ? 2.0 : 1.0) * grams / std::pow(4.0, (double)Q));
-      const double tail = clumped_tail(64.0 * W * dens, t);
-      if (tail < (v[1] == 1 ? 0.1 * best : best)) { best = tail; bq = Q; br = v[1]; }
-    }
-    // (the piece-table kernel this competes with is the slower kernel -- 1.0 against 0.64 ms per 3 GB -- so a
-    // modest candidate rate is enough; beyond ~5 % of the blocks the chunk DP behind it would dominate)
-    if (bq && best < 0.05) {
-      const bool cached = L.table_q == bq && L.table_r == br && L.table_k == k && L.table_profile == (int)S->profile &&
-                          L.table_rc == with_rc &&
-                          L.table_pattern.size() == plan.m && memcmp(L.table_pattern.data(), pat, plan.m) == 0;
-      bool ok = true;
-      if (!cached) {
-        ok = build_count_table(S->profile, pat, with_rc ? rc_fwd.data() : nullptr, plan.m, bq, br, L.h_table, &L.table_density);
-        if (ok) {
-          if (int rc = L.d_table.reserve(L.h_table.size())) return rc;
-          if (int rc = L.upload(L.d_table.p, L.h_table.data(), L.h_table.size())) return rc;
-          L.table_q = bq; L.table_r = br; L.table_k = k; L.table_profile = (int)S->profile;
-          L.table_rc = with_rc;
-          L.table_pattern.assign(pat, pat + plan.m);
-        } else {
-          L.table_q = 0;
-        }
-      }
-      if (ok) {
-        fkind = kFilterCount;
-        rc_marked = with_rc;
-        q = bq;
-        count_r = br;
-        count_w = (plan.m + k - bq + 63) / 64 + 1;
-        count_t = plan.m + 1 - pieces * bq;
-        count_tail = clumped_tail(64.0 * count_w * L.table_density, count_t);
-      }
-    }
-  }
-  if (pair_ok && fkind != kFilterCount) {
-    pair = pair_s;
-    q = pair_q;
-    iupac_planes = S->profile == PROFILE_IUPAC;
-    can_planes = true;
-  } else if (short_ok && fkind != kFilterCount) {
-    q = plan.m / pieces;
-    iupac_planes = plain_pattern && plan.nslots <= 4;
-    can_planes = S->profile == PROFILE_DNA || iupac_planes;
-  }
-  filtered = q > 0;
-  if (filtered && !ext_bitmap && !ext_desc && fkind != kFilterCount) {
-    const bool can_table = !is_ascii(S->profile) && q >= 7;
-    const bool can_generic = (uint64_t)pieces * q <= 255;   // its term table holds 256 piece rows
-    if (can_planes && (env_kind == 0 || env_kind == kFilterPlanes)) fkind = kFilterPlanes;
-    else if (can_table && (env_kind == 0 || env_kind == kFilterTable || !can_generic)) fkind = kFilterTable;
-    else if (!can_generic) { q = 0; filtered = false; }  // too many piece rows for any filter: stream the full DP
-    if (fkind == kFilterTable) {
-      const uint32_t tq = std::min<uint32_t>(q, 9);
-      const bool cached = L.table_q == tq && L.table_r == 0 && L.table_k == k && L.table_profile == (int)S->profile &&
-                          L.table_pattern.size() == plan.m && memcmp(L.table_pattern.data(), pat, plan.m) == 0;
-      if (!cached) {
-        if (build_qgram_table(S->profile, pat, tq, pieces, L.h_table)) {
-          if (int rc = L.d_table.reserve(L.h_table.size())) return rc;
-          if (int rc = L.upload(L.d_table.p, L.h_table.data(), L.h_table.size())) return rc;
-          L.table_q = tq; L.table_r = 0; L.table_k = k; L.table_profile = (int)S->profile;
-          L.table_pattern.assign(pat, pat + plan.m);
-        } else {
-          L.table_q = 0;
-          fkind = kFilterGeneric;
-          if (!can_generic) { q = 0; filtered = false; }
-        }
-      }
-      if (fkind == kFilterTable) q = tq;
-    }
-  }
+  q = route.q;
+  filtered = route.filtered;
+  fkind = route.fkind;
+  pair = route.pair;
+  count_r = route.count_r;
+  count_w = route.count_w;
+  count_t = route.count_t;
+  count_tail = route.count_tail;
+  count_direct = route.count_direct;
+  fused = route.fused;
+  use_wave = route.use_wave;
+  rc_marked = route.rc_marked;
 
   // pattern-dependent device data is uploaded only when the pattern changed since the last call
   if (int rc = L.d_rowoff.reserve(plan.row_tab.size())) return rc;
@@ -481,10 +204,7 @@ int ScanJob::prepare() {
   //             [0] word rows, [1] blocks, [2] hit blocks
   //   [64, ..)  rank counters of the first kRankLimit reports
   //   [kCtlHead, ..)  the prefilter's hit bitmap (one bit per text block)
-  // The counting filter of ONE strand files its chunk descriptors itself (count_filter.hip, DIRECT): no hit bitmap (and no
-  // 6 MB memset per 3 GB), no chunk-list launch.  Switch count_fused = 0: bitmap + build_chunks_kernel as before.
-  count_direct = filtered && fkind == kFilterCount && !rc_marked && !ext_bitmap && !ext_desc && sw.count_fused != 0 &&
-                 n_blocks < 0xFFFFFFFFull && !no_fuse && L.fuse_backoff == 0;
+  // (count_direct: the counting filter files its chunk descriptors itself -- no hit bitmap)
   n_words = filtered && !count_direct ? (n_blocks + 63) / 64 : 0;
   {
     // this search takes the lane's other control block (see ScanLane::d_ctl_twin)
@@ -517,7 +237,7 @@ int ScanJob::prepare() {
   Tw = TraceParams{};
   trace_blocks = wave_blocks = 0;
   use_thread = false;
-  if (do_trace) {  // (use_wave: decided with the shape, in front of the route choice)
+  if (do_trace) {  // (use_wave: the route's)
     use_thread = !use_wave || (k <= 6 && !overhang);  // overhang: wave shape or the generic thread shape
     const uint64_t stride = ts.thread_stride;
     if (stride > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "pattern/k too large for the traceback band");
@@ -565,11 +285,6 @@ int ScanJob::prepare() {
     Tw.count_max = use_thread ? kTraceWaveMax : 0xFFFFFFFFu;
   }
 
-  // ---- one launch for filter + chunk DP?  (bit-plane filter, one strand, one text, reports ranked by the
-  // traceback waves themselves; the chunk DP's masks and carries must fit the filter's 8 KiB tile)
-  fused = filtered && fkind == kFilterPlanes && fuse_ok;
-  if (S->profile == PROFILE_IUPAC && fkind == kFilterPlanes && !fused && !ext_bitmap && !ext_desc)
-    return fail(SASSY_HIP_EUNSUPPORTED, "internal: the Iupac bit-plane filter exists as the fused launch only");
   if (L.fuse_backoff && !no_fuse) --L.fuse_backoff;
 
   // ---- geometry of the streaming kernel (full DP, or the prefilter) ----
@@ -599,77 +314,9 @@ int ScanJob::prepare() {
     // owned one is affected.
     const uint64_t look = std::min<uint64_t>(first_owned, (uint64_t)P.wb + 2);
     F.first_owned_block = first_owned - look;
-    F.n_pieces = pair ? 2 * pair : k + 1;
-    F.pair = pair;
-    F.piece_len = q;
-    F.piece_groups = F.n_pieces <= 4 ? 1u : F.n_pieces <= 8 ? 2u : 0u;
-    if (F.piece_groups) {
-      auto row_byte = [&](uint32_t r) { return (plan.row_tab[r >> 2] >> (8 * (r & 3))) & 0xFFu; };
-      for (uint32_t g = 0; g < F.piece_groups; ++g) {
-        for (uint32_t j = 0; j < 12; ++j) F.piece_tab[g][j] = 0;
-        F.piece_last[g] = 0;
-        for (uint32_t pp = 0; pp < 4; ++pp) {
-          uint32_t piece = 4 * g + pp;
-          if (piece >= F.n_pieces) piece = 0;  // a repeated piece changes nothing
-          for (uint32_t j = 0; j + 1 < q; ++j) F.piece_tab[g][j] |= row_byte(piece * q + j) << (8 * pp);
-          F.piece_last[g] |= row_byte(piece * q + q - 1) << (8 * pp);
-        }
-      }
-    }
-    // Dna with <= 8 pieces: the filter works on the two code bit planes (filter_dna_kernel)
-    F.piece_planes = fkind == kFilterPlanes ? 1u : 0u;
-    F.qgram_table = fkind == kFilterTable || fkind == kFilterCount ? L.d_table.p : nullptr;
-    F.count_r = count_r;
-    F.count_window = count_w;
-    F.count_thresh = count_t;
-    F.piece_mirror = 0;
+    pack_filter(F, route, plan.row_tab, pat, rc_pat, plan.m, k, rc_bitmap != nullptr && !ext_bitmap && !ext_desc, &rc_marked, &rc_second_pass);
+    F.qgram_table = route.table != kTableNone ? L.d_table.p : nullptr;
     F.hit_bitmap_rc = rc_bitmap;
-    F.count_rc = fkind == kFilterCount && rc_marked ? 1u : 0u;
-    if (F.piece_planes) {
-      // piece `piece` of the forward pattern, or (mirror) of the Rc strand's pattern with its string
-      // reversed: rows q-1 .. 0 of complement(pattern)'s piece, as they read on the forward text
-      auto set_piece = [&](ScanParams& X, uint32_t pp, uint32_t piece, bool mirror) {
-        uint32_t b0 = 0, b1 = 0;
-        for (uint32_t j = 0; j < q; ++j) {
-          const uint8_t ch = mirror ? rc_pat[piece * q + (q - 1 - j)] : pat[piece * q + j];
-          const uint32_t code = (ch >> 1) & 3u;  // src/profiles/dna.rs:19-40
-          b0 |= (code & 1u) << j;
-          b1 |= (code >> 1) << j;
-        }
-        X.piece_bits[pp][0] = b0;
-        X.piece_bits[pp][1] = b1;
-        X.piece_rem[pp] = plan.m - (piece + 1) * q;
-        // (paired filter: an A-type sub-piece is detected q + 2 columns behind its end)
-        if (pair && (piece & 1u) == 0) X.piece_rem[pp] = (uint32_t)((int32_t)X.piece_rem[pp] - (int32_t)(q + 2));
-        if (mirror) X.piece_mirror |= 1u << pp;
-      };
-      if (pair) {
-        for (uint32_t w = 0; w < 4; ++w) F.pair_y[w] = 0;
-        for (uint32_t pp = 0; pp < 2 * pair; ++pp) {
-          const uint32_t sib = pp ^ 1u;
-          for (uint32_t j = 0; j < q; ++j) {
-            // piece pp even (A): its B read forwards; odd (B): its A read backwards
-            const uint32_t code = (pat[sib * q + ((pp & 1u) ? q - 1 - j : j)] >> 1) & 3u;
-            F.pair_y[2 * (pp >> 2)] |= (code & 1u) << (8 * (pp & 3u) + j);
-            F.pair_y[2 * (pp >> 2) + 1] |= (code >> 1) << (8 * (pp & 3u) + j);
-          }
-        }
-      }
-      const uint32_t np = k + 1;
-      const bool with_rc = rc_bitmap != nullptr && !ext_bitmap && !ext_desc;
-      if (with_rc && np <= 4) {  // both strands' pieces in one launch (a repeated piece changes nothing)
-        for (uint32_t pp = 0; pp < 4; ++pp) set_piece(F, pp, pp < np ? pp : 0, false);
-        for (uint32_t pp = 0; pp < 4; ++pp) set_piece(F, 4 + pp, pp < np ? pp : 0, true);
-        F.n_pieces = 8;
-        F.piece_groups = 2;
-        rc_marked = true;
-      } else {
-        for (uint32_t pp = 0; pp < 8; ++pp) set_piece(F, pp, pp < F.n_pieces ? pp : 0, false);
-        if (with_rc) {  // 5 .. 8 pieces per strand: a second launch for the Rc strand's pieces
-          rc_marked = rc_second_pass = true;
-        }
-      }
-    }
     int fwpc = 16;
     // fused: ONE round of workgroups (as many as are resident at once) -- every workgroup ends with the chunk DP of
     // what it found, a phase in which it does not stream; with two rounds the chip goes through that twice (3 GB:
@@ -739,20 +386,7 @@ int ScanJob::prepare() {
     }
     if (rc_second_pass) {  // same launch, the Rc strand's pieces (all mirrored) instead of the forward ones
       F2 = F;
-      F2.piece_mirror = 0;
-      for (uint32_t pp = 0; pp < 8; ++pp) {
-        const uint32_t piece = pp < k + 1 ? pp : 0;
-        uint32_t b0 = 0, b1 = 0;
-        for (uint32_t j = 0; j < q; ++j) {
-          const uint32_t code = (rc_pat[piece * q + (q - 1 - j)] >> 1) & 3u;
-          b0 |= (code & 1u) << j;
-          b1 |= (code >> 1) << j;
-        }
-        F2.piece_bits[pp][0] = b0;
-        F2.piece_bits[pp][1] = b1;
-        F2.piece_rem[pp] = plan.m - (piece + 1) * q;
-        F2.piece_mirror |= 1u << pp;
-      }
+      rc_pieces(F2, rc_pat, plan.m, k, q);
     }
     // (the chunk DP's carries: in LDS, fewer waves per workgroup for long patterns; beyond ~10 000 rows in global memory and
     // a fixed number of waves -- list_kernel<.., GC>)
@@ -1855,6 +1489,31 @@ int post_filter(sassy_SearcherType* S, ScanOut& so, const PatternPlan& plan, con
   return 0;
 }
 
+// The Rc strand's records were found on the reversed text: strand, and the span mapped back to the forward text.
+static void flip_rc_coordinates(sassy_hip_Result* R, size_t first, uint64_t tlen, bool wo) {
+  for (size_t i = first; i < R->matches.size(); ++i) {
+    sassy_hip_Match& r = R->matches[i];
+    const uint64_t rs = r.text_start, re = r.text_end;
+    r.strand = 1;
+    r.text_start = tlen - re;
+    r.text_end = wo ? UINT64_MAX : tlen - rs;  // reference: src/search.rs:868-873
+  }
+}
+
+// The reversed copy of the text in S->d_rev.  The caller may promise that a device text did not change since this searcher
+// last saw it (SASSY_HIP_TEXT_UNCHANGED): the copy (n bytes read + n written, more than the search itself) is then still valid.
+static int reversed_copy(sassy_SearcherType* S, const uint8_t* d_fwd, size_t tlen, bool on_dev, uint32_t flags) {
+  const bool reuse = on_dev && (flags & SASSY_HIP_TEXT_UNCHANGED) && S->rev_src == d_fwd && S->rev_len == tlen &&
+                     S->d_rev.p != nullptr;
+  if (reuse) return 0;
+  S->rev_src = nullptr;
+  if (int rc = S->d_rev.reserve(tlen + 64)) return rc;
+  hipError_t le = launch_reverse(d_fwd, S->d_rev.p, tlen, S->stream);
+  if (le != hipSuccess) return hip_fail(le, "reverse kernel launch");
+  if (on_dev) { S->rev_src = d_fwd; S->rev_len = tlen; }
+  return 0;
+}
+
 int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, const uint8_t* text,
                        size_t tlen, size_t k, uint32_t flags, uint64_t pattern_idx, bool fwd_strand,
                        bool rc_strand, sassy_hip_Result* R, const EndFilter& ef,
@@ -1907,7 +1566,7 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
   const int env_pair_rc = (int)S->sw.pair_rc;
   uint32_t ps_ = 0, pq_ = 0;
   const bool pair_strands = env_pair_rc != 0 && S->fuse && !wo && k <= 0xFFFFu &&
-                            pair_eligible(S, pattern, plan.m, (uint32_t)k, &ps_, &pq_);
+                            pair_eligible(S->profile, S->sw, S->prefilter, pattern, plan.m, (uint32_t)k, &ps_, &pq_);
   const bool can_fuse = fwd_strand && rc_strand && env_fuse != 0 && !ef.fn && std::isnan(S->max_n_frac) &&
                         std::isnan(S->alpha) && !is_ascii(S->profile) && ref_lanes == 0 && !pair_strands;
   bool rc_by_bitmap = false;
@@ -1919,28 +1578,13 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
   const bool env_two = S->sw.strands_in_flight != 0;
   if (fwd_strand && rc_strand && !can_fuse && env_two && ref_lanes == 0 && !ef.fn && std::isnan(S->alpha) &&
       !is_ascii(S->profile)) {
-    const bool reuse = on_dev && (flags & SASSY_HIP_TEXT_UNCHANGED) && S->rev_src == d_fwd && S->rev_len == tlen &&
-                       S->d_rev.p != nullptr;
-    if (!reuse) {
-      S->rev_src = nullptr;
-      if (int rc = S->d_rev.reserve(tlen + 64)) return rc;
-      hipError_t le = launch_reverse(d_fwd, S->d_rev.p, tlen, S->stream);
-      if (le != hipSuccess) return hip_fail(le, "reverse kernel launch");
-      if (on_dev) { S->rev_src = d_fwd; S->rev_len = tlen; }
-    }
+    if (int rc = reversed_copy(S, d_fwd, tlen, on_dev, flags)) return rc;
     ScanQueue queue(S, [&](uint64_t strand, ScanOut& so, const PatternPlan& pl, const uint8_t* pat) -> int {
       if (int rc = post_filter(S, so, pl, pat, (uint32_t)k, (int)strand, strand == 0 && !on_dev ? text : nullptr,
                                strand ? S->d_rev.p : d_fwd, tlen, !wo, ef)) return rc;
       size_t first = 0;
       if (int rc = append_matches(so, tlen, pl, wo, pattern_idx, R, first)) return rc;
-      if (strand)
-        for (size_t i = first; i < R->matches.size(); ++i) {
-          sassy_hip_Match& r = R->matches[i];
-          const uint64_t rs = r.text_start, re = r.text_end;
-          r.strand = 1;
-          r.text_start = tlen - re;
-          r.text_end = wo ? UINT64_MAX : tlen - rs;  // reference: src/search.rs:868-873
-        }
+      if (strand) flip_rc_coordinates(R, first, tlen, wo);
       return 0;
     });
     const TextTable no_texts{};
@@ -1990,13 +1634,7 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
         if (int rc = rj->finish(so_rc)) return rc;
         if (int rc = post_filter(S, so_rc, cplan, cp.data(), (uint32_t)k, 1, nullptr, nullptr, tlen, !wo, ef)) return rc;
         if (int rc = append_matches(so_rc, tlen, cplan, wo, pattern_idx, R, first)) return rc;
-        for (size_t i = first; i < R->matches.size(); ++i) {
-          sassy_hip_Match& r = R->matches[i];
-          const uint64_t rs = r.text_start, re = r.text_end;
-          r.strand = 1;
-          r.text_start = tlen - re;
-          r.text_end = wo ? UINT64_MAX : tlen - rs;  // reference: src/search.rs:868-873
-        }
+        flip_rc_coordinates(R, first, tlen, wo);
       }
     } else {
       if (ref_lanes) {
@@ -2011,17 +1649,7 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
     // done above, next to the forward strand
   } else if (rc_strand) {
     // complement(pattern) against a reversed copy of the text, coordinates mapped back
-    // the caller may promise that a device text did not change since this searcher last saw it:
-    // the reversed copy (n bytes read + n written, more than the search itself) is then still valid
-    const bool reuse = on_dev && (flags & SASSY_HIP_TEXT_UNCHANGED) && S->rev_src == d_fwd && S->rev_len == tlen &&
-                       S->d_rev.p != nullptr;
-    if (!reuse) {
-      S->rev_src = nullptr;
-      if (int rc = S->d_rev.reserve(tlen + 64)) return rc;
-      hipError_t le = launch_reverse(d_fwd, S->d_rev.p, tlen, S->stream);
-      if (le != hipSuccess) return hip_fail(le, "reverse kernel launch");
-      if (on_dev) { S->rev_src = d_fwd; S->rev_len = tlen; }
-    }
+    if (int rc = reversed_copy(S, d_fwd, tlen, on_dev, flags)) return rc;
     ShardView sh{S->d_rev.p, tlen, 0, 0, true, true};
     ScanOut so;
     if (ref_lanes) {
@@ -2034,13 +1662,7 @@ int search_text(sassy_SearcherType* S, const uint8_t* pattern, size_t plen, cons
                              S->d_rev.p, tlen, !wo, ef)) return rc;
     size_t first = 0;
     if (int rc = append_matches(so, tlen, cplan, wo, pattern_idx, R, first)) return rc;
-    for (size_t i = first; i < R->matches.size(); ++i) {
-      sassy_hip_Match& r = R->matches[i];
-      const uint64_t rs = r.text_start, re = r.text_end;
-      r.strand = 1;
-      r.text_start = tlen - re;
-      r.text_end = wo ? UINT64_MAX : tlen - rs;  // reference: src/search.rs:868-873
-    }
+    flip_rc_coordinates(R, first, tlen, wo);
   }
   return 0;
 }
