@@ -63,6 +63,13 @@ extern "C" {
     // Hamming search (include/sassy_hip.h): every start with at most k mismatches of every pattern, one text
     fn sassy_hip_search_hamming(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
                                 text: *const u8, text_len: usize, k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
+    // ... over a batch of texts: every hit with its text_idx / per text the best (cost, pattern, strand, start), no records
+    fn sassy_hip_search_hamming_many(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                     texts: *const *const u8, text_lens: *const usize, n_texts: usize, k: usize, flags: u32,
+                                     out: *mut *mut RawResult) -> c_int;
+    fn sassy_hip_hamming_best_pattern(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                      texts: *const *const u8, text_lens: *const usize, n_texts: usize, k: usize, flags: u32,
+                                      out_cost: *mut u8, out_pattern: *mut u32, out_strand: *mut u8, out_start: *mut u64) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;
@@ -307,6 +314,35 @@ impl<P: Profile> Searcher<P> {
         };
         assert_eq!(rc, 0, "{}", last_error());
         (0..texts.len()).map(|t| (cost[t], pat[t], if strand[t] != 0 { Strand::Rc } else { Strand::Fwd })).collect()
+    }
+
+    /// Hamming search over a batch of texts: every start with at most `k` mismatches of every pattern in every text, ordered
+    /// by (pattern_idx, Fwd before Rc, text_idx, text_start); coordinates are relative to the record's text.
+    pub fn search_hamming_many(&mut self, patterns: &[&[u8]], texts: &[&[u8]], k: usize) -> Vec<Match> {
+        let (pp, pl): (Vec<*const u8>, Vec<usize>) = patterns.iter().map(|p| (p.as_ptr(), p.len())).unzip();
+        let (tp, tl): (Vec<*const u8>, Vec<usize>) = texts.iter().map(|t| (t.as_ptr(), t.len())).unzip();
+        let mut res = std::ptr::null_mut();
+        let rc = unsafe {
+            sassy_hip_search_hamming_many(self.raw, pp.as_ptr(), pl.as_ptr(), pp.len(), tp.as_ptr(), tl.as_ptr(), tp.len(), k, 0, &mut res)
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        unsafe { collect(res) }
+    }
+
+    /// Per text the best Hamming hit over all patterns and strands: (cost, pattern, strand, start) -- lowest cost, then
+    /// lowest pattern index, then Fwd before Rc, then the leftmost start; (`NO_MATCH`, `u32::MAX`, Fwd, `u64::MAX`) where no
+    /// pattern has a hit with at most `k` mismatches.
+    pub fn hamming_best_pattern(&mut self, patterns: &[&[u8]], texts: &[&[u8]], k: usize) -> Vec<(u8, u32, Strand, u64)> {
+        let (pp, pl): (Vec<*const u8>, Vec<usize>) = patterns.iter().map(|p| (p.as_ptr(), p.len())).unzip();
+        let (tp, tl): (Vec<*const u8>, Vec<usize>) = texts.iter().map(|t| (t.as_ptr(), t.len())).unzip();
+        let n = texts.len();
+        let (mut cost, mut pat, mut strand, mut start) = (vec![NO_MATCH; n], vec![u32::MAX; n], vec![0u8; n], vec![u64::MAX; n]);
+        let rc = unsafe {
+            sassy_hip_hamming_best_pattern(self.raw, pp.as_ptr(), pl.as_ptr(), pp.len(), tp.as_ptr(), tl.as_ptr(), tp.len(), k, 0,
+                                           cost.as_mut_ptr(), pat.as_mut_ptr(), strand.as_mut_ptr(), start.as_mut_ptr())
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        (0..n).map(|t| (cost[t], pat[t], if strand[t] != 0 { Strand::Rc } else { Strand::Fwd }, start[t])).collect()
     }
 
     /// Per text the one best match over all patterns and strands as a complete record: lowest cost, then lowest pattern

@@ -358,7 +358,7 @@ int sassy_hip_best_matches(sassy_SearcherType *s, const uint8_t *const *patterns
  * pattern direction (op j = match(complement(P[j]), T[s + m - 1 - j])), as sassy_hip_search's Rc records do.  max_n_frac
  * set: a hit is kept iff float(N in its span) / float(m) <= max_n_frac, decided on the device before the hit takes any
  * list space.  Order: (pattern_idx, Fwd before Rc, text_start) ascending -- part of the contract.
- *  - one text, n_patterns >= 1 patterns of any (mixed) lengths; the patterns of a launch share one pass over the text;
+ *  - one text (a batch of texts: sassy_hip_search_hamming_many), n_patterns >= 1 patterns of any (mixed) lengths; the patterns of a launch share one pass over the text;
  *  - flags: SASSY_HIP_WITHOUT_TRACE (the same records without cigar), SASSY_HIP_TEXT_ON_DEVICE, SASSY_HIP_TEXT_UNCHANGED
  *    (accepted, nothing is cached); anything else SASSY_HIP_EINVAL;
  *  - refused before any device work: overhang searchers and only_best_match (SASSY_HIP_EUNSUPPORTED), Ascii with rc (as
@@ -372,6 +372,35 @@ int sassy_hip_best_matches(sassy_SearcherType *s, const uint8_t *const *patterns
 int sassy_hip_search_hamming(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
                              size_t n_patterns, const void *text, size_t text_len, size_t k, uint32_t flags,
                              sassy_hip_Result **out);
+
+/* Hamming search over a batch of texts (reads) in one call: the records are the union over t of what
+ * sassy_hip_search_hamming(patterns, texts[t], k) returns for the same searcher, each with text_idx = t and coordinates
+ * relative to text t; every other field is that call's (pattern_idx, cost, strand, cigar, pattern_start / pattern_end, the
+ * max_n_frac rule per span).  Order: (pattern_idx, Fwd before Rc, text_idx, text_start) ascending -- part of the contract.
+ * A text shorter than a pattern has no hits of it (empty texts included); n_texts == 0: an empty result, 0.
+ *  - flags: SASSY_HIP_WITHOUT_TRACE (the same records without cigar); anything else, SASSY_HIP_TEXT_ON_DEVICE included,
+ *    SASSY_HIP_EINVAL (host texts only);
+ *  - the refusals of sassy_hip_search_hamming, with the same codes, before any device work;
+ *  - the texts are laid out in one buffer, each from a multiple of 64 bytes on, in batches of at most 1 GiB (option
+ *    hamming_many_batch); the scan masks every start by the bytes left in its block's own text, the emit kernel finds a
+ *    hit's text in the batch's start table. */
+int sassy_hip_search_hamming_many(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                                  size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
+                                  size_t k, uint32_t flags, sassy_hip_Result **out);
+
+/* Per text the best record of sassy_hip_search_hamming_many: the smallest under (cost, pattern_idx, Fwd before Rc,
+ * text_start) -- sassy_hip_best_pattern's tie rule, then the leftmost start.  out_cost[t], out_pattern[t], out_strand[t]
+ * (0 Fwd / 1 Rc) and out_start[t], the start in the forward text relative to text t; a text without a hit gets
+ * SASSY_HIP_NO_MATCH, UINT32_MAX, 0, UINT64_MAX.  out_pattern, out_strand and out_start may be NULL.  Demultiplexing by
+ * mismatch count: which barcode, at how many mismatches, where.
+ *  - no flags (host texts only): anything else SASSY_HIP_EINVAL; k > 254 SASSY_HIP_EINVAL (costs are bytes);
+ *  - the refusals of sassy_hip_search_hamming; 2^23 patterns or more, or a text of 2^32 bytes or more,
+ *    SASSY_HIP_EUNSUPPORTED (the device keeps cost:8 | 2 pattern_idx + strand:24 | start:32 in one 64-bit cell per text);
+ *  - no records leave the device: every block's minimum goes into its text's cell, the cells come back once per batch. */
+int sassy_hip_hamming_best_pattern(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                                   size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
+                                   size_t k, uint32_t flags, uint8_t *out_cost, uint32_t *out_pattern, uint8_t *out_strand,
+                                   uint64_t *out_start);
 
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar

@@ -152,7 +152,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_malloc", "sassy_hip_free", "sassy_hip_memcpy_h2d", "sassy_hip_memcpy_d2h",
     "sassy_hip_line_spans", "sassy_hip_result_line_spans", "sassy_hip_line_tile", "sassy_hip_line_span_times",
     "sassy_hip_search_classes", "sassy_hip_class_cover",
-    "sassy_hip_search_hamming",
+    "sassy_hip_search_hamming", "sassy_hip_search_hamming_many", "sassy_hip_hamming_best_pattern",
 ]
 
 _lib = None
@@ -285,6 +285,10 @@ def lib():
     L.sassy_hip_search_classes.argtypes = [vp, u8p, sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
     L.sassy_hip_search_hamming.restype = C.c_int
     L.sassy_hip_search_hamming.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, vp, sz, sz, C.c_uint32, C.POINTER(vp)]
+    L.sassy_hip_search_hamming_many.restype = C.c_int
+    L.sassy_hip_search_hamming_many.argtypes = list(L.sassy_hip_search_many.argtypes)
+    L.sassy_hip_hamming_best_pattern.restype = C.c_int
+    L.sassy_hip_hamming_best_pattern.argtypes = list(L.sassy_hip_search_many.argtypes[:-1]) + [vp, vp, vp, vp]
     L.sassy_hip_class_cover.restype = C.c_long
     L.sassy_hip_class_cover.argtypes = [u8p, vp, vp, sz, C.POINTER(C.c_int)]
     L.sassy_hip_search_all_alignments.restype = C.c_int
@@ -881,6 +885,49 @@ class Searcher:
         _check(lib().sassy_hip_search_hamming(self._h, pp, pl, len(patterns), addr, n, k, flags, C.byref(out)))
         r = Result(out)
         return r if as_result else r.matches
+
+    @staticmethod
+    def _hamming_patterns(patterns, who: str):
+        if isinstance(patterns, ClassPattern) or (not isinstance(patterns, (bytes, bytearray, memoryview)) and
+                                                  any(isinstance(p, ClassPattern) for p in patterns)):
+            raise SassyHipError(f"{who} takes byte patterns only: a ClassPattern is not supported")
+        if isinstance(patterns, (bytes, bytearray, memoryview)):
+            patterns = [patterns]
+        return [bytes(p) for p in patterns]
+
+    def search_hamming_many(self, patterns, texts: Sequence, k: int, without_trace: bool = False, as_result: bool = False):
+        """search_hamming over a batch of texts (reads) in one call (sassy_hip_search_hamming_many): the records of
+        search_hamming(patterns, texts[t], k) for every t, each with text_idx = t and coordinates relative to its text,
+        ordered by (pattern_idx, '+' before '-', text_idx, text_start).  `texts`: a list of host texts or a TextBatch, as
+        search_many (host texts only).  without_trace: the same records without cigar.  as_result: the Result."""
+        patterns = self._hamming_patterns(patterns, "search_hamming_many")
+        pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
+        if on_device:
+            raise SassyHipError("search_hamming_many takes host texts only")
+        out = C.c_void_p()
+        _check(lib().sassy_hip_search_hamming_many(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, WITHOUT_TRACE if without_trace else 0,
+                                                   C.byref(out)))
+        r = Result(out)
+        return r if as_result else r.matches
+
+    def hamming_best_pattern(self, patterns, texts: Sequence, k: int):
+        """Per text the best Hamming hit over all patterns and strands (sassy_hip_hamming_best_pattern): (cost uint8,
+        pattern uint32, strand uint8, start uint64) arrays of n_texts entries -- of search_hamming_many's records of a text
+        the smallest under (cost, pattern_idx, '+' before '-', text_start); NO_MATCH (255), 0xFFFFFFFF, 0 and
+        0xFFFFFFFFFFFFFFFF where no pattern has a hit with at most k mismatches.  Reduced on the device: no records, no
+        cigars.  k <= 254.  Demultiplexing by mismatch count."""
+        import numpy as np
+        patterns = self._hamming_patterns(patterns, "hamming_best_pattern")
+        pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
+        if on_device:
+            raise SassyHipError("hamming_best_pattern takes host texts only")
+        cost = np.empty(n_texts, dtype=np.uint8)
+        pattern = np.empty(n_texts, dtype=np.uint32)
+        strand = np.empty(n_texts, dtype=np.uint8)
+        start = np.empty(n_texts, dtype=np.uint64)
+        _check(lib().sassy_hip_hamming_best_pattern(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, 0, cost.ctypes.data,
+                                                    pattern.ctypes.data, strand.ctypes.data, start.ctypes.data))
+        return cost, pattern, strand, start
 
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k

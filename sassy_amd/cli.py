@@ -1,4 +1,4 @@
-"""`python -m sassy_amd search | filter ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
+"""`python -m sassy_amd search | filter | demux ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
 
 Mirrors `sassy search` (reference: bin/grep.rs:30-157 arguments, :465-470 header, :623-660 pattern
 sources, :710-757 rows; FASTA/FASTQ records as bin/input_iterator.rs:125-137 reads them): every
@@ -17,6 +17,18 @@ line.  It asks `Searcher.best_pattern` for one cost per record: no match records
 
 `search --best` writes at most one row per record: its best match over all patterns and strands (lowest cost, then
 the first pattern, then the forward strand, then the rightmost end), through `Searcher.best_matches`.
+
+`search --hamming` counts mismatches only (no insertions or deletions): every start with at most k mismatching positions,
+all patterns against all records of a batch in one `Searcher.search_hamming_many` call; rows record by record, inside a
+record by (pattern, strand, start).
+
+`demux [-p/-f patterns] -k K [--no-rc] [--max-n-frac F] PATH ...` writes one row per record: the barcode (pattern) with the
+fewest mismatches in it, through `Searcher.hamming_best_pattern` (lowest cost, then the first pattern, then the forward
+strand, then the leftmost start):
+
+    text_id  pat_id  cost  strand  start
+
+A record that holds no pattern within k mismatches gets `*` for pat_id and strand, and -1 for cost and start.
 
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
@@ -225,6 +237,48 @@ def hamming_rows(searcher, patterns, text_id, where, matches, sam=False):
     return [searcher.format_tsv(m, patterns[m.pattern_idx][0], text_id, where, sam=sam) for m in matches]
 
 
+def hamming_batch_rows(searcher, patterns, batch, matches, sam=False):
+    """The TSV rows of one batch's Hamming hits (Searcher.search_hamming_many's records of batch.texts), in the order the
+    per-record calls gave them: record by record, inside a record (pattern, strand, start) -- the call's own order is
+    (pattern, strand, record, start), so a stable sort on the record index is all it takes."""
+    base = int(batch.texts.buffer.ctypes.data)
+    rows = []
+    for m in sorted(matches, key=lambda x: x.text_idx):
+        ti = m.text_idx
+        where = (base + int(batch.texts.starts[ti]), int(batch.texts.lens[ti]))
+        rows.extend(hamming_rows(searcher, patterns, batch.id(ti), where, [m], sam=sam))
+    return rows
+
+
+DEMUX_HEADER = "text_id\tpat_id\tcost\tstrand\tstart\n"
+
+
+def demux_rows(patterns, ids, best):
+    """One row per record from Searcher.hamming_best_pattern's four arrays: text_id, pat_id, cost, strand, start; a record
+    without a hit: `*` for the pattern and the strand, -1 for cost and start."""
+    cost, pattern, strand, start = best
+    rows = []
+    for i, text_id in enumerate(ids):
+        if int(cost[i]) == NO_MATCH:
+            rows.append(f"{text_id}\t*\t-1\t*\t-1\n")
+        else:
+            rows.append(f"{text_id}\t{patterns[int(pattern[i])][0]}\t{int(cost[i])}\t{'-' if int(strand[i]) else '+'}\t{int(start[i])}\n")
+    return rows
+
+
+def run_demux(args, searcher, patterns, out) -> int:
+    out.write(DEMUX_HEADER)
+    pats = [p for _, p in patterns]
+    for path in args.paths:
+        for batch in read_fastx_batches(path, BATCH_BYTES):
+            if not len(batch):
+                continue
+            best = searcher.hamming_best_pattern(pats, batch.texts, args.k)
+            out.writelines(demux_rows(patterns, [batch.id(i) for i in range(len(batch))], best))
+    out.flush()
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m sassy_amd", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -236,13 +290,18 @@ def main(argv=None) -> int:
                     help="at most one row per record: its best match over all patterns and strands (Searcher.best_matches)")
     sp.add_argument("--hamming", action="store_true",
                     help="mismatches only (no insertions or deletions): every start with at most k mismatching positions "
-                         "(Searcher.search_hamming), all patterns in one call per record")
+                         "(Searcher.search_hamming_many), all patterns against all records of a batch in one call")
     sp.add_argument("paths", nargs="+")
     fp = sub.add_parser("filter", help="write the records that hold a match (-v: that hold none) to stdout")
     add_search_arguments(fp)
     fp.add_argument("-v", "--invert", action="store_true", help="write the records WITHOUT a match")
     fp.add_argument("paths", nargs="+")
+    dp = sub.add_parser("demux", help="write per record the pattern (barcode) with the fewest mismatches as TSV to stdout")
+    add_search_arguments(dp)
+    dp.add_argument("paths", nargs="+")
     args = ap.parse_args(argv)
+    if args.cmd == "demux" and args.overhang is not None:
+        ap.error("demux counts mismatches: it does not take --overhang")
     if args.cmd == "agrep":
         return run_agrep(args)
     if args.cmd == "search" and args.hamming and (args.best or args.overhang is not None):
@@ -253,6 +312,8 @@ def main(argv=None) -> int:
     searcher = Searcher(args.alphabet, rc=rc, alpha=args.overhang).with_max_n_frac(args.max_n_frac)
     if args.cmd == "filter":
         return run_filter(args, searcher, [p for _, p in patterns], sys.stdout.buffer)
+    if args.cmd == "demux":
+        return run_demux(args, searcher, patterns, sys.stdout)
     out = sys.stdout
     out.write("pat_id\ttext_id\tcost\tstrand\tstart\tend\tmatch_region\tcigar\n")
     pats = [p for _, p in patterns]
@@ -266,12 +327,9 @@ def main(argv=None) -> int:
         for batch in read_fastx_batches(path, BATCH_BYTES):
             if not len(batch):
                 continue
-            if args.hamming:  # one call per record with all patterns
-                base = int(batch.texts.buffer.ctypes.data)
-                for ti in range(len(batch)):
-                    lo, ln = int(batch.texts.starts[ti]), int(batch.texts.lens[ti])
-                    hits = searcher.search_hamming(pats, batch.texts.buffer[lo:lo + ln], args.k)
-                    out.writelines(hamming_rows(searcher, patterns, batch.id(ti), (base + lo, ln), hits, sam=args.sam))
+            if args.hamming:  # one call per batch: all patterns, all records
+                hits = searcher.search_hamming_many(pats, batch.texts, args.k)
+                out.writelines(hamming_batch_rows(searcher, patterns, batch, hits, sam=args.sam))
                 continue
             if args.best:  # (one record per text at most, in text order already)
                 res = searcher.best_matches(pats, batch.texts, args.k, as_result=True)

@@ -9,6 +9,10 @@
 //                    mask leaves as one 16-byte item (pattern | strand, block, mask), one atomic per wavefront.
 //   ham_emit_kernel  the items sorted by (pattern | strand, block) and their popcount prefix give every hit its record
 //                    index: a lane per hit reads the m window bytes once for cost and cigar.
+// sassy_hip_search_hamming_many / sassy_hip_hamming_best_pattern: a batch of texts in one buffer, each from a multiple of 64
+// bytes on.  The scan kernel's MANY instantiations mask the starts by rem[block], the bytes left in the block's own text
+// (ham_rem_kernel builds it on the device); the emit kernel finds a hit's text in the start table.  Best pattern: no items --
+// the block's minimum (ham_min_cost) goes into one 64-bit cell per text.
 #include "host_internal.h"
 #include "profile_masks.h"
 #include "hamming_step.h"
@@ -52,6 +56,14 @@ struct HamParams {
   uint32_t* item_count;  // keeps counting past item_cap
 };
 
+// The batch of texts a MANY launch scans (all device pointers); unused by the single-text instantiations.
+struct HamMany {
+  const uint32_t* rem;          // per block: bytes from its first byte to its text's end, saturated
+  const uint64_t* starts;       // per text: its first byte in the buffer
+  uint32_t n_texts;
+  unsigned long long* cells;    // != nullptr: best pattern -- per text cost:8 | 2 pattern_idx + strand:24 | start:32, all ones = none
+};
+
 // LDS of one wavefront: the staged tile, then (slots + 1) rows of nb masks -- the last row is the N mask --, whole 16 bytes
 __host__ __device__ constexpr uint32_t ham_lds_per_wave(uint32_t slots, uint32_t nb) {
   return (kHamStageBytes + (slots + 1) * nb * 8u + 15u) & ~15u;
@@ -76,8 +88,8 @@ __device__ __forceinline__ uint2 n_mask(const uint32_t (&x)[16]) {  // bit i: te
   return r;
 }
 
-template <int PROFILE, int NS, int P>
-__global__ __launch_bounds__(256) void ham_scan_kernel(const HamParams H, const ScanParams SP) {
+template <int PROFILE, int NS, int P, bool MANY>
+__global__ __launch_bounds__(256) void ham_scan_kernel(const HamParams H, const ScanParams SP, const HamMany M) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ham_lds[];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, wpg = blockDim.x >> 6;
   const uint64_t t_rel = (uint64_t)blockIdx.x * wpg + wave;
@@ -147,14 +159,32 @@ __global__ __launch_bounds__(256) void ham_scan_kernel(const HamParams H, const 
     return *reinterpret_cast<const uint64_t*>(masks + ((size_t)slot * nb + lane + q) * 8u);
   };
   auto all_over = [](uint64_t over) { return __all(over == ~(uint64_t)0) != 0; };
+  uint32_t rem = 0;  // (MANY) what is left of this block's own text; a block behind the buffer has none
+  if constexpr (MANY) rem = block < H.n_blocks ? M.rem[block] : 0u;
   for (uint32_t p = 0; p < H.n_pat; ++p) {
     const uint32_t m = tab[kHamTabWords * p], roff = tab[kHamTabWords * p + 1], nmax = tab[kHamTabWords * p + 3];
     auto row_word = [&](uint32_t w) { return rows[roff + w]; };
-    uint64_t hit = ham_hit_mask<P, true>(fetch, row_word, m, H.k, all_over) & ham_valid_mask(block, H.n, m);
+    HamCounter<P> cnt;
+    ham_count<P, true>(fetch, row_word, m, all_over, cnt);
+    uint64_t hit = cnt.le(H.k) & (MANY ? ham_valid_mask_rem(rem, m) : ham_valid_mask(block, H.n, m));
     // the N filter, before a hit takes list space -- and only where some block of the tile holds a hit
     if (nmax != kHamNoFilter && __any(hit != 0)) {
       auto n_word = [](uint32_t) { return (uint32_t)NS * 0x01010101u; };
       hit &= ham_hit_mask<kHamNPlanes, false>(fetch, n_word, m, nmax, all_over);
+    }
+    if constexpr (MANY) {
+      if (M.cells) {  // best pattern: the block's minimum into its text's cell, the key's order is the tie order
+        if (hit != 0) {
+          uint64_t at;
+          const uint32_t cost = ham_min_cost<P>(cnt, hit, &at);
+          const uint64_t s = block * 64 + (uint32_t)__builtin_ctzll(at);
+          const uint32_t t = ham_text_of([&](uint32_t i) { return M.starts[i]; }, M.n_texts, s);
+          const uint64_t who = 2ull * tab[kHamTabWords * p + 4] + tab[kHamTabWords * p + 5];
+          const unsigned long long key = ((unsigned long long)cost << 56) | (who << 32) | (uint32_t)(s - M.starts[t]);
+          if (M.cells[t] > key) atomicMin(M.cells + t, key);
+        }
+        continue;
+      }
     }
     const bool has = hit != 0;
     const uint64_t bal = __ballot(has);
@@ -169,6 +199,15 @@ __global__ __launch_bounds__(256) void ham_scan_kernel(const HamParams H, const 
   }
 }
 
+// rem[b] for every block of a laid-out batch, from the (start, len) table: a thread per block
+__global__ __launch_bounds__(256) void ham_rem_kernel(const uint64_t* __restrict__ starts, const uint64_t* __restrict__ lens, uint32_t n_texts,
+                                                      uint64_t n_blocks, uint32_t* __restrict__ rem) {
+  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n_blocks) return;
+  const uint32_t t = ham_text_of([&](uint32_t i) { return starts[i]; }, n_texts, b * 64);
+  rem[b] = ham_rem(b, starts[t], lens[t]);
+}
+
 struct EmitParams {
   const uint8_t* text;
   const HamItem* items;      // sorted
@@ -181,6 +220,9 @@ struct EmitParams {
   uint32_t str_stride;       // 0: without trace
   MatchOut* out;             // count records
   char* strs;                // count * str_stride bytes
+  const uint64_t* starts;    // != nullptr: the text is a batch of n_texts texts, the records are relative to their text
+  uint32_t n_texts;
+  uint64_t text0;            // index of the batch's first text in the call
 };
 
 __global__ __launch_bounds__(256) void ham_emit_kernel(const EmitParams E) {
@@ -205,9 +247,15 @@ __global__ __launch_bounds__(256) void ham_emit_kernel(const EmitParams E) {
                E.str_stride ? E.strs + (size_t)t * E.str_stride : nullptr, &cost, &n_count, &cigar_len);
   MatchOut o{};
   o.pattern_idx = row[4];
+  uint64_t rel = s;
   o.text_idx = 0;
-  o.text_start = s;
-  o.text_end = s + m;
+  if (E.starts) {
+    const uint32_t ti = ham_text_of([&](uint32_t i) { return E.starts[i]; }, E.n_texts, s);
+    rel = s - E.starts[ti];
+    o.text_idx = E.text0 + ti;
+  }
+  o.text_start = rel;
+  o.text_end = rel + m;
   o.pattern_start = 0;
   o.pattern_end = m;
   o.cost = (int32_t)cost;
@@ -217,41 +265,51 @@ __global__ __launch_bounds__(256) void ham_emit_kernel(const EmitParams E) {
   E.out[t] = o;
 }
 
-template <int PROFILE, int NS, int P>
-hipError_t launch_scan_k(const HamParams& H, const ScanParams& SP, uint32_t grid, uint32_t threads, size_t smem, hipStream_t st) {
+template <int PROFILE, int NS, int P, bool MANY>
+hipError_t launch_scan_k(const HamParams& H, const ScanParams& SP, const HamMany& M, uint32_t grid, uint32_t threads, size_t smem,
+                         hipStream_t st) {
   static DeviceOnce attr_set;  // LDS beyond the 64 KiB default needs an explicit opt-in
   if (attr_set.need()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ham_scan_kernel<PROFILE, NS, P>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ham_scan_kernel<PROFILE, NS, P, MANY>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHamLdsBudget);
     if (e != hipSuccess) return e;
     attr_set.done();
   }
-  hipLaunchKernelGGL((ham_scan_kernel<PROFILE, NS, P>), dim3(grid), dim3(threads), smem, st, H, SP);
+  hipLaunchKernelGGL((ham_scan_kernel<PROFILE, NS, P, MANY>), dim3(grid), dim3(threads), smem, st, H, SP, M);
   return hipGetLastError();
 }
 
-template <int PROFILE, int NS>
-hipError_t launch_scan_p(const HamParams& H, const ScanParams& SP, uint32_t grid, uint32_t threads, size_t smem, hipStream_t st) {
+template <int PROFILE, int NS, bool MANY>
+hipError_t launch_scan_p(const HamParams& H, const ScanParams& SP, const HamMany& M, uint32_t grid, uint32_t threads, size_t smem,
+                         hipStream_t st) {
   switch (ham_planes(H.k)) {
-    case 2: return launch_scan_k<PROFILE, NS, 2>(H, SP, grid, threads, smem, st);
-    case 4: return launch_scan_k<PROFILE, NS, 4>(H, SP, grid, threads, smem, st);
-    case 8: return launch_scan_k<PROFILE, NS, 8>(H, SP, grid, threads, smem, st);
-    default: return launch_scan_k<PROFILE, NS, 11>(H, SP, grid, threads, smem, st);
+    case 2: return launch_scan_k<PROFILE, NS, 2, MANY>(H, SP, M, grid, threads, smem, st);
+    case 4: return launch_scan_k<PROFILE, NS, 4, MANY>(H, SP, M, grid, threads, smem, st);
+    case 8: return launch_scan_k<PROFILE, NS, 8, MANY>(H, SP, M, grid, threads, smem, st);
+    default: return launch_scan_k<PROFILE, NS, 11, MANY>(H, SP, M, grid, threads, smem, st);
   }
 }
 
-hipError_t launch_scan(Profile pr, uint32_t ns, const HamParams& H, const ScanParams& SP, uint32_t grid, uint32_t threads, size_t smem,
-                       hipStream_t st) {
+template <bool MANY>
+hipError_t launch_scan_m(Profile pr, uint32_t ns, const HamParams& H, const ScanParams& SP, const HamMany& M, uint32_t grid, uint32_t threads,
+                         size_t smem, hipStream_t st) {
   switch (pr) {
-    case PROFILE_DNA: return launch_scan_p<(int)PROFILE_DNA, 4>(H, SP, grid, threads, smem, st);
-    case PROFILE_IUPAC: return launch_scan_p<(int)PROFILE_IUPAC, 16>(H, SP, grid, threads, smem, st);
+    case PROFILE_DNA: return launch_scan_p<(int)PROFILE_DNA, 4, MANY>(H, SP, M, grid, threads, smem, st);
+    case PROFILE_IUPAC: return launch_scan_p<(int)PROFILE_IUPAC, 16, MANY>(H, SP, M, grid, threads, smem, st);
     case PROFILE_ASCII_CI:
-      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII_CI, 16>(H, SP, grid, threads, smem, st)
-                      : launch_scan_p<(int)PROFILE_ASCII_CI, 64>(H, SP, grid, threads, smem, st);
+      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII_CI, 16, MANY>(H, SP, M, grid, threads, smem, st)
+                      : launch_scan_p<(int)PROFILE_ASCII_CI, 64, MANY>(H, SP, M, grid, threads, smem, st);
     default:
-      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII, 16>(H, SP, grid, threads, smem, st)
-                      : launch_scan_p<(int)PROFILE_ASCII, 64>(H, SP, grid, threads, smem, st);
+      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII, 16, MANY>(H, SP, M, grid, threads, smem, st)
+                      : launch_scan_p<(int)PROFILE_ASCII, 64, MANY>(H, SP, M, grid, threads, smem, st);
   }
+}
+
+// many == nullptr: one text
+hipError_t launch_scan(Profile pr, uint32_t ns, const HamParams& H, const ScanParams& SP, const HamMany* many, uint32_t grid, uint32_t threads,
+                       size_t smem, hipStream_t st) {
+  return many ? launch_scan_m<true>(pr, ns, H, SP, *many, grid, threads, smem, st)
+              : launch_scan_m<false>(pr, ns, H, SP, HamMany{}, grid, threads, smem, st);
 }
 
 // One pattern of the call on one strand, as it is scanned.
@@ -267,11 +325,20 @@ uint32_t slot_byte(Profile pr, uint8_t c) {  // what a pattern byte's slot is ke
   return pr == PROFILE_ASCII_CI ? fold_ascii(c) : c;
 }
 
+// A laid-out batch of texts on the device (hamming_many_on_device): d_text is the whole buffer, n its size.
+struct HamTexts {
+  HamMany dev;
+  uint64_t text0;    // index of the batch's first text in the call
+  uint64_t longest;  // the batch's longest text
+};
+
 }  // namespace
 
-// The search proper: refusals are the caller's; d_text is readable up to the next multiple of 64 bytes.
-int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
-                      const uint8_t* d_text, uint64_t n, uint32_t k, bool without_trace, sassy_hip_Result* R) {
+// The search proper: refusals are the caller's; d_text is readable up to the next multiple of 64 bytes.  many != nullptr:
+// d_text is a batch of texts; with many->dev.cells the launches reduce into the cells and R stays as it is.
+static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                             const uint8_t* d_text, uint64_t n, uint32_t k, bool without_trace, sassy_hip_Result* R,
+                             const HamTexts* many = nullptr) {
   const Profile pr = S->profile;
   hipStream_t st = S->stream;
   ScanLane& L = S->lanes[0];
@@ -290,7 +357,7 @@ int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, con
       if (c < 0) continue;  // not even a span without N passes: the pattern has no hits
       if (c < (int64_t)m) nmax = (uint32_t)c;
     }
-    if (n < m) continue;
+    if ((many ? many->longest : n) < m) continue;
     all.push_back(HamPattern{(uint32_t)i, 0, std::vector<uint8_t>(patterns[i], patterns[i] + m), nmax});
     if (S->rc) {
       HamPattern rc{(uint32_t)i, 1, {}, nmax};
@@ -371,6 +438,27 @@ int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, con
     const uint64_t max_cap = items_sw > 0 ? item_cap : std::max<uint64_t>(min_cap, 1u << 22);
     const uint64_t rec_cap = records_sw > 0 ? (uint64_t)records_sw : (1u << 20);
     const uint64_t span_max = std::max<uint64_t>(1, (0x7FFFFFFFull / kHamTileBlocks) / np);  // the counter cannot wrap
+    if (many && many->dev.cells) {  // best pattern: nothing is listed, one launch takes every tile
+      HamParams H{};
+      H.text = d_text; H.n = n; H.n_blocks = n_blocks; H.tile0 = 0; H.n_tiles = n_tiles;
+      H.k = k; H.n_pat = np; H.halo = halo; H.nb = nb; H.n_filter = n_filter ? 1u : 0u; H.item_cap = 0;
+      H.tab = d_tab; H.rows = d_rows; H.items = nullptr; H.item_count = nullptr;
+      if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
+      const uint32_t grid = (uint32_t)((n_tiles + wpg - 1) / wpg);
+      HIP_TRY(launch_scan(pr, ns, H, SP, &many->dev, grid, wpg * 64, smem, st));
+      if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
+      HIP_TRY(hipStreamSynchronize(st));  // (the next group reuses the pinned upload area)
+      if (timed) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, L.ev_a, L.ev_b) == hipSuccess) S->stats.scan_ms += ms;
+      }
+      S->stats.scan_launches += 1;
+      S->stats.grid = grid;
+      S->stats.blocks += n_blocks;
+      S->stats.text_bytes += n;
+      a0 = a1;
+      continue;
+    }
     uint64_t tile0 = 0, span = std::min(n_tiles, span_max);
     size_t first_row = R->matches.size();
     uint32_t ranges = 0;
@@ -384,7 +472,7 @@ int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, con
       HIP_TRY(hipMemsetAsync(S->d_ham_count.p, 0, 4, st));
       if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
       const uint32_t grid = (uint32_t)((span + wpg - 1) / wpg);
-      HIP_TRY(launch_scan(pr, ns, H, SP, grid, wpg * 64, smem, st));
+      HIP_TRY(launch_scan(pr, ns, H, SP, many ? &many->dev : nullptr, grid, wpg * 64, smem, st));
       if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
       uint32_t count = 0;
       HIP_TRY(hipMemcpyAsync(&count, S->d_ham_count.p, 4, hipMemcpyDeviceToHost, st));
@@ -439,6 +527,7 @@ int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, con
           E.text = d_text; E.items = reinterpret_cast<const HamItem*>(S->d_ham_sorted.p); E.prefix = S->d_ham_prefix.p; E.n_items = count;
           E.first = (uint32_t)r0; E.count = cnt; E.tab = d_tab; E.pats = d_pats; E.profile = (uint32_t)pr; E.str_stride = stride;
           E.out = L.d_trace.p; E.strs = reinterpret_cast<char*>(L.d_str.p);
+          if (many) { E.starts = many->dev.starts; E.n_texts = many->dev.n_texts; E.text0 = many->text0; }
           hipLaunchKernelGGL(ham_emit_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, E);
           HIP_TRY(hipGetLastError());
           rows_h.resize(cnt);
@@ -477,23 +566,82 @@ int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, con
   return 0;
 }
 
-}  // namespace sassy_hip
+// A batch call: the texts in batches of at most `hamming_many_batch` bytes laid out, each text from a multiple of 64 bytes on
+// (an empty text takes no block).  Records into R in the contract's order, or -- cells != nullptr -- per text of the call
+// its best-pattern cell (all ones: no hit), nothing into R.
+static int hamming_many_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                                  const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, uint32_t k, bool without_trace,
+                                  sassy_hip_Result* R, unsigned long long* cells) {
+  hipStream_t st = S->stream;
+  const uint64_t batch_cap = S->sw.hamming_many_batch > 0 ? (uint64_t)S->sw.hamming_many_batch : (1ull << 30);
+  HostTexts ht;
+  uint64_t all_tiles = 0;
+  size_t t0 = 0;
+  while (t0 < n_texts) {
+    size_t t1 = t0;
+    uint64_t total = 0, longest = 0;
+    ht.start.clear(); ht.len.clear();
+    while (t1 < n_texts) {
+      const uint64_t slot = ((uint64_t)text_lens[t1] + 63) / 64 * 64;
+      if (t1 > t0 && total + slot > batch_cap) break;
+      ht.start.push_back(total);
+      ht.len.push_back(text_lens[t1]);
+      longest = std::max<uint64_t>(longest, text_lens[t1]);
+      total += slot;
+      ++t1;
+    }
+    const size_t nt = t1 - t0;
+    if (total == 0 || nt > 0xFFFFFFFFull) {  // (only empty texts: no hits)
+      if (nt > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "Hamming search: more than 2^32 texts in one batch");
+      t0 = t1;
+      continue;
+    }
+    if (int rc = S->reserve_stage(total + 64)) return rc;
+    if (int rc = S->d_text.reserve(total + 64)) return rc;
+    if (int rc = layout_and_upload(S->h_stage, S->d_text.p, texts + t0, text_lens + t0, ht.start.data(), nt, total, (uint8_t)0, st)) return rc;
+    const uint64_t n_blocks = total / 64;
+    if (int rc = S->d_ham_texts.reserve(2 * nt)) return rc;
+    if (int rc = S->d_ham_rem.reserve(n_blocks)) return rc;
+    HIP_TRY(hipMemcpyAsync(S->d_ham_texts.p, ht.start.data(), nt * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S->d_ham_texts.p + nt, ht.len.data(), nt * 8, hipMemcpyHostToDevice, st));
+    if (n_blocks + 255 > 0xFFFFFFFFull * 256ull) return fail(SASSY_HIP_EUNSUPPORTED, "text batch too long for the Hamming search");
+    hipLaunchKernelGGL(ham_rem_kernel, dim3((uint32_t)((n_blocks + 255) / 256)), dim3(256), 0, st, S->d_ham_texts.p, S->d_ham_texts.p + nt,
+                       (uint32_t)nt, n_blocks, S->d_ham_rem.p);
+    HIP_TRY(hipGetLastError());
+    HamTexts B{};
+    B.dev.rem = S->d_ham_rem.p; B.dev.starts = S->d_ham_texts.p; B.dev.n_texts = (uint32_t)nt; B.dev.cells = nullptr;
+    B.text0 = t0; B.longest = longest;
+    if (cells) {
+      if (int rc = S->d_ham_cells.reserve(nt)) return rc;
+      HIP_TRY(hipMemsetAsync(S->d_ham_cells.p, 0xFF, nt * 8, st));
+      B.dev.cells = S->d_ham_cells.p;
+    }
+    if (int rc = hamming_on_device(S, patterns, pattern_lens, n_patterns, S->d_text.p, total, k, without_trace, R, &B)) return rc;
+    if (cells) HIP_TRY(hipMemcpyAsync(cells + t0, S->d_ham_cells.p, nt * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // (the tables of the next batch overwrite this one's)
+    all_tiles += S->stats.chunks;
+    t0 = t1;
+  }
+  S->stats.chunks = all_tiles;
+  S->stats.filtered = 7;
+  S->stats.blocks_per_chunk = kHamTileBlocks;
+  // batches, pattern groups and ranges each came in the contract's order, and all of them ascend in text order: a stable
+  // sort on (pattern, strand) restores it for the call
+  auto by_pattern = [](const sassy_hip_Match& a, const sassy_hip_Match& b) {
+    return a.pattern_idx != b.pattern_idx ? a.pattern_idx < b.pattern_idx : a.strand < b.strand;
+  };
+  if (R && !std::is_sorted(R->matches.begin(), R->matches.end(), by_pattern)) std::stable_sort(R->matches.begin(), R->matches.end(), by_pattern);
+  return 0;
+}
 
-using namespace sassy_hip;
-
-extern "C" {
-
-int sassy_hip_search_hamming(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
-                             const void* text, size_t text_len, size_t k, uint32_t flags, sassy_hip_Result** out) {
-  if (!s || !out || (n_patterns && (!patterns || !pattern_lens)) || (!text && text_len))
-    return fail(SASSY_HIP_EINVAL, "Pointers in search_hamming() must not be null");
-  if (flags & ~(uint32_t)(SASSY_HIP_WITHOUT_TRACE | SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_TEXT_UNCHANGED))
-    return fail(SASSY_HIP_EINVAL, "search_hamming takes SASSY_HIP_WITHOUT_TRACE, _TEXT_ON_DEVICE and _TEXT_UNCHANGED only");
+// What every Hamming entry point refuses, before any device work; `who` names the entry point.
+static int hamming_refusals(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, size_t k,
+                            const char* who) {
   if (!std::isnan(s->alpha) || s->max_overhang >= 0)
     return fail(SASSY_HIP_EUNSUPPORTED, "the Hamming search does not take overhang (alpha): a hit spans the whole pattern");
   if (s->only_best) return fail(SASSY_HIP_EUNSUPPORTED, "the Hamming search reports every hit: only_best_match is not supported");
   if (is_ascii(s->profile) && s->rc) return fail(SASSY_HIP_EUNSUPPORTED, "reverse complement is not defined for the ascii alphabet");
-  if (n_patterns == 0) return fail(SASSY_HIP_EINVAL, "search_hamming needs at least one pattern");
+  if (n_patterns == 0) return fail(SASSY_HIP_EINVAL, std::string(who) + " needs at least one pattern");
   for (size_t i = 0; i < n_patterns; ++i) {
     if (!patterns[i] || pattern_lens[i] == 0) return fail(SASSY_HIP_EINVAL, "empty pattern (pattern " + std::to_string(i) + ")");
     if (!valid_pattern(s->profile, patterns[i], pattern_lens[i])) return fail(SASSY_HIP_EINVAL, "Pattern is not valid IUPAC");
@@ -516,6 +664,78 @@ int sassy_hip_search_hamming(sassy_SearcherType* s, const uint8_t* const* patter
     }
   }
   SASSY_NO_TICKETS(s);
+  return 0;
+}
+
+// both batch entry points: out != nullptr the records, else the per-text outputs
+static int hamming_many(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                        const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags, sassy_hip_Result** out,
+                        uint8_t* out_cost, uint32_t* out_pattern, uint8_t* out_strand, uint64_t* out_start) {
+  const bool best = out == nullptr;
+  const char* who = best ? "hamming_best_pattern" : "search_hamming_many";
+  if (!s || (!out && !out_cost) || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!texts || !text_lens)))
+    return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null");
+  for (size_t t = 0; t < n_texts; ++t)
+    if (!texts[t] && text_lens[t]) return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null (text " + std::to_string(t) + ")");
+  if (flags & ~(uint32_t)(best ? 0u : SASSY_HIP_WITHOUT_TRACE))
+    return fail(SASSY_HIP_EINVAL, best ? "hamming_best_pattern takes no flags (host texts only)"
+                                       : "search_hamming_many takes SASSY_HIP_WITHOUT_TRACE only (host texts only)");
+  if (best && k > 254) return fail(SASSY_HIP_EINVAL, "hamming_best_pattern: k must be <= 254 (costs are bytes, 255 = no match)");
+  if (int rc = hamming_refusals(s, patterns, pattern_lens, n_patterns, k, who)) return rc;
+  if (best) {  // what the device cell cannot hold
+    if (n_patterns >= (1u << 23)) return fail(SASSY_HIP_EUNSUPPORTED, "hamming_best_pattern takes fewer than 2^23 patterns (the cell keeps 2 pattern + strand in 24 bits)");
+    for (size_t t = 0; t < n_texts; ++t)
+      if ((uint64_t)text_lens[t] >= (1ull << 32))
+        return fail(SASSY_HIP_EUNSUPPORTED, "hamming_best_pattern takes texts shorter than 2^32 bytes (text " + std::to_string(t) + ": the cell keeps the start in 32 bits)");
+  }
+  sassy_hip_Result* R = best ? nullptr : new sassy_hip_Result();
+  std::unique_ptr<sassy_hip_Result> owned(R);
+  std::vector<unsigned long long> cells;
+  if (n_texts) {
+    DeviceGuard on_device(s);
+    const double t0 = now_ms();
+    reset_stats(s);
+    if (int rc = s->ensure_device()) return rc;
+    size_t longest = 0;
+    for (size_t i = 0; i < n_patterns; ++i) longest = std::max(longest, pattern_lens[i]);
+    const uint32_t kk = (uint32_t)std::min<size_t>(k, longest);  // k >= m reports every start
+    if (best) cells.assign(n_texts, ~0ull);
+    if (int rc = hamming_many_on_device(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, kk, (flags & SASSY_HIP_WITHOUT_TRACE) != 0,
+                                        R, best ? cells.data() : nullptr)) {
+      (void)hipStreamSynchronize(s->stream);
+      return rc;
+    }
+    s->stats.total_ms = now_ms() - t0;
+  }
+  if (best) {
+    for (size_t t = 0; t < n_texts; ++t) {
+      const unsigned long long c = cells[t];
+      const bool none = c == ~0ull;
+      out_cost[t] = none ? (uint8_t)SASSY_HIP_NO_MATCH : (uint8_t)(c >> 56);
+      if (out_pattern) out_pattern[t] = none ? 0xFFFFFFFFu : (uint32_t)((c >> 33) & 0x7FFFFFu);
+      if (out_strand) out_strand[t] = none ? 0 : (uint8_t)((c >> 32) & 1u);
+      if (out_start) out_start[t] = none ? UINT64_MAX : (uint64_t)(c & 0xFFFFFFFFull);
+    }
+    return 0;
+  }
+  if (R->pool.empty()) R->pool.push_back('\0');
+  *out = owned.release();
+  return 0;
+}
+
+}  // namespace sassy_hip
+
+using namespace sassy_hip;
+
+extern "C" {
+
+int sassy_hip_search_hamming(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                             const void* text, size_t text_len, size_t k, uint32_t flags, sassy_hip_Result** out) {
+  if (!s || !out || (n_patterns && (!patterns || !pattern_lens)) || (!text && text_len))
+    return fail(SASSY_HIP_EINVAL, "Pointers in search_hamming() must not be null");
+  if (flags & ~(uint32_t)(SASSY_HIP_WITHOUT_TRACE | SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_TEXT_UNCHANGED))
+    return fail(SASSY_HIP_EINVAL, "search_hamming takes SASSY_HIP_WITHOUT_TRACE, _TEXT_ON_DEVICE and _TEXT_UNCHANGED only");
+  if (int rc = hamming_refusals(s, patterns, pattern_lens, n_patterns, k, "search_hamming")) return rc;
   DeviceGuard on_device(s);
   const double t0 = now_ms();
   reset_stats(s);
@@ -541,6 +761,22 @@ int sassy_hip_search_hamming(sassy_SearcherType* s, const uint8_t* const* patter
   s->stats.total_ms = now_ms() - t0;
   *out = R;
   return 0;
+}
+
+int sassy_hip_search_hamming_many(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                                  const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
+                                  sassy_hip_Result** out) {
+  if (!out) return fail(SASSY_HIP_EINVAL, "Pointers in search_hamming_many() must not be null");
+  return hamming_many(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, out, nullptr, nullptr, nullptr, nullptr);
+}
+
+int sassy_hip_hamming_best_pattern(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                                   const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
+                                   uint8_t* out_cost, uint32_t* out_pattern, uint8_t* out_strand, uint64_t* out_start) {
+  if (!out_cost && n_texts) return fail(SASSY_HIP_EINVAL, "Pointers in hamming_best_pattern() must not be null");
+  uint8_t none = 0;
+  return hamming_many(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, nullptr, out_cost ? out_cost : &none,
+                      out_pattern, out_strand, out_start);
 }
 
 }  // extern "C"

@@ -82,9 +82,9 @@ struct HamCounter {
 //   row_word(w)     the slots of rows 4w .. 4w + 3, one byte each, row 4w in the low byte
 //   all_over(over)  may the loop stop: true only if no start of any block that shares this loop can still pass
 //                   (one block: over == ~0; a wavefront: a vote over its lanes)
+//   cnt             the counter planes as the loop leaves them (stopped early: over == ~0 in every block of the loop)
 template <int P, bool INVERT, typename Fetch, typename RowWord, typename AllOver>
-SASSY_HAM_HD uint64_t ham_hit_mask(const Fetch& fetch, const RowWord& row_word, uint32_t m, uint32_t k, const AllOver& all_over) {
-  HamCounter<P> cnt;
+SASSY_HAM_HD void ham_count(const Fetch& fetch, const RowWord& row_word, uint32_t m, const AllOver& all_over, HamCounter<P>& cnt) {
   cnt.clear();
   const uint32_t nw = (m + 3) / 4;
   for (uint32_t w = 0; w < nw; ++w) {
@@ -102,7 +102,31 @@ SASSY_HAM_HD uint64_t ham_hit_mask(const Fetch& fetch, const RowWord& row_word, 
     }
     if (all_over(cnt.over)) break;
   }
+}
+template <int P, bool INVERT, typename Fetch, typename RowWord, typename AllOver>
+SASSY_HAM_HD uint64_t ham_hit_mask(const Fetch& fetch, const RowWord& row_word, uint32_t m, uint32_t k, const AllOver& all_over) {
+  HamCounter<P> cnt;
+  ham_count<P, INVERT>(fetch, row_word, m, all_over, cnt);
   return cnt.le(k);
+}
+
+// The smallest count among the starts of `hit` (a subset of the starts whose count did not saturate) and, in *at, the starts
+// that attain it: the planes narrow the candidates from the top -- where some candidate has a 0 in plane p, the minimum has,
+// and only those stay.  P steps, no count is extracted per start.  hit == 0 (after ~over): 0xFFFFFFFF, *at = 0.
+template <int P>
+SASSY_HAM_HD uint32_t ham_min_cost(const HamCounter<P>& cnt, uint64_t hit, uint64_t* at) {
+  uint64_t cand = hit & ~cnt.over;
+  *at = cand;
+  if (cand == 0) return 0xFFFFFFFFu;
+  uint32_t cost = 0;
+#pragma unroll
+  for (int p = P - 1; p >= 0; --p) {
+    const uint64_t t = cand & ~cnt.c[p];
+    if (t) cand = t;
+    else cost |= 1u << p;
+  }
+  *at = cand;
+  return cost;
 }
 
 // starts of block b that lie in the text: 64 b + i + m <= n.  By position -- no byte value excludes a start.
@@ -112,6 +136,35 @@ SASSY_HAM_HD uint64_t ham_valid_mask(uint64_t block, uint64_t n, uint32_t m) {
   if (s0 > last) return 0;
   if (last - s0 >= 63) return ~(uint64_t)0;
   return ((uint64_t)2 << (last - s0)) - 1;
+}
+
+// ---- a batch of texts in one buffer, each from a multiple of 64 bytes on (search_hamming_many) ----
+// bytes from the first byte of block `block` to the end of the text [start, start + len) it lies in, saturated
+SASSY_HAM_HD uint32_t ham_rem(uint64_t block, uint64_t start, uint64_t len) {
+  const uint64_t end = start + len, s0 = block * 64;
+  if (end <= s0) return 0;
+  return end - s0 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(end - s0);
+}
+// starts of a block that lie in the block's own text: i + m <= rem.  By position, as ham_valid_mask: the halo blocks may hold
+// the next text, and a start whose window reaches them is dropped whatever they hold.
+SASSY_HAM_HD uint64_t ham_valid_mask_rem(uint32_t rem, uint32_t m) {
+  if (rem < m) return 0;
+  const uint32_t last = rem - m;
+  if (last >= 63) return ~(uint64_t)0;
+  return ((uint64_t)2 << last) - 1;
+}
+// The text that byte `pos` of the buffer lies in: the last t < n_texts with start(t) <= pos (start ascends, start(0) == 0).  An
+// empty text takes no block and shares its start with the text behind it, so the last of a run of equal starts is the one
+// that owns the bytes; empty texts at the buffer's end start at its size, behind every block.
+template <typename Start>
+SASSY_HAM_HD uint32_t ham_text_of(const Start& start, uint32_t n_texts, uint64_t pos) {
+  uint32_t lo = 0, hi = n_texts;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (start(mid) <= pos) lo = mid;
+    else hi = mid;
+  }
+  return lo;
 }
 
 // ---- the relation, per byte (the emit kernel; profiles.h: scan_eq) ----

@@ -59,7 +59,8 @@ namespace sassy_hip {
   X(best_match_device, 1, "best_matches: 0: never the device path (locating reduction of the scan's list, one traceback per text); search_many's records reduced by the host") \
   X(hamming_items, 0, "search_hamming: > 0: the item list holds exactly this many 16-byte items (at least one tile's worth) and never grows -- a text range whose items overflow it is cut down and launched again (0: 65536, grown up to 4 Mi items before ranges are cut)") \
   X(hamming_records, 0, "search_hamming: > 0: records are emitted at most this many per launch of the emit kernel (0: 1 Mi)") \
-  X(hamming_batch, 0, "search_hamming: > 0: at most this many scanned patterns (a strand counts as one) share a launch of the scan kernel (0: 512)")
+  X(hamming_batch, 0, "search_hamming: > 0: at most this many scanned patterns (a strand counts as one) share a launch of the scan kernel (0: 512)") \
+  X(hamming_many_batch, 0, "search_hamming_many / hamming_best_pattern: > 0: a batch of texts is at most this many bytes laid out (each text from a multiple of 64 on; a longer text is a batch of its own) (0: 1 GiB)")
 
 struct Switches {
 #define SASSY_HIP_SWITCH_FIELD(name, dflt, doc) long name = (dflt);
