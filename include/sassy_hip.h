@@ -109,6 +109,8 @@ typedef struct sassy_hip_Stats {
                              rows (one half exact, the other half with <= 1 edit next to it; SASSY_HIP_PAIR=0: never) */
   uint32_t pass_patterns; /* the largest number of searches a launch of this search's text pass served: 2 when a search
                              in flight shared one of them (sassy_hip_search_shard_begin), else 1 */
+  uint32_t plane_launches; /* how many of the launches that served this search's text pass read the text's kept code
+                              planes instead of the text (searches in flight, switch plane_cache); 0 for a lone search */
 } sassy_hip_Stats;
 
 const char *sassy_hip_last_error(void);
@@ -446,7 +448,19 @@ uint64_t sassy_hip_required_halo(size_t pattern_len, size_t k);
  * streaming is launched whole; a search that cannot share is begun behind what the open ones still need; finish
  * launches what its own ticket still needs -- no ticket waits on a launch that only a later call would make.
  * Results are unchanged; SASSY_HIP_SHARED_PASS=0
- * (sassy_hip_set_option "shared_pass") turns it off.  The calls of
+ * (sassy_hip_set_option "shared_pass") turns it off.
+ * Kept code planes.  Because the text may not change while a ticket is open, what a pass derives from the text alone --
+ * the two code bit planes of every 64-byte block, 16 bytes -- is kept across such searches: the first launch over a half
+ * of the grid stores them, the launches behind it read them instead of the text (sassy_hip_Stats.plane_launches).  The
+ * planes live exactly as long as the searcher has had at least one ticket open without a break: when the last open ticket
+ * is finished they are forgotten, and the caller may rewrite the buffer as before; the flag SASSY_HIP_TEXT_UNCHANGED
+ * does not extend that.  Only tickets of one buffer and geometry use them at a time; a ticket over another buffer
+ * or shard in between reads its text as ever.  The store costs a quarter of the text (0.76 GB of device memory for 3 GB),
+ * is allocated per searcher at the first launch that can use it, reused while it is large enough and freed with the
+ * searcher; if it cannot be allocated, or is larger than the switch plane_cache_max_mb allows, nothing is kept.
+ * Planes are written only where a reader can follow: a search begun and finished with nothing else in flight takes its
+ * own launch, and no store is made for it.
+ * SASSY_HIP_PLANE_CACHE=0 (sassy_hip_set_option "plane_cache") turns it off.  The calls of
  * one searcher must still come from one thread at a time.  sassy_hip_get_stats describes the search finished last.
  * While a ticket is open the searcher's synchronous entry points (sassy_hip_search, _search_shard, _search_many,
  * _search_encoded, _search_with_fn, the drop-in search) and sassy_hip_set_stream fail with SASSY_HIP_EINVAL: they

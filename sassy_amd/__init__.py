@@ -112,6 +112,7 @@ class Stats(C.Structure):
         ("live_blocks", C.c_uint64),
         ("pair", C.c_uint32),
         ("pass_patterns", C.c_uint32),
+        ("plane_launches", C.c_uint32),
     ]
 
     def as_dict(self):

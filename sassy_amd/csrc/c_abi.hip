@@ -610,16 +610,73 @@ static PassSlot* take_pass_slot(sassy_SearcherType* s, int users) {
   return nullptr;
 }
 
-// queues one launch of the planner: a whole launch of a ticket on its own is the search's plain chain (ScanJob::enqueue);
-// everything else is head (at the ticket's first launch), the launch over the range, and the tail of every member that
-// needs nothing more
+// ---- kept code planes (plane_cache.h; switches plane_cache, plane_cache_max_mb) ----
+// A launch can take its planes from the store when the searcher keeps several searches in flight and all its members are
+// on the path the grouped pass serves (ScanJob::group_ok) and index the store by the whole grid.
+static bool plane_eligible(const sassy_SearcherType* s, const ScanJob* j) {
+  return s->sw.plane_cache != 0 && s->pipe_depth > 1 && j->group_ok() && j->F.group_offset == 0;
+}
+static PlaneKey plane_key(const ScanJob* j) {
+  PlaneKey k;
+  k.text = j->F.text;
+  k.text_len = j->F.text_len;
+  k.n_blocks = j->F.n_blocks;
+  k.first_owned_block = j->F.first_owned_block;
+  k.n_chunks = j->F.n_chunks;
+  k.bpl = j->F.bpl;
+  k.n_iter = j->F.n_iter;
+  k.fgrid = j->fgrid;
+  k.flags = j->F.flags;
+  return k;
+}
+// the store holds `bytes`: as it is, or allocated now (only while nothing is written and so nothing reads it).  A store
+// beyond the cap is not made; an allocation that fails is no error -- the pass reads the text as ever.
+static bool plane_store_fits(sassy_SearcherType* s, uint64_t bytes) {
+  if (bytes == 0) return false;
+  if (s->sw.plane_cache_max_mb > 0 && bytes > ((uint64_t)s->sw.plane_cache_max_mb << 20)) return false;
+  if (bytes <= s->plane_store_bytes) return true;
+  if (s->plane_store) (void)hipFree(s->plane_store);
+  s->plane_store = nullptr;
+  s->plane_store_bytes = 0;
+  if (hipMalloc(reinterpret_cast<void**>(&s->plane_store), bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    s->plane_store = nullptr;
+    return false;
+  }
+  s->plane_store_bytes = bytes;
+  return true;
+}
+
+// queues one launch of the planner: a whole launch of a ticket on its own is the search's plain chain (ScanJob::enqueue)
+// unless it writes or reads kept planes; everything else is head (at the ticket's first launch), the launch over the
+// range, and the tail of every member that needs nothing more
 static int run_pass_launch(sassy_SearcherType* s, const PassLaunch& pl) {
   sassy_hip_Ticket* ta = s->lane_ticket[pl.leader];
   sassy_hip_Ticket* tb = pl.member >= 0 ? s->lane_ticket[pl.member] : nullptr;
   ScanJob* a = ticket_job(ta);
   ScanJob* b = tb ? ticket_job(tb) : nullptr;
   int rc = 0;
-  if (!b && pl.range == kPassWhole && !ta->head_done) {
+  // where the launch's planes come from: asked with the slot the launch would carry
+  PassSlot* slot = nullptr;
+  ScanJob::KeptPlanes kept;
+  if (plane_eligible(s, a) && (!b || plane_eligible(s, b))) {
+    slot = take_pass_slot(s, b ? 2 : 1);
+    if (slot) {
+      const PlaneKey key = plane_key(a);
+      // planes are written only where a reader can follow: a second ticket is open, the launch has a second member, or it
+      // is a half whose other half waits for the next begin.  A search with nothing else in flight keeps its own launch.
+      const bool may_write = s->planes.open_tickets() >= 2 || b != nullptr || pl.range != kPassWhole;
+      const bool store_ok = s->planes.wants_store(may_write) ? plane_store_fits(s, key.store_bytes()) : s->plane_store != nullptr;
+      const PlaneUse use = s->planes.launch(key, pl.range, (int)(slot - s->pass_slots), may_write, store_ok);
+      kept.source = use.source;
+      kept.store = s->plane_store;
+      kept.store_bytes = s->plane_store_bytes;
+      for (int i = 0; i < 2; ++i)
+        if (use.wait[i] >= 0) kept.wait[i] = s->pass_slots[use.wait[i]].ev_done;
+    }
+  }
+  if (!b && pl.range == kPassWhole && !ta->head_done && kept.source == kPlaneRaw) {
+    if (slot) slot->users = 0;
     rc = a->enqueue(0);
     s->last_pass_event = s->lanes[ta->lane].ev_filter_done;
   } else {
@@ -630,12 +687,13 @@ static int run_pass_launch(sassy_SearcherType* s, const PassLaunch& pl) {
         rc = ticket_job(t)->enqueue_head(0, true);
         t->head_done = true;
       }
-    PassSlot* slot = rc == 0 ? take_pass_slot(s, b ? 2 : 1) : nullptr;
+    if (rc == 0 && !slot) slot = take_pass_slot(s, b ? 2 : 1);
     if (rc == 0 && !slot) rc = fail(SASSY_HIP_ENOMEM, "shared pass: no free launch slot");
+    if (rc != 0 && slot) slot->users = 0;
     if (rc == 0) {
       ta->slots.push_back(slot);
       if (tb) tb->slots.push_back(slot);
-      rc = a->enqueue_pass(b, g0, g1, *slot);
+      rc = a->enqueue_pass(b, g0, g1, *slot, &kept);
       s->last_pass_event = slot->ev_done;
     }
     for (sassy_hip_Ticket* t : {ta, tb})
@@ -644,8 +702,10 @@ static int run_pass_launch(sassy_SearcherType* s, const PassLaunch& pl) {
   for (sassy_hip_Ticket* t : {ta, tb})
     if (t) {
       t->pass_patterns = std::max<uint32_t>(t->pass_patterns, b ? 2u : 1u);
+      if (rc == 0 && kept.source == kPlaneRead) t->plane_launches += 1;
       if (rc != 0) t->launch_rc = rc;
     }
+  if (rc != 0) s->planes.drop_all();  // (a launch error drops everything)
   if (rc != 0)
     for (sassy_hip_Ticket* t : {ta, tb})
       if (t) (void)hipStreamSynchronize(s->lanes[t->lane].stream);
@@ -726,12 +786,15 @@ int sassy_hip_search_shard_begin(sassy_SearcherType* s, const uint8_t* pattern, 
   const bool groupable = has_pass && s->sw.shared_pass != 0 && depth > 1 && ticket_job(t.get())->group_ok();
   const bool splittable = groupable && ticket_job(t.get())->fgrid >= 2;
   s->lane_ticket[lane] = t.get();
+  s->planes.ticket_opened();
   std::vector<PassLaunch> launches;
   s->planner.begin(lane, groupable, splittable, has_pass, groupable && pass_streaming(s), (int)s->sw.shared_pass, tickets_fit, s, launches);
   if (int rc = run_pass_launches(s, launches)) {
     s->planner.drop(lane);
     for (PassSlot* ps : t->slots) ps->users -= 1;
     s->lane_ticket[lane] = nullptr;
+    s->planes.drop_all();
+    s->planes.ticket_closed();
     (void)hipStreamSynchronize(s->lanes[lane].stream);
     return rc;
   }
@@ -758,14 +821,27 @@ int sassy_hip_search_finish(sassy_SearcherType* s, sassy_hip_Ticket* t, sassy_hi
   for (PassSlot* ps : t->slots) ps->users -= 1;  // (read by ScanJob::finish below: nobody takes a slot before this call returns)
   s->lane_ticket[t->lane] = nullptr;
   reset_stats(s);
+  // kept planes: the ticket leaves when this call returns (the last one takes the planes with it); a failure drops them all
+  struct PlanesLeave {
+    sassy_SearcherType* s;
+    bool ok = false;
+    ~PlanesLeave() {
+      if (!ok) s->planes.drop_all();
+      s->planes.ticket_closed();
+    }
+  } leave{s};
   if (t->launch_rc != 0) return t->launch_rc;
   if (lrc != 0) return lrc;
   s->stats.pass_patterns = t->pass_patterns;
+  s->stats.plane_launches = t->plane_launches;
   std::unique_ptr<sassy_hip_Result> R(new sassy_hip_Result());
   if (t->job) {
     ScanJob* job = static_cast<ScanJob*>(t->job.get());
     ScanOut so;
     if (int rc = job->finish(so)) return rc;
+    // (the host has waited for this search, and this search's tail for every launch that served it: what they wrote is
+    // read without a wait from now on)
+    for (PassSlot* ps : t->slots) s->planes.slot_done((int)(ps - s->pass_slots));
     if (out) {
       size_t first = 0;
       if (int rc = append_matches(so, t->total_len, t->plan, t->without_trace, 0, R.get(), first)) return rc;
@@ -777,6 +853,7 @@ int sassy_hip_search_finish(sassy_SearcherType* s, sassy_hip_Ticket* t, sassy_hi
   s->stats.total_ms = now_ms() - t->t0;
   s->stats.host_post_ms = std::max(0.0, s->stats.total_ms - s->stats.host_enqueue_ms - s->stats.host_wait_ms);
   if (out) *out = R.release();
+  leave.ok = true;
   return 0;
 }
 

@@ -3,6 +3,8 @@
 #include <atomic>
 #include <cstdint>
 
+#include "plane_cache.h"  // (kPlaneRaw / kPlaneWrite / kPlaneRead)
+
 namespace sassy_hip {
 
 // PROFILE_ASCII_CI: Ascii where A-Z and a-z fold onto each other (the reference's Ascii<false>::is_match,
@@ -242,6 +244,9 @@ struct ScanParams {
   } member1;
   uint32_t piece_member;
   const uint32_t* class_tab;  // PROFILE_CLASSES: device, kClassTabWords words (read through scalar loads)
+  // ---- kept code planes (filter_dna_kernel<.., SRC>; plane_cache.h) ----
+  uint4* plane_store;         // device: {t0.x, t0.y, t1.x, t1.y} per [workgroup of the whole grid][wave 0..3][iteration 0..n_iter)
+                              // [lane 0..63] -- fgrid * 4 * n_iter KiB; written by kPlaneWrite launches, read by kPlaneRead ones
 };
 constexpr uint32_t kFuseGroupMaxWords = 4;  // grouped pass: pattern words per member (the carries leave the tile's upper half free)
 

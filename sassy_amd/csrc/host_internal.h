@@ -43,6 +43,8 @@ hipError_t launch_scan_ascii_ci(const ScanParams& P, uint32_t grid, size_t smem,
 hipError_t launch_scan_classes(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);  // (PROFILE_CLASSES)
 hipError_t launch_filter_dna(const ScanParams& P, uint32_t grid, size_t smem, hipStream_t stream);
 hipError_t launch_filter_group(const ScanParams& P, uint32_t grid, hipStream_t stream);  // (two searches, one pass)
+// (one or two searches on kept code planes: src = kPlaneWrite / kPlaneRead)
+hipError_t launch_filter_kept(const ScanParams& P, uint32_t grid, uint32_t members, uint32_t src, hipStream_t stream);
 hipError_t launch_filter_table(const ScanParams& P, uint32_t grid, hipStream_t stream);
 hipError_t launch_filter_dna_multi(const ScanParams& P, uint32_t grid, hipStream_t stream);
 hipError_t launch_filter_count(const ScanParams& P, uint32_t grid, hipStream_t stream);
@@ -299,6 +301,7 @@ struct sassy_hip_Ticket {
   // shared pass (c_abi.hip): the largest member count among the launches that served it; what a launch made for it after
   // its begin returned; the launches' event slots it holds until it is finished
   uint32_t pass_patterns = 1;
+  uint32_t plane_launches = 0;  // launches of its pass that read kept code planes (plane_cache.h)
   int launch_rc = 0;
   bool head_done = false;  // ScanJob::enqueue_head ran (a ticket served by range launches)
   std::vector<struct PassSlot*> slots;
@@ -631,6 +634,11 @@ struct sassy_SearcherType {
   sassy_hip::PassPlanner planner;
   PassSlot pass_slots[kPassSlots];
   hipEvent_t last_pass_event = nullptr;
+  // kept code planes (switch plane_cache; plane_cache.h): what is written and may be read, and the store itself --
+  // allocated at the first launch that can use it, reused while the size fits, freed with the searcher
+  sassy_hip::PlaneCache planes;
+  uint4* plane_store = nullptr;
+  uint64_t plane_store_bytes = 0;
   // reporting modes of the reference's Searcher (src/search.rs:442-475)
   float alpha = NAN;             // overhang cost per pattern character (NaN = no overhang), Iupac only
   long max_overhang = -1;        // with_max_overhang(): -1 = none
@@ -699,6 +707,7 @@ struct sassy_SearcherType {
       for (hipEvent_t e : {ps.ev_start, ps.ev_stop, ps.ev_done})
         if (e) (void)hipEventDestroy(e);
     for (sassy_hip_Ticket*& t : lane_ticket) { delete t; t = nullptr; }
+    if (plane_store) (void)hipFree(plane_store);
     d_text.release(); d_rev.release(); d_rc_bitmap.release();
     free_stage();
     d_line_tiles.release(); d_line_prefix.release(); d_line_pos.release(); d_line_out.release();
@@ -935,7 +944,14 @@ struct ScanJob {
   int enqueue_tail(int attempt);
   // the fused filter over the workgroups [g0, g1) for this job alone (the G = 1 launch) or with `other` (the G = 2
   // launch) on this job's lane; slot: the launch's events
-  int enqueue_pass(ScanJob* other, uint32_t g0, uint32_t g1, PassSlot& slot);
+  // (kept: where the launch's code planes come from -- the searcher's store, behind the events in kept->wait)
+  struct KeptPlanes {
+    int source = kPlaneRaw;
+    uint4* store = nullptr;
+    uint64_t store_bytes = 0;
+    hipEvent_t wait[2] = {nullptr, nullptr};
+  };
+  int enqueue_pass(ScanJob* other, uint32_t g0, uint32_t g1, PassSlot& slot, const KeptPlanes* kept = nullptr);
   int finish(ScanOut& out);
   int finish_once(ScanOut& out, bool& redo);
 };

@@ -656,10 +656,28 @@ int ScanJob::enqueue_tail(int attempt) {
 // this job (member 0: F) and `other` (member 1: its pieces, pattern rows and report arrays), on this job's lane.  The
 // workgroups are independent (each wave owns its lane chunks, its LDS queues and its reports; the control block takes
 // atomics only), so the launches that serve a job may run in any order and side by side.
-int ScanJob::enqueue_pass(ScanJob* other, uint32_t g0, uint32_t g1, PassSlot& slot) {
+int ScanJob::enqueue_pass(ScanJob* other, uint32_t g0, uint32_t g1, PassSlot& slot, const KeptPlanes* kept) {
   if (g0 >= g1 || g1 > fgrid) return fail(SASSY_HIP_EINVAL, "shared pass: workgroup range outside the grid");
   ScanParams GP = F;
   GP.group_offset = F.group_offset + g0;
+  const int src = kept ? kept->source : (int)kPlaneRaw;
+  if (src != kPlaneRaw) {
+    // every index the launch's workgroups [g0, g1) form -- [workgroup][wave][iteration][lane] x 16 bytes -- lies in the store
+    if (!kept->store || F.group_offset != 0 || (uint64_t)g1 * kWavesPerGroup * F.n_iter * 1024u > kept->store_bytes)
+      return fail(SASSY_HIP_EINVAL, "shared pass: the plane store does not cover the launch");
+    GP.plane_store = kept->store;
+    if (!other) {  // (the kept-plane kernels have eight piece slots: the slots behind the search's pieces repeat its first)
+      for (uint32_t pp = F.n_pieces; pp < 8; ++pp) {
+        GP.piece_bits[pp][0] = F.piece_bits[0][0];
+        GP.piece_bits[pp][1] = F.piece_bits[0][1];
+        GP.piece_rem[pp] = F.piece_rem[0];
+      }
+      GP.piece_member = 0;
+      GP.piece_groups = 2;
+    }
+    for (hipEvent_t e : kept->wait)  // (a reader: behind the launch that wrote its half)
+      if (e) HIP_TRY(hipStreamWaitEvent(L.stream, e, 0));
+  }
   if (other) {
     const ScanJob& B = *other;
     // The tile and both members' queues and counts, WITHOUT the pipelining pad of prepare(): 4 x (8192 + 2 x 1552) =
@@ -686,8 +704,9 @@ int ScanJob::enqueue_pass(ScanJob* other, uint32_t g0, uint32_t g1, PassSlot& sl
   slot.lane = &L;
   slot.timed = timing >= 1 || (other && other->timing >= 1);
   if (slot.timed) g_launch_events = LaunchEvents{slot.ev_start, slot.ev_stop};
-  const hipError_t le = other ? launch_filter_group(GP, g1 - g0, L.stream)
-                              : launch_filter_any(S->profile, GP, g1 - g0, 1024 + (size_t)kWavesPerGroup * GP.lds_per_wave, L.stream);
+  const hipError_t le = src != kPlaneRaw ? launch_filter_kept(GP, g1 - g0, other ? 2u : 1u, (uint32_t)src, L.stream)
+                        : other          ? launch_filter_group(GP, g1 - g0, L.stream)
+                                         : launch_filter_any(S->profile, GP, g1 - g0, 1024 + (size_t)kWavesPerGroup * GP.lds_per_wave, L.stream);
   g_launch_events = LaunchEvents{};
   if (le != hipSuccess) return hip_fail(le, other ? "shared fused filter kernel launch" : "fused filter kernel launch");
   HIP_TRY(hipEventRecord(slot.ev_done, L.stream));

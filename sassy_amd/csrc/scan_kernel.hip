@@ -1702,12 +1702,22 @@ __device__ __forceinline__ bool other_letters16(const uint4 v) { return other_le
 // own run in registers, and its own control block: fuse word, statistics, reports -- a member whose reports need the
 // classic chain sends only itself there.  (Both members at most kFuseGroupMaxWords pattern words: their carries then end
 // at 4 KiB, and the segment state of both runs waits in the tile's upper half.)
-template <int Q, int NPG, bool FUSED, bool CHECK = false, bool PAIR = false, int DPNS = 4, int G = 1>
+// SRC (fused, NPG = 2, neither CHECK nor PAIR): where a block's two code planes come from.  They depend on the text alone,
+// and in a stream of searches over one resident text every pass derives the same ones (plane_cache.h says when they may be
+// kept).  kPlaneRaw: from the text, as above.  kPlaneWrite: the same, and every lane also stores {t0, t1} of every block of
+// its iterations into ScanParams::plane_store, indexed by the kernel's own iteration space [workgroup of the whole grid]
+// [wave][iteration][lane] -- one 16-byte vector store, 1 KiB contiguous per wave and iteration.  kPlaneRead: no staging,
+// no tile reads, no bit_plane: the lane loads its 16 bytes back (a few iterations ahead, in registers) and goes on from
+// b0 / b1 as ever; the tile is only the chunk DP's.  A reader sees what the writer computed, tail bytes included, so
+// `interior` plays no part; a wave with nothing to do neither writes nor reads.
+template <int Q, int NPG, bool FUSED, bool CHECK = false, bool PAIR = false, int DPNS = 4, int G = 1, int SRC = kPlaneRaw>
 // (CHECK: four waves per SIMD are asked for -- left to itself the compiler settles for three, 0.59 instead of 0.52 ms)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || PAIR) ? 4 : 1))) void filter_dna_kernel(const ScanParams P) {
   static_assert(!CHECK || FUSED, "the text check exists in the fused launch only");
   static_assert(!PAIR || (FUSED && 2 * Q + 2 <= 31), "the paired filter exists in the fused launch only; its look-back stays inside one plane half");
   static_assert(G == 1 || (G == 2 && FUSED && !CHECK && !PAIR && NPG == 2), "the grouped pass: two members, fused Dna bit planes, eight piece slots");
+  static_assert(SRC == kPlaneRaw || (FUSED && !CHECK && !PAIR && NPG == 2), "kept planes: the fused Dna launch with eight piece slots");
+  constexpr int kPlaneAhead = 4;  // kPlaneRead: iterations a lane's plane loads run ahead (even)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int SB = 2;
   constexpr uint32_t kRowBytes = 64u * SB;
@@ -1797,6 +1807,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   const uint64_t wave_last = chunk_blk0(u_first, u_bpl, back, lc0 + 63) + n_iter + 2;
   const bool interior = wave_last * 64 <= Pk->text_len;
   uint32_t prev0 = 0, prev1 = 0;  // high halves of the previous block's planes
+  // (SRC) the wave's first iteration in the plane store (wave-uniform: a scalar base, the lane's 16 bytes as the offset)
+  const uint8_t* plane_base = nullptr;
+  if constexpr (SRC != kPlaneRaw)
+    plane_base = reinterpret_cast<const uint8_t*>(Pk->plane_store) + (group * 4u + wave) * (uint64_t)Pk->n_iter * 1024u;
 
   // FUSED: the run of match-end columns this lane is collecting, and the end of the last window it queued
   rep4 run = make_rep4(kRunNone, 0u, 0u, 0u);
@@ -1813,10 +1827,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
 
   // software pipeline: the loads of the next staging step are in flight while this one is processed
   uint4 nxt[kStageInstr];
+  uint4 pln[kPlaneAhead + 2];  // (kPlaneRead) [0], [1]: the block pair at work; behind them the planes on their way
 #pragma unroll
   for (int i = 0; i < kStageInstr; ++i) {
     nxt[i] = make_uint4(0u, 0u, 0u, 0u);
-    if (interior && seg_it < n_iter) nxt[i] = stream_load16<SASSY_NT_DNA>(text_base + (uint64_t)seg_it * 64 + soff[i]);
+    if constexpr (SRC != kPlaneRead)
+      if (interior && seg_it < n_iter) nxt[i] = stream_load16<SASSY_NT_DNA>(text_base + (uint64_t)seg_it * 64 + soff[i]);
+  }
+  if constexpr (SRC == kPlaneRead) {
+#pragma unroll
+    for (int j = 0; j < kPlaneAhead + 2; ++j) {
+      pln[j] = make_uint4(0u, 0u, 0u, 0u);
+      if (j >= 2 && seg_it + (uint32_t)(j - 2) < n_iter) pln[j] = stream_load16<true>(plane_base + (uint64_t)(seg_it + (uint32_t)(j - 2)) * 1024u + lane * 16u);
+    }
   }
   uint32_t npure = 0;  // (CHECK) how many blocks of nothing but N the lane has just walked over
   if constexpr (CHECK) {
@@ -1826,7 +1849,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   uint32_t it = seg_it;
   for (; it < n_iter; ++it) {
     const uint32_t sub = it & 1u;
-    if (sub == 0) {
+    if constexpr (SRC == kPlaneRead) {
+      if (sub == 0) {  // the next pair moves up; the pair kPlaneAhead iterations on is asked for
+#pragma unroll
+        for (int j = 0; j < kPlaneAhead; ++j) pln[j] = pln[j + 2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          if (it + (uint32_t)(kPlaneAhead + j) < n_iter)
+            pln[kPlaneAhead + j] = stream_load16<true>(plane_base + (uint64_t)(it + (uint32_t)(kPlaneAhead + j)) * 1024u + lane * 16u);
+      }
+    } else if (sub == 0) {
       if (interior) {
 #pragma unroll
         for (int i = 0; i < kStageInstr; ++i) *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = nxt[i];
@@ -1848,7 +1880,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     }
     uint2 t0, t1;
     uint32_t dsum = 0;  // (CHECK) != 0: the block holds other letters
-    {
+    if constexpr (SRC == kPlaneRead) {
+      const uint4 pv = sub ? pln[1] : pln[0];
+      t0 = make_uint2(pv.x, pv.y);
+      t1 = make_uint2(pv.z, pv.w);
+    } else {
       const uint32_t hs = (((sub << 2) ^ (fsw & 4u)) << 4);
       uint32_t x[16];
 #pragma unroll
@@ -1871,6 +1907,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
         }
         dsum = (d4[0] | d4[1]) | (d4[2] | d4[3]);
       }
+      if constexpr (SRC == kPlaneWrite)
+        *reinterpret_cast<uint4*>(const_cast<uint8_t*>(plane_base) + (uint64_t)it * 1024u + lane * 16u) = make_uint4(t0.x, t0.y, t1.x, t1.y);
     }
     // the piece rows' bits, opaque to the optimiser inside the loop: what is derived from them below (one scalar
     // per term) is computed here, per iteration, on the scalar unit, instead of living in 2 * Q * pieces registers
@@ -2882,6 +2920,40 @@ hipError_t launch_filter_group(const ScanParams& P, uint32_t grid, hipStream_t s
     case 12: return launch_filter_group_q<12>(P, grid, stream);
     default: return hipErrorInvalidValue;
   }
+}
+// the fused pass on kept code planes (filter_dna_kernel<.., SRC>): members = 1 / 2 searches in eight piece slots, src =
+// kPlaneWrite (from the text, storing the planes) / kPlaneRead (from the store); piece lengths 7 .. 12
+template <int Q, int G, int SRC>
+static hipError_t launch_filter_kept_q(const ScanParams& P, uint32_t grid, hipStream_t stream) {
+  const size_t smem = (size_t)kWavesPerGroup * P.lds_per_wave;
+  const LaunchEvents ev = g_launch_events;
+  g_launch_events = LaunchEvents{};
+  if (ev.start)
+    hipExtLaunchKernelGGL((filter_dna_kernel<Q, 2, true, false, false, 4, G, SRC>), dim3(grid), dim3(256), smem, stream, ev.start, ev.stop, 0, P);
+  else hipLaunchKernelGGL((filter_dna_kernel<Q, 2, true, false, false, 4, G, SRC>), dim3(grid), dim3(256), smem, stream, P);
+  return hipGetLastError();
+}
+template <int G, int SRC>
+static hipError_t launch_filter_kept_g(const ScanParams& P, uint32_t grid, hipStream_t stream) {
+  switch (P.piece_len) {
+    case 7: return launch_filter_kept_q<7, G, SRC>(P, grid, stream);
+    case 8: return launch_filter_kept_q<8, G, SRC>(P, grid, stream);
+    case 9: return launch_filter_kept_q<9, G, SRC>(P, grid, stream);
+    case 10: return launch_filter_kept_q<10, G, SRC>(P, grid, stream);
+    case 11: return launch_filter_kept_q<11, G, SRC>(P, grid, stream);
+    case 12: return launch_filter_kept_q<12, G, SRC>(P, grid, stream);
+    default: return hipErrorInvalidValue;
+  }
+}
+hipError_t launch_filter_kept(const ScanParams& P, uint32_t grid, uint32_t members, uint32_t src, hipStream_t stream) {
+  if (!P.piece_planes || !P.fused || P.pair || P.piece_groups != 2 || P.plane_store == nullptr || P.nwords > kFuseGroupMaxWords ||
+      (members == 2 && P.member1.nwords > kFuseGroupMaxWords))
+    return hipErrorInvalidValue;
+  if (members == 1 && src == kPlaneWrite) return launch_filter_kept_g<1, kPlaneWrite>(P, grid, stream);
+  if (members == 1 && src == kPlaneRead) return launch_filter_kept_g<1, kPlaneRead>(P, grid, stream);
+  if (members == 2 && src == kPlaneWrite) return launch_filter_kept_g<2, kPlaneWrite>(P, grid, stream);
+  if (members == 2 && src == kPlaneRead) return launch_filter_kept_g<2, kPlaneRead>(P, grid, stream);
+  return hipErrorInvalidValue;
 }
 #elif SASSY_SCAN_PROFILE == 6
 // Character classes (sassy_hip_search_classes): the streaming DP only -- no prefilter and no chunk list build their masks.

@@ -54,6 +54,8 @@ namespace sassy_hip {
   X(tiled, -1, "search_encoded: 1 force / 0 forbid the pattern-tiled scan")                                                 \
   X(seeded, -1, "search_encoded: 1 force / 0 forbid the seeded search")                                                 \
   X(shared_pass, 1, "searches in flight over one buffer share text passes, two per fused bit-plane launch: 1 staggered in halves of the grid (a begin launches the previous search's second half with this one's first; a search with no partner and no pass streaming goes whole); 4: as 1, but a search without a partner always keeps its second half back; 0: a pass per search; 3: whole passes, a groupable search always waits for a partner; 2: as 3 while a pass streams, and a waiting search is launched before a finish that has to wait") \
+  X(plane_cache, 1, "searches in flight keep the text's two code planes (16 bytes per 64-byte block, in a store per searcher) while tickets over one buffer are open without a break: the first launch over a half of the grid writes them, later ones read them instead of the text (0: every pass derives them from the text)") \
+  X(plane_cache_max_mb, 0, "> 0: a plane store larger than this many MiB is not made (0: no cap)") \
   X(aa_batch, 0, "search_all_alignments: at most this many alignments per emit batch (0: 32 MiB of rows / cigar text)") \
   X(min_cost_device, 1, "min_costs / best_pattern: 0: never the device reduction of the scan's list (search_many's records reduced by the host)") \
   X(best_match_device, 1, "best_matches: 0: never the device path (locating reduction of the scan's list, one traceback per text); search_many's records reduced by the host") \
