@@ -70,6 +70,12 @@ extern "C" {
     fn sassy_hip_hamming_best_pattern(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
                                       texts: *const *const u8, text_lens: *const usize, n_texts: usize, k: usize, flags: u32,
                                       out_cost: *mut u8, out_pattern: *mut u32, out_strand: *mut u8, out_start: *mut u64) -> c_int;
+    // ... counted, not listed: out_counts[(2 p + strand) (k + 1) + c] = records with that pattern, strand and cost
+    fn sassy_hip_hamming_counts(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                text: *const u8, text_len: usize, k: usize, flags: u32, out_counts: *mut u64) -> c_int;
+    fn sassy_hip_hamming_counts_many(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                     texts: *const *const u8, text_lens: *const usize, n_texts: usize, k: usize, flags: u32,
+                                     out_counts: *mut u64) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;
@@ -343,6 +349,31 @@ impl<P: Profile> Searcher<P> {
         };
         assert_eq!(rc, 0, "{}", last_error());
         (0..n).map(|t| (cost[t], pat[t], if strand[t] != 0 { Strand::Rc } else { Strand::Fwd }, start[t])).collect()
+    }
+
+    /// Hamming hit counts of one host text: `[(2 p + strand) (k + 1) + c]` = the number of hits of pattern `p` on that strand
+    /// (0 Fwd, 1 Rc) with exactly `c` mismatches -- what `search_hamming` would list, counted on the device.  `k <= 254`.
+    pub fn hamming_counts(&mut self, patterns: &[&[u8]], text: &[u8], k: usize) -> Vec<u64> {
+        let (pp, pl): (Vec<*const u8>, Vec<usize>) = patterns.iter().map(|p| (p.as_ptr(), p.len())).unzip();
+        let mut counts = vec![0u64; patterns.len() * 2 * (k + 1)];
+        let rc = unsafe {
+            sassy_hip_hamming_counts(self.raw, pp.as_ptr(), pl.as_ptr(), pp.len(), text.as_ptr(), text.len(), k, 0, counts.as_mut_ptr())
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        counts
+    }
+
+    /// `hamming_counts` over a batch of texts, summed over all of them (the records of `search_hamming_many`, counted).
+    pub fn hamming_counts_many(&mut self, patterns: &[&[u8]], texts: &[&[u8]], k: usize) -> Vec<u64> {
+        let (pp, pl): (Vec<*const u8>, Vec<usize>) = patterns.iter().map(|p| (p.as_ptr(), p.len())).unzip();
+        let (tp, tl): (Vec<*const u8>, Vec<usize>) = texts.iter().map(|t| (t.as_ptr(), t.len())).unzip();
+        let mut counts = vec![0u64; patterns.len() * 2 * (k + 1)];
+        let rc = unsafe {
+            sassy_hip_hamming_counts_many(self.raw, pp.as_ptr(), pl.as_ptr(), pp.len(), tp.as_ptr(), tl.as_ptr(), tp.len(), k, 0,
+                                          counts.as_mut_ptr())
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        counts
     }
 
     /// Per text the one best match over all patterns and strands as a complete record: lowest cost, then lowest pattern

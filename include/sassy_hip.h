@@ -404,6 +404,28 @@ int sassy_hip_hamming_best_pattern(sassy_SearcherType *s, const uint8_t *const *
                                    size_t k, uint32_t flags, uint8_t *out_cost, uint32_t *out_pattern, uint8_t *out_strand,
                                    uint64_t *out_start);
 
+/* Hamming hit counts per pattern, strand and cost, reduced on the device: out_counts[(2 p + strand) (k + 1) + c] is the
+ * number of records of sassy_hip_search_hamming(patterns, text, k) with pattern_idx = p, that strand (0 Fwd / 1 Rc) and
+ * cost = c, for the same searcher -- the same profile relation, rc and max_n_frac rule; the _many call counts the records of
+ * sassy_hip_search_hamming_many, summed over all texts.  out_counts holds n_patterns * 2 * (k + 1) counters and is written
+ * whole: the strand-1 rows of a searcher without rc are zero, and so are the bins with c > m and the rows of a pattern
+ * longer than the text.  The histogram that guide and primer design ranks candidates by; no record is made.
+ *  - flags: sassy_hip_hamming_counts takes SASSY_HIP_TEXT_ON_DEVICE and SASSY_HIP_TEXT_UNCHANGED (accepted, nothing is
+ *    cached), sassy_hip_hamming_counts_many none (host texts only); anything else SASSY_HIP_EINVAL;
+ *  - the refusals of sassy_hip_search_hamming, with the same codes, before any device work; also k > 254 (the family's
+ *    byte-cost limit) and out_counts == NULL SASSY_HIP_EINVAL, a table of more than 2^32 - 1 bins SASSY_HIP_EUNSUPPORTED;
+ *  - the scan kernel folds a wavefront's hits per cost into 64-bit counters, one atomic add per wavefront, pattern and cost
+ *    that is present: no items, no sort, no emit kernel, no replay of a text range; one launch per pattern group takes
+ *    every tile.  A small table is kept in several copies (option hamming_count_copies) that the host sums;
+ *  - options hamming_batch and hamming_many_batch keep their meaning; hamming_items and hamming_records have none here;
+ *  - sassy_hip_get_stats afterwards: scan_ms, scan_launches, candidates = the total of the table, filtered = 7. */
+int sassy_hip_hamming_counts(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                             size_t n_patterns, const void *text, size_t text_len, size_t k, uint32_t flags,
+                             uint64_t *out_counts /* n_patterns * 2 * (k + 1) */);
+int sassy_hip_hamming_counts_many(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                                  size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
+                                  size_t k, uint32_t flags, uint64_t *out_counts);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is

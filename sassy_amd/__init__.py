@@ -154,6 +154,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_line_spans", "sassy_hip_result_line_spans", "sassy_hip_line_tile", "sassy_hip_line_span_times",
     "sassy_hip_search_classes", "sassy_hip_class_cover",
     "sassy_hip_search_hamming", "sassy_hip_search_hamming_many", "sassy_hip_hamming_best_pattern",
+    "sassy_hip_hamming_counts", "sassy_hip_hamming_counts_many",
 ]
 
 _lib = None
@@ -290,6 +291,10 @@ def lib():
     L.sassy_hip_search_hamming_many.argtypes = list(L.sassy_hip_search_many.argtypes)
     L.sassy_hip_hamming_best_pattern.restype = C.c_int
     L.sassy_hip_hamming_best_pattern.argtypes = list(L.sassy_hip_search_many.argtypes[:-1]) + [vp, vp, vp, vp]
+    L.sassy_hip_hamming_counts.restype = C.c_int
+    L.sassy_hip_hamming_counts.argtypes = list(L.sassy_hip_search_hamming.argtypes[:-1]) + [vp]
+    L.sassy_hip_hamming_counts_many.restype = C.c_int
+    L.sassy_hip_hamming_counts_many.argtypes = list(L.sassy_hip_search_many.argtypes[:-1]) + [vp]
     L.sassy_hip_class_cover.restype = C.c_long
     L.sassy_hip_class_cover.argtypes = [u8p, vp, vp, sz, C.POINTER(C.c_int)]
     L.sassy_hip_search_all_alignments.restype = C.c_int
@@ -929,6 +934,38 @@ class Searcher:
         _check(lib().sassy_hip_hamming_best_pattern(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, 0, cost.ctypes.data,
                                                     pattern.ctypes.data, strand.ctypes.data, start.ctypes.data))
         return cost, pattern, strand, start
+
+    def hamming_counts(self, patterns, text, k: int):
+        """How many hits `search_hamming(patterns, text, k)` has per pattern, strand and cost (sassy_hip_hamming_counts): a
+        numpy.uint64 array of shape (n_patterns, 2, k + 1) -- [p, 0 '+' / 1 '-', c] --, counted on the device: no records are
+        made.  The same searcher, so the same profile, rc and max_n_frac rule; the '-' rows of a searcher without rc are
+        zero.  `text` as for `search_hamming` (a DeviceBuffer included; `text_unchanged()` is honoured).  k <= 254."""
+        import numpy as np
+        patterns = self._hamming_patterns(patterns, "hamming_counts")
+        pp = (C.c_char_p * len(patterns))(*patterns)
+        pl = (C.c_size_t * len(patterns))(*[len(p) for p in patterns])
+        flags = 0
+        addr, n, keep, on_dev = _ptr_len(text)
+        if on_dev:
+            flags |= TEXT_ON_DEVICE
+            if getattr(self, "_text_unchanged", False):
+                flags |= TEXT_UNCHANGED
+        counts = np.zeros((len(patterns), 2, max(0, min(int(k), 254)) + 1), dtype=np.uint64)
+        _check(lib().sassy_hip_hamming_counts(self._h, pp, pl, len(patterns), addr, n, k, flags, counts.ctypes.data))
+        return counts
+
+    def hamming_counts_many(self, patterns, texts: Sequence, k: int):
+        """`hamming_counts` over a batch of texts, summed over all of them (sassy_hip_hamming_counts_many): the records of
+        `search_hamming_many(patterns, texts, k)` counted per pattern, strand and cost, shape (n_patterns, 2, k + 1).
+        `texts`: a list of host texts or a TextBatch (host texts only)."""
+        import numpy as np
+        patterns = self._hamming_patterns(patterns, "hamming_counts_many")
+        pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
+        if on_device:
+            raise SassyHipError("hamming_counts_many takes host texts only")
+        counts = np.zeros((n_patterns, 2, max(0, min(int(k), 254)) + 1), dtype=np.uint64)
+        _check(lib().sassy_hip_hamming_counts_many(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, 0, counts.ctypes.data))
+        return counts
 
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k

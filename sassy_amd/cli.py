@@ -1,4 +1,4 @@
-"""`python -m sassy_amd search | filter | demux ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
+"""`python -m sassy_amd search | filter | demux | count ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
 
 Mirrors `sassy search` (reference: bin/grep.rs:30-157 arguments, :465-470 header, :623-660 pattern
 sources, :710-757 rows; FASTA/FASTQ records as bin/input_iterator.rs:125-137 reads them): every
@@ -29,6 +29,16 @@ strand, then the leftmost start):
     text_id  pat_id  cost  strand  start
 
 A record that holds no pattern within k mismatches gets `*` for pat_id and strand, and -1 for cost and start.
+
+`count PATTERNS FASTX ... -k K [--rc] [--alphabet A] [--max-n-frac F] [--per-record]` writes how many places every pattern
+has at 0, 1, ..., K mismatches per strand -- the table guide and primer design ranks candidates by --, through
+`Searcher.hamming_counts_many`: one call per FASTX batch, summed on the host; no match records are made.  PATTERNS is a
+FASTA / FASTQ file or a file with one pattern per line (ids 1, 2, ...).  Forward strand only unless `--rc`; no N rule unless
+`--max-n-frac`.  A header row, then one row per pattern and scanned strand:
+
+    pat_id  strand  n_0 ... n_K
+
+`--per-record` writes the rows per record instead (one call per record: the per-chromosome table), `text_id` in front.
 
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
@@ -279,6 +289,65 @@ def run_demux(args, searcher, patterns, out) -> int:
     return 0
 
 
+def count_header(k: int, per_record: bool = False) -> str:
+    return ("text_id\t" if per_record else "") + "pat_id\tstrand\t" + "\t".join(f"n_{c}" for c in range(k + 1)) + "\n"
+
+
+def count_rows(patterns, table, rc: bool, text_id=None):
+    """The TSV rows of one counts table (Searcher.hamming_counts' shape (n_patterns, 2, k + 1)): per pattern its '+' row and,
+    for an rc searcher, its '-' row; text_id in front for --per-record."""
+    rows = []
+    front = "" if text_id is None else f"{text_id}\t"
+    for p, (pat_id, _) in enumerate(patterns):
+        for strand in range(2 if rc else 1):
+            rows.append(front + f"{pat_id}\t{'-' if strand else '+'}\t" + "\t".join(str(int(v)) for v in table[p][strand]) + "\n")
+    return rows
+
+
+def load_count_patterns(path: str) -> List[Tuple[str, bytes]]:
+    """PATTERNS of `count`: FASTA / FASTQ records, or one pattern per line with ids 1, 2, ... (empty lines skipped)."""
+    with open(path, "rb") as fh:
+        first = fh.read(1)
+    if first in (b">", b"@"):
+        return list(read_fastx(path))
+    with open(path, "rb") as fh:
+        lines = [line.rstrip(b"\r\n") for line in fh]
+    return [(str(i + 1), line) for i, line in enumerate(line for line in lines if line)]
+
+
+def run_count(args, searcher, patterns, out) -> int:
+    import numpy as np
+    pats = [p for _, p in patterns]
+    out.write(count_header(args.k, args.per_record))
+    total = np.zeros((len(pats), 2, args.k + 1), dtype=np.uint64)
+    for path in args.paths:
+        for batch in read_fastx_batches(path, BATCH_BYTES):
+            if not len(batch):
+                continue
+            if args.per_record:
+                for i in range(len(batch)):
+                    out.writelines(count_rows(patterns, searcher.hamming_counts(pats, batch.sequence(i), args.k), searcher.rc,
+                                              text_id=batch.id(i)))
+            else:
+                total += searcher.hamming_counts_many(pats, batch.texts, args.k)
+    if not args.per_record:
+        out.writelines(count_rows(patterns, total, searcher.rc))
+    out.flush()
+    return 0
+
+
+def count_parser(sub):
+    cp = sub.add_parser("count", help="write per pattern and strand how many places it has at 0 .. k mismatches as TSV to stdout")
+    cp.add_argument("patterns", metavar="PATTERNS", help="FASTA / FASTQ of patterns, or one pattern per line")
+    cp.add_argument("paths", metavar="FASTX", nargs="+")
+    cp.add_argument("-k", type=int, required=True)
+    cp.add_argument("--rc", action="store_true", help="count the reverse complement's places as strand '-' as well")
+    cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac", "ascii", "ascii_ci"], default="iupac")
+    cp.add_argument("--max-n-frac", type=float, default=None, help="drop places whose span holds a larger fraction of N (default: none dropped)")
+    cp.add_argument("--per-record", action="store_true", help="rows per record (text_id in front) instead of summed over all records")
+    return cp
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m sassy_amd", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -299,7 +368,15 @@ def main(argv=None) -> int:
     dp = sub.add_parser("demux", help="write per record the pattern (barcode) with the fewest mismatches as TSV to stdout")
     add_search_arguments(dp)
     dp.add_argument("paths", nargs="+")
+    count_parser(sub)
     args = ap.parse_args(argv)
+    if args.cmd == "count":
+        if not 0 <= args.k <= 254:
+            ap.error("count takes 0 <= k <= 254")
+        if args.rc and args.alphabet.startswith("ascii"):
+            ap.error("count --rc: there is no reverse complement of plain text")
+        searcher = Searcher(args.alphabet, rc=args.rc).with_max_n_frac(args.max_n_frac)
+        return run_count(args, searcher, load_count_patterns(args.patterns), sys.stdout)
     if args.cmd == "demux" and args.overhang is not None:
         ap.error("demux counts mismatches: it does not take --overhang")
     if args.cmd == "agrep":

@@ -13,6 +13,8 @@
 // bytes on.  The scan kernel's MANY instantiations mask the starts by rem[block], the bytes left in the block's own text
 // (ham_rem_kernel builds it on the device); the emit kernel finds a hit's text in the start table.  Best pattern: no items --
 // the block's minimum (ham_min_cost) goes into one 64-bit cell per text.
+// sassy_hip_hamming_counts / _counts_many: no items either -- the COUNT instantiations fold a wavefront's hits per cost
+// (HamCounter::eq) into a table of 64-bit counters, one atomic per wavefront, pattern and present cost.
 #include "host_internal.h"
 #include "profile_masks.h"
 #include "hamming_step.h"
@@ -64,6 +66,14 @@ struct HamMany {
   unsigned long long* cells;    // != nullptr: best pattern -- per text cost:8 | 2 pattern_idx + strand:24 | start:32, all ones = none
 };
 
+// The table a COUNT launch adds into (hamming_counts); unused by the other instantiations.
+struct HamCounts {
+  unsigned long long* bins;  // (copy_mask + 1) copies of n_bins counters: bin (2 pattern_idx + strand) * stride + cost
+  uint32_t n_bins;
+  uint32_t stride;           // k + 1 of the call (the launch's k may be smaller: k >= m is cut to the longest pattern)
+  uint32_t copy_mask;        // copies - 1, copies a power of two: a workgroup adds into copy blockIdx.x & copy_mask
+};
+
 // LDS of one wavefront: the staged tile, then (slots + 1) rows of nb masks -- the last row is the N mask --, whole 16 bytes
 __host__ __device__ constexpr uint32_t ham_lds_per_wave(uint32_t slots, uint32_t nb) {
   return (kHamStageBytes + (slots + 1) * nb * 8u + 15u) & ~15u;
@@ -88,8 +98,24 @@ __device__ __forceinline__ uint2 n_mask(const uint32_t (&x)[16]) {  // bit i: te
   return r;
 }
 
-template <int PROFILE, int NS, int P, bool MANY>
-__global__ __launch_bounds__(256) void ham_scan_kernel(const HamParams H, const ScanParams SP, const HamMany M) {
+__device__ __forceinline__ uint32_t ham_wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ uint32_t ham_wave_min(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ uint32_t ham_wave_max(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor(v, o, 64));
+  return v;
+}
+
+template <int PROFILE, int NS, int P, bool MANY, bool COUNT>
+__global__ __launch_bounds__(256) void ham_scan_kernel(const HamParams H, const ScanParams SP, const HamMany M, const HamCounts C) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ham_lds[];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, wpg = blockDim.x >> 6;
   const uint64_t t_rel = (uint64_t)blockIdx.x * wpg + wave;
@@ -171,6 +197,23 @@ __global__ __launch_bounds__(256) void ham_scan_kernel(const HamParams H, const 
     if (nmax != kHamNoFilter && __any(hit != 0)) {
       auto n_word = [](uint32_t) { return (uint32_t)NS * 0x01010101u; };
       hit &= ham_hit_mask<kHamNPlanes, false>(fetch, n_word, m, nmax, all_over);
+    }
+    if constexpr (COUNT) {
+      // hamming_counts: the hits of the wavefront per cost.  `hit` is what search_hamming would list (position mask and N
+      // filter are behind it) and every start in it has an exact count <= H.k <= C.stride - 1 (HamCounter::eq).  Two wave
+      // reductions bound the costs that are present; per cost one wave sum and one add without a return value by one lane.
+      if (__any(hit != 0)) {
+        uint64_t at;
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)ham_wave_min(ham_min_cost<P>(cnt, hit, &at)));
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)ham_wave_max(ham_max_cost<P>(cnt, hit)));
+        unsigned long long* row = C.bins + (size_t)(blockIdx.x & C.copy_mask) * C.n_bins +
+                                  (size_t)(2u * tab[kHamTabWords * p + 4] + tab[kHamTabWords * p + 5]) * C.stride;
+        for (uint32_t c = lo; c <= hi; ++c) {
+          const uint32_t sum = ham_wave_sum((uint32_t)__builtin_popcountll(cnt.eq(c) & hit));
+          if (sum != 0 && lane == 0) (void)__hip_atomic_fetch_add(row + c, (unsigned long long)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
+      continue;
     }
     if constexpr (MANY) {
       if (M.cells) {  // best pattern: the block's minimum into its text's cell, the key's order is the tie order
@@ -265,51 +308,54 @@ __global__ __launch_bounds__(256) void ham_emit_kernel(const EmitParams E) {
   E.out[t] = o;
 }
 
-template <int PROFILE, int NS, int P, bool MANY>
-hipError_t launch_scan_k(const HamParams& H, const ScanParams& SP, const HamMany& M, uint32_t grid, uint32_t threads, size_t smem,
-                         hipStream_t st) {
+template <int PROFILE, int NS, int P, bool MANY, bool COUNT>
+hipError_t launch_scan_k(const HamParams& H, const ScanParams& SP, const HamMany& M, const HamCounts& C, uint32_t grid, uint32_t threads,
+                         size_t smem, hipStream_t st) {
   static DeviceOnce attr_set;  // LDS beyond the 64 KiB default needs an explicit opt-in
   if (attr_set.need()) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ham_scan_kernel<PROFILE, NS, P, MANY>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ham_scan_kernel<PROFILE, NS, P, MANY, COUNT>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHamLdsBudget);
     if (e != hipSuccess) return e;
     attr_set.done();
   }
-  hipLaunchKernelGGL((ham_scan_kernel<PROFILE, NS, P, MANY>), dim3(grid), dim3(threads), smem, st, H, SP, M);
+  hipLaunchKernelGGL((ham_scan_kernel<PROFILE, NS, P, MANY, COUNT>), dim3(grid), dim3(threads), smem, st, H, SP, M, C);
   return hipGetLastError();
 }
 
-template <int PROFILE, int NS, bool MANY>
-hipError_t launch_scan_p(const HamParams& H, const ScanParams& SP, const HamMany& M, uint32_t grid, uint32_t threads, size_t smem,
-                         hipStream_t st) {
-  switch (ham_planes(H.k)) {
-    case 2: return launch_scan_k<PROFILE, NS, 2, MANY>(H, SP, M, grid, threads, smem, st);
-    case 4: return launch_scan_k<PROFILE, NS, 4, MANY>(H, SP, M, grid, threads, smem, st);
-    case 8: return launch_scan_k<PROFILE, NS, 8, MANY>(H, SP, M, grid, threads, smem, st);
-    default: return launch_scan_k<PROFILE, NS, 11, MANY>(H, SP, M, grid, threads, smem, st);
-  }
-}
-
-template <bool MANY>
-hipError_t launch_scan_m(Profile pr, uint32_t ns, const HamParams& H, const ScanParams& SP, const HamMany& M, uint32_t grid, uint32_t threads,
+template <int PROFILE, int NS, bool MANY, bool COUNT>
+hipError_t launch_scan_p(const HamParams& H, const ScanParams& SP, const HamMany& M, const HamCounts& C, uint32_t grid, uint32_t threads,
                          size_t smem, hipStream_t st) {
-  switch (pr) {
-    case PROFILE_DNA: return launch_scan_p<(int)PROFILE_DNA, 4, MANY>(H, SP, M, grid, threads, smem, st);
-    case PROFILE_IUPAC: return launch_scan_p<(int)PROFILE_IUPAC, 16, MANY>(H, SP, M, grid, threads, smem, st);
-    case PROFILE_ASCII_CI:
-      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII_CI, 16, MANY>(H, SP, M, grid, threads, smem, st)
-                      : launch_scan_p<(int)PROFILE_ASCII_CI, 64, MANY>(H, SP, M, grid, threads, smem, st);
-    default:
-      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII, 16, MANY>(H, SP, M, grid, threads, smem, st)
-                      : launch_scan_p<(int)PROFILE_ASCII, 64, MANY>(H, SP, M, grid, threads, smem, st);
+  switch (ham_planes(H.k)) {
+    case 2: return launch_scan_k<PROFILE, NS, 2, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st);
+    case 4: return launch_scan_k<PROFILE, NS, 4, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st);
+    case 8: return launch_scan_k<PROFILE, NS, 8, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st);
+    default: return launch_scan_k<PROFILE, NS, 11, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st);
   }
 }
 
-// many == nullptr: one text
-hipError_t launch_scan(Profile pr, uint32_t ns, const HamParams& H, const ScanParams& SP, const HamMany* many, uint32_t grid, uint32_t threads,
-                       size_t smem, hipStream_t st) {
-  return many ? launch_scan_m<true>(pr, ns, H, SP, *many, grid, threads, smem, st)
-              : launch_scan_m<false>(pr, ns, H, SP, HamMany{}, grid, threads, smem, st);
+template <bool MANY, bool COUNT>
+hipError_t launch_scan_m(Profile pr, uint32_t ns, const HamParams& H, const ScanParams& SP, const HamMany& M, const HamCounts& C, uint32_t grid,
+                         uint32_t threads, size_t smem, hipStream_t st) {
+  switch (pr) {
+    case PROFILE_DNA: return launch_scan_p<(int)PROFILE_DNA, 4, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st);
+    case PROFILE_IUPAC: return launch_scan_p<(int)PROFILE_IUPAC, 16, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st);
+    case PROFILE_ASCII_CI:
+      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII_CI, 16, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st)
+                      : launch_scan_p<(int)PROFILE_ASCII_CI, 64, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st);
+    default:
+      return ns <= 16 ? launch_scan_p<(int)PROFILE_ASCII, 16, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st)
+                      : launch_scan_p<(int)PROFILE_ASCII, 64, MANY, COUNT>(H, SP, M, C, grid, threads, smem, st);
+  }
+}
+
+// many == nullptr: one text; counts != nullptr: the COUNT instantiations
+hipError_t launch_scan(Profile pr, uint32_t ns, const HamParams& H, const ScanParams& SP, const HamMany* many, const HamCounts* counts,
+                       uint32_t grid, uint32_t threads, size_t smem, hipStream_t st) {
+  if (counts)
+    return many ? launch_scan_m<true, true>(pr, ns, H, SP, *many, *counts, grid, threads, smem, st)
+                : launch_scan_m<false, true>(pr, ns, H, SP, HamMany{}, *counts, grid, threads, smem, st);
+  return many ? launch_scan_m<true, false>(pr, ns, H, SP, *many, HamCounts{}, grid, threads, smem, st)
+              : launch_scan_m<false, false>(pr, ns, H, SP, HamMany{}, HamCounts{}, grid, threads, smem, st);
 }
 
 // One pattern of the call on one strand, as it is scanned.
@@ -335,10 +381,11 @@ struct HamTexts {
 }  // namespace
 
 // The search proper: refusals are the caller's; d_text is readable up to the next multiple of 64 bytes.  many != nullptr:
-// d_text is a batch of texts; with many->dev.cells the launches reduce into the cells and R stays as it is.
+// d_text is a batch of texts; with many->dev.cells the launches reduce into the cells and R stays as it is.  counts != nullptr:
+// the launches add into the table, nothing is listed and R is not touched (it may be nullptr).
 static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
                              const uint8_t* d_text, uint64_t n, uint32_t k, bool without_trace, sassy_hip_Result* R,
-                             const HamTexts* many = nullptr) {
+                             const HamTexts* many = nullptr, const HamCounts* counts = nullptr) {
   const Profile pr = S->profile;
   hipStream_t st = S->stream;
   ScanLane& L = S->lanes[0];
@@ -438,14 +485,14 @@ static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patter
     const uint64_t max_cap = items_sw > 0 ? item_cap : std::max<uint64_t>(min_cap, 1u << 22);
     const uint64_t rec_cap = records_sw > 0 ? (uint64_t)records_sw : (1u << 20);
     const uint64_t span_max = std::max<uint64_t>(1, (0x7FFFFFFFull / kHamTileBlocks) / np);  // the counter cannot wrap
-    if (many && many->dev.cells) {  // best pattern: nothing is listed, one launch takes every tile
+    if (counts || (many && many->dev.cells)) {  // counts, best pattern: nothing is listed, one launch takes every tile
       HamParams H{};
       H.text = d_text; H.n = n; H.n_blocks = n_blocks; H.tile0 = 0; H.n_tiles = n_tiles;
       H.k = k; H.n_pat = np; H.halo = halo; H.nb = nb; H.n_filter = n_filter ? 1u : 0u; H.item_cap = 0;
       H.tab = d_tab; H.rows = d_rows; H.items = nullptr; H.item_count = nullptr;
       if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
       const uint32_t grid = (uint32_t)((n_tiles + wpg - 1) / wpg);
-      HIP_TRY(launch_scan(pr, ns, H, SP, &many->dev, grid, wpg * 64, smem, st));
+      HIP_TRY(launch_scan(pr, ns, H, SP, many ? &many->dev : nullptr, counts, grid, wpg * 64, smem, st));
       if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
       HIP_TRY(hipStreamSynchronize(st));  // (the next group reuses the pinned upload area)
       if (timed) {
@@ -472,7 +519,7 @@ static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patter
       HIP_TRY(hipMemsetAsync(S->d_ham_count.p, 0, 4, st));
       if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
       const uint32_t grid = (uint32_t)((span + wpg - 1) / wpg);
-      HIP_TRY(launch_scan(pr, ns, H, SP, many ? &many->dev : nullptr, grid, wpg * 64, smem, st));
+      HIP_TRY(launch_scan(pr, ns, H, SP, many ? &many->dev : nullptr, nullptr, grid, wpg * 64, smem, st));
       if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
       uint32_t count = 0;
       HIP_TRY(hipMemcpyAsync(&count, S->d_ham_count.p, 4, hipMemcpyDeviceToHost, st));
@@ -568,10 +615,10 @@ static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patter
 
 // A batch call: the texts in batches of at most `hamming_many_batch` bytes laid out, each text from a multiple of 64 bytes on
 // (an empty text takes no block).  Records into R in the contract's order, or -- cells != nullptr -- per text of the call
-// its best-pattern cell (all ones: no hit), nothing into R.
+// its best-pattern cell (all ones: no hit), nothing into R; or -- counts != nullptr -- every batch adds into the one table.
 static int hamming_many_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
                                   const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, uint32_t k, bool without_trace,
-                                  sassy_hip_Result* R, unsigned long long* cells) {
+                                  sassy_hip_Result* R, unsigned long long* cells, const HamCounts* counts = nullptr) {
   hipStream_t st = S->stream;
   const uint64_t batch_cap = S->sw.hamming_many_batch > 0 ? (uint64_t)S->sw.hamming_many_batch : (1ull << 30);
   HostTexts ht;
@@ -616,7 +663,7 @@ static int hamming_many_on_device(sassy_SearcherType* S, const uint8_t* const* p
       HIP_TRY(hipMemsetAsync(S->d_ham_cells.p, 0xFF, nt * 8, st));
       B.dev.cells = S->d_ham_cells.p;
     }
-    if (int rc = hamming_on_device(S, patterns, pattern_lens, n_patterns, S->d_text.p, total, k, without_trace, R, &B)) return rc;
+    if (int rc = hamming_on_device(S, patterns, pattern_lens, n_patterns, S->d_text.p, total, k, without_trace, R, &B, counts)) return rc;
     if (cells) HIP_TRY(hipMemcpyAsync(cells + t0, S->d_ham_cells.p, nt * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));  // (the tables of the next batch overwrite this one's)
     all_tiles += S->stats.chunks;
@@ -723,6 +770,92 @@ static int hamming_many(sassy_SearcherType* s, const uint8_t* const* patterns, c
   return 0;
 }
 
+// Copies of a counts table of n_bins counters (a power of two).  In the worst case -- every wavefront holds hits of one cost of
+// one pattern -- every tile adds to one word, and a launch of few patterns streams tiles at the rate of HBM: 6.3 TB/s over 4 KiB
+// tiles is about 1 500 adds per microsecond where one contended word takes about 88: 18 words are needed, 32
+// are kept while 32 tables stay within 2^16 counters (512 KiB to clear and to read back), fewer for a larger table -- whose
+// launches hold more patterns per tile and so add to one word less often --, one at least.  `forced` > 0: that many (option
+// hamming_count_copies; rounded down to a power of two, at most 1024, within 2^26 counters).
+static uint32_t hamming_count_copies(uint64_t n_bins, long forced) {
+  uint32_t copies = 32;
+  uint64_t room = 1ull << 16;
+  if (forced > 0) {
+    copies = 1;
+    while (copies * 2 <= (uint64_t)std::min<long>(forced, 1024)) copies *= 2;
+    room = 1ull << 26;
+  }
+  while (copies > 1 && (uint64_t)copies * n_bins > room) copies /= 2;
+  return copies;
+}
+
+// both counting entry points: texts == nullptr the single text (text, text_len), else the batch
+static int hamming_counts(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, const void* text,
+                          size_t text_len, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
+                          uint64_t* out_counts, bool batch) {
+  const char* who = batch ? "hamming_counts_many" : "hamming_counts";
+  if (!s || !out_counts || (n_pats && (!pats || !lens)) || (!batch && !text && text_len) || (batch && n_texts && (!texts || !text_lens)))
+    return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null");
+  if (batch)
+    for (size_t t = 0; t < n_texts; ++t)
+      if (!texts[t] && text_lens[t])
+        return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null (text " + std::to_string(t) + ")");
+  if (batch && flags) return fail(SASSY_HIP_EINVAL, "hamming_counts_many takes no flags (host texts only)");
+  if (flags & ~(uint32_t)(SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_TEXT_UNCHANGED))
+    return fail(SASSY_HIP_EINVAL, "hamming_counts takes SASSY_HIP_TEXT_ON_DEVICE and _TEXT_UNCHANGED only");
+  if (k > 254) return fail(SASSY_HIP_EINVAL, std::string(who) + ": k must be <= 254 (the Hamming family's costs are bytes)");
+  if (int rc = hamming_refusals(s, pats, lens, n_pats, k, who)) return rc;
+  const uint64_t stride = (uint64_t)k + 1;
+  if ((uint64_t)n_pats > 0xFFFFFFFFull / (2 * stride))
+    return fail(SASSY_HIP_EUNSUPPORTED, std::string(who) + ": the table has more than 2^32 - 1 bins (" + std::to_string(n_pats) + " patterns x 2 x " +
+                                            std::to_string(stride) + ")");
+  const uint64_t n_bins = (uint64_t)n_pats * 2 * stride;
+  std::fill(out_counts, out_counts + n_bins, (uint64_t)0);
+  if (batch && n_texts == 0) return 0;
+  DeviceGuard on_device(s);
+  const double t0 = now_ms();
+  reset_stats(s);
+  if (int rc = s->ensure_device()) return rc;
+  const uint32_t copies = hamming_count_copies(n_bins, s->sw.hamming_count_copies);
+  if (int rc = s->d_ham_bins.reserve((size_t)copies * n_bins)) return rc;
+  HIP_TRY(hipMemsetAsync(s->d_ham_bins.p, 0, (size_t)copies * n_bins * 8, s->stream));
+  HamCounts C{};
+  C.bins = s->d_ham_bins.p; C.n_bins = (uint32_t)n_bins; C.stride = (uint32_t)stride; C.copy_mask = copies - 1;
+  size_t longest = 0;
+  for (size_t i = 0; i < n_pats; ++i) longest = std::max(longest, lens[i]);
+  const uint32_t kk = (uint32_t)std::min<size_t>(k, longest);  // k >= m counts every start
+  int rc = 0;
+  if (batch) {
+    rc = hamming_many_on_device(s, pats, lens, n_pats, texts, text_lens, n_texts, kk, true, nullptr, nullptr, &C);
+  } else {
+    const uint8_t* d_text = static_cast<const uint8_t*>(text);
+    if (flags & SASSY_HIP_TEXT_ON_DEVICE) {
+      if (((uintptr_t)text & 15) != 0) return fail(SASSY_HIP_EINVAL, "device text pointer must be 16-byte aligned");
+    } else if (text_len) {
+      if (int rc2 = s->d_text.reserve(text_len + 64)) return rc2;
+      HIP_TRY(hipMemcpyAsync(s->d_text.p, text, text_len, hipMemcpyHostToDevice, s->stream));
+      d_text = s->d_text.p;
+    }
+    rc = hamming_on_device(s, pats, lens, n_pats, d_text, text_len, kk, true, nullptr, nullptr, &C);
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(s->stream);
+    return rc;
+  }
+  // the copies come back once and are summed here
+  std::vector<uint64_t> all((size_t)copies * n_bins);
+  HIP_TRY(hipMemcpyAsync(all.data(), s->d_ham_bins.p, all.size() * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  uint64_t total = 0;
+  for (uint32_t c = 0; c < copies; ++c)
+    for (uint64_t b = 0; b < n_bins; ++b) out_counts[b] += all[(size_t)c * n_bins + b];
+  for (uint64_t b = 0; b < n_bins; ++b) total += out_counts[b];
+  s->stats.candidates = total;
+  s->stats.filtered = 7;
+  s->stats.blocks_per_chunk = kHamTileBlocks;
+  s->stats.total_ms = now_ms() - t0;
+  return 0;
+}
+
 }  // namespace sassy_hip
 
 using namespace sassy_hip;
@@ -777,6 +910,17 @@ int sassy_hip_hamming_best_pattern(sassy_SearcherType* s, const uint8_t* const* 
   uint8_t none = 0;
   return hamming_many(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, nullptr, out_cost ? out_cost : &none,
                       out_pattern, out_strand, out_start);
+}
+
+int sassy_hip_hamming_counts(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                             const void* text, size_t text_len, size_t k, uint32_t flags, uint64_t* out_counts) {
+  return hamming_counts(s, patterns, pattern_lens, n_patterns, text, text_len, nullptr, nullptr, 0, k, flags, out_counts, false);
+}
+
+int sassy_hip_hamming_counts_many(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                                  const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
+                                  uint64_t* out_counts) {
+  return hamming_counts(s, patterns, pattern_lens, n_patterns, nullptr, 0, texts, text_lens, n_texts, k, flags, out_counts, true);
 }
 
 }  // extern "C"

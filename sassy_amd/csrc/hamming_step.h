@@ -1,5 +1,5 @@
 // hamming_step.h -- the arithmetic of the Hamming search (hamming.hip), free of HIP: plain C++17 that the device kernels and
-// the host test driver (tests/c/hamming_step_driver.cc) compile alike.
+// the host test drivers (tests/c/hamming_step_driver.cc, hamming_many_step_driver.cc, hamming_counts_step_driver.cc) compile alike.
 //
 // H(s) = #{ j < m : !match(P[j], T[s + j]) }.  The text comes as slot masks: per 64-byte block b and profile slot c one
 // 64-bit word, bit i = "text byte 64 b + i matches slot c".  Row j of the pattern names its slot.  For the 64 starts of one
@@ -74,6 +74,14 @@ struct HamCounter {
     }
     return ~gt & ~over;
   }
+  // bit i: count i == v, for v < 2^P; a start with `over` set never matches.  A start that survives le(k) did not saturate,
+  // so its planes hold its exact count: eq(v) & hit is exact for every v <= k, and the eq(v), v <= k, partition le(k).
+  SASSY_HAM_HD uint64_t eq(uint32_t v) const {
+    uint64_t e = ~over;
+#pragma unroll
+    for (int p = 0; p < P; ++p) e &= ((v >> p) & 1u) ? c[p] : ~c[p];
+    return e;
+  }
 };
 
 // The 64 starts of one block: bit i = "at most k of the m rows mismatch at start 64 b + i" (invert = true), or, with
@@ -126,6 +134,24 @@ SASSY_HAM_HD uint32_t ham_min_cost(const HamCounter<P>& cnt, uint64_t hit, uint6
     else cost |= 1u << p;
   }
   *at = cand;
+  return cost;
+}
+// The largest count among the starts of `hit`, the mirror image: where some candidate has a 1 in plane p, the maximum has.
+// hit == 0 (after ~over): 0 -- a caller that has to tell "none" from "all zero" asks ham_min_cost.  With the minimum it bounds
+// the costs a block's hits can have (hamming_counts: the wavefront's loop over costs).
+template <int P>
+SASSY_HAM_HD uint32_t ham_max_cost(const HamCounter<P>& cnt, uint64_t hit) {
+  uint64_t cand = hit & ~cnt.over;
+  if (cand == 0) return 0;
+  uint32_t cost = 0;
+#pragma unroll
+  for (int p = P - 1; p >= 0; --p) {
+    const uint64_t t = cand & cnt.c[p];
+    if (t) {
+      cand = t;
+      cost |= 1u << p;
+    }
+  }
   return cost;
 }
 

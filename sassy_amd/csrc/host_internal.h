@@ -3,7 +3,7 @@
 //   scan_driver.hip   one pattern over one buffer: ScanJob (prepare / enqueue / finish), strands, search_text
 //   many_patterns.hip search_encoded / search_many: pattern-tiled scan, seeded search, lists -> reports -> records
 //   multi_device.hip  sassy_hip_multi_*: one text over several devices inside one process
-//   hamming.hip       sassy_hip_search_hamming, _search_hamming_many, _hamming_best_pattern: the Hamming scan and emit kernels
+//   hamming.hip       sassy_hip_search_hamming, _search_hamming_many, _hamming_best_pattern, _hamming_counts(_many): the Hamming scan and emit kernels
 //                     with their drivers and entry points
 //   c_abi.hip         the C-ABI of include/sassy.h + sassy_hip.h, the switch table, synthetic inputs
 #pragma once
@@ -689,6 +689,7 @@ struct sassy_SearcherType {
   DevBuf<uint64_t> d_ham_texts;
   DevBuf<uint32_t> d_ham_rem;
   DevBuf<unsigned long long> d_ham_cells;
+  DevBuf<unsigned long long> d_ham_bins;  // hamming_counts: the copies of the counts table
   DevBuf<uint64_t> d_range;      // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
@@ -712,7 +713,7 @@ struct sassy_SearcherType {
     free_stage();
     d_line_tiles.release(); d_line_prefix.release(); d_line_pos.release(); d_line_out.release();
     d_ham_tab.release(); d_ham_count.release(); d_ham_prefix.release(); d_ham_items.release(); d_ham_sorted.release(); d_ham_sort.release();
-    d_ham_texts.release(); d_ham_rem.release(); d_ham_cells.release();
+    d_ham_texts.release(); d_ham_rem.release(); d_ham_cells.release(); d_ham_bins.release();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();
