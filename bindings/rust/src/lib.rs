@@ -23,6 +23,19 @@ struct RawMatch {
     cigar_off: u32,
     cigar_len: u32,
 }
+/// One product of a primer pair (include/sassy_hip.h: sassy_hip_Amplicon, 24 bytes): `strand` 0 = fwd on the forward strand
+/// at `start`, 1 = rev; `fwd_cost` / `rev_cost` are the mismatches of fwd and of rev, whichever side they sit on.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct Amplicon {
+    pub start: u64,
+    pub end: u64,
+    pub pair_idx: u32,
+    pub strand: u8,
+    pub fwd_cost: u8,
+    pub rev_cost: u8,
+    _pad: u8,
+}
 #[repr(C)]
 struct RawSearcher {
     _p: [u8; 0],
@@ -76,6 +89,11 @@ extern "C" {
     fn sassy_hip_hamming_counts_many(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
                                      texts: *const *const u8, text_lens: *const usize, n_texts: usize, k: usize, flags: u32,
                                      out_counts: *mut u64) -> c_int;
+    // ... joined: the products of primer pairs (in-silico PCR), records freed with sassy_hip_amplicons_free
+    fn sassy_hip_hamming_amplicons(s: *mut RawSearcher, fwd: *const *const u8, fwd_lens: *const usize, rev: *const *const u8,
+                                   rev_lens: *const usize, n_pairs: usize, text: *const u8, text_len: usize, k: usize, min_len: u64,
+                                   max_len: u64, flags: u32, out: *mut *mut Amplicon, n_out: *mut usize) -> c_int;
+    fn sassy_hip_amplicons_free(p: *mut Amplicon);
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;
@@ -374,6 +392,24 @@ impl<P: Profile> Searcher<P> {
         };
         assert_eq!(rc, 0, "{}", last_error());
         counts
+    }
+
+    /// The products of primer pairs `(fwd, rev)`, both written 5'->3', in one host text (in-silico PCR): every `(strand,
+    /// start, end)` with `min_len <= end - start <= max_len` whose two primer sites have at most `k` mismatches each, ordered
+    /// by `(pair_idx, strand, start, end)`; joined on the device.  `k <= 254`, `max_len <= 2^24`, Dna and Iupac searchers.
+    pub fn hamming_amplicons(&mut self, pairs: &[(&[u8], &[u8])], text: &[u8], k: usize, min_len: u64, max_len: u64) -> Vec<Amplicon> {
+        let (fp, fl): (Vec<*const u8>, Vec<usize>) = pairs.iter().map(|p| (p.0.as_ptr(), p.0.len())).unzip();
+        let (rp, rl): (Vec<*const u8>, Vec<usize>) = pairs.iter().map(|p| (p.1.as_ptr(), p.1.len())).unzip();
+        let mut out: *mut Amplicon = std::ptr::null_mut();
+        let mut n = 0usize;
+        let rc = unsafe {
+            sassy_hip_hamming_amplicons(self.raw, fp.as_ptr(), fl.as_ptr(), rp.as_ptr(), rl.as_ptr(), pairs.len(), text.as_ptr(), text.len(),
+                                        k, min_len, max_len, 0, &mut out, &mut n)
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        let v = if n == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(out, n) }.to_vec() };
+        unsafe { sassy_hip_amplicons_free(out) };
+        v
     }
 
     /// Per text the one best match over all patterns and strands as a complete record: lowest cost, then lowest pattern

@@ -426,6 +426,39 @@ int sassy_hip_hamming_counts_many(sassy_SearcherType *s, const uint8_t *const *p
                                   size_t n_patterns, const uint8_t *const *texts, const size_t *text_lens, size_t n_texts,
                                   size_t k, uint32_t flags, uint64_t *out_counts);
 
+/* Amplicons: which products a primer PAIR makes (in-silico PCR), joined on the device from the Hamming scan's hits.
+ * With H_P(s) the mismatch count of pattern P at start s of the forward text (sassy_hip_search_hamming) and H-_P(s) that of
+ * reverse_complement(P) -- what an rc searcher reports as strand 1 --, an amplicon of pair i = (F, R), both written 5'->3',
+ * of lengths a and b, is (strand, start, end), L = end - start, with min_len <= L <= max_len, L >= max(a, b), and
+ *   strand 0: H_F(start) <= k and H-_R(end - b) <= k;
+ *   strand 1: H_R(start) <= k and H-_F(end - a) <= k (an rc searcher only).
+ * EVERY such combination is a record (no nearest-partner rule); F == R or a palindromic site gives a strand-0 and a strand-1
+ * record of one span, and both stay.  max_n_frac applies per primer site, as in sassy_hip_search_hamming.  A searcher
+ * without rc reports strand 0 only (it still scans reverse_complement(R)).  The records are the join of what
+ * sassy_hip_search_hamming({F, R}, text, k) returns on an rc searcher; order (pair_idx, strand, start, end).
+ *  - flags: SASSY_HIP_TEXT_ON_DEVICE and SASSY_HIP_TEXT_UNCHANGED (accepted, nothing is cached); anything else SASSY_HIP_EINVAL;
+ *  - refusals, before any device work: those of sassy_hip_search_hamming for all 2 n_pairs primers; an Ascii / ascii_ci
+ *    searcher SASSY_HIP_EUNSUPPORTED (no reverse complement); k > 254, min_len == 0, min_len > max_len or
+ *    max_len > SASSY_HIP_AMPLICON_MAX_LEN SASSY_HIP_EINVAL;
+ *  - more than 2^32 - 1 records: SASSY_HIP_ENOMEM, the message carries the count;
+ *  - *out = NULL and *n_out = 0 when there is nothing: a valid result.  A pair with a primer longer than the text has none;
+ *  - options hamming_batch (scanned patterns per launch: four per pair of an rc searcher, two otherwise, a pair never
+ *    split), hamming_items and hamming_records keep their meaning.  Free *out with sassy_hip_amplicons_free. */
+typedef struct sassy_hip_Amplicon {
+  uint64_t start, end;
+  uint32_t pair_idx;
+  uint8_t strand;    /* 0: F on the forward strand at start; 1: R on the forward strand at start */
+  uint8_t fwd_cost;  /* the mismatches of F, whichever side it sits on */
+  uint8_t rev_cost;  /* the mismatches of R */
+  uint8_t pad_;      /* zero */
+} sassy_hip_Amplicon;
+#define SASSY_HIP_AMPLICON_MAX_LEN (1u << 24)
+int sassy_hip_hamming_amplicons(sassy_SearcherType *s, const uint8_t *const *fwd, const size_t *fwd_lens,
+                                const uint8_t *const *rev, const size_t *rev_lens, size_t n_pairs, const void *text,
+                                size_t text_len, size_t k, uint64_t min_len, uint64_t max_len, uint32_t flags,
+                                sassy_hip_Amplicon **out, size_t *n_out);
+void sassy_hip_amplicons_free(sassy_hip_Amplicon *p);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is

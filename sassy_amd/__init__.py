@@ -155,6 +155,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_search_classes", "sassy_hip_class_cover",
     "sassy_hip_search_hamming", "sassy_hip_search_hamming_many", "sassy_hip_hamming_best_pattern",
     "sassy_hip_hamming_counts", "sassy_hip_hamming_counts_many",
+    "sassy_hip_hamming_amplicons", "sassy_hip_amplicons_free",
 ]
 
 _lib = None
@@ -295,6 +296,11 @@ def lib():
     L.sassy_hip_hamming_counts.argtypes = list(L.sassy_hip_search_hamming.argtypes[:-1]) + [vp]
     L.sassy_hip_hamming_counts_many.restype = C.c_int
     L.sassy_hip_hamming_counts_many.argtypes = list(L.sassy_hip_search_many.argtypes[:-1]) + [vp]
+    L.sassy_hip_hamming_amplicons.restype = C.c_int
+    L.sassy_hip_hamming_amplicons.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), C.POINTER(C.c_char_p), C.POINTER(sz), sz, vp, sz, sz,
+                                              C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
+    L.sassy_hip_amplicons_free.restype = None
+    L.sassy_hip_amplicons_free.argtypes = [vp]
     L.sassy_hip_class_cover.restype = C.c_long
     L.sassy_hip_class_cover.argtypes = [u8p, vp, vp, sz, C.POINTER(C.c_int)]
     L.sassy_hip_search_all_alignments.restype = C.c_int
@@ -408,6 +414,13 @@ def line_span_dtype():
     """numpy view of include/sassy_hip.h: sassy_hip_LineSpan (32 bytes)."""
     import numpy as np
     return np.dtype([("line_no", "<u8"), ("last_line_no", "<u8"), ("line_start", "<u8"), ("line_end", "<u8")])
+
+
+def amplicon_dtype():
+    """numpy view of include/sassy_hip.h: sassy_hip_Amplicon (24 bytes)."""
+    import numpy as np
+    return np.dtype([("start", "<u8"), ("end", "<u8"), ("pair_idx", "<u4"), ("strand", "u1"), ("fwd_cost", "u1"), ("rev_cost", "u1"),
+                     ("pad_", "u1")])
 
 
 def line_tile() -> int:
@@ -966,6 +979,37 @@ class Searcher:
         counts = np.zeros((n_patterns, 2, max(0, min(int(k), 254)) + 1), dtype=np.uint64)
         _check(lib().sassy_hip_hamming_counts_many(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, 0, counts.ctypes.data))
         return counts
+
+    def hamming_amplicons(self, pairs, text, k: int, min_len: int, max_len: int):
+        """Which products primer pairs make (in-silico PCR, sassy_hip_hamming_amplicons): a numpy structured array of
+        `amplicon_dtype()` -- start, end, pair_idx, strand, fwd_cost, rev_cost -- ordered by (pair_idx, strand, start, end).
+        `pairs`: a sequence of (fwd, rev) bytes, both written 5'->3'.  Strand 0: fwd matches at `start` and
+        reverse_complement(rev) ends at `end`; strand 1 (an rc searcher only): rev at `start`, reverse_complement(fwd) at the
+        end; each with at most k mismatches, min_len <= end - start <= max_len, and every such combination a record.  Joined
+        on the device: no Hamming records are made.  `text` as for `search_hamming` (a DeviceBuffer included).  Dna and Iupac
+        searchers, k <= 254, max_len <= 2^24."""
+        import numpy as np
+        pairs = [(bytes(f), bytes(r)) for f, r in pairs]
+        n = len(pairs)
+        fp = (C.c_char_p * max(1, n))(*[f for f, _ in pairs])
+        fl = (C.c_size_t * max(1, n))(*[len(f) for f, _ in pairs])
+        rp = (C.c_char_p * max(1, n))(*[r for _, r in pairs])
+        rl = (C.c_size_t * max(1, n))(*[len(r) for _, r in pairs])
+        flags = 0
+        addr, tn, keep, on_dev = _ptr_len(text)
+        if on_dev:
+            flags |= TEXT_ON_DEVICE
+            if getattr(self, "_text_unchanged", False):
+                flags |= TEXT_UNCHANGED
+        out, n_out = C.c_void_p(), C.c_size_t()
+        _check(lib().sassy_hip_hamming_amplicons(self._h, fp, fl, rp, rl, n, addr, tn, k, min_len, max_len, flags, C.byref(out), C.byref(n_out)))
+        dt = amplicon_dtype()
+        if not n_out.value:
+            return np.zeros(0, dtype=dt)
+        try:
+            return np.frombuffer(_bytes_at(out.value, n_out.value * dt.itemsize), dtype=dt).copy()
+        finally:
+            lib().sassy_hip_amplicons_free(out)
 
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k

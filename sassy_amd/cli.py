@@ -1,4 +1,4 @@
-"""`python -m sassy_amd search | filter | demux | count ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
+"""`python -m sassy_amd search | filter | demux | count | amplicon ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
 
 Mirrors `sassy search` (reference: bin/grep.rs:30-157 arguments, :465-470 header, :623-660 pattern
 sources, :710-757 rows; FASTA/FASTQ records as bin/input_iterator.rs:125-137 reads them): every
@@ -39,6 +39,16 @@ FASTA / FASTQ file or a file with one pattern per line (ids 1, 2, ...).  Forward
     pat_id  strand  n_0 ... n_K
 
 `--per-record` writes the rows per record instead (one call per record: the per-chromosome table), `text_id` in front.
+
+`amplicon PRIMERS FASTX ... -k K --min-len A --max-len B [--no-rc] [-a dna|iupac] [--max-n-frac X] [--seq]` writes which
+products primer pairs make (in-silico PCR) through `Searcher.hamming_amplicons`, one call per FASTX record.  PRIMERS is a TSV
+of `name<TAB>fwd<TAB>rev`, both primers written 5'->3'.  Strand `+`: fwd matches at `start` and the reverse complement of rev
+ends at `end`; strand `-` (not with `--no-rc`): the other way round; each primer with at most K mismatches, A <= length <= B,
+every combination a row.  A header row, then rows by (record, pair, strand, start, end):
+
+    pair_id  text_id  strand  start  end  length  fwd_cost  rev_cost
+
+`--seq` appends the product's bytes, reverse-complemented for strand `-`.
 
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
@@ -348,6 +358,73 @@ def count_parser(sub):
     return cp
 
 
+def load_primers(path: str) -> List[Tuple[str, bytes, bytes]]:
+    """PRIMERS of `amplicon`: rows of name<TAB>fwd<TAB>rev (empty lines and lines from `#` on skipped)."""
+    pairs = []
+    with open(path, "rb") as fh:
+        for no, line in enumerate(fh, 1):
+            line = line.rstrip(b"\r\n")
+            if not line or line.startswith(b"#"):
+                continue
+            cols = line.split(b"\t")
+            if len(cols) != 3 or not cols[1] or not cols[2]:
+                raise SystemExit(f"{path}:{no}: a primer row is name<TAB>fwd<TAB>rev")
+            pairs.append((cols[0].decode(), cols[1], cols[2]))
+    return pairs
+
+
+_IUPAC_COMPLEMENT = bytes.maketrans(b"ACTGRYSWKMBDHVNXactgryswkmbdhvnx", b"TGACYRSWMKVHDBNXtgacyrswmkvhdbnx")
+_DNA_COMPLEMENT = bytes.maketrans(b"ACTG", b"TGAC")
+
+
+def product_bytes(alphabet: str, text: bytes, start: int, end: int, strand: int) -> bytes:
+    """A product as `--seq` writes it: text[start:end], reverse-complemented for strand 1 under the alphabet's complement."""
+    seq = bytes(text[start:end])
+    return seq.translate(_DNA_COMPLEMENT if alphabet == "dna" else _IUPAC_COMPLEMENT)[::-1] if strand else seq
+
+
+AMPLICON_HEADER = "pair_id\ttext_id\tstrand\tstart\tend\tlength\tfwd_cost\trev_cost\n"
+
+
+def amplicon_rows(pairs, text_id: str, records, alphabet: str = "iupac", text: bytes = None):
+    """The TSV rows of one record's amplicons (Searcher.hamming_amplicons' array, in its order); `text`: append the product."""
+    rows = []
+    for r in records:
+        start, end, strand = int(r["start"]), int(r["end"]), int(r["strand"])
+        row = f"{pairs[int(r['pair_idx'])][0]}\t{text_id}\t{'-' if strand else '+'}\t{start}\t{end}\t{end - start}\t{int(r['fwd_cost'])}\t{int(r['rev_cost'])}"
+        if text is not None:
+            row += "\t" + product_bytes(alphabet, text, start, end, strand).decode("latin-1")
+        rows.append(row + "\n")
+    return rows
+
+
+def run_amplicon(args, searcher, pairs, out) -> int:
+    out.write(AMPLICON_HEADER[:-1] + ("\tproduct\n" if args.seq else "\n"))
+    primers = [(f, r) for _, f, r in pairs]
+    for path in args.paths:
+        for batch in read_fastx_batches(path, BATCH_BYTES):
+            for i in range(len(batch)):
+                text = batch.sequence(i)
+                records = searcher.hamming_amplicons(primers, text, args.k, args.min_len, args.max_len)
+                out.writelines(amplicon_rows(pairs, batch.id(i), records, args.alphabet, text if args.seq else None))
+    out.flush()
+    return 0
+
+
+def amplicon_parser(sub):
+    cp = sub.add_parser("amplicon", help="write the products of primer pairs (in-silico PCR) as TSV to stdout")
+    cp.add_argument("primers", metavar="PRIMERS", help="TSV of name<TAB>fwd<TAB>rev, both primers 5'->3'")
+    cp.add_argument("paths", metavar="FASTX", nargs="+")
+    cp.add_argument("-k", type=int, required=True, help="mismatches allowed per primer")
+    cp.add_argument("--min-len", type=int, required=True)
+    cp.add_argument("--max-len", type=int, required=True)
+    cp.add_argument("--no-rc", action="store_true", help="strand '+' only: fwd on the forward strand")
+    cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac"], default="iupac")
+    cp.add_argument("--max-n-frac", type=float, default=None, help="drop primer sites whose span holds a larger fraction of N (default: none dropped)")
+    cp.add_argument("--seq", action="store_true", help="append the product's bytes (reverse-complemented for strand '-')")
+    return cp
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m sassy_amd", description=__doc__.split("\n\n")[0])
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -369,7 +446,15 @@ def main(argv=None) -> int:
     add_search_arguments(dp)
     dp.add_argument("paths", nargs="+")
     count_parser(sub)
+    amplicon_parser(sub)
     args = ap.parse_args(argv)
+    if args.cmd == "amplicon":
+        if not 0 <= args.k <= 254:
+            ap.error("amplicon takes 0 <= k <= 254")
+        if not 1 <= args.min_len <= args.max_len <= (1 << 24):
+            ap.error("amplicon takes 1 <= --min-len <= --max-len <= 2^24")
+        searcher = Searcher(args.alphabet, rc=not args.no_rc).with_max_n_frac(args.max_n_frac)
+        return run_amplicon(args, searcher, load_primers(args.primers), sys.stdout)
     if args.cmd == "count":
         if not 0 <= args.k <= 254:
             ap.error("count takes 0 <= k <= 254")

@@ -28,18 +28,7 @@ static_assert((uint32_t)PROFILE_DNA == kHamDna && (uint32_t)PROFILE_IUPAC == kHa
 
 constexpr uint32_t kHamStageBytes = kHamTileBlocks * 64;  // a tile's text
 constexpr uint32_t kHamLdsBudget = 160 * 1024;
-constexpr uint32_t kHamNoFilter = 0xFFFFFFFFu;
-
-// One item: the hits of one pattern in one block.  Laid out as a Candidate so that sort_kernels.hip sorts it by `key`.
-struct HamItem {
-  uint64_t key;   // launch-local pattern index (pattern and strand) << 32 | block
-  uint64_t mask;  // bit i: start 64 block + i is a hit
-};
-static_assert(sizeof(HamItem) == sizeof(Candidate) && offsetof(Candidate, pos) == 0, "items are sorted as candidates");
-
-// per pattern of a launch, kHamTabWords words: rows, offset of its row slots (words) in `rows`, offset of its bytes in `pats`,
-// N threshold (kHamNoFilter: none), pattern index of the call, strand
-constexpr uint32_t kHamTabWords = 8;
+// (HamItem, the pattern table's layout -- kHamTabWords, kHamNoFilter -- and HamPattern: host_internal.h)
 
 struct HamParams {
   const uint8_t* text;
@@ -358,18 +347,13 @@ hipError_t launch_scan(Profile pr, uint32_t ns, const HamParams& H, const ScanPa
               : launch_scan_m<false, false>(pr, ns, H, SP, HamMany{}, HamCounts{}, grid, threads, smem, st);
 }
 
-// One pattern of the call on one strand, as it is scanned.
-struct HamPattern {
-  uint32_t idx, strand;
-  std::vector<uint8_t> bytes;  // strand 1: the reverse complement
-  uint32_t nmax;               // most N a hit's span may hold (kHamNoFilter: no filter)
-};
-
 uint32_t slot_byte(Profile pr, uint8_t c) {  // what a pattern byte's slot is keyed by
   if (pr == PROFILE_DNA) return (c >> 1) & 3u;
   if (pr == PROFILE_IUPAC) return iupac_code(c) & 0x0Fu;
   return pr == PROFILE_ASCII_CI ? fold_ascii(c) : c;
 }
+
+}  // namespace
 
 // A laid-out batch of texts on the device (hamming_many_on_device): d_text is the whole buffer, n its size.
 struct HamTexts {
@@ -378,7 +362,126 @@ struct HamTexts {
   uint64_t longest;  // the batch's longest text
 };
 
-}  // namespace
+// The tables of a launch group (HamRange, host_internal.h): tab, rows and pats built and uploaded, the launch's shape, the
+// item list's sizes.
+static int ham_prepare(sassy_SearcherType* S, HamRange& G) {
+  const Profile pr = S->profile;
+  ScanLane& L = S->lanes[0];
+  const uint32_t np = G.np, ns = G.ns;
+  const long items_sw = S->sw.hamming_items;
+  std::vector<uint32_t>& tab = G.tab;
+  tab.assign((size_t)np * kHamTabWords, 0u);
+  std::vector<uint32_t> rows;
+  std::vector<uint8_t> pats;
+  uint32_t longest = 0;
+  bool n_filter = false;
+  for (uint32_t p = 0; p < np; ++p) {
+    const HamPattern& hp = G.pats[p];
+    const uint32_t m = (uint32_t)hp.bytes.size();
+    longest = std::max(longest, m);
+    const uint32_t nmax = hp.nmax;
+    uint32_t* row = &tab[(size_t)p * kHamTabWords];
+    row[0] = m; row[1] = (uint32_t)rows.size(); row[2] = (uint32_t)pats.size(); row[3] = nmax; row[4] = hp.idx; row[5] = hp.strand;
+    n_filter = n_filter || nmax != kHamNoFilter;
+    rows.resize(rows.size() + (m + 3) / 4, 0u);
+    for (uint32_t j = 0; j < m; ++j) rows[row[1] + (j >> 2)] |= (uint32_t)G.slot_of[slot_byte(pr, hp.bytes[j])] << (8 * (j & 3));
+    pats.insert(pats.end(), hp.bytes.begin(), hp.bytes.end());
+  }
+  G.longest = longest;
+  G.n_filter = n_filter;
+  G.halo = ham_halo_blocks(longest);
+  G.nb = kHamTileBlocks + G.halo;
+  const uint32_t ns_t = pr == PROFILE_DNA ? 4u : (pr == PROFILE_IUPAC || ns <= 16) ? 16u : 64u;
+  const uint32_t per_wave = ham_lds_per_wave(ns_t, G.nb);
+  G.wpg = std::min<uint32_t>(4, kHamLdsBudget / per_wave);
+  G.smem = (size_t)G.wpg * per_wave;
+
+  if (int rc = S->d_ham_tab.reserve(tab.size() + rows.size() + (pats.size() + 3) / 4 + 16)) return rc;
+  G.d_tab = S->d_ham_tab.p;
+  G.d_rows = G.d_tab + tab.size();
+  G.d_pats = reinterpret_cast<uint8_t*>(G.d_rows + rows.size());
+  if (int rc = S->d_ham_count.reserve(16)) return rc;
+  L.h_up_used = 0;
+  if (int rc = L.upload(G.d_tab, tab.data(), tab.size() * 4)) return rc;
+  if (int rc = L.upload(G.d_rows, rows.data(), rows.size() * 4)) return rc;
+  if (int rc = L.upload(G.d_pats, pats.data(), pats.size())) return rc;
+
+  const uint64_t min_cap = (uint64_t)np * kHamTileBlocks;  // one tile always fits
+  G.item_cap = std::max<uint64_t>(items_sw > 0 ? (uint64_t)items_sw : (1u << 16), min_cap);
+  G.max_cap = items_sw > 0 ? G.item_cap : std::max<uint64_t>(min_cap, 1u << 22);
+  G.span_max = std::max<uint64_t>(1, (0x7FFFFFFFull / kHamTileBlocks) / np);  // the counter cannot wrap
+  G.ready = true;
+  return 0;
+}
+
+// One range of a launch group's tiles: the scan, the counter, a list that overflows (a larger list, or a shorter range, and
+// the launch again), the sort by (pattern | strand, block), the items on the host.
+int ham_scan_range(sassy_SearcherType* S, HamRange& G) {
+  if (!G.ready)
+    if (int rc = ham_prepare(S, G)) return rc;
+  const Profile pr = S->profile;
+  hipStream_t st = S->stream;
+  ScanLane& L = S->lanes[0];
+  const bool timed = S->timing >= 1;
+  const uint64_t n_blocks = (G.n + 63) / 64, n_tiles = (n_blocks + kHamTileBlocks - 1) / kHamTileBlocks;
+  const uint32_t np = G.np, wpg = G.wpg;
+  G.span = std::min(G.span, G.span_max);
+  G.overflow = false;
+  G.items.clear();
+  uint32_t count = 0;
+  for (;;) {
+    uint64_t& span = G.span;
+    uint64_t& item_cap = G.item_cap;
+    const uint64_t max_cap = G.max_cap;
+    span = std::min(span, n_tiles - G.tile0);
+    if (int rc = S->d_ham_items.reserve(item_cap)) return rc;
+    HamParams H{};
+    H.text = G.d_text; H.n = G.n; H.n_blocks = n_blocks; H.tile0 = G.tile0; H.n_tiles = span;
+    H.k = G.k; H.n_pat = np; H.halo = G.halo; H.nb = G.nb; H.n_filter = G.n_filter ? 1u : 0u; H.item_cap = (uint32_t)item_cap;
+    H.tab = G.d_tab; H.rows = G.d_rows; H.items = reinterpret_cast<HamItem*>(S->d_ham_items.p); H.item_count = S->d_ham_count.p;
+    HIP_TRY(hipMemsetAsync(S->d_ham_count.p, 0, 4, st));
+    if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
+    const uint32_t grid = (uint32_t)((span + wpg - 1) / wpg);
+    HIP_TRY(launch_scan(pr, G.ns, H, G.SP, G.many ? &G.many->dev : nullptr, nullptr, grid, wpg * 64, G.smem, st));
+    if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
+    HIP_TRY(hipMemcpyAsync(&count, S->d_ham_count.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (timed) {
+      float ms = 0;
+      if (hipEventElapsedTime(&ms, L.ev_a, L.ev_b) == hipSuccess) S->stats.scan_ms += ms;
+    }
+    S->stats.scan_launches += 1;
+    S->stats.grid = grid;
+    if (count <= item_cap) break;
+    // nothing of this launch is used: a larger list, or a shorter range
+    if (item_cap < max_cap && (uint64_t)count <= max_cap) item_cap = std::min<uint64_t>(max_cap, (uint64_t)count + count / 4);
+    else if (item_cap < max_cap) item_cap = max_cap;
+    if (count > item_cap) {
+      if (span <= G.min_span) {  // (never with min_span == 1: one tile always fits)
+        G.overflow = true;
+        G.count = count;
+        return 0;
+      }
+      span = std::max<uint64_t>(G.min_span, std::min<uint64_t>(span - 1, span * item_cap / count));
+    }
+  }
+  G.count = count;
+  S->stats.blocks += std::min<uint64_t>(G.span * kHamTileBlocks, n_blocks - G.tile0 * kHamTileBlocks);
+  S->stats.hit_blocks += count;
+  if (count) {
+    // items by (pattern | strand, block)
+    if (int rc = S->d_ham_sorted.reserve(count)) return rc;
+    const size_t sb = sort_scratch_bytes(count);
+    if (int rc = S->d_ham_sort.reserve(sb)) return rc;
+    int key_bits = 33;
+    while (key_bits < 64 && ((uint64_t)(np - 1) >> (key_bits - 32)) != 0) ++key_bits;
+    HIP_TRY(launch_sort_candidates(S->d_ham_items.p, S->d_ham_sorted.p, count, S->d_ham_sort.p, S->d_ham_sort.cap, st, 0, key_bits));
+    G.items.resize(count);
+    HIP_TRY(hipMemcpyAsync(G.items.data(), S->d_ham_sorted.p, (size_t)count * sizeof(HamItem), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return 0;
+}
 
 // The search proper: refusals are the caller's; d_text is readable up to the next multiple of 64 bytes.  many != nullptr:
 // d_text is a batch of texts; with many->dev.cells the launches reduce into the cells and R stays as it is.  counts != nullptr:
@@ -412,21 +515,18 @@ static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patter
       all.push_back(std::move(rc));
     }
   }
-  const long batch_sw = S->sw.hamming_batch, items_sw = S->sw.hamming_items, records_sw = S->sw.hamming_records;
+  const long batch_sw = S->sw.hamming_batch, records_sw = S->sw.hamming_records;
   const size_t max_batch = batch_sw > 0 ? (size_t)batch_sw : 512;
   const bool timed = S->timing >= 1;
 
   size_t a0 = 0;
   while (a0 < all.size()) {
     // ---- a launch's patterns: as many as share the slots (Ascii: at most kMaxSlots distinct bytes) ----
-    ScanParams SP{};
-    uint32_t ns = pr == PROFILE_DNA ? 4u : pr == PROFILE_IUPAC ? 16u : 0u;
-    if (pr == PROFILE_IUPAC)
-      for (uint32_t s = 0; s < 16; ++s) SP.slot_val[s] = (uint8_t)s;  // a slot per base set
-    int slot_of[256];
-    std::fill(slot_of, slot_of + 256, -1);
-    if (!is_ascii(pr))
-      for (uint32_t s = 0; s < ns; ++s) slot_of[s] = (int)s;
+    HamRange G;
+    ham_slots_init(pr, G);
+    uint32_t& ns = G.ns;
+    int* slot_of = G.slot_of;
+    ScanParams& SP = G.SP;
     size_t a1 = a0;
     while (a1 < all.size() && a1 - a0 < max_batch) {
       uint32_t add = 0;
@@ -447,44 +547,19 @@ static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patter
     SP.nslots = ns;
     SP.profile = (uint32_t)pr;
     const uint32_t np = (uint32_t)(a1 - a0);
-    std::vector<uint32_t> tab((size_t)np * kHamTabWords, 0u), rows;
-    std::vector<uint8_t> pats;
-    uint32_t longest = 0;
-    bool n_filter = false;
-    for (uint32_t p = 0; p < np; ++p) {
-      const HamPattern& hp = all[a0 + p];
-      const uint32_t m = (uint32_t)hp.bytes.size();
-      longest = std::max(longest, m);
-      const uint32_t nmax = hp.nmax;
-      uint32_t* row = &tab[(size_t)p * kHamTabWords];
-      row[0] = m; row[1] = (uint32_t)rows.size(); row[2] = (uint32_t)pats.size(); row[3] = nmax; row[4] = hp.idx; row[5] = hp.strand;
-      n_filter = n_filter || nmax != kHamNoFilter;
-      rows.resize(rows.size() + (m + 3) / 4, 0u);
-      for (uint32_t j = 0; j < m; ++j) rows[row[1] + (j >> 2)] |= (uint32_t)slot_of[slot_byte(pr, hp.bytes[j])] << (8 * (j & 3));
-      pats.insert(pats.end(), hp.bytes.begin(), hp.bytes.end());
-    }
-    const uint32_t halo = ham_halo_blocks(longest), nb = kHamTileBlocks + halo;
-    const uint32_t ns_t = pr == PROFILE_DNA ? 4u : (pr == PROFILE_IUPAC || ns <= 16) ? 16u : 64u;
-    const uint32_t per_wave = ham_lds_per_wave(ns_t, nb);
-    const uint32_t wpg = std::min<uint32_t>(4, kHamLdsBudget / per_wave);
-    const size_t smem = (size_t)wpg * per_wave;
-
-    if (int rc = S->d_ham_tab.reserve(tab.size() + rows.size() + (pats.size() + 3) / 4 + 16)) return rc;
-    uint32_t* d_tab = S->d_ham_tab.p;
-    uint32_t* d_rows = d_tab + tab.size();
-    uint8_t* d_pats = reinterpret_cast<uint8_t*>(d_rows + rows.size());
-    if (int rc = S->d_ham_count.reserve(16)) return rc;
-    L.h_up_used = 0;
-    if (int rc = L.upload(d_tab, tab.data(), tab.size() * 4)) return rc;
-    if (int rc = L.upload(d_rows, rows.data(), rows.size() * 4)) return rc;
-    if (int rc = L.upload(d_pats, pats.data(), pats.size())) return rc;
+    G.pats = &all[a0]; G.np = np;
+    G.d_text = d_text; G.n = n; G.k = k; G.many = many;
+    if (int rc = ham_prepare(S, G)) return rc;
+    const uint32_t longest = G.longest, halo = G.halo, nb = G.nb, wpg = G.wpg;
+    const bool n_filter = G.n_filter;
+    const size_t smem = G.smem;
+    uint32_t* d_tab = G.d_tab;
+    uint32_t* d_rows = G.d_rows;
+    uint8_t* d_pats = G.d_pats;
 
     // ---- the text in ranges of tiles: a range whose items overflow the list is cut down and launched again ----
-    const uint64_t min_cap = (uint64_t)np * kHamTileBlocks;  // one tile always fits
-    uint64_t item_cap = std::max<uint64_t>(items_sw > 0 ? (uint64_t)items_sw : (1u << 16), min_cap);
-    const uint64_t max_cap = items_sw > 0 ? item_cap : std::max<uint64_t>(min_cap, 1u << 22);
     const uint64_t rec_cap = records_sw > 0 ? (uint64_t)records_sw : (1u << 20);
-    const uint64_t span_max = std::max<uint64_t>(1, (0x7FFFFFFFull / kHamTileBlocks) / np);  // the counter cannot wrap
+    const uint64_t span_max = G.span_max;
     if (counts || (many && many->dev.cells)) {  // counts, best pattern: nothing is listed, one launch takes every tile
       HamParams H{};
       H.text = d_text; H.n = n; H.n_blocks = n_blocks; H.tile0 = 0; H.n_tiles = n_tiles;
@@ -506,50 +581,18 @@ static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patter
       a0 = a1;
       continue;
     }
-    uint64_t tile0 = 0, span = std::min(n_tiles, span_max);
+    uint64_t tile0 = 0;
+    G.span = std::min(n_tiles, span_max);
     size_t first_row = R->matches.size();
     uint32_t ranges = 0;
     while (tile0 < n_tiles) {
-      span = std::min(span, n_tiles - tile0);
-      if (int rc = S->d_ham_items.reserve(item_cap)) return rc;
-      HamParams H{};
-      H.text = d_text; H.n = n; H.n_blocks = n_blocks; H.tile0 = tile0; H.n_tiles = span;
-      H.k = k; H.n_pat = np; H.halo = halo; H.nb = nb; H.n_filter = n_filter ? 1u : 0u; H.item_cap = (uint32_t)item_cap;
-      H.tab = d_tab; H.rows = d_rows; H.items = reinterpret_cast<HamItem*>(S->d_ham_items.p); H.item_count = S->d_ham_count.p;
-      HIP_TRY(hipMemsetAsync(S->d_ham_count.p, 0, 4, st));
-      if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
-      const uint32_t grid = (uint32_t)((span + wpg - 1) / wpg);
-      HIP_TRY(launch_scan(pr, ns, H, SP, many ? &many->dev : nullptr, nullptr, grid, wpg * 64, smem, st));
-      if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
-      uint32_t count = 0;
-      HIP_TRY(hipMemcpyAsync(&count, S->d_ham_count.p, 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      if (timed) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, L.ev_a, L.ev_b) == hipSuccess) S->stats.scan_ms += ms;
-      }
-      S->stats.scan_launches += 1;
-      S->stats.grid = grid;
-      if (count > item_cap) {  // nothing of this launch is used: a larger list, or a shorter range
-        if (item_cap < max_cap && (uint64_t)count <= max_cap) item_cap = std::min<uint64_t>(max_cap, (uint64_t)count + count / 4);
-        else if (item_cap < max_cap) item_cap = max_cap;
-        if (count > item_cap) span = std::max<uint64_t>(1, std::min<uint64_t>(span - 1, span * item_cap / count));
-        continue;
-      }
+      G.tile0 = tile0;
+      if (int rc = ham_scan_range(S, G)) return rc;
+      const uint32_t count = G.count;
+      const std::vector<HamItem>& items = G.items;
       ++ranges;
-      S->stats.blocks += std::min<uint64_t>(span * kHamTileBlocks, n_blocks - tile0 * kHamTileBlocks);
-      S->stats.hit_blocks += count;
       if (count) {
-        // items by (pattern | strand, block), then their popcount prefix
-        if (int rc = S->d_ham_sorted.reserve(count)) return rc;
-        const size_t sb = sort_scratch_bytes(count);
-        if (int rc = S->d_ham_sort.reserve(sb)) return rc;
-        int key_bits = 33;
-        while (key_bits < 64 && ((uint64_t)(np - 1) >> (key_bits - 32)) != 0) ++key_bits;
-        HIP_TRY(launch_sort_candidates(S->d_ham_items.p, S->d_ham_sorted.p, count, S->d_ham_sort.p, S->d_ham_sort.cap, st, 0, key_bits));
-        std::vector<HamItem> items(count);
-        HIP_TRY(hipMemcpyAsync(items.data(), S->d_ham_sorted.p, (size_t)count * sizeof(HamItem), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        // the items' popcount prefix
         std::vector<uint32_t> prefix(count);
         uint64_t hits = 0;
         for (uint32_t i = 0; i < count; ++i) {
@@ -598,8 +641,8 @@ static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patter
         }
         S->stats.candidates += hits;
       }
-      tile0 += span;
-      span = std::min(n_tiles, span_max);  // the next range tries everything that is left
+      tile0 += G.span;
+      G.span = std::min(n_tiles, span_max);  // the next range tries everything that is left
     }
     // several ranges: each came sorted by (pattern, strand, start); the ranges ascend, so a stable sort restores the order
     if (ranges > 1)
@@ -712,6 +755,10 @@ static int hamming_refusals(sassy_SearcherType* s, const uint8_t* const* pattern
   }
   SASSY_NO_TICKETS(s);
   return 0;
+}
+
+int hamming_family_refusals(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, size_t k, const char* who) {
+  return hamming_refusals(s, pats, lens, n_pats, k, who);
 }
 
 // both batch entry points: out != nullptr the records, else the per-text outputs

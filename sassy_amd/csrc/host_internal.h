@@ -5,6 +5,7 @@
 //   multi_device.hip  sassy_hip_multi_*: one text over several devices inside one process
 //   hamming.hip       sassy_hip_search_hamming, _search_hamming_many, _hamming_best_pattern, _hamming_counts(_many): the Hamming scan and emit kernels
 //                     with their drivers and entry points
+//   amplicons.hip     sassy_hip_hamming_amplicons: primer pairs joined on the sorted items of the Hamming scan
 //   c_abi.hip         the C-ABI of include/sassy.h + sassy_hip.h, the switch table, synthetic inputs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -690,6 +691,10 @@ struct sassy_SearcherType {
   DevBuf<uint32_t> d_ham_rem;
   DevBuf<unsigned long long> d_ham_cells;
   DevBuf<unsigned long long> d_ham_bins;  // hamming_counts: the copies of the counts table
+  // amplicons (amplicons.hip): the join's pattern table, the partners per left hit, their exclusive scan, a launch's records
+  DevBuf<uint32_t> d_amp_tab, d_amp_counts;
+  DevBuf<uint64_t> d_amp_offs;
+  DevBuf<sassy_hip_Amplicon> d_amp_out;
   DevBuf<uint64_t> d_range;      // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
@@ -1130,7 +1135,70 @@ struct DeviceGuard {
       return fail(SASSY_HIP_EUNSUPPORTED, "SASSY_HIP_LINE_SPANS is a flag of sassy_hip_search only");                    \
   } while (0)
 
+// ---- the Hamming scan of one launch group over one range of tiles (hamming.hip), shared with amplicons.hip ----
+// One item: the hits of one pattern in one block.  Laid out as a Candidate so that sort_kernels.hip sorts it by `key`.
+struct HamItem {
+  uint64_t key;   // launch-local pattern index (pattern and strand) << 32 | block
+  uint64_t mask;  // bit i: start 64 block + i is a hit
+};
+static_assert(sizeof(HamItem) == sizeof(Candidate) && offsetof(Candidate, pos) == 0, "items are sorted as candidates");
+// per pattern of a launch, kHamTabWords words: rows, offset of its row slots (words) in `rows`, offset of its bytes in `pats`,
+// N threshold (kHamNoFilter: none), pattern index of the call, strand
+constexpr uint32_t kHamTabWords = 8;
+constexpr uint32_t kHamNoFilter = 0xFFFFFFFFu;
+// One pattern of the call on one strand, as it is scanned.
+struct HamPattern {
+  uint32_t idx, strand;
+  std::vector<uint8_t> bytes;  // strand 1: the reverse complement
+  uint32_t nmax;               // most N a hit's span may hold (kHamNoFilter: no filter)
+};
+struct HamTexts;  // (hamming.hip: a laid-out batch of texts)
+// A launch group and one range of its tiles.  The caller names the group (pats, np, the slots), the text and the range; the
+// first call builds and uploads the group's tables and sizes the item list, every call scans [tile0, tile0 + span) -- cut
+// down and launched again while its items overflow the list -- and leaves the items sorted by (pattern | strand, block) in
+// S->d_ham_sorted and in `items`.
+struct HamRange {
+  const HamPattern* pats = nullptr;
+  uint32_t np = 0;
+  ScanParams SP{};
+  uint32_t ns = 0;       // slots in use
+  int slot_of[256];      // slot of a pattern byte's key (slot_byte), -1: none
+  const uint8_t* d_text = nullptr;
+  uint64_t n = 0;
+  uint32_t k = 0;
+  const HamTexts* many = nullptr;
+  uint64_t min_span = 1;  // a range is never cut below this many tiles: `overflow` instead
+  // the group's tables, by the first call
+  bool ready = false;
+  std::vector<uint32_t> tab;
+  uint32_t *d_tab = nullptr, *d_rows = nullptr;
+  uint8_t* d_pats = nullptr;
+  uint32_t longest = 0, halo = 0, nb = 0, wpg = 0;
+  size_t smem = 0;
+  bool n_filter = false;
+  uint64_t item_cap = 0, max_cap = 0, span_max = 0;
+  // the range: span in = the tiles wanted, out = the tiles scanned
+  uint64_t tile0 = 0, span = 0;
+  uint32_t count = 0;          // its items
+  std::vector<HamItem> items;  // sorted
+  bool overflow = false;       // min_span tiles do not fit the list at its cap: nothing was scanned
+};
+// the slots of a launch before its first pattern: Dna and Iupac have theirs, Ascii patterns add their bytes
+inline void ham_slots_init(Profile pr, HamRange& G) {
+  G.SP = ScanParams{};
+  G.ns = pr == PROFILE_DNA ? 4u : pr == PROFILE_IUPAC ? 16u : 0u;
+  if (pr == PROFILE_IUPAC)
+    for (uint32_t s = 0; s < 16; ++s) G.SP.slot_val[s] = (uint8_t)s;  // a slot per base set
+  std::fill(G.slot_of, G.slot_of + 256, -1);
+  if (!is_ascii(pr))
+    for (uint32_t s = 0; s < G.ns; ++s) G.slot_of[s] = (int)s;
+}
+
 // ---- functions one unit calls in another ----
+// hamming.hip
+int ham_scan_range(sassy_SearcherType* S, HamRange& G);
+// what every Hamming entry point refuses, before any device work (hamming_refusals)
+int hamming_family_refusals(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, size_t k, const char* who);
 // line_index.hip
 int line_spans_on_device(sassy_SearcherType* S, const uint8_t* d_text, uint64_t text_len, const uint64_t* first, const uint64_t* last,
                          size_t n, sassy_hip_LineSpan* out);
