@@ -36,6 +36,20 @@ pub struct Amplicon {
     pub rev_cost: u8,
     _pad: u8,
 }
+/// One record of an unwrapped FASTA chunk (include/sassy_hip.h: sassy_hip_FastaRecord, 32 bytes): the id in the raw bytes,
+/// the sequence in the device text.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct FastaRecord {
+    pub id_start: u64,
+    pub id_len: u64,
+    pub seq_start: u64,
+    pub seq_len: u64,
+}
+#[repr(C)]
+pub struct RawFasta {
+    _p: [u8; 0],
+}
 #[repr(C)]
 struct RawSearcher {
     _p: [u8; 0],
@@ -94,6 +108,13 @@ extern "C" {
                                    rev_lens: *const usize, n_pairs: usize, text: *const u8, text_len: usize, k: usize, min_len: u64,
                                    max_len: u64, flags: u32, out: *mut *mut Amplicon, n_out: *mut usize) -> c_int;
     fn sassy_hip_amplicons_free(p: *mut Amplicon);
+    // FASTA unwrap on the device: raw bytes in, a device text per record and a host table out (flags: TEXT_ON_DEVICE)
+    pub fn sassy_hip_fasta_unwrap(raw: *const u8, n: u64, flags: u32, hip_stream: *mut std::ffi::c_void, out: *mut *mut RawFasta) -> c_int;
+    pub fn sassy_hip_fasta_n_records(f: *const RawFasta) -> u64;
+    pub fn sassy_hip_fasta_records(f: *const RawFasta) -> *const FastaRecord;
+    pub fn sassy_hip_fasta_text(f: *const RawFasta) -> *mut std::ffi::c_void;
+    pub fn sassy_hip_fasta_text_bytes(f: *const RawFasta) -> u64;
+    pub fn sassy_hip_fasta_free(f: *mut RawFasta);
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

@@ -459,6 +459,37 @@ int sassy_hip_hamming_amplicons(sassy_SearcherType *s, const uint8_t *const *fwd
                                 sassy_hip_Amplicon **out, size_t *n_out);
 void sassy_hip_amplicons_free(sassy_hip_Amplicon *p);
 
+/* FASTA unwrap on the device (sassy_amd/csrc/fasta_unwrap.hip): the raw bytes of a chunk of FASTA in, every
+ * record's sequence out as a device-resident text that the one-text entry points take with SASSY_HIP_TEXT_ON_DEVICE, plus a
+ * small host table.  `raw` holds n bytes, is empty or begins with '>', and holds whole records.  The definition is the
+ * line-by-line parse: split at '\n' (a final empty piece is no line), strip one trailing '\r' from each line; a line that begins
+ * with '>' opens a record whose id is the rest of that line; every other line is appended to the open record's sequence.
+ * Nothing else is touched (case, N, a '>' that does not begin a line, a '\r' elsewhere).
+ *  - the text: one device buffer of sassy_hip_fasta_text_bytes bytes; record r's sequence lies at [seq_start, seq_start +
+ *    seq_len), seq_start a multiple of 64; the bytes between the sequences are 0 and 64 zero bytes follow the last one (they
+ *    are counted in text_bytes); an empty record takes no block and shares its start with the next record;
+ *  - the table: one sassy_hip_FastaRecord per record in file order; id_start / id_len index `raw` (the id without '>' and
+ *    without the line's trailing '\r'), seq_start / seq_len the text;
+ *  - flags: SASSY_HIP_TEXT_ON_DEVICE: `raw` is a device pointer, 16-byte aligned and readable up to the next multiple of 64
+ *    behind n; 0: host bytes, uploaded once.  Takes no searcher: it runs on the calling thread's current device, on
+ *    `hip_stream` (NULL: the default stream), and returns when the table is on the host;
+ *  - refused before any device work: null arguments with n > 0, an unknown flag bit, a device pointer that is not 16-byte
+ *    aligned, a first byte that is not '>' (SASSY_HIP_EINVAL; a device-resident first byte is read back first); more than
+ *    2^31 - 1 super-tiles of 64 KiB, i.e. n > 2^47 - 65536 (SASSY_HIP_EUNSUPPORTED); no device SASSY_HIP_ENODEVICE.  More
+ *    than 2^32 - 1 records is SASSY_HIP_EUNSUPPORTED as well, known once the count pass has run.
+ * The handle owns the text: sassy_hip_fasta_free releases it (the text of every record with it). */
+typedef struct sassy_hip_FastaRecord {
+  uint64_t id_start, id_len;   /* in the raw bytes */
+  uint64_t seq_start, seq_len; /* in the device text */
+} sassy_hip_FastaRecord;
+typedef struct sassy_hip_Fasta sassy_hip_Fasta;
+int sassy_hip_fasta_unwrap(const void *raw, uint64_t n, uint32_t flags, void *hip_stream, sassy_hip_Fasta **out);
+uint64_t sassy_hip_fasta_n_records(const sassy_hip_Fasta *f);
+const sassy_hip_FastaRecord *sassy_hip_fasta_records(const sassy_hip_Fasta *f); /* NULL without records */
+void *sassy_hip_fasta_text(const sassy_hip_Fasta *f);                           /* the device pointer */
+uint64_t sassy_hip_fasta_text_bytes(const sassy_hip_Fasta *f);
+void sassy_hip_fasta_free(sassy_hip_Fasta *f);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is

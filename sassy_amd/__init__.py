@@ -156,6 +156,8 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_search_hamming", "sassy_hip_search_hamming_many", "sassy_hip_hamming_best_pattern",
     "sassy_hip_hamming_counts", "sassy_hip_hamming_counts_many",
     "sassy_hip_hamming_amplicons", "sassy_hip_amplicons_free",
+    "sassy_hip_fasta_unwrap", "sassy_hip_fasta_n_records", "sassy_hip_fasta_records", "sassy_hip_fasta_text",
+    "sassy_hip_fasta_text_bytes", "sassy_hip_fasta_free",
 ]
 
 _lib = None
@@ -362,6 +364,18 @@ def lib():
         L.sassy_hip_line_tile.argtypes = []
         L.sassy_hip_line_span_times.restype = C.c_int
         L.sassy_hip_line_span_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sassy_hip_fasta_unwrap.restype = C.c_int
+    L.sassy_hip_fasta_unwrap.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.POINTER(vp)]
+    L.sassy_hip_fasta_n_records.restype = C.c_uint64
+    L.sassy_hip_fasta_n_records.argtypes = [vp]
+    L.sassy_hip_fasta_records.restype = vp
+    L.sassy_hip_fasta_records.argtypes = [vp]
+    L.sassy_hip_fasta_text.restype = vp
+    L.sassy_hip_fasta_text.argtypes = [vp]
+    L.sassy_hip_fasta_text_bytes.restype = C.c_uint64
+    L.sassy_hip_fasta_text_bytes.argtypes = [vp]
+    L.sassy_hip_fasta_free.restype = None
+    L.sassy_hip_fasta_free.argtypes = [vp]
     L.sassy_hip_malloc.restype = vp
     L.sassy_hip_malloc.argtypes = [sz]
     L.sassy_hip_free.restype = None
@@ -421,6 +435,12 @@ def amplicon_dtype():
     import numpy as np
     return np.dtype([("start", "<u8"), ("end", "<u8"), ("pair_idx", "<u4"), ("strand", "u1"), ("fwd_cost", "u1"), ("rev_cost", "u1"),
                      ("pad_", "u1")])
+
+
+def fasta_record_dtype():
+    """numpy view of include/sassy_hip.h: sassy_hip_FastaRecord (32 bytes)."""
+    import numpy as np
+    return np.dtype([("id_start", "<u8"), ("id_len", "<u8"), ("seq_start", "<u8"), ("seq_len", "<u8")])
 
 
 def line_tile() -> int:
@@ -1519,6 +1539,106 @@ class DeviceBuffer:
         if self.ptr:
             lib().sassy_hip_free(self.ptr)
             self.ptr = None
+
+    def __del__(self):
+        self.free()
+
+
+class DeviceText:
+    """`nbytes` device-resident bytes at `ptr` as a `text` argument: the parts of a device tensor the searcher reads (data_ptr,
+    numel, is_cuda, a 1-byte dtype).  The pointer is 16-byte aligned and readable up to the next multiple of 64 behind the
+    text (SASSY_HIP_TEXT_ON_DEVICE); `owner` is whatever keeps the memory alive."""
+
+    class _Byte:
+        itemsize = 1
+
+    dtype = _Byte()
+    is_cuda = True
+
+    def __init__(self, ptr: int, nbytes: int, owner=None):
+        self._p, self._n, self._owner = int(ptr or 0), int(nbytes), owner
+
+    def data_ptr(self) -> int:
+        return self._p
+
+    def numel(self) -> int:
+        return self._n
+
+    def is_contiguous(self) -> bool:
+        return True
+
+    def download(self) -> bytes:
+        if not self._n:
+            return b""
+        buf = C.create_string_buffer(self._n)
+        _check(lib().sassy_hip_memcpy_d2h(buf, self._p, self._n))
+        return buf.raw
+
+
+class DeviceFasta:
+    """A chunk of FASTA unwrapped on the device (sassy_hip_fasta_unwrap): `raw` -- bytes, a numpy uint8 array, or a device
+    text (DeviceText, a torch tensor) -- holds whole records and is empty or begins with '>'.  Headers and line ends are
+    dropped by kernels; record i's sequence is `text(i)`, a device view that every `text` argument accepting device texts
+    takes without a copy; only the record table comes back: `id_starts` / `id_lens` index `raw`, `seq_starts` (multiples of
+    64) / `seq_lens` the device buffer.  The definition is the line-by-line parse (tests/helpers/fasta_ref.py)."""
+
+    def __init__(self, raw, stream: int = 0):
+        import numpy as np
+        addr, n, keep, on_dev = _ptr_len(raw)
+        self._raw, self._raw_on_device = keep, on_dev
+        self._h = None
+        out = C.c_void_p()
+        _check(lib().sassy_hip_fasta_unwrap(addr, n, TEXT_ON_DEVICE if on_dev else 0, stream or None, C.byref(out)))
+        self._h = out
+        count = int(lib().sassy_hip_fasta_n_records(out))
+        dt = fasta_record_dtype()
+        table = (np.frombuffer(_bytes_at(lib().sassy_hip_fasta_records(out), count * dt.itemsize), dtype=dt) if count
+                 else np.zeros(0, dtype=dt))
+        self.id_starts, self.id_lens = table["id_start"].copy(), table["id_len"].copy()
+        self.seq_starts, self.seq_lens = table["seq_start"].copy(), table["seq_len"].copy()
+        self.ptr = int(lib().sassy_hip_fasta_text(out) or 0)
+        self.text_bytes = int(lib().sassy_hip_fasta_text_bytes(out))
+
+    def __len__(self) -> int:
+        return len(self.id_starts)
+
+    def _live(self):
+        if self._h is None:
+            raise SassyHipError("DeviceFasta: freed")
+
+    def id(self, i: int) -> str:
+        a, n = int(self.id_starts[i]), int(self.id_lens[i])
+        if self._raw is None:
+            raise SassyHipError("DeviceFasta: the raw bytes were let go (the ids are with whoever released them)")
+        if self._raw_on_device:
+            return DeviceText(self._raw.data_ptr() + a, n).download().decode()
+        if isinstance(self._raw, bytes):
+            return self._raw[a:a + n].decode()
+        return self._raw[a:a + n].tobytes().decode()
+
+    def text(self, i: int) -> DeviceText:
+        """Record i's sequence on the device."""
+        self._live()
+        return DeviceText(self.ptr + int(self.seq_starts[i]), int(self.seq_lens[i]), owner=self)
+
+    def download(self, i: int, start: int = 0, end: Optional[int] = None) -> bytes:
+        """Record i's sequence, or its bytes [start, end), on the host."""
+        self._live()
+        n = int(self.seq_lens[i])
+        end = n if end is None else min(int(end), n)
+        start = max(0, int(start))
+        if end <= start:
+            return b""
+        return DeviceText(self.ptr + int(self.seq_starts[i]) + start, end - start).download()
+
+    def free(self):
+        if getattr(self, "_h", None) is not None:
+            try:
+                lib().sassy_hip_fasta_free(self._h)
+            except Exception:  # interpreter shutdown
+                pass
+            self._h = None
+            self.ptr = 0
 
     def __del__(self):
         self.free()

@@ -39,6 +39,8 @@ FASTA / FASTQ file or a file with one pattern per line (ids 1, 2, ...).  Forward
     pat_id  strand  n_0 ... n_K
 
 `--per-record` writes the rows per record instead (one call per record: the per-chromosome table), `text_id` in front.
+`--device-unwrap` (with `--per-record`, and on `amplicon`; FASTA only) reads the records through `read_fasta_device_batches`:
+the file's bytes go up once, kernels drop headers and line ends, every call gets a device-resident text; the output is the same.
 
 `amplicon PRIMERS FASTX ... -k K --min-len A --max-len B [--no-rc] [-a dna|iupac] [--max-n-frac X] [--seq]` writes which
 products primer pairs make (in-silico PCR) through `Searcher.hamming_amplicons`, one call per FASTX record.  PRIMERS is a TSV
@@ -73,7 +75,7 @@ BATCH_BYTES = 64 << 20  # input bytes per search_many call (a longer record is a
 
 
 # (the reader: sassy_amd/fastx.py -- batches of whole records as one buffer + offsets, numpy over an mmap)
-from .fastx import read_fastx, read_fastx_batches  # noqa: E402,F401
+from .fastx import read_fasta_device_batches, read_fastx, read_fastx_batches  # noqa: E402,F401
 
 
 def load_patterns(args) -> List[Tuple[str, bytes]]:
@@ -331,6 +333,13 @@ def run_count(args, searcher, patterns, out) -> int:
     out.write(count_header(args.k, args.per_record))
     total = np.zeros((len(pats), 2, args.k + 1), dtype=np.uint64)
     for path in args.paths:
+        if getattr(args, "device_unwrap", False):  # (--per-record only: every record's text stays on the device)
+            for batch in read_fasta_device_batches(path, BATCH_BYTES):
+                for i in range(len(batch)):
+                    out.writelines(count_rows(patterns, searcher.hamming_counts(pats, batch.text(i), args.k), searcher.rc,
+                                              text_id=batch.id(i)))
+                batch.free()
+            continue
         for batch in read_fastx_batches(path, BATCH_BYTES):
             if not len(batch):
                 continue
@@ -355,6 +364,8 @@ def count_parser(sub):
     cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac", "ascii", "ascii_ci"], default="iupac")
     cp.add_argument("--max-n-frac", type=float, default=None, help="drop places whose span holds a larger fraction of N (default: none dropped)")
     cp.add_argument("--per-record", action="store_true", help="rows per record (text_id in front) instead of summed over all records")
+    cp.add_argument("--device-unwrap", action="store_true",
+                    help="with --per-record, FASTA only: upload the file's bytes and drop headers and line ends on the device")
     return cp
 
 
@@ -386,13 +397,16 @@ def product_bytes(alphabet: str, text: bytes, start: int, end: int, strand: int)
 AMPLICON_HEADER = "pair_id\ttext_id\tstrand\tstart\tend\tlength\tfwd_cost\trev_cost\n"
 
 
-def amplicon_rows(pairs, text_id: str, records, alphabet: str = "iupac", text: bytes = None):
-    """The TSV rows of one record's amplicons (Searcher.hamming_amplicons' array, in its order); `text`: append the product."""
+def amplicon_rows(pairs, text_id: str, records, alphabet: str = "iupac", text: bytes = None, span=None):
+    """The TSV rows of one record's amplicons (Searcher.hamming_amplicons' array, in its order); `text`: append the product;
+    `span(start, end)` instead of `text`: the product's bytes from wherever the text lives."""
     rows = []
     for r in records:
         start, end, strand = int(r["start"]), int(r["end"]), int(r["strand"])
         row = f"{pairs[int(r['pair_idx'])][0]}\t{text_id}\t{'-' if strand else '+'}\t{start}\t{end}\t{end - start}\t{int(r['fwd_cost'])}\t{int(r['rev_cost'])}"
-        if text is not None:
+        if span is not None:
+            row += "\t" + product_bytes(alphabet, span(start, end), 0, end - start, strand).decode("latin-1")
+        elif text is not None:
             row += "\t" + product_bytes(alphabet, text, start, end, strand).decode("latin-1")
         rows.append(row + "\n")
     return rows
@@ -402,6 +416,14 @@ def run_amplicon(args, searcher, pairs, out) -> int:
     out.write(AMPLICON_HEADER[:-1] + ("\tproduct\n" if args.seq else "\n"))
     primers = [(f, r) for _, f, r in pairs]
     for path in args.paths:
+        if getattr(args, "device_unwrap", False):  # the records stay on the device; --seq downloads the product spans only
+            for batch in read_fasta_device_batches(path, BATCH_BYTES):
+                for i in range(len(batch)):
+                    records = searcher.hamming_amplicons(primers, batch.text(i), args.k, args.min_len, args.max_len)
+                    span = (lambda a, b, i=i, batch=batch: batch.sequence(i, a, b)) if args.seq else None
+                    out.writelines(amplicon_rows(pairs, batch.id(i), records, args.alphabet, span=span))
+                batch.free()
+            continue
         for batch in read_fastx_batches(path, BATCH_BYTES):
             for i in range(len(batch)):
                 text = batch.sequence(i)
@@ -422,6 +444,8 @@ def amplicon_parser(sub):
     cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac"], default="iupac")
     cp.add_argument("--max-n-frac", type=float, default=None, help="drop primer sites whose span holds a larger fraction of N (default: none dropped)")
     cp.add_argument("--seq", action="store_true", help="append the product's bytes (reverse-complemented for strand '-')")
+    cp.add_argument("--device-unwrap", action="store_true",
+                    help="FASTA only: upload the file's bytes and drop headers and line ends on the device (the same output)")
     return cp
 
 
@@ -460,6 +484,8 @@ def main(argv=None) -> int:
             ap.error("count takes 0 <= k <= 254")
         if args.rc and args.alphabet.startswith("ascii"):
             ap.error("count --rc: there is no reverse complement of plain text")
+        if args.device_unwrap and not args.per_record:
+            ap.error("count --device-unwrap needs --per-record: the batch call takes host texts only")
         searcher = Searcher(args.alphabet, rc=args.rc).with_max_n_frac(args.max_n_frac)
         return run_count(args, searcher, load_count_patterns(args.patterns), sys.stdout)
     if args.cmd == "demux" and args.overhang is not None:

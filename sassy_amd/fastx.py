@@ -13,6 +13,9 @@ out in batches of about 1 MB), here per batch of `batch_bytes`:
 
 Ids stay in the file's bytes until somebody asks for one (`RecordBatch.id(i)`): a read set has a million of them, and
 only the records with a match are printed.
+
+`read_fasta_device_batches` is the same stream of chunks with the unwrap on the device (`sassy_amd.DeviceFasta`): the raw bytes
+of a chunk are uploaded once, and every record comes back as a device-resident text for the one-text calls.  FASTA only.
 """
 from __future__ import annotations
 
@@ -349,6 +352,84 @@ def read_fastx_batches(path: str, batch_bytes: int = 256 << 20) -> Iterator[Reco
             raw2[:rest] = raw[end:have]
             carry = rest
             yield batch
+            if eof and carry == 0:
+                return
+    finally:
+        if path not in ("", "-"):
+            fh.close()
+
+
+class DeviceRecordBatch:
+    """Records of one FASTA chunk, unwrapped on the device (sassy_amd.DeviceFasta): `text(i)` is record i's sequence as a
+    device view for the one-text calls, `sequence(i)` a download of it.  The device buffer lives as long as the batch (or a
+    view taken from it); the ids are copied out of the reader's reused buffer when the batch is made."""
+
+    def __init__(self, fasta, ids: List[bytes]):
+        self.fasta, self._ids = fasta, ids
+
+    def __len__(self) -> int:
+        return len(self.fasta)
+
+    def id(self, i: int) -> str:
+        return self._ids[i].decode()
+
+    def text(self, i: int):
+        return self.fasta.text(i)
+
+    def sequence(self, i: int, start: int = 0, end: Optional[int] = None) -> bytes:
+        return self.fasta.download(i, start, end)
+
+    def free(self):
+        self.fasta.free()
+
+
+def read_fasta_device_batches(path: str, batch_bytes: int = 256 << 20) -> Iterator[DeviceRecordBatch]:
+    """read_fastx_batches for FASTA with the unwrap on the device: the same chunks, cut at the same record boundaries; the raw
+    bytes of a chunk are uploaded once and kernels drop headers and line ends (sassy_hip_fasta_unwrap).  FASTQ is refused:
+    its sequences are single lines, which read_fastx_batches hands out without a copy."""
+    from . import DeviceFasta
+    # (read_fastx_batches' own loop over chunks, FASTA only: that function stays as it is, so the loop is written out here)
+    work = _Work()
+    fill, fh = _sources(path)
+    try:
+        carry = 0
+        eof = False
+        first = True
+        while True:
+            want = batch_bytes
+            m, raw = work.raw_buffer(carry + want, carry)
+            have = carry
+            while True:
+                while have < carry + want and not eof:
+                    got = fill(memoryview(m)[have:carry + want])
+                    if got == 0:
+                        eof = True
+                    have += got
+                if have == 0:
+                    return
+                if first:
+                    head = bytes(raw[:1])
+                    if head == b"@":
+                        raise ValueError(f"{path}: FASTQ needs no unwrap: read it with read_fastx_batches (its sequences are "
+                                         "single lines and are handed out without a copy)")
+                    if head != b">":
+                        raise ValueError(f"{path}: not FASTA (first byte {head!r})")
+                    first = False
+                end = _cut(m, 0, have, False, eof)
+                if end > 0:
+                    break
+                want *= 2  # a record longer than the batch: read on
+                m, raw = work.raw_buffer(carry + want, have)
+            chunk = raw[:end]
+            fasta = DeviceFasta(chunk)
+            ids = [chunk[int(a):int(a) + int(n)].tobytes() for a, n in zip(fasta.id_starts, fasta.id_lens)]
+            fasta._raw = None  # (the reader's buffer is reused: the batch keeps the ids, not the chunk)
+            rest = have - end
+            work.turn ^= 1
+            m2, raw2 = work.raw_buffer(rest + batch_bytes, 0)
+            raw2[:rest] = raw[end:have]
+            carry = rest
+            yield DeviceRecordBatch(fasta, ids)
             if eof and carry == 0:
                 return
     finally:
