@@ -40,6 +40,7 @@
 
 #include "common.h"
 #include "profile_masks.h"
+#include "piece_pair_step.h"
 
 namespace sassy_hip {
 
@@ -1166,7 +1167,9 @@ __global__ __launch_bounds__(256) void filter_dna_multi_kernel(const ScanParams 
             if (d < Q || is_long) {  // wave-uniform
               const uint32_t n0s = (uint32_t)__builtin_amdgcn_sbfe(nb0, d, 1);  // 0 or ~0 (uniform)
               const uint32_t n1s = (uint32_t)__builtin_amdgcn_sbfe(nb1, d, 1);
-              // into vector registers once: v_bitop3 with a scalar source operand issues at half rate
+              // into vector registers once: a vector instruction with a scalar source operand issues every 4.5 cycles
+              // instead of every 2.8 at three waves per SIMD -- v_bitop3_b32, and the v_mov_b32 itself (measured:
+              // tools/ubench/piece_pair.hip, profiles/r12_piece_pair.txt section 1), so the move pays from the second use on
               uint32_t n0, n1;
               asm volatile("v_mov_b32 %0, %1" : "=v"(n0) : "s"(n0s));
               asm volatile("v_mov_b32 %0, %1" : "=v"(n1) : "s"(n1s));
@@ -1710,6 +1713,15 @@ __device__ __forceinline__ bool other_letters16(const uint4 v) { return other_le
 // no tile reads, no bit_plane: the lane loads its 16 bytes back (a few iterations ahead, in registers) and goes on from
 // b0 / b1 as ever; the tile is only the chunk DP's.  A reader sees what the writer computed, tail bytes included, so
 // `interior` plays no part; a wave with nothing to do neither writes nor reads.
+// The pair step takes the rows of 0 / ~0 words of every piece slot from a table the workgroup writes once (Q * 64 bytes of
+// static LDS in front of the launch's own -- in the G = 2 instantiations only, which are the ones that call this); the piece
+// test of a block pair: piece_pair_step.h.  Per block it measured 0.73-0.76 of the time of the form with scalar constants,
+// which G = 1 keeps (profiles/r12_piece_pair.txt section 1).
+template <int Q, int NS>
+__device__ __forceinline__ uint32_t* piece_row_table_lds() {
+  __shared__ __attribute__((aligned(16))) uint32_t tab[piece_row_table_words<Q, NS>()];
+  return tab;
+}
 template <int Q, int NPG, bool FUSED, bool CHECK = false, bool PAIR = false, int DPNS = 4, int G = 1, int SRC = kPlaneRaw>
 // (CHECK: four waves per SIMD are asked for -- left to itself the compiler settles for three, 0.59 instead of 0.52 ms)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || PAIR) ? 4 : 1))) void filter_dna_kernel(const ScanParams P) {
@@ -1746,6 +1758,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   uint32_t seg_it = 0;                             // wave-uniform, even
   bool first_segment = true;
   const uint32_t wave_s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // (G = 2) The piece rows' 0 / ~0 words as a table in LDS, written once: the block-pair test reads them into vector
+  // registers from there (piece_pair_step.h).  Static LDS, Q * 64 bytes in front of the launch's own.
+  if constexpr (G == 2) {
+    kparams_ptr Pt = (kparams_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    piece_row_table_fill<Q, NP>(piece_row_table_lds<Q, NP>(), threadIdx.x, 256u, [&](uint32_t sl, int plane) { return ~Pt->piece_bits[sl][plane]; });
+    __syncthreads();
+  }
   for (;;) {
   kparams_ptr Pk = (kparams_ptr)__builtin_amdgcn_kernarg_segment_ptr();
   uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -1846,6 +1865,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     if (!first_segment) npure = (reinterpret_cast<const uint32_t*>(tile + kSegState) + lane)[384];
   }
 
+  uint32_t bl[G == 2 ? NP : 1] = {}, bh[G == 2 ? NP : 1] = {};  // (G = 2) the pair's second block's masks, until its turn
   uint32_t it = seg_it;
   for (; it < n_iter; ++it) {
     const uint32_t sub = it & 1u;
@@ -1880,6 +1900,48 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     }
     uint2 t0, t1;
     uint32_t dsum = 0;  // (CHECK) != 0: the block holds other letters
+    uint32_t al[NP], ah[NP];
+    if constexpr (G == 2) {
+      // The grouped pass tests the blocks of a pair together, in the pair's first iteration: every constant then serves
+      // four independent accumulators, from a vector register.  The second iteration takes its masks from there and goes
+      // on as ever.  A pair whose second block lies behind n_iter (n_iter is odd when `back` is 1) still has that block's
+      // text in the tile -- the staging reads whole pairs -- or, reading planes, whatever pln[1] held: its masks are never
+      // looked at, its planes are not stored, and nothing is read behind n_iter.
+      if (sub == 0) {
+        PiecePlanes pa, pb;
+        if constexpr (SRC == kPlaneRead) {
+          pa = PiecePlanes{pln[0].x, pln[0].y, pln[0].z, pln[0].w};
+          pb = PiecePlanes{pln[1].x, pln[1].y, pln[1].z, pln[1].w};
+        } else {
+          auto tile_planes = [&](uint32_t half) {
+            const uint32_t hs = (((half << 2) ^ (fsw & 4u)) << 4);
+            uint32_t x[16];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const uint4 v = *reinterpret_cast<const uint4*>(tile + rc[c] + hs);
+              x[4 * c] = v.x; x[4 * c + 1] = v.y; x[4 * c + 2] = v.z; x[4 * c + 3] = v.w;
+            }
+            const uint2 c0 = bit_plane<1>(x), c1 = bit_plane<2>(x);
+            return PiecePlanes{c0.x, c0.y, c1.x, c1.y};
+          };
+          pa = tile_planes(0u);
+          pb = tile_planes(1u);
+          if constexpr (SRC == kPlaneWrite) {
+            uint8_t* const at = const_cast<uint8_t*>(plane_base) + (uint64_t)it * 1024u + lane * 16u;
+            *reinterpret_cast<uint4*>(at) = make_uint4(pa.p0l, pa.p0h, pa.p1l, pa.p1h);
+            if (it + 1u < n_iter) *reinterpret_cast<uint4*>(at + 1024u) = make_uint4(pb.p0l, pb.p0h, pb.p1l, pb.p1h);
+          }
+        }
+        // (the table's address, opaque to the optimiser inside the loop: its words are read here, per pair, not held
+        // in 2 * Q * pieces registers across the loop)
+        uint32_t tab_at = 0;
+        asm volatile("" : "+v"(tab_at));
+        piece_pair_step<Q, NP>(pa, pb, prev0, prev1, piece_row_table_lds<Q, NP>() + tab_at, al, ah, bl, bh);
+      } else {
+#pragma unroll
+        for (int pp = 0; pp < NP; ++pp) { al[pp] = bl[pp]; ah[pp] = bh[pp]; }
+      }
+    } else {
     if constexpr (SRC == kPlaneRead) {
       const uint4 pv = sub ? pln[1] : pln[0];
       t0 = make_uint2(pv.x, pv.y);
@@ -1919,7 +1981,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
       b1[pp] = nb1[pp];
       asm volatile("" : "+s"(b0[pp]), "+s"(b1[pp]));
     }
-    uint32_t al[NP], ah[NP];
 #pragma unroll
     for (int pp = 0; pp < NP; ++pp) { al[pp] = 0xFFFFFFFFu; ah[pp] = 0xFFFFFFFFu; }
 #pragma unroll
@@ -2019,6 +2080,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     }
     prev0 = t0.y;
     prev1 = t1.y;
+    }
     uint32_t hit = 0;
 #pragma unroll
     for (int pp = 0; pp < NP; ++pp) hit |= al[pp] | ah[pp];
