@@ -47,7 +47,7 @@ UNITS = [
     ("fasta_unwrap.hip", "fasta_unwrap.o", []),
     ("c_abi.hip", "c_abi.o", []),
 ]
-HEADERS = ["common.h", "profiles.h", "profile_masks.h", "hamming_step.h", "amplicon_step.h", "fasta_step.h", "piece_pair_step.h", "tiled_step.h", "switches.h", "pass_planner.h", "plane_cache.h", "scan_route.h", "host_internal.h", os.path.join("..", "..", "include", "sassy.h"),
+HEADERS = ["common.h", "profiles.h", "profile_masks.h", "hamming_step.h", "hamming_plan.h", "amplicon_step.h", "fasta_step.h", "piece_pair_step.h", "tiled_step.h", "switches.h", "pass_planner.h", "plane_cache.h", "scan_route.h", "host_internal.h", os.path.join("..", "..", "include", "sassy.h"),
            os.path.join("..", "..", "include", "sassy_hip.h")]
 
 

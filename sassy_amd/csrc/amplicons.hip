@@ -111,122 +111,91 @@ __global__ __launch_bounds__(256) void amp_emit_kernel(const AmpParams A) {
   A.out[t] = o;
 }
 
-struct AmpPair {
-  uint32_t idx;
-  uint32_t nmax_f, nmax_r;
-};
-
-// The join proper: refusals are the caller's; d_text is readable up to the next multiple of 64 bytes.
+// The join proper: refusals are the caller's.
 int amplicons_on_device(sassy_SearcherType* S, const uint8_t* const* fwd, const size_t* fwd_lens, const uint8_t* const* rev,
-                        const size_t* rev_lens, size_t n_pairs, const uint8_t* d_text, uint64_t n, uint32_t k, uint64_t min_len,
-                        uint64_t max_len, std::vector<sassy_hip_Amplicon>& out) {
+                        const size_t* rev_lens, size_t n_pairs, const HamText& text, uint32_t k, uint64_t min_len, uint64_t max_len,
+                        std::vector<sassy_hip_Amplicon>& out) {
   const Profile pr = S->profile;
   hipStream_t st = S->stream;
   ScanLane& L = S->lanes[0];
-  const uint64_t n_blocks = (n + 63) / 64, n_tiles = (n_blocks + kHamTileBlocks - 1) / kHamTileBlocks;
-  if (n_blocks + kHamMaxHalo > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "text too long for the Hamming search (2^32 blocks)");
+  const uint64_t n = text.n, n_tiles = text.n_tiles();
+  if (text.n_blocks() + kHamMaxHalo > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "text too long for the Hamming search (2^32 blocks)");
   S->stats.filtered = 7;
   S->stats.blocks_per_chunk = kHamTileBlocks;
   S->stats.chunks = n_tiles;
 
-  // the pairs that can have a record at all
-  std::vector<AmpPair> pairs;
+  // the pairs that can have a record at all, four scanned patterns each: F, rc(F), R, rc(R)
+  std::vector<HamPattern> primers;
+  auto complement = [pr](uint8_t c) { return complement_char(pr, c); };
   for (size_t i = 0; i < n_pairs; ++i) {
     const uint64_t a = fwd_lens[i], b = rev_lens[i];
     if (n < a || n < b || std::max(a, b) > max_len || std::max(std::max(a, b), min_len) > n) continue;
-    uint32_t nmax[2] = {kHamNoFilter, kHamNoFilter};
-    bool none = false;
-    if (!std::isnan(S->max_n_frac))
-      for (int e = 0; e < 2; ++e) {
-        const uint32_t m = (uint32_t)(e ? b : a);
-        const int64_t c = ham_n_max(m, S->max_n_frac);
-        if (c < 0) none = true;  // not even a site without N passes
-        else if (c < (int64_t)m) nmax[e] = (uint32_t)c;
-      }
-    if (!none) pairs.push_back(AmpPair{(uint32_t)i, nmax[0], nmax[1]});
+    const size_t at = primers.size();
+    if (!ham_add_scanned((uint32_t)i, fwd[i], a, true, S->max_n_frac, n, complement, primers) ||
+        !ham_add_scanned((uint32_t)i, rev[i], b, true, S->max_n_frac, n, complement, primers))
+      primers.resize(at);  // not even a site without N passes
   }
-  auto revcomp = [&](const uint8_t* p, size_t m) {
-    std::vector<uint8_t> r;
-    for (size_t j = m; j-- > 0;) r.push_back(complement_char(pr, p[j]));
-    return r;
-  };
   const uint32_t sides = S->rc ? 2u : 1u;  // left patterns per pair, and partner patterns
-  const long batch_sw = S->sw.hamming_batch, records_sw = S->sw.hamming_records;
-  const size_t max_batch = batch_sw > 0 ? (size_t)batch_sw : 512;
-  const size_t group_pairs = std::max<size_t>(1, max_batch / (2 * sides));  // a pair's patterns never straddle two groups
-  const uint64_t rec_cap = records_sw > 0 ? (uint64_t)records_sw : (1u << 20);
+  const size_t group_pairs = ham_group_pairs(ham_batch_patterns(S->sw.hamming_batch), sides), kept = primers.size() / 4;
   const uint64_t min_span = amp_min_span(max_len);
   uint64_t total = 0;  // records of the call; past 2^32 - 1 the ranges are only counted
   bool counting_only = false;
 
-  for (size_t g0 = 0; g0 < pairs.size(); g0 += group_pairs) {
-    const size_t gp = std::min(group_pairs, pairs.size() - g0);
+  for (size_t g0 = 0; g0 < kept; g0 += group_pairs) {
+    const size_t gp = std::min(group_pairs, kept - g0);
     const uint32_t nl = (uint32_t)gp * sides, np = 2 * nl;
-    std::vector<HamPattern> all(np);
+    std::vector<HamPattern> all(np);  // the left patterns F and -- rc -- R, then their partners rc(R) and rc(F)
     for (size_t q = 0; q < gp; ++q) {
-      const AmpPair& P = pairs[g0 + q];
-      const uint8_t *F = fwd[P.idx], *R = rev[P.idx];
-      const size_t a = fwd_lens[P.idx], b = rev_lens[P.idx];
-      all[q * sides] = HamPattern{P.idx, 0, std::vector<uint8_t>(F, F + a), P.nmax_f};
-      all[nl + q * sides] = HamPattern{P.idx, 0, revcomp(R, b), P.nmax_r};
+      const HamPattern* P4 = &primers[4 * (g0 + q)];
+      all[q * sides] = P4[0];
+      all[nl + q * sides] = P4[3];
+      all[nl + q * sides].strand = 0;
       if (S->rc) {
-        all[q * sides + 1] = HamPattern{P.idx, 1, std::vector<uint8_t>(R, R + b), P.nmax_r};
-        all[nl + q * sides + 1] = HamPattern{P.idx, 1, revcomp(F, a), P.nmax_f};
+        all[q * sides + 1] = P4[2];
+        all[q * sides + 1].strand = 1;
+        all[nl + q * sides + 1] = P4[1];
       }
     }
-    HamRange G;
-    ham_slots_init(pr, G);
-    G.SP.nslots = G.ns;
-    G.SP.profile = (uint32_t)pr;
-    G.pats = all.data(); G.np = np;
-    G.d_text = d_text; G.n = n; G.k = k;
-    G.min_span = min_span;
+    HamJob J;
+    J.group = ham_next_group((uint32_t)pr, all, 0, np);  // (Dna and Iupac: every pattern shares the slots)
+    J.pats = all.data(); J.np = np;
+    J.text = text; J.k = k; J.min_span = min_span;
+    HamPrepared P;
+    if (int rc = ham_prepare(S, J, P)) return rc;
     const size_t first_row = out.size();
-    uint32_t ranges = 0;
-    uint64_t tile0 = 0, own_from = 0;
-    for (;;) {
-      G.tile0 = tile0;
-      G.span = n_tiles - tile0;  // everything that is left (ham_scan_range keeps it within what the counter takes)
-      if (int rc = ham_scan_range(S, G)) return rc;
-      const uint64_t t1 = tile0 + G.span;
-      const bool last = t1 >= n_tiles;
-      if (G.overflow || (!last && G.span < min_span))
+    uint64_t own_from = 0;
+    auto per_range = [&](const HamRangeOut& range, uint64_t t1, bool last, uint64_t* next) {
+      if (range.overflow || (!last && range.span < min_span))
         return fail(SASSY_HIP_ENOMEM, "hamming_amplicons: a range of " + std::to_string(min_span) + " tiles (max_len = " + std::to_string(max_len) +
-                                          ") does not fit the item list of " + std::to_string(G.item_cap) + " items (" + std::to_string(G.count) +
+                                          ") does not fit the item list of " + std::to_string(P.item_cap) + " items (" + std::to_string(range.count) +
                                           " items; option hamming_items)");
-      ++ranges;
-      const uint32_t count = G.count;
-      const std::vector<HamItem>& items = G.items;
+      const uint32_t count = range.count;
       // every pattern's run of items, the popcount prefix
-      std::vector<uint32_t> run(np + 1, count), prefix((size_t)count + 1);
+      std::vector<uint32_t> run(np + 1, count), prefix;
       uint64_t hits = 0;
-      for (uint32_t i = count; i-- > 0;) run[(uint32_t)(items[i].key >> 32)] = i;
+      for (uint32_t i = count; i-- > 0;) run[(uint32_t)(range.items[i].key >> 32)] = i;
       for (uint32_t p = np; p-- > 0;) run[p] = std::min(run[p], run[p + 1]);  // (a pattern without items: an empty run)
-      for (uint32_t i = 0; i < count; ++i) {
-        prefix[i] = (uint32_t)hits;
-        hits += (uint64_t)__builtin_popcountll(items[i].mask);
-      }
-      if (hits > 0xFFFFFFFFull) return fail(SASSY_HIP_ENOMEM, "hamming_amplicons: more than 2^32 primer sites in one range (" + std::to_string(hits) + ")");
-      prefix[count] = (uint32_t)hits;
+      if (!ham_prefix(range.items, 0, prefix, &hits))
+        return fail(SASSY_HIP_ENOMEM, "hamming_amplicons: more than 2^32 primer sites in one range (" + std::to_string(hits) + ")");
       const uint32_t n_left_items = run[nl], n_left = prefix[n_left_items];
       if (n_left != 0 && n_left_items != count) {
         std::vector<uint32_t> tab((size_t)np * kAmpTabWords, 0u);
         for (uint32_t p = 0; p < nl; ++p) {
           uint32_t* row = &tab[(size_t)p * kAmpTabWords];
           const uint32_t q = nl + p;  // its partner
-          row[0] = G.tab[(size_t)p * kHamTabWords]; row[1] = G.tab[(size_t)p * kHamTabWords + 2];
+          row[0] = P.t.tab[(size_t)p * kHamTabWords]; row[1] = P.t.tab[(size_t)p * kHamTabWords + 2];
           row[2] = run[q]; row[3] = run[q + 1];
           row[4] = all[p].idx; row[5] = all[p].strand;
-          row[6] = G.tab[(size_t)q * kHamTabWords]; row[7] = G.tab[(size_t)q * kHamTabWords + 2];
+          row[6] = P.t.tab[(size_t)q * kHamTabWords]; row[7] = P.t.tab[(size_t)q * kHamTabWords + 2];
         }
         if (int rc = S->d_amp_tab.reserve(tab.size())) return rc;
-        if (int rc = S->d_ham_prefix.reserve((size_t)count + 1)) return rc;
         if (int rc = S->d_amp_counts.reserve(n_left)) return rc;
         HIP_TRY(hipMemcpyAsync(S->d_amp_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(S->d_ham_prefix.p, prefix.data(), ((size_t)count + 1) * 4, hipMemcpyHostToDevice, st));
+        if (int rc = S->d_ham_prefix.reserve(prefix.size())) return rc;
+        HIP_TRY(hipMemcpyAsync(S->d_ham_prefix.p, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, st));
         AmpParams A{};
-        A.text = d_text; A.items = reinterpret_cast<const HamItem*>(S->d_ham_sorted.p); A.prefix = S->d_ham_prefix.p;
-        A.n_left_items = n_left_items; A.n_left = n_left; A.tab = S->d_amp_tab.p; A.pats = G.d_pats; A.profile = (uint32_t)pr;
+        A.text = text.d_text; A.items = reinterpret_cast<const HamItem*>(S->d_ham_sorted.p); A.prefix = S->d_ham_prefix.p;
+        A.n_left_items = n_left_items; A.n_left = n_left; A.tab = S->d_amp_tab.p; A.pats = P.d_pats; A.profile = (uint32_t)pr;
         A.min_len = min_len; A.max_len = max_len; A.own_from = own_from; A.t1 = t1; A.last = last ? 1u : 0u;
         A.counts = S->d_amp_counts.p;
         hipLaunchKernelGGL(amp_count_kernel, dim3((n_left + 255) / 256), dim3(256), 0, st, A);
@@ -249,12 +218,9 @@ int amplicons_on_device(sassy_SearcherType* S, const uint8_t* const* fwd, const 
         if (recs && !counting_only) {
           if (int rc = S->d_amp_offs.reserve((size_t)n_left + 1)) return rc;
           HIP_TRY(hipMemcpyAsync(S->d_amp_offs.p, offs.data(), ((size_t)n_left + 1) * 8, hipMemcpyHostToDevice, st));
-          const uint64_t batch = std::min<uint64_t>(recs, rec_cap);
-          if (int rc = S->d_amp_out.reserve(batch)) return rc;
-          A.offs = S->d_amp_offs.p;
-          A.out = S->d_amp_out.p;
-          for (uint64_t r0 = 0; r0 < recs; r0 += batch) {
-            const uint32_t cnt = (uint32_t)std::min<uint64_t>(batch, recs - r0);
+          auto reserve = [&](uint64_t batch) { return S->d_amp_out.reserve(batch); };
+          auto emit = [&](uint64_t r0, uint32_t cnt) {
+            A.offs = S->d_amp_offs.p; A.out = S->d_amp_out.p;
             A.first = r0; A.count = cnt;
             hipLaunchKernelGGL(amp_emit_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, A);
             HIP_TRY(hipGetLastError());
@@ -264,20 +230,27 @@ int amplicons_on_device(sassy_SearcherType* S, const uint8_t* const* fwd, const 
             HIP_TRY(hipStreamSynchronize(st));
             for (size_t i = at; i < out.size(); ++i)
               if (out[i].pad_ != 0) return fail(SASSY_HIP_EINVAL, "hamming_amplicons: internal error: a counted partner was not found");
-          }
+            return 0;
+          };
+          if (int rc = ham_emit_batches(S, recs, reserve, emit)) return rc;
         }
         S->stats.candidates += recs;
       }
-      if (last) break;
-      own_from = amp_next_from(own_from, t1, max_len);
-      tile0 = own_from / kAmpTileBytes;  // (beyond this range's first tile: it spans min_span tiles or more)
-    }
+      if (!last) {
+        own_from = amp_next_from(own_from, t1, max_len);
+        *next = own_from / kAmpTileBytes;  // (beyond this range's first tile: it spans min_span tiles or more)
+      }
+      return 0;
+    };
     // several ranges: each came sorted by (pair, strand, start, end); the owned starts ascend from range to range, so a stable
     // sort restores the order
-    if (ranges > 1 && !counting_only)
-      std::stable_sort(out.begin() + (long)first_row, out.end(), [](const sassy_hip_Amplicon& a, const sassy_hip_Amplicon& b) {
-        return a.pair_idx != b.pair_idx ? a.pair_idx < b.pair_idx : a.strand < b.strand;
-      });
+    auto reorder = [&] {
+      if (!counting_only)
+        std::stable_sort(out.begin() + (long)first_row, out.end(), [](const sassy_hip_Amplicon& a, const sassy_hip_Amplicon& b) {
+          return a.pair_idx != b.pair_idx ? a.pair_idx < b.pair_idx : a.strand < b.strand;
+        });
+    };
+    if (int rc = ham_walk_ranges(S, J, P, per_range, reorder)) return rc;
     S->stats.text_bytes += n;
   }
   if (counting_only) return fail(SASSY_HIP_ENOMEM, "hamming_amplicons: more than 2^32 - 1 records (" + std::to_string(total) + ")");
@@ -316,36 +289,21 @@ int sassy_hip_hamming_amplicons(sassy_SearcherType* s, const uint8_t* const* fwd
     pats[2 * i] = fwd[i]; lens[2 * i] = fwd_lens[i];
     pats[2 * i + 1] = rev[i]; lens[2 * i + 1] = rev_lens[i];
   }
-  if (int rc = hamming_family_refusals(s, pats.data(), lens.data(), pats.size(), k, "hamming_amplicons")) return rc;
-  DeviceGuard on_device(s);
-  const double t0 = now_ms();
-  reset_stats(s);
-  if (int rc = s->ensure_device()) return rc;
-  const uint8_t* d_text = static_cast<const uint8_t*>(text);
-  if (flags & SASSY_HIP_TEXT_ON_DEVICE) {
-    if (((uintptr_t)text & 15) != 0) return fail(SASSY_HIP_EINVAL, "device text pointer must be 16-byte aligned");
-  } else if (text_len) {
-    if (int rc = s->d_text.reserve(text_len + 64)) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_text.p, text, text_len, hipMemcpyHostToDevice, s->stream));
-    d_text = s->d_text.p;
-  }
-  size_t longest = 0;
-  for (size_t m : lens) longest = std::max(longest, m);
-  const uint32_t kk = (uint32_t)std::min<size_t>(k, longest);  // k >= m: every start is a site
-  std::vector<sassy_hip_Amplicon> recs;
-  if (int rc = amplicons_on_device(s, fwd, fwd_lens, rev, rev_lens, n_pairs, d_text, text_len, kk, min_len, max_len, recs)) {
-    (void)hipStreamSynchronize(s->stream);
-    return rc;
-  }
-  if (!recs.empty()) {
-    sassy_hip_Amplicon* p = static_cast<sassy_hip_Amplicon*>(malloc(recs.size() * sizeof(sassy_hip_Amplicon)));
-    if (!p) return fail(SASSY_HIP_ENOMEM, "out of host memory (amplicon records)");
-    memcpy(p, recs.data(), recs.size() * sizeof(sassy_hip_Amplicon));
-    *out = p;
-    *n_out = recs.size();
-  }
-  s->stats.total_ms = now_ms() - t0;
-  return 0;
+  if (int rc = hamming_refusals(s, pats.data(), lens.data(), pats.size(), k, "hamming_amplicons")) return rc;
+  return hamming_call(s, lens.data(), lens.size(), k, [&](uint32_t kk) {  // (k >= m: every start is a site)
+    HamText one;
+    if (int rc = ham_one_text(s, text, text_len, flags, &one)) return rc;
+    std::vector<sassy_hip_Amplicon> recs;
+    if (int rc = amplicons_on_device(s, fwd, fwd_lens, rev, rev_lens, n_pairs, one, kk, min_len, max_len, recs)) return rc;
+    if (!recs.empty()) {
+      sassy_hip_Amplicon* p = static_cast<sassy_hip_Amplicon*>(malloc(recs.size() * sizeof(sassy_hip_Amplicon)));
+      if (!p) return fail(SASSY_HIP_ENOMEM, "out of host memory (amplicon records)");
+      memcpy(p, recs.data(), recs.size() * sizeof(sassy_hip_Amplicon));
+      *out = p;
+      *n_out = recs.size();
+    }
+    return 0;
+  });
 }
 
 void sassy_hip_amplicons_free(sassy_hip_Amplicon* p) { free(p); }

@@ -15,6 +15,16 @@
 // the block's minimum (ham_min_cost) goes into one 64-bit cell per text.
 // sassy_hip_hamming_counts / _counts_many: no items either -- the COUNT instantiations fold a wavefront's hits per cost
 // (HamCounter::eq) into a table of 64-bit counters, one atomic per wavefront, pattern and present cost.
+//
+// The host side, behind the kernels.  What needs no device is decided in hamming_plan.h (scanned patterns, launch groups, a
+// group's tables and shape, the overflow step, text batches, count copies, the prefix).  Here:
+//   ham_prepare / launch_range / ham_scan_range   a group's tables uploaded once; the one place that fills HamParams and
+//                    launches; one range of tiles scanned until its items fit the list, sorted, on the host
+//   ham_for_groups   the group loop of the three drivers: hamming_records (lists into a Result, ranges through
+//                    ham_walk_ranges), hamming_cells (best pattern), hamming_add_counts -- each over one HamText, which is
+//                    one device text or one laid-out batch
+//   ham_for_text_batches   the _many calls: one loop over text batches that calls one of the three
+//   hamming_refusals, hamming_count_call and the five entry points, each behind hamming_call (host_internal.h)
 #include "host_internal.h"
 #include "profile_masks.h"
 #include "hamming_step.h"
@@ -26,9 +36,8 @@ static_assert(kHamMaxHalo == (kHamMaxRows - 1 + 63) / 64, "halo of the longest p
 static_assert((uint32_t)PROFILE_DNA == kHamDna && (uint32_t)PROFILE_IUPAC == kHamIupac && (uint32_t)PROFILE_ASCII_CI == kHamAsciiCi,
               "hamming_step.h names the profiles by value");
 
-constexpr uint32_t kHamStageBytes = kHamTileBlocks * 64;  // a tile's text
-constexpr uint32_t kHamLdsBudget = 160 * 1024;
-// (HamItem, the pattern table's layout -- kHamTabWords, kHamNoFilter -- and HamPattern: host_internal.h)
+// (HamItem, the pattern table's layout -- kHamTabWords, kHamNoFilter --, HamPattern, kHamStageBytes, kHamLdsBudget and
+// ham_lds_per_wave: hamming_plan.h)
 
 struct HamParams {
   const uint8_t* text;
@@ -62,11 +71,6 @@ struct HamCounts {
   uint32_t stride;           // k + 1 of the call (the launch's k may be smaller: k >= m is cut to the longest pattern)
   uint32_t copy_mask;        // copies - 1, copies a power of two: a workgroup adds into copy blockIdx.x & copy_mask
 };
-
-// LDS of one wavefront: the staged tile, then (slots + 1) rows of nb masks -- the last row is the N mask --, whole 16 bytes
-__host__ __device__ constexpr uint32_t ham_lds_per_wave(uint32_t slots, uint32_t nb) {
-  return (kHamStageBytes + (slots + 1) * nb * 8u + 15u) & ~15u;
-}
 
 typedef const uint32_t __attribute__((address_space(4)))* ham_u32_ptr;  // scalar reads of wave-uniform tables
 
@@ -347,386 +351,302 @@ hipError_t launch_scan(Profile pr, uint32_t ns, const HamParams& H, const ScanPa
               : launch_scan_m<false, false>(pr, ns, H, SP, HamMany{}, HamCounts{}, grid, threads, smem, st);
 }
 
-uint32_t slot_byte(Profile pr, uint8_t c) {  // what a pattern byte's slot is keyed by
-  if (pr == PROFILE_DNA) return (c >> 1) & 3u;
-  if (pr == PROFILE_IUPAC) return iupac_code(c) & 0x0Fu;
-  return pr == PROFILE_ASCII_CI ? fold_ascii(c) : c;
-}
-
 }  // namespace
 
-// A laid-out batch of texts on the device (hamming_many_on_device): d_text is the whole buffer, n its size.
-struct HamTexts {
-  HamMany dev;
-  uint64_t text0;    // index of the batch's first text in the call
-  uint64_t longest;  // the batch's longest text
-};
-
-// The tables of a launch group (HamRange, host_internal.h): tab, rows and pats built and uploaded, the launch's shape, the
-// item list's sizes.
-static int ham_prepare(sassy_SearcherType* S, HamRange& G) {
-  const Profile pr = S->profile;
+// ---- the device side of the driver: prepare a group, launch a range, scan a range ----
+int ham_prepare(sassy_SearcherType* S, const HamJob& J, HamPrepared& P) {
   ScanLane& L = S->lanes[0];
-  const uint32_t np = G.np, ns = G.ns;
-  const long items_sw = S->sw.hamming_items;
-  std::vector<uint32_t>& tab = G.tab;
-  tab.assign((size_t)np * kHamTabWords, 0u);
-  std::vector<uint32_t> rows;
-  std::vector<uint8_t> pats;
-  uint32_t longest = 0;
-  bool n_filter = false;
-  for (uint32_t p = 0; p < np; ++p) {
-    const HamPattern& hp = G.pats[p];
-    const uint32_t m = (uint32_t)hp.bytes.size();
-    longest = std::max(longest, m);
-    const uint32_t nmax = hp.nmax;
-    uint32_t* row = &tab[(size_t)p * kHamTabWords];
-    row[0] = m; row[1] = (uint32_t)rows.size(); row[2] = (uint32_t)pats.size(); row[3] = nmax; row[4] = hp.idx; row[5] = hp.strand;
-    n_filter = n_filter || nmax != kHamNoFilter;
-    rows.resize(rows.size() + (m + 3) / 4, 0u);
-    for (uint32_t j = 0; j < m; ++j) rows[row[1] + (j >> 2)] |= (uint32_t)G.slot_of[slot_byte(pr, hp.bytes[j])] << (8 * (j & 3));
-    pats.insert(pats.end(), hp.bytes.begin(), hp.bytes.end());
-  }
-  G.longest = longest;
-  G.n_filter = n_filter;
-  G.halo = ham_halo_blocks(longest);
-  G.nb = kHamTileBlocks + G.halo;
-  const uint32_t ns_t = pr == PROFILE_DNA ? 4u : (pr == PROFILE_IUPAC || ns <= 16) ? 16u : 64u;
-  const uint32_t per_wave = ham_lds_per_wave(ns_t, G.nb);
-  G.wpg = std::min<uint32_t>(4, kHamLdsBudget / per_wave);
-  G.smem = (size_t)G.wpg * per_wave;
-
-  if (int rc = S->d_ham_tab.reserve(tab.size() + rows.size() + (pats.size() + 3) / 4 + 16)) return rc;
-  G.d_tab = S->d_ham_tab.p;
-  G.d_rows = G.d_tab + tab.size();
-  G.d_pats = reinterpret_cast<uint8_t*>(G.d_rows + rows.size());
+  P.t = ham_tables((uint32_t)S->profile, J.pats, J.np, J.group, S->sw.hamming_items);
+  const HamTables& T = P.t;
+  memcpy(P.SP.slot_val, J.group.slot_val, sizeof(J.group.slot_val));
+  P.SP.nslots = J.group.ns;
+  P.SP.profile = (uint32_t)S->profile;
+  P.item_cap = T.item_cap;
+  if (int rc = S->d_ham_tab.reserve(T.tab.size() + T.rows.size() + (T.pats.size() + 3) / 4 + 16)) return rc;
+  P.d_tab = S->d_ham_tab.p;
+  P.d_rows = P.d_tab + T.tab.size();
+  P.d_pats = reinterpret_cast<uint8_t*>(P.d_rows + T.rows.size());
   if (int rc = S->d_ham_count.reserve(16)) return rc;
   L.h_up_used = 0;
-  if (int rc = L.upload(G.d_tab, tab.data(), tab.size() * 4)) return rc;
-  if (int rc = L.upload(G.d_rows, rows.data(), rows.size() * 4)) return rc;
-  if (int rc = L.upload(G.d_pats, pats.data(), pats.size())) return rc;
-
-  const uint64_t min_cap = (uint64_t)np * kHamTileBlocks;  // one tile always fits
-  G.item_cap = std::max<uint64_t>(items_sw > 0 ? (uint64_t)items_sw : (1u << 16), min_cap);
-  G.max_cap = items_sw > 0 ? G.item_cap : std::max<uint64_t>(min_cap, 1u << 22);
-  G.span_max = std::max<uint64_t>(1, (0x7FFFFFFFull / kHamTileBlocks) / np);  // the counter cannot wrap
-  G.ready = true;
-  return 0;
+  if (int rc = L.upload(P.d_tab, T.tab.data(), T.tab.size() * 4)) return rc;
+  if (int rc = L.upload(P.d_rows, T.rows.data(), T.rows.size() * 4)) return rc;
+  return L.upload(P.d_pats, T.pats.data(), T.pats.size());
 }
 
-// One range of a launch group's tiles: the scan, the counter, a list that overflows (a larger list, or a shorter range, and
-// the launch again), the sort by (pattern | strand, block), the items on the host.
-int ham_scan_range(sassy_SearcherType* S, HamRange& G) {
-  if (!G.ready)
-    if (int rc = ham_prepare(S, G)) return rc;
-  const Profile pr = S->profile;
+namespace {
+// Where a launch's hits go: into the item list, into the best-pattern cells of a batch's texts, or into a counts table.
+struct HamSink {
+  enum Kind { Items, Cells, Counts } kind;
+  unsigned long long* cells;  // Cells: one per text of the batch (device)
+  HamCounts counts;           // Counts
+};
+
+// One launch over tiles [tile0, tile0 + n_tiles) and the wait for it: the parameters, the event pair of a timed searcher, the
+// stats lines.  Items: the list takes P.item_cap of them and *count is what the launch counted, which goes on past the list.
+int launch_range(sassy_SearcherType* S, const HamJob& J, const HamPrepared& P, uint64_t tile0, uint64_t n_tiles, const HamSink& sink,
+                 uint32_t* count) {
   hipStream_t st = S->stream;
   ScanLane& L = S->lanes[0];
-  const bool timed = S->timing >= 1;
-  const uint64_t n_blocks = (G.n + 63) / 64, n_tiles = (n_blocks + kHamTileBlocks - 1) / kHamTileBlocks;
-  const uint32_t np = G.np, wpg = G.wpg;
-  G.span = std::min(G.span, G.span_max);
-  G.overflow = false;
-  G.items.clear();
-  uint32_t count = 0;
-  for (;;) {
-    uint64_t& span = G.span;
-    uint64_t& item_cap = G.item_cap;
-    const uint64_t max_cap = G.max_cap;
-    span = std::min(span, n_tiles - G.tile0);
-    if (int rc = S->d_ham_items.reserve(item_cap)) return rc;
-    HamParams H{};
-    H.text = G.d_text; H.n = G.n; H.n_blocks = n_blocks; H.tile0 = G.tile0; H.n_tiles = span;
-    H.k = G.k; H.n_pat = np; H.halo = G.halo; H.nb = G.nb; H.n_filter = G.n_filter ? 1u : 0u; H.item_cap = (uint32_t)item_cap;
-    H.tab = G.d_tab; H.rows = G.d_rows; H.items = reinterpret_cast<HamItem*>(S->d_ham_items.p); H.item_count = S->d_ham_count.p;
+  const bool timed = S->timing >= 1, list = sink.kind == HamSink::Items, many = J.text.starts != nullptr;
+  HamParams H{};
+  H.text = J.text.d_text; H.n = J.text.n; H.n_blocks = J.text.n_blocks(); H.tile0 = tile0; H.n_tiles = n_tiles;
+  H.k = J.k; H.n_pat = J.np; H.halo = P.t.halo; H.nb = P.t.nb; H.n_filter = P.t.n_filter ? 1u : 0u;
+  H.tab = P.d_tab; H.rows = P.d_rows;
+  if (list) {
+    H.item_cap = (uint32_t)P.item_cap; H.items = reinterpret_cast<HamItem*>(S->d_ham_items.p); H.item_count = S->d_ham_count.p;
     HIP_TRY(hipMemsetAsync(S->d_ham_count.p, 0, 4, st));
-    if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
-    const uint32_t grid = (uint32_t)((span + wpg - 1) / wpg);
-    HIP_TRY(launch_scan(pr, G.ns, H, G.SP, G.many ? &G.many->dev : nullptr, nullptr, grid, wpg * 64, G.smem, st));
-    if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
-    HIP_TRY(hipMemcpyAsync(&count, S->d_ham_count.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (timed) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, L.ev_a, L.ev_b) == hipSuccess) S->stats.scan_ms += ms;
-    }
-    S->stats.scan_launches += 1;
-    S->stats.grid = grid;
-    if (count <= item_cap) break;
-    // nothing of this launch is used: a larger list, or a shorter range
-    if (item_cap < max_cap && (uint64_t)count <= max_cap) item_cap = std::min<uint64_t>(max_cap, (uint64_t)count + count / 4);
-    else if (item_cap < max_cap) item_cap = max_cap;
-    if (count > item_cap) {
-      if (span <= G.min_span) {  // (never with min_span == 1: one tile always fits)
-        G.overflow = true;
-        G.count = count;
-        return 0;
-      }
-      span = std::max<uint64_t>(G.min_span, std::min<uint64_t>(span - 1, span * item_cap / count));
-    }
   }
-  G.count = count;
-  S->stats.blocks += std::min<uint64_t>(G.span * kHamTileBlocks, n_blocks - G.tile0 * kHamTileBlocks);
+  const HamMany M{J.text.rem, J.text.starts, J.text.n_texts, sink.cells};
+  if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
+  const uint32_t grid = (uint32_t)((n_tiles + P.t.wpg - 1) / P.t.wpg);
+  HIP_TRY(launch_scan(S->profile, J.group.ns, H, P.SP, many ? &M : nullptr, sink.kind == HamSink::Counts ? &sink.counts : nullptr, grid,
+                      P.t.wpg * 64, P.t.smem, st));
+  if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
+  if (list) HIP_TRY(hipMemcpyAsync(count, S->d_ham_count.p, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the next group reuses the pinned upload area)
+  if (timed) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, L.ev_a, L.ev_b) == hipSuccess) S->stats.scan_ms += ms;
+  }
+  S->stats.scan_launches += 1;
+  S->stats.grid = grid;
+  return 0;
+}
+}  // namespace
+
+// One range of a prepared group's tiles, from tile0 to the text's end or as far as the item list holds: the scan, the step
+// after an overflow (hamming_plan.h) and the launch again, the sort by (pattern | strand, block), the items on the host.
+int ham_scan_range(sassy_SearcherType* S, const HamJob& J, HamPrepared& P, uint64_t tile0, HamRangeOut& out) {
+  hipStream_t st = S->stream;
+  const uint64_t n_blocks = J.text.n_blocks();
+  uint64_t span = std::min(J.text.n_tiles() - tile0, P.t.span_max);
+  uint32_t count = 0;
+  out = HamRangeOut{};
+  while (!out.overflow) {
+    if (int rc = S->d_ham_items.reserve(P.item_cap)) return rc;
+    if (int rc = launch_range(S, J, P, tile0, span, HamSink{HamSink::Items, nullptr, {}}, &count)) return rc;
+    const HamStep step = ham_overflow_step(count, P.item_cap, P.t.max_cap, span, J.min_span);
+    P.item_cap = step.item_cap;
+    span = step.span;
+    if (step.what == HamStep::Done) break;
+    out.overflow = step.what == HamStep::Overflow;
+  }
+  out.span = span;
+  out.count = count;
+  if (out.overflow) return 0;
+  S->stats.blocks += std::min<uint64_t>(span * kHamTileBlocks, n_blocks - tile0 * kHamTileBlocks);
   S->stats.hit_blocks += count;
   if (count) {
-    // items by (pattern | strand, block)
     if (int rc = S->d_ham_sorted.reserve(count)) return rc;
-    const size_t sb = sort_scratch_bytes(count);
-    if (int rc = S->d_ham_sort.reserve(sb)) return rc;
+    if (int rc = S->d_ham_sort.reserve(sort_scratch_bytes(count))) return rc;
     int key_bits = 33;
-    while (key_bits < 64 && ((uint64_t)(np - 1) >> (key_bits - 32)) != 0) ++key_bits;
+    while (key_bits < 64 && ((uint64_t)(J.np - 1) >> (key_bits - 32)) != 0) ++key_bits;
     HIP_TRY(launch_sort_candidates(S->d_ham_items.p, S->d_ham_sorted.p, count, S->d_ham_sort.p, S->d_ham_sort.cap, st, 0, key_bits));
-    G.items.resize(count);
-    HIP_TRY(hipMemcpyAsync(G.items.data(), S->d_ham_sorted.p, (size_t)count * sizeof(HamItem), hipMemcpyDeviceToHost, st));
+    out.items.resize(count);
+    HIP_TRY(hipMemcpyAsync(out.items.data(), S->d_ham_sorted.p, (size_t)count * sizeof(HamItem), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
   return 0;
 }
 
-// The search proper: refusals are the caller's; d_text is readable up to the next multiple of 64 bytes.  many != nullptr:
-// d_text is a batch of texts; with many->dev.cells the launches reduce into the cells and R stays as it is.  counts != nullptr:
-// the launches add into the table, nothing is listed and R is not touched (it may be nullptr).
-static int hamming_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
-                             const uint8_t* d_text, uint64_t n, uint32_t k, bool without_trace, sassy_hip_Result* R,
-                             const HamTexts* many = nullptr, const HamCounts* counts = nullptr) {
+namespace {
+// ---- the three drivers: refusals are the caller's ----
+// The loop over launch groups that they share: the patterns as scanned, cut into groups, every group prepared once and
+// handed to per_group(J, P), which scans the whole text.
+template <typename PerGroup>
+int ham_for_groups(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, const HamText& text,
+                   uint32_t k, PerGroup&& per_group) {
   const Profile pr = S->profile;
-  hipStream_t st = S->stream;
-  ScanLane& L = S->lanes[0];
-  const uint64_t n_blocks = (n + 63) / 64, n_tiles = (n_blocks + kHamTileBlocks - 1) / kHamTileBlocks;
-  if (n_blocks + kHamMaxHalo > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "text too long for the Hamming search (2^32 blocks)");
+  if (text.n_blocks() + kHamMaxHalo > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "text too long for the Hamming search (2^32 blocks)");
   S->stats.filtered = 7;
   S->stats.blocks_per_chunk = kHamTileBlocks;
-
-  // the patterns as scanned, in the contract's order: pattern, then + before -
-  std::vector<HamPattern> all;
-  for (size_t i = 0; i < n_patterns; ++i) {
-    const uint32_t m = (uint32_t)pattern_lens[i];
-    uint32_t nmax = kHamNoFilter;
-    if (!std::isnan(S->max_n_frac)) {
-      const int64_t c = ham_n_max(m, S->max_n_frac);
-      if (c < 0) continue;  // not even a span without N passes: the pattern has no hits
-      if (c < (int64_t)m) nmax = (uint32_t)c;
-    }
-    if ((many ? many->longest : n) < m) continue;
-    all.push_back(HamPattern{(uint32_t)i, 0, std::vector<uint8_t>(patterns[i], patterns[i] + m), nmax});
-    if (S->rc) {
-      HamPattern rc{(uint32_t)i, 1, {}, nmax};
-      for (size_t j = m; j-- > 0;) rc.bytes.push_back(complement_char(pr, patterns[i][j]));
-      all.push_back(std::move(rc));
-    }
+  const std::vector<HamPattern> all = ham_scanned_patterns(patterns, pattern_lens, n_patterns, S->rc, S->max_n_frac, text.longest,
+                                                           [pr](uint8_t c) { return complement_char(pr, c); });
+  const size_t max_batch = ham_batch_patterns(S->sw.hamming_batch);
+  for (size_t a0 = 0; a0 < all.size();) {
+    HamJob J;
+    J.group = ham_next_group((uint32_t)pr, all, a0, max_batch);
+    J.pats = &all[a0]; J.np = (uint32_t)(J.group.a1 - a0);
+    J.text = text; J.k = k;
+    HamPrepared P;
+    if (int rc = ham_prepare(S, J, P)) return rc;
+    if (int rc = per_group(J, P)) return rc;
+    S->stats.text_bytes += text.n;
+    a0 = J.group.a1;
   }
-  const long batch_sw = S->sw.hamming_batch, records_sw = S->sw.hamming_records;
-  const size_t max_batch = batch_sw > 0 ? (size_t)batch_sw : 512;
-  const bool timed = S->timing >= 1;
-
-  size_t a0 = 0;
-  while (a0 < all.size()) {
-    // ---- a launch's patterns: as many as share the slots (Ascii: at most kMaxSlots distinct bytes) ----
-    HamRange G;
-    ham_slots_init(pr, G);
-    uint32_t& ns = G.ns;
-    int* slot_of = G.slot_of;
-    ScanParams& SP = G.SP;
-    size_t a1 = a0;
-    while (a1 < all.size() && a1 - a0 < max_batch) {
-      uint32_t add = 0;
-      bool seen[256] = {};
-      if (is_ascii(pr))
-        for (uint8_t c : all[a1].bytes) {
-          const uint32_t key = slot_byte(pr, c);
-          if (slot_of[key] < 0 && !seen[key]) { seen[key] = true; ++add; }
-        }
-      if (ns + add > (uint32_t)kMaxSlots) break;  // (a pattern alone always fits: the caller checked)
-      if (is_ascii(pr))
-        for (uint8_t c : all[a1].bytes) {
-          const uint32_t key = slot_byte(pr, c);
-          if (slot_of[key] < 0) { slot_of[key] = (int)ns; SP.slot_val[ns++] = (uint8_t)key; }
-        }
-      ++a1;
-    }
-    SP.nslots = ns;
-    SP.profile = (uint32_t)pr;
-    const uint32_t np = (uint32_t)(a1 - a0);
-    G.pats = &all[a0]; G.np = np;
-    G.d_text = d_text; G.n = n; G.k = k; G.many = many;
-    if (int rc = ham_prepare(S, G)) return rc;
-    const uint32_t longest = G.longest, halo = G.halo, nb = G.nb, wpg = G.wpg;
-    const bool n_filter = G.n_filter;
-    const size_t smem = G.smem;
-    uint32_t* d_tab = G.d_tab;
-    uint32_t* d_rows = G.d_rows;
-    uint8_t* d_pats = G.d_pats;
-
-    // ---- the text in ranges of tiles: a range whose items overflow the list is cut down and launched again ----
-    const uint64_t rec_cap = records_sw > 0 ? (uint64_t)records_sw : (1u << 20);
-    const uint64_t span_max = G.span_max;
-    if (counts || (many && many->dev.cells)) {  // counts, best pattern: nothing is listed, one launch takes every tile
-      HamParams H{};
-      H.text = d_text; H.n = n; H.n_blocks = n_blocks; H.tile0 = 0; H.n_tiles = n_tiles;
-      H.k = k; H.n_pat = np; H.halo = halo; H.nb = nb; H.n_filter = n_filter ? 1u : 0u; H.item_cap = 0;
-      H.tab = d_tab; H.rows = d_rows; H.items = nullptr; H.item_count = nullptr;
-      if (timed) HIP_TRY(hipEventRecord(L.ev_a, st));
-      const uint32_t grid = (uint32_t)((n_tiles + wpg - 1) / wpg);
-      HIP_TRY(launch_scan(pr, ns, H, SP, many ? &many->dev : nullptr, counts, grid, wpg * 64, smem, st));
-      if (timed) HIP_TRY(hipEventRecord(L.ev_b, st));
-      HIP_TRY(hipStreamSynchronize(st));  // (the next group reuses the pinned upload area)
-      if (timed) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, L.ev_a, L.ev_b) == hipSuccess) S->stats.scan_ms += ms;
-      }
-      S->stats.scan_launches += 1;
-      S->stats.grid = grid;
-      S->stats.blocks += n_blocks;
-      S->stats.text_bytes += n;
-      a0 = a1;
-      continue;
-    }
-    uint64_t tile0 = 0;
-    G.span = std::min(n_tiles, span_max);
-    size_t first_row = R->matches.size();
-    uint32_t ranges = 0;
-    while (tile0 < n_tiles) {
-      G.tile0 = tile0;
-      if (int rc = ham_scan_range(S, G)) return rc;
-      const uint32_t count = G.count;
-      const std::vector<HamItem>& items = G.items;
-      ++ranges;
-      if (count) {
-        // the items' popcount prefix
-        std::vector<uint32_t> prefix(count);
-        uint64_t hits = 0;
-        for (uint32_t i = 0; i < count; ++i) {
-          prefix[i] = (uint32_t)hits;
-          hits += (uint64_t)__builtin_popcountll(items[i].mask);
-        }
-        if (hits > 0xFFFFFFFFull || R->matches.size() + hits > 0xFFFFFFFFull)
-          return fail(SASSY_HIP_ENOMEM, "Hamming search: more than 2^32 records (" + std::to_string(R->matches.size() + hits) + ")");
-        if (int rc = S->d_ham_prefix.reserve(count)) return rc;
-        HIP_TRY(hipMemcpyAsync(S->d_ham_prefix.p, prefix.data(), (size_t)count * 4, hipMemcpyHostToDevice, st));
-        // records in batches of the record block
-        const uint32_t stride = without_trace ? 0u : 2u * longest + 8u;
-        const uint64_t batch = std::min<uint64_t>(hits, rec_cap);
-        if (int rc = L.d_trace.reserve(batch)) return rc;
-        if (stride)
-          if (int rc = L.d_str.reserve(batch * stride)) return rc;
-        std::vector<MatchOut> rows_h;
-        std::vector<char> strs_h;
-        for (uint64_t r0 = 0; r0 < hits; r0 += batch) {
-          const uint32_t cnt = (uint32_t)std::min<uint64_t>(batch, hits - r0);
-          EmitParams E{};
-          E.text = d_text; E.items = reinterpret_cast<const HamItem*>(S->d_ham_sorted.p); E.prefix = S->d_ham_prefix.p; E.n_items = count;
-          E.first = (uint32_t)r0; E.count = cnt; E.tab = d_tab; E.pats = d_pats; E.profile = (uint32_t)pr; E.str_stride = stride;
-          E.out = L.d_trace.p; E.strs = reinterpret_cast<char*>(L.d_str.p);
-          if (many) { E.starts = many->dev.starts; E.n_texts = many->dev.n_texts; E.text0 = many->text0; }
-          hipLaunchKernelGGL(ham_emit_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, E);
-          HIP_TRY(hipGetLastError());
-          rows_h.resize(cnt);
-          if (int rc = L.download(rows_h.data(), L.d_trace.p, (size_t)cnt * sizeof(MatchOut))) return rc;
-          if (stride) {
-            strs_h.resize((size_t)cnt * stride);
-            if (int rc = L.download(strs_h.data(), L.d_str.p, strs_h.size())) return rc;
-          }
-          HIP_TRY(hipStreamSynchronize(st));
-          for (uint32_t i = 0; i < cnt; ++i) {
-            sassy_hip_Match mo;
-            memcpy(&mo, &rows_h[i], sizeof(mo));
-            if (R->pool.size() + mo.cigar_len + 1 > 0xFFFFFFFFull)
-              return fail(SASSY_HIP_ENOMEM, "Hamming search: more than 4 GiB of cigar text");
-            const uint32_t off = (uint32_t)R->pool.size();
-            if (stride) R->pool.append(strs_h.data() + (size_t)i * stride, mo.cigar_len);
-            R->pool.push_back('\0');
-            mo.cigar_off = off;
-            R->matches.push_back(mo);
-          }
-        }
-        S->stats.candidates += hits;
-      }
-      tile0 += G.span;
-      G.span = std::min(n_tiles, span_max);  // the next range tries everything that is left
-    }
-    // several ranges: each came sorted by (pattern, strand, start); the ranges ascend, so a stable sort restores the order
-    if (ranges > 1)
-      std::stable_sort(R->matches.begin() + (long)first_row, R->matches.end(), [](const sassy_hip_Match& a, const sassy_hip_Match& b) {
-        return a.pattern_idx != b.pattern_idx ? a.pattern_idx < b.pattern_idx : a.strand < b.strand;
-      });
-    S->stats.text_bytes += n;
-    a0 = a1;
-  }
-  S->stats.chunks = n_tiles;
+  S->stats.chunks = text.n_tiles();
   return 0;
 }
 
-// A batch call: the texts in batches of at most `hamming_many_batch` bytes laid out, each text from a multiple of 64 bytes on
-// (an empty text takes no block).  Records into R in the contract's order, or -- cells != nullptr -- per text of the call
-// its best-pattern cell (all ones: no hit), nothing into R; or -- counts != nullptr -- every batch adds into the one table.
-static int hamming_many_on_device(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
-                                  const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, uint32_t k, bool without_trace,
-                                  sassy_hip_Result* R, unsigned long long* cells, const HamCounts* counts = nullptr) {
+// the contract's order of records as far as groups, ranges and batches disturb it: a stable sort on it restores the rest
+bool by_pattern(const sassy_hip_Match& a, const sassy_hip_Match& b) {
+  return a.pattern_idx != b.pattern_idx ? a.pattern_idx < b.pattern_idx : a.strand < b.strand;
+}
+
+// List records into R: the text in ranges of tiles, every range's hits emitted in batches of the record block.
+int hamming_records(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, const HamText& text,
+                    uint32_t k, bool without_trace, sassy_hip_Result* R) {
   hipStream_t st = S->stream;
-  const uint64_t batch_cap = S->sw.hamming_many_batch > 0 ? (uint64_t)S->sw.hamming_many_batch : (1ull << 30);
-  HostTexts ht;
+  ScanLane& L = S->lanes[0];
+  return ham_for_groups(S, patterns, pattern_lens, n_patterns, text, k, [&](const HamJob& J, HamPrepared& P) {
+    const size_t first_row = R->matches.size();
+    auto per_range = [&](const HamRangeOut& range, uint64_t, bool, uint64_t*) {
+      if (range.count == 0) return 0;
+      std::vector<uint32_t> prefix;
+      uint64_t hits = 0;
+      if (!ham_prefix(range.items, R->matches.size(), prefix, &hits))
+        return fail(SASSY_HIP_ENOMEM, "Hamming search: more than 2^32 records (" + std::to_string(R->matches.size() + hits) + ")");
+      if (int rc = S->d_ham_prefix.reserve(range.count)) return rc;
+      HIP_TRY(hipMemcpyAsync(S->d_ham_prefix.p, prefix.data(), (size_t)range.count * 4, hipMemcpyHostToDevice, st));
+      const uint32_t stride = without_trace ? 0u : 2u * P.t.longest + 8u;
+      std::vector<MatchOut> rows_h;
+      std::vector<char> strs_h;
+      auto reserve = [&](uint64_t batch) {
+        if (int rc = L.d_trace.reserve(batch)) return rc;
+        return stride ? L.d_str.reserve(batch * stride) : 0;
+      };
+      auto emit = [&](uint64_t r0, uint32_t cnt) {
+        EmitParams E{};
+        E.text = text.d_text; E.items = reinterpret_cast<const HamItem*>(S->d_ham_sorted.p); E.prefix = S->d_ham_prefix.p; E.n_items = range.count;
+        E.first = (uint32_t)r0; E.count = cnt; E.tab = P.d_tab; E.pats = P.d_pats; E.profile = (uint32_t)S->profile; E.str_stride = stride;
+        E.out = L.d_trace.p; E.strs = reinterpret_cast<char*>(L.d_str.p);
+        E.starts = text.starts; E.n_texts = text.n_texts; E.text0 = text.text0;
+        hipLaunchKernelGGL(ham_emit_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, E);
+        HIP_TRY(hipGetLastError());
+        rows_h.resize(cnt);
+        if (int rc = L.download(rows_h.data(), L.d_trace.p, (size_t)cnt * sizeof(MatchOut))) return rc;
+        if (stride) {
+          strs_h.resize((size_t)cnt * stride);
+          if (int rc = L.download(strs_h.data(), L.d_str.p, strs_h.size())) return rc;
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t i = 0; i < cnt; ++i) {
+          sassy_hip_Match mo;
+          memcpy(&mo, &rows_h[i], sizeof(mo));
+          if (R->pool.size() + mo.cigar_len + 1 > 0xFFFFFFFFull) return fail(SASSY_HIP_ENOMEM, "Hamming search: more than 4 GiB of cigar text");
+          const uint32_t off = (uint32_t)R->pool.size();
+          if (stride) R->pool.append(strs_h.data() + (size_t)i * stride, mo.cigar_len);
+          R->pool.push_back('\0');
+          mo.cigar_off = off;
+          R->matches.push_back(mo);
+        }
+        return 0;
+      };
+      if (int rc = ham_emit_batches(S, hits, reserve, emit)) return rc;
+      S->stats.candidates += hits;
+      return 0;
+    };
+    return ham_walk_ranges(S, J, P, per_range, [&] { std::stable_sort(R->matches.begin() + (long)first_row, R->matches.end(), by_pattern); });
+  });
+}
+
+// Reduce into cells, or add into a counts table: nothing is listed, one launch per group takes every tile.
+int hamming_into(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, const HamText& text,
+                 uint32_t k, const HamSink& sink) {
+  return ham_for_groups(S, patterns, pattern_lens, n_patterns, text, k, [&](const HamJob& J, HamPrepared& P) {
+    if (int rc = launch_range(S, J, P, 0, text.n_tiles(), sink, nullptr)) return rc;
+    S->stats.blocks += text.n_blocks();
+    return 0;
+  });
+}
+// per text of the batch its best-pattern cell (device; all ones: no hit)
+int hamming_cells(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, const HamText& batch,
+                  uint32_t k, unsigned long long* d_cells) {
+  return hamming_into(S, patterns, pattern_lens, n_patterns, batch, k, HamSink{HamSink::Cells, d_cells, {}});
+}
+int hamming_add_counts(sassy_SearcherType* S, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, const HamText& text,
+                       uint32_t k, const HamCounts& C) {
+  return hamming_into(S, patterns, pattern_lens, n_patterns, text, k, HamSink{HamSink::Counts, nullptr, C});
+}
+
+// A batch call: the texts in batches of at most `hamming_many_batch` bytes (hamming_plan.h) laid out and uploaded, rem[] built
+// on the device, every batch handed to per_batch(text, t0, nt) -- one of the three drivers over texts [t0, t0 + nt) of the call.
+template <typename PerBatch>
+int ham_for_text_batches(sassy_SearcherType* S, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, PerBatch&& per_batch) {
+  hipStream_t st = S->stream;
+  const uint64_t batch_cap = ham_many_batch_bytes(S->sw.hamming_many_batch);
   uint64_t all_tiles = 0;
-  size_t t0 = 0;
-  while (t0 < n_texts) {
-    size_t t1 = t0;
-    uint64_t total = 0, longest = 0;
-    ht.start.clear(); ht.len.clear();
-    while (t1 < n_texts) {
-      const uint64_t slot = ((uint64_t)text_lens[t1] + 63) / 64 * 64;
-      if (t1 > t0 && total + slot > batch_cap) break;
-      ht.start.push_back(total);
-      ht.len.push_back(text_lens[t1]);
-      longest = std::max<uint64_t>(longest, text_lens[t1]);
-      total += slot;
-      ++t1;
-    }
-    const size_t nt = t1 - t0;
-    if (total == 0 || nt > 0xFFFFFFFFull) {  // (only empty texts: no hits)
-      if (nt > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "Hamming search: more than 2^32 texts in one batch");
-      t0 = t1;
-      continue;
-    }
+  for (size_t t0 = 0; t0 < n_texts;) {
+    const HamTextBatch B = ham_next_text_batch(text_lens, n_texts, t0, batch_cap);
+    const size_t nt = B.t1 - t0;
+    const uint64_t total = B.total, n_blocks = total / 64;
+    t0 = B.t1;
+    if (nt > 0xFFFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "Hamming search: more than 2^32 texts in one batch");
+    if (total == 0) continue;  // (only empty texts: no hits)
     if (int rc = S->reserve_stage(total + 64)) return rc;
     if (int rc = S->d_text.reserve(total + 64)) return rc;
-    if (int rc = layout_and_upload(S->h_stage, S->d_text.p, texts + t0, text_lens + t0, ht.start.data(), nt, total, (uint8_t)0, st)) return rc;
-    const uint64_t n_blocks = total / 64;
+    if (int rc = layout_and_upload(S->h_stage, S->d_text.p, texts + B.t0, text_lens + B.t0, B.start.data(), nt, total, (uint8_t)0, st)) return rc;
     if (int rc = S->d_ham_texts.reserve(2 * nt)) return rc;
     if (int rc = S->d_ham_rem.reserve(n_blocks)) return rc;
-    HIP_TRY(hipMemcpyAsync(S->d_ham_texts.p, ht.start.data(), nt * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(S->d_ham_texts.p + nt, ht.len.data(), nt * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S->d_ham_texts.p, B.start.data(), nt * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(S->d_ham_texts.p + nt, B.len.data(), nt * 8, hipMemcpyHostToDevice, st));
     if (n_blocks + 255 > 0xFFFFFFFFull * 256ull) return fail(SASSY_HIP_EUNSUPPORTED, "text batch too long for the Hamming search");
     hipLaunchKernelGGL(ham_rem_kernel, dim3((uint32_t)((n_blocks + 255) / 256)), dim3(256), 0, st, S->d_ham_texts.p, S->d_ham_texts.p + nt,
                        (uint32_t)nt, n_blocks, S->d_ham_rem.p);
     HIP_TRY(hipGetLastError());
-    HamTexts B{};
-    B.dev.rem = S->d_ham_rem.p; B.dev.starts = S->d_ham_texts.p; B.dev.n_texts = (uint32_t)nt; B.dev.cells = nullptr;
-    B.text0 = t0; B.longest = longest;
-    if (cells) {
-      if (int rc = S->d_ham_cells.reserve(nt)) return rc;
-      HIP_TRY(hipMemsetAsync(S->d_ham_cells.p, 0xFF, nt * 8, st));
-      B.dev.cells = S->d_ham_cells.p;
-    }
-    if (int rc = hamming_on_device(S, patterns, pattern_lens, n_patterns, S->d_text.p, total, k, without_trace, R, &B, counts)) return rc;
-    if (cells) HIP_TRY(hipMemcpyAsync(cells + t0, S->d_ham_cells.p, nt * 8, hipMemcpyDeviceToHost, st));
+    HamText text;
+    text.d_text = S->d_text.p; text.n = total; text.longest = B.longest;
+    text.rem = S->d_ham_rem.p; text.starts = S->d_ham_texts.p; text.n_texts = (uint32_t)nt; text.text0 = B.t0;
+    if (int rc = per_batch(text, B.t0, nt)) return rc;
     HIP_TRY(hipStreamSynchronize(st));  // (the tables of the next batch overwrite this one's)
     all_tiles += S->stats.chunks;
-    t0 = t1;
   }
   S->stats.chunks = all_tiles;
   S->stats.filtered = 7;
   S->stats.blocks_per_chunk = kHamTileBlocks;
-  // batches, pattern groups and ranges each came in the contract's order, and all of them ascend in text order: a stable
-  // sort on (pattern, strand) restores it for the call
-  auto by_pattern = [](const sassy_hip_Match& a, const sassy_hip_Match& b) {
-    return a.pattern_idx != b.pattern_idx ? a.pattern_idx < b.pattern_idx : a.strand < b.strand;
-  };
-  if (R && !std::is_sorted(R->matches.begin(), R->matches.end(), by_pattern)) std::stable_sort(R->matches.begin(), R->matches.end(), by_pattern);
   return 0;
 }
 
+// ---- what the entry points share ----
+// the pointers of a batch call; have_out: its output pointers are there
+int many_pointers(const sassy_SearcherType* s, bool have_out, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                  const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, const char* who) {
+  if (!s || !have_out || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!texts || !text_lens)))
+    return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null");
+  for (size_t t = 0; t < n_texts; ++t)
+    if (!texts[t] && text_lens[t]) return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null (text " + std::to_string(t) + ")");
+  return 0;
+}
+
+// Both counting entry points behind their pointer and flag checks: the refusals, the table cleared, scan(k, C) -- the driver
+// over the one text or over the batches -- between the table's copies on the device and their sum in out_counts.
+template <typename Scan>
+int hamming_count_call(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, size_t k, const char* who,
+                       bool nothing_to_scan, uint64_t* out_counts, Scan&& scan) {
+  if (k > 254) return fail(SASSY_HIP_EINVAL, std::string(who) + ": k must be <= 254 (the Hamming family's costs are bytes)");
+  if (int rc = hamming_refusals(s, pats, lens, n_pats, k, who)) return rc;
+  const uint64_t stride = (uint64_t)k + 1;
+  if ((uint64_t)n_pats > 0xFFFFFFFFull / (2 * stride))
+    return fail(SASSY_HIP_EUNSUPPORTED, std::string(who) + ": the table has more than 2^32 - 1 bins (" + std::to_string(n_pats) + " patterns x 2 x " +
+                                            std::to_string(stride) + ")");
+  const uint64_t n_bins = (uint64_t)n_pats * 2 * stride;
+  std::fill(out_counts, out_counts + n_bins, (uint64_t)0);
+  if (nothing_to_scan) return 0;
+  return hamming_call(s, lens, n_pats, k, [&](uint32_t kk) {
+    const uint32_t copies = hamming_count_copies(n_bins, s->sw.hamming_count_copies);
+    if (int rc = s->d_ham_bins.reserve((size_t)copies * n_bins)) return rc;
+    HIP_TRY(hipMemsetAsync(s->d_ham_bins.p, 0, (size_t)copies * n_bins * 8, s->stream));
+    HamCounts C{};
+    C.bins = s->d_ham_bins.p; C.n_bins = (uint32_t)n_bins; C.stride = (uint32_t)stride; C.copy_mask = copies - 1;
+    if (int rc = scan(kk, C)) return rc;
+    // the copies come back once and are summed here
+    std::vector<uint64_t> all((size_t)copies * n_bins);
+    HIP_TRY(hipMemcpyAsync(all.data(), s->d_ham_bins.p, all.size() * 8, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    uint64_t total = 0;
+    for (uint32_t c = 0; c < copies; ++c)
+      for (uint64_t b = 0; b < n_bins; ++b) out_counts[b] += all[(size_t)c * n_bins + b];
+    for (uint64_t b = 0; b < n_bins; ++b) total += out_counts[b];
+    s->stats.candidates = total;
+    return 0;
+  });
+}
+
+}  // namespace
+
 // What every Hamming entry point refuses, before any device work; `who` names the entry point.
-static int hamming_refusals(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, size_t k,
-                            const char* who) {
+int hamming_refusals(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, size_t k,
+                     const char* who) {
   if (!std::isnan(s->alpha) || s->max_overhang >= 0)
     return fail(SASSY_HIP_EUNSUPPORTED, "the Hamming search does not take overhang (alpha): a hit spans the whole pattern");
   if (s->only_best) return fail(SASSY_HIP_EUNSUPPORTED, "the Hamming search reports every hit: only_best_match is not supported");
@@ -757,152 +677,6 @@ static int hamming_refusals(sassy_SearcherType* s, const uint8_t* const* pattern
   return 0;
 }
 
-int hamming_family_refusals(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, size_t k, const char* who) {
-  return hamming_refusals(s, pats, lens, n_pats, k, who);
-}
-
-// both batch entry points: out != nullptr the records, else the per-text outputs
-static int hamming_many(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
-                        const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags, sassy_hip_Result** out,
-                        uint8_t* out_cost, uint32_t* out_pattern, uint8_t* out_strand, uint64_t* out_start) {
-  const bool best = out == nullptr;
-  const char* who = best ? "hamming_best_pattern" : "search_hamming_many";
-  if (!s || (!out && !out_cost) || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!texts || !text_lens)))
-    return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null");
-  for (size_t t = 0; t < n_texts; ++t)
-    if (!texts[t] && text_lens[t]) return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null (text " + std::to_string(t) + ")");
-  if (flags & ~(uint32_t)(best ? 0u : SASSY_HIP_WITHOUT_TRACE))
-    return fail(SASSY_HIP_EINVAL, best ? "hamming_best_pattern takes no flags (host texts only)"
-                                       : "search_hamming_many takes SASSY_HIP_WITHOUT_TRACE only (host texts only)");
-  if (best && k > 254) return fail(SASSY_HIP_EINVAL, "hamming_best_pattern: k must be <= 254 (costs are bytes, 255 = no match)");
-  if (int rc = hamming_refusals(s, patterns, pattern_lens, n_patterns, k, who)) return rc;
-  if (best) {  // what the device cell cannot hold
-    if (n_patterns >= (1u << 23)) return fail(SASSY_HIP_EUNSUPPORTED, "hamming_best_pattern takes fewer than 2^23 patterns (the cell keeps 2 pattern + strand in 24 bits)");
-    for (size_t t = 0; t < n_texts; ++t)
-      if ((uint64_t)text_lens[t] >= (1ull << 32))
-        return fail(SASSY_HIP_EUNSUPPORTED, "hamming_best_pattern takes texts shorter than 2^32 bytes (text " + std::to_string(t) + ": the cell keeps the start in 32 bits)");
-  }
-  sassy_hip_Result* R = best ? nullptr : new sassy_hip_Result();
-  std::unique_ptr<sassy_hip_Result> owned(R);
-  std::vector<unsigned long long> cells;
-  if (n_texts) {
-    DeviceGuard on_device(s);
-    const double t0 = now_ms();
-    reset_stats(s);
-    if (int rc = s->ensure_device()) return rc;
-    size_t longest = 0;
-    for (size_t i = 0; i < n_patterns; ++i) longest = std::max(longest, pattern_lens[i]);
-    const uint32_t kk = (uint32_t)std::min<size_t>(k, longest);  // k >= m reports every start
-    if (best) cells.assign(n_texts, ~0ull);
-    if (int rc = hamming_many_on_device(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, kk, (flags & SASSY_HIP_WITHOUT_TRACE) != 0,
-                                        R, best ? cells.data() : nullptr)) {
-      (void)hipStreamSynchronize(s->stream);
-      return rc;
-    }
-    s->stats.total_ms = now_ms() - t0;
-  }
-  if (best) {
-    for (size_t t = 0; t < n_texts; ++t) {
-      const unsigned long long c = cells[t];
-      const bool none = c == ~0ull;
-      out_cost[t] = none ? (uint8_t)SASSY_HIP_NO_MATCH : (uint8_t)(c >> 56);
-      if (out_pattern) out_pattern[t] = none ? 0xFFFFFFFFu : (uint32_t)((c >> 33) & 0x7FFFFFu);
-      if (out_strand) out_strand[t] = none ? 0 : (uint8_t)((c >> 32) & 1u);
-      if (out_start) out_start[t] = none ? UINT64_MAX : (uint64_t)(c & 0xFFFFFFFFull);
-    }
-    return 0;
-  }
-  if (R->pool.empty()) R->pool.push_back('\0');
-  *out = owned.release();
-  return 0;
-}
-
-// Copies of a counts table of n_bins counters (a power of two).  In the worst case -- every wavefront holds hits of one cost of
-// one pattern -- every tile adds to one word, and a launch of few patterns streams tiles at the rate of HBM: 6.3 TB/s over 4 KiB
-// tiles is about 1 500 adds per microsecond where one contended word takes about 88: 18 words are needed, 32
-// are kept while 32 tables stay within 2^16 counters (512 KiB to clear and to read back), fewer for a larger table -- whose
-// launches hold more patterns per tile and so add to one word less often --, one at least.  `forced` > 0: that many (option
-// hamming_count_copies; rounded down to a power of two, at most 1024, within 2^26 counters).
-static uint32_t hamming_count_copies(uint64_t n_bins, long forced) {
-  uint32_t copies = 32;
-  uint64_t room = 1ull << 16;
-  if (forced > 0) {
-    copies = 1;
-    while (copies * 2 <= (uint64_t)std::min<long>(forced, 1024)) copies *= 2;
-    room = 1ull << 26;
-  }
-  while (copies > 1 && (uint64_t)copies * n_bins > room) copies /= 2;
-  return copies;
-}
-
-// both counting entry points: texts == nullptr the single text (text, text_len), else the batch
-static int hamming_counts(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, const void* text,
-                          size_t text_len, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
-                          uint64_t* out_counts, bool batch) {
-  const char* who = batch ? "hamming_counts_many" : "hamming_counts";
-  if (!s || !out_counts || (n_pats && (!pats || !lens)) || (!batch && !text && text_len) || (batch && n_texts && (!texts || !text_lens)))
-    return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null");
-  if (batch)
-    for (size_t t = 0; t < n_texts; ++t)
-      if (!texts[t] && text_lens[t])
-        return fail(SASSY_HIP_EINVAL, std::string("Pointers in ") + who + "() must not be null (text " + std::to_string(t) + ")");
-  if (batch && flags) return fail(SASSY_HIP_EINVAL, "hamming_counts_many takes no flags (host texts only)");
-  if (flags & ~(uint32_t)(SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_TEXT_UNCHANGED))
-    return fail(SASSY_HIP_EINVAL, "hamming_counts takes SASSY_HIP_TEXT_ON_DEVICE and _TEXT_UNCHANGED only");
-  if (k > 254) return fail(SASSY_HIP_EINVAL, std::string(who) + ": k must be <= 254 (the Hamming family's costs are bytes)");
-  if (int rc = hamming_refusals(s, pats, lens, n_pats, k, who)) return rc;
-  const uint64_t stride = (uint64_t)k + 1;
-  if ((uint64_t)n_pats > 0xFFFFFFFFull / (2 * stride))
-    return fail(SASSY_HIP_EUNSUPPORTED, std::string(who) + ": the table has more than 2^32 - 1 bins (" + std::to_string(n_pats) + " patterns x 2 x " +
-                                            std::to_string(stride) + ")");
-  const uint64_t n_bins = (uint64_t)n_pats * 2 * stride;
-  std::fill(out_counts, out_counts + n_bins, (uint64_t)0);
-  if (batch && n_texts == 0) return 0;
-  DeviceGuard on_device(s);
-  const double t0 = now_ms();
-  reset_stats(s);
-  if (int rc = s->ensure_device()) return rc;
-  const uint32_t copies = hamming_count_copies(n_bins, s->sw.hamming_count_copies);
-  if (int rc = s->d_ham_bins.reserve((size_t)copies * n_bins)) return rc;
-  HIP_TRY(hipMemsetAsync(s->d_ham_bins.p, 0, (size_t)copies * n_bins * 8, s->stream));
-  HamCounts C{};
-  C.bins = s->d_ham_bins.p; C.n_bins = (uint32_t)n_bins; C.stride = (uint32_t)stride; C.copy_mask = copies - 1;
-  size_t longest = 0;
-  for (size_t i = 0; i < n_pats; ++i) longest = std::max(longest, lens[i]);
-  const uint32_t kk = (uint32_t)std::min<size_t>(k, longest);  // k >= m counts every start
-  int rc = 0;
-  if (batch) {
-    rc = hamming_many_on_device(s, pats, lens, n_pats, texts, text_lens, n_texts, kk, true, nullptr, nullptr, &C);
-  } else {
-    const uint8_t* d_text = static_cast<const uint8_t*>(text);
-    if (flags & SASSY_HIP_TEXT_ON_DEVICE) {
-      if (((uintptr_t)text & 15) != 0) return fail(SASSY_HIP_EINVAL, "device text pointer must be 16-byte aligned");
-    } else if (text_len) {
-      if (int rc2 = s->d_text.reserve(text_len + 64)) return rc2;
-      HIP_TRY(hipMemcpyAsync(s->d_text.p, text, text_len, hipMemcpyHostToDevice, s->stream));
-      d_text = s->d_text.p;
-    }
-    rc = hamming_on_device(s, pats, lens, n_pats, d_text, text_len, kk, true, nullptr, nullptr, &C);
-  }
-  if (rc) {
-    (void)hipStreamSynchronize(s->stream);
-    return rc;
-  }
-  // the copies come back once and are summed here
-  std::vector<uint64_t> all((size_t)copies * n_bins);
-  HIP_TRY(hipMemcpyAsync(all.data(), s->d_ham_bins.p, all.size() * 8, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  uint64_t total = 0;
-  for (uint32_t c = 0; c < copies; ++c)
-    for (uint64_t b = 0; b < n_bins; ++b) out_counts[b] += all[(size_t)c * n_bins + b];
-  for (uint64_t b = 0; b < n_bins; ++b) total += out_counts[b];
-  s->stats.candidates = total;
-  s->stats.filtered = 7;
-  s->stats.blocks_per_chunk = kHamTileBlocks;
-  s->stats.total_ms = now_ms() - t0;
-  return 0;
-}
-
 }  // namespace sassy_hip
 
 using namespace sassy_hip;
@@ -916,58 +690,103 @@ int sassy_hip_search_hamming(sassy_SearcherType* s, const uint8_t* const* patter
   if (flags & ~(uint32_t)(SASSY_HIP_WITHOUT_TRACE | SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_TEXT_UNCHANGED))
     return fail(SASSY_HIP_EINVAL, "search_hamming takes SASSY_HIP_WITHOUT_TRACE, _TEXT_ON_DEVICE and _TEXT_UNCHANGED only");
   if (int rc = hamming_refusals(s, patterns, pattern_lens, n_patterns, k, "search_hamming")) return rc;
-  DeviceGuard on_device(s);
-  const double t0 = now_ms();
-  reset_stats(s);
-  if (int rc = s->ensure_device()) return rc;
-  const uint8_t* d_text = static_cast<const uint8_t*>(text);
-  if (flags & SASSY_HIP_TEXT_ON_DEVICE) {
-    if (((uintptr_t)text & 15) != 0) return fail(SASSY_HIP_EINVAL, "device text pointer must be 16-byte aligned");
-  } else if (text_len) {
-    if (int rc = s->d_text.reserve(text_len + 64)) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_text.p, text, text_len, hipMemcpyHostToDevice, s->stream));
-    d_text = s->d_text.p;
-  }
-  sassy_hip_Result* R = new sassy_hip_Result();
-  size_t longest = 0;
-  for (size_t i = 0; i < n_patterns; ++i) longest = std::max(longest, pattern_lens[i]);
-  const uint32_t kk = (uint32_t)std::min<size_t>(k, longest);  // k >= m reports every start
-  if (int rc = hamming_on_device(s, patterns, pattern_lens, n_patterns, d_text, text_len, kk, (flags & SASSY_HIP_WITHOUT_TRACE) != 0, R)) {
-    (void)hipStreamSynchronize(s->stream);
-    delete R;
-    return rc;
-  }
-  if (R->pool.empty()) R->pool.push_back('\0');
-  s->stats.total_ms = now_ms() - t0;
-  *out = R;
-  return 0;
+  return hamming_call(s, pattern_lens, n_patterns, k, [&](uint32_t kk) {
+    HamText one;
+    if (int rc = ham_one_text(s, text, text_len, flags, &one)) return rc;
+    std::unique_ptr<sassy_hip_Result> R(new sassy_hip_Result());
+    if (int rc = hamming_records(s, patterns, pattern_lens, n_patterns, one, kk, (flags & SASSY_HIP_WITHOUT_TRACE) != 0, R.get())) return rc;
+    if (R->pool.empty()) R->pool.push_back('\0');
+    *out = R.release();
+    return 0;
+  });
 }
 
 int sassy_hip_search_hamming_many(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
                                   const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
                                   sassy_hip_Result** out) {
-  if (!out) return fail(SASSY_HIP_EINVAL, "Pointers in search_hamming_many() must not be null");
-  return hamming_many(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, out, nullptr, nullptr, nullptr, nullptr);
+  const char* who = "search_hamming_many";
+  if (int rc = many_pointers(s, out != nullptr, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, who)) return rc;
+  if (flags & ~(uint32_t)SASSY_HIP_WITHOUT_TRACE)
+    return fail(SASSY_HIP_EINVAL, "search_hamming_many takes SASSY_HIP_WITHOUT_TRACE only (host texts only)");
+  if (int rc = hamming_refusals(s, patterns, pattern_lens, n_patterns, k, who)) return rc;
+  std::unique_ptr<sassy_hip_Result> R(new sassy_hip_Result());
+  auto all_batches = [&](uint32_t kk) {
+    if (int rc = ham_for_text_batches(s, texts, text_lens, n_texts, [&](const HamText& batch, size_t, size_t) {
+          return hamming_records(s, patterns, pattern_lens, n_patterns, batch, kk, (flags & SASSY_HIP_WITHOUT_TRACE) != 0, R.get());
+        }))
+      return rc;
+    // batches, pattern groups and ranges each came in the contract's order, and all of them ascend in text order: a stable
+    // sort on (pattern, strand) restores it for the call
+    if (!std::is_sorted(R->matches.begin(), R->matches.end(), by_pattern)) std::stable_sort(R->matches.begin(), R->matches.end(), by_pattern);
+    return 0;
+  };
+  if (n_texts)
+    if (int rc = hamming_call(s, pattern_lens, n_patterns, k, all_batches)) return rc;
+  if (R->pool.empty()) R->pool.push_back('\0');
+  *out = R.release();
+  return 0;
 }
 
 int sassy_hip_hamming_best_pattern(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
                                    const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
                                    uint8_t* out_cost, uint32_t* out_pattern, uint8_t* out_strand, uint64_t* out_start) {
-  if (!out_cost && n_texts) return fail(SASSY_HIP_EINVAL, "Pointers in hamming_best_pattern() must not be null");
-  uint8_t none = 0;
-  return hamming_many(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, nullptr, out_cost ? out_cost : &none,
-                      out_pattern, out_strand, out_start);
+  const char* who = "hamming_best_pattern";
+  if (int rc = many_pointers(s, out_cost || !n_texts, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, who)) return rc;
+  if (flags) return fail(SASSY_HIP_EINVAL, "hamming_best_pattern takes no flags (host texts only)");
+  if (k > 254) return fail(SASSY_HIP_EINVAL, "hamming_best_pattern: k must be <= 254 (costs are bytes, 255 = no match)");
+  if (int rc = hamming_refusals(s, patterns, pattern_lens, n_patterns, k, who)) return rc;
+  // what the device cell cannot hold
+  if (n_patterns >= (1u << 23)) return fail(SASSY_HIP_EUNSUPPORTED, "hamming_best_pattern takes fewer than 2^23 patterns (the cell keeps 2 pattern + strand in 24 bits)");
+  for (size_t t = 0; t < n_texts; ++t)
+    if ((uint64_t)text_lens[t] >= (1ull << 32))
+      return fail(SASSY_HIP_EUNSUPPORTED, "hamming_best_pattern takes texts shorter than 2^32 bytes (text " + std::to_string(t) + ": the cell keeps the start in 32 bits)");
+  if (n_texts == 0) return 0;
+  std::vector<unsigned long long> cells(n_texts, ~0ull);
+  auto all_batches = [&](uint32_t kk) {
+    return ham_for_text_batches(s, texts, text_lens, n_texts, [&](const HamText& batch, size_t t0, size_t nt) {
+      if (int rc = s->d_ham_cells.reserve(nt)) return rc;
+      HIP_TRY(hipMemsetAsync(s->d_ham_cells.p, 0xFF, nt * 8, s->stream));
+      if (int rc = hamming_cells(s, patterns, pattern_lens, n_patterns, batch, kk, s->d_ham_cells.p)) return rc;
+      HIP_TRY(hipMemcpyAsync(cells.data() + t0, s->d_ham_cells.p, nt * 8, hipMemcpyDeviceToHost, s->stream));
+      return 0;
+    });
+  };
+  if (int rc = hamming_call(s, pattern_lens, n_patterns, k, all_batches)) return rc;
+  for (size_t t = 0; t < n_texts; ++t) {
+    const unsigned long long c = cells[t];
+    const bool none = c == ~0ull;
+    out_cost[t] = none ? (uint8_t)SASSY_HIP_NO_MATCH : (uint8_t)(c >> 56);
+    if (out_pattern) out_pattern[t] = none ? 0xFFFFFFFFu : (uint32_t)((c >> 33) & 0x7FFFFFu);
+    if (out_strand) out_strand[t] = none ? 0 : (uint8_t)((c >> 32) & 1u);
+    if (out_start) out_start[t] = none ? UINT64_MAX : (uint64_t)(c & 0xFFFFFFFFull);
+  }
+  return 0;
 }
 
 int sassy_hip_hamming_counts(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
                              const void* text, size_t text_len, size_t k, uint32_t flags, uint64_t* out_counts) {
-  return hamming_counts(s, patterns, pattern_lens, n_patterns, text, text_len, nullptr, nullptr, 0, k, flags, out_counts, false);
+  if (!s || !out_counts || (n_patterns && (!patterns || !pattern_lens)) || (!text && text_len))
+    return fail(SASSY_HIP_EINVAL, "Pointers in hamming_counts() must not be null");
+  if (flags & ~(uint32_t)(SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_TEXT_UNCHANGED))
+    return fail(SASSY_HIP_EINVAL, "hamming_counts takes SASSY_HIP_TEXT_ON_DEVICE and _TEXT_UNCHANGED only");
+  return hamming_count_call(s, patterns, pattern_lens, n_patterns, k, "hamming_counts", false, out_counts, [&](uint32_t kk, const HamCounts& C) {
+    HamText one;
+    if (int rc = ham_one_text(s, text, text_len, flags, &one)) return rc;
+    return hamming_add_counts(s, patterns, pattern_lens, n_patterns, one, kk, C);
+  });
 }
 
 int sassy_hip_hamming_counts_many(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
                                   const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
                                   uint64_t* out_counts) {
-  return hamming_counts(s, patterns, pattern_lens, n_patterns, nullptr, 0, texts, text_lens, n_texts, k, flags, out_counts, true);
+  const char* who = "hamming_counts_many";
+  if (int rc = many_pointers(s, out_counts != nullptr, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, who)) return rc;
+  if (flags) return fail(SASSY_HIP_EINVAL, "hamming_counts_many takes no flags (host texts only)");
+  return hamming_count_call(s, patterns, pattern_lens, n_patterns, k, who, n_texts == 0, out_counts, [&](uint32_t kk, const HamCounts& C) {
+    return ham_for_text_batches(s, texts, text_lens, n_texts, [&](const HamText& batch, size_t, size_t) {
+      return hamming_add_counts(s, patterns, pattern_lens, n_patterns, batch, kk, C);
+    });
+  });
 }
 
 }  // extern "C"

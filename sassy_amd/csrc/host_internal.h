@@ -3,9 +3,10 @@
 //   scan_driver.hip   one pattern over one buffer: ScanJob (prepare / enqueue / finish), strands, search_text
 //   many_patterns.hip search_encoded / search_many: pattern-tiled scan, seeded search, lists -> reports -> records
 //   multi_device.hip  sassy_hip_multi_*: one text over several devices inside one process
-//   hamming.hip       sassy_hip_search_hamming, _search_hamming_many, _hamming_best_pattern, _hamming_counts(_many): the Hamming scan and emit kernels
-//                     with their drivers and entry points
-//   amplicons.hip     sassy_hip_hamming_amplicons: primer pairs joined on the sorted items of the Hamming scan
+//   hamming.hip       sassy_hip_search_hamming, _search_hamming_many, _hamming_best_pattern, _hamming_counts(_many): the Hamming scan and emit kernels,
+//                     the device side of their one driver (ham_prepare, ham_scan_range; records / cells / counts) and the entry points
+//   hamming_plan.h    that driver's decisions that need no device (patterns as scanned, groups, tables, overflow step, text batches), free of HIP
+//   amplicons.hip     sassy_hip_hamming_amplicons: primer pairs joined on the sorted items of the Hamming scan (ham_walk_ranges, below)
 //   c_abi.hip         the C-ABI of include/sassy.h + sassy_hip.h, the switch table, synthetic inputs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +32,7 @@
 #include "switches.h"
 #include "pass_planner.h"
 #include "scan_route.h"
+#include "hamming_plan.h"
 
 namespace sassy_hip {
 // (thread_local LaunchEvents g_launch_events: defined in scan_driver.hip, declared in common.h)
@@ -1135,70 +1137,117 @@ struct DeviceGuard {
       return fail(SASSY_HIP_EUNSUPPORTED, "SASSY_HIP_LINE_SPANS is a flag of sassy_hip_search only");                    \
   } while (0)
 
-// ---- the Hamming scan of one launch group over one range of tiles (hamming.hip), shared with amplicons.hip ----
-// One item: the hits of one pattern in one block.  Laid out as a Candidate so that sort_kernels.hip sorts it by `key`.
-struct HamItem {
-  uint64_t key;   // launch-local pattern index (pattern and strand) << 32 | block
-  uint64_t mask;  // bit i: start 64 block + i is a hit
-};
+// ---- the Hamming scan of one launch group over ranges of tiles (hamming.hip), shared with amplicons.hip ----
+// (HamItem, HamPattern, HamGroup, HamTables and every decision that needs no device: hamming_plan.h)
 static_assert(sizeof(HamItem) == sizeof(Candidate) && offsetof(Candidate, pos) == 0, "items are sorted as candidates");
-// per pattern of a launch, kHamTabWords words: rows, offset of its row slots (words) in `rows`, offset of its bytes in `pats`,
-// N threshold (kHamNoFilter: none), pattern index of the call, strand
-constexpr uint32_t kHamTabWords = 8;
-constexpr uint32_t kHamNoFilter = 0xFFFFFFFFu;
-// One pattern of the call on one strand, as it is scanned.
-struct HamPattern {
-  uint32_t idx, strand;
-  std::vector<uint8_t> bytes;  // strand 1: the reverse complement
-  uint32_t nmax;               // most N a hit's span may hold (kHamNoFilter: no filter)
-};
-struct HamTexts;  // (hamming.hip: a laid-out batch of texts)
-// A launch group and one range of its tiles.  The caller names the group (pats, np, the slots), the text and the range; the
-// first call builds and uploads the group's tables and sizes the item list, every call scans [tile0, tile0 + span) -- cut
-// down and launched again while its items overflow the list -- and leaves the items sorted by (pattern | strand, block) in
-// S->d_ham_sorted and in `items`.
-struct HamRange {
-  const HamPattern* pats = nullptr;
-  uint32_t np = 0;
-  ScanParams SP{};
-  uint32_t ns = 0;       // slots in use
-  int slot_of[256];      // slot of a pattern byte's key (slot_byte), -1: none
+static_assert(kHamSlots == (uint32_t)kMaxSlots, "a launch's slots are ScanParams::slot_val");
+// The text on the device, readable up to the next multiple of 64 bytes: one text, or -- starts != nullptr -- a laid-out batch.
+struct HamText {
   const uint8_t* d_text = nullptr;
-  uint64_t n = 0;
+  uint64_t n = 0;        // bytes (a batch: of the whole buffer)
+  uint64_t longest = 0;  // the longest text: n, or the batch's
+  // a batch (device pointers): per block the bytes left in its own text, per text its first byte; the first text's index in the call
+  const uint32_t* rem = nullptr;
+  const uint64_t* starts = nullptr;
+  uint32_t n_texts = 0;
+  uint64_t text0 = 0;
+  uint64_t n_blocks() const { return (n + 63) / 64; }
+  uint64_t n_tiles() const { return (n_blocks() + kHamTileBlocks - 1) / kHamTileBlocks; }
+};
+// What the caller names: the group's patterns -- all[group.a0 .. group.a1) --, the text, the threshold.
+struct HamJob {
+  const HamPattern* pats = nullptr;  // the group's first
+  uint32_t np = 0;
+  HamGroup group;
+  HamText text;
   uint32_t k = 0;
-  const HamTexts* many = nullptr;
-  uint64_t min_span = 1;  // a range is never cut below this many tiles: `overflow` instead
-  // the group's tables, by the first call
-  bool ready = false;
-  std::vector<uint32_t> tab;
+  uint64_t min_span = 1;  // a range is never cut below this many tiles: it overflows instead
+};
+// What ham_prepare leaves, once per group: the tables as built and where they are on the device, the kernels' slot values, the
+// item list's size (ham_scan_range grows it).
+struct HamPrepared {
+  HamTables t;
+  ScanParams SP{};
   uint32_t *d_tab = nullptr, *d_rows = nullptr;
   uint8_t* d_pats = nullptr;
-  uint32_t longest = 0, halo = 0, nb = 0, wpg = 0;
-  size_t smem = 0;
-  bool n_filter = false;
-  uint64_t item_cap = 0, max_cap = 0, span_max = 0;
-  // the range: span in = the tiles wanted, out = the tiles scanned
-  uint64_t tile0 = 0, span = 0;
-  uint32_t count = 0;          // its items
-  std::vector<HamItem> items;  // sorted
-  bool overflow = false;       // min_span tiles do not fit the list at its cap: nothing was scanned
+  uint64_t item_cap = 0;
 };
-// the slots of a launch before its first pattern: Dna and Iupac have theirs, Ascii patterns add their bytes
-inline void ham_slots_init(Profile pr, HamRange& G) {
-  G.SP = ScanParams{};
-  G.ns = pr == PROFILE_DNA ? 4u : pr == PROFILE_IUPAC ? 16u : 0u;
-  if (pr == PROFILE_IUPAC)
-    for (uint32_t s = 0; s < 16; ++s) G.SP.slot_val[s] = (uint8_t)s;  // a slot per base set
-  std::fill(G.slot_of, G.slot_of + 256, -1);
-  if (!is_ascii(pr))
-    for (uint32_t s = 0; s < G.ns; ++s) G.slot_of[s] = (int)s;
-}
+// What one range returns: the tiles scanned, their items sorted by (pattern | strand, block) -- here and in S->d_ham_sorted.
+struct HamRangeOut {
+  uint64_t span = 0;
+  uint32_t count = 0;
+  std::vector<HamItem> items;
+  bool overflow = false;  // min_span tiles do not fit the list at its cap: nothing was scanned
+};
 
 // ---- functions one unit calls in another ----
 // hamming.hip
-int ham_scan_range(sassy_SearcherType* S, HamRange& G);
-// what every Hamming entry point refuses, before any device work (hamming_refusals)
-int hamming_family_refusals(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, size_t k, const char* who);
+int ham_prepare(sassy_SearcherType* S, const HamJob& J, HamPrepared& P);
+int ham_scan_range(sassy_SearcherType* S, const HamJob& J, HamPrepared& P, uint64_t tile0, HamRangeOut& out);
+// what every Hamming entry point refuses, before any device work; `who` names the entry point
+int hamming_refusals(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, size_t k, const char* who);
+// A group's tiles in ranges, for the callers that list records: every range asks for all that is left and ham_scan_range cuts
+// it to what the item list holds.  per_range(range, t1, last, &next) makes the records of tiles [.., t1) and may move `next`,
+// the tile the next range starts at (t1 as it comes).  Each range's records come in the contract's order and the ranges
+// ascend, so behind more than one range reorder() -- a stable sort of the group's records -- restores it.
+template <typename PerRange, typename Reorder>
+int ham_walk_ranges(sassy_SearcherType* S, const HamJob& J, HamPrepared& P, PerRange&& per_range, Reorder&& reorder) {
+  const uint64_t n_tiles = J.text.n_tiles();
+  HamRangeOut range;
+  uint32_t ranges = 0;
+  for (uint64_t tile0 = 0;;) {
+    if (int rc = ham_scan_range(S, J, P, tile0, range)) return rc;
+    const uint64_t t1 = tile0 + range.span;
+    const bool last = t1 >= n_tiles;
+    uint64_t next = t1;
+    if (int rc = per_range(range, t1, last, &next)) return rc;
+    ++ranges;
+    if (last) break;
+    tile0 = next;
+  }
+  if (ranges > 1) reorder();
+  return 0;
+}
+// `recs` records of a range in batches of the record block (option hamming_records): reserve(batch) sizes the device buffers
+// once, emit(first, count) launches, downloads and appends.
+template <typename Reserve, typename Emit>
+int ham_emit_batches(const sassy_SearcherType* S, uint64_t recs, Reserve&& reserve, Emit&& emit) {
+  const uint64_t batch = std::min<uint64_t>(recs, S->sw.hamming_records > 0 ? (uint64_t)S->sw.hamming_records : (1u << 20));
+  if (int rc = reserve(batch)) return rc;
+  for (uint64_t r0 = 0; r0 < recs; r0 += batch)
+    if (int rc = emit(r0, (uint32_t)std::min<uint64_t>(batch, recs - r0))) return rc;
+  return 0;
+}
+// What a Hamming entry point does around its device work, behind its refusals: the device, fresh stats, k cut to the longest
+// pattern (k >= m takes every start), run(k), a stream sync where that failed, total_ms.
+template <typename Run>
+int hamming_call(sassy_SearcherType* s, const size_t* lens, size_t n_pats, size_t k, Run&& run) {
+  DeviceGuard on_device(s);
+  const double t0 = now_ms();
+  reset_stats(s);
+  if (int rc = s->ensure_device()) return rc;
+  size_t longest = 0;
+  for (size_t i = 0; i < n_pats; ++i) longest = std::max(longest, lens[i]);
+  if (int rc = run((uint32_t)std::min<size_t>(k, longest))) {
+    (void)hipStreamSynchronize(s->stream);
+    return rc;
+  }
+  s->stats.total_ms = now_ms() - t0;
+  return 0;
+}
+// The one text of search_hamming, hamming_counts and hamming_amplicons on the device: the caller's device pointer, or an upload.
+inline int ham_one_text(sassy_SearcherType* s, const void* text, size_t text_len, uint32_t flags, HamText* out) {
+  const uint8_t* d_text = static_cast<const uint8_t*>(text);
+  if (flags & SASSY_HIP_TEXT_ON_DEVICE) {
+    if (((uintptr_t)text & 15) != 0) return fail(SASSY_HIP_EINVAL, "device text pointer must be 16-byte aligned");
+  } else if (text_len) {
+    if (int rc = s->d_text.reserve(text_len + 64)) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_text.p, text, text_len, hipMemcpyHostToDevice, s->stream));
+    d_text = s->d_text.p;
+  }
+  *out = HamText{d_text, text_len, text_len};
+  return 0;
+}
 // line_index.hip
 int line_spans_on_device(sassy_SearcherType* S, const uint8_t* d_text, uint64_t text_len, const uint64_t* first, const uint64_t* last,
                          size_t n, sassy_hip_LineSpan* out);

@@ -112,13 +112,17 @@ print("ok")
 
 def test_refusals_and_scan_are_the_familys_functions():
     """No copy of the checks and none of the scan: the entry point hands all primers to the family's refusals once, before the
-    device, and the driver scans through ham_scan_range as hamming_on_device does; amplicons.hip has no scan kernel."""
+    device (hamming_call), and the driver scans through the one range walker -- and so through ham_scan_range -- as the record
+    driver of hamming.hip does; amplicons.hip has no scan kernel."""
     amp = open(os.path.join(ROOT, "sassy_amd", "csrc", "amplicons.hip")).read()
     ham = open(os.path.join(ROOT, "sassy_amd", "csrc", "hamming.hip")).read()
-    assert amp.count("hamming_family_refusals(") == 1 and amp.index("hamming_family_refusals(") < amp.index("ensure_device")
+    shared = open(os.path.join(ROOT, "sassy_amd", "csrc", "host_internal.h")).read()
+    assert amp.count("hamming_refusals(") == 1 and amp.index("hamming_refusals(") < amp.index("hamming_call(")
+    assert "ensure_device" not in amp and "ensure_device()" in shared[shared.index("int hamming_call("):shared.index("int ham_one_text(")]
     assert "SASSY_NO_TICKETS" not in amp and "only_best_match" not in amp
-    assert "return hamming_refusals(s, pats, lens, n_pats, k, who);" in ham
-    assert amp.count("ham_scan_range(S, G)") == 1 and ham.count("ham_scan_range(S, G)") == 1
+    assert ham.count("\nint hamming_refusals(") == 1 and "hamming_family_refusals" not in amp + ham + shared
+    assert amp.count("ham_walk_ranges(S, J, P") == 1 and ham.count("ham_walk_ranges(S, J, P") == 1
+    assert shared.count("ham_scan_range(S, J, P") == 1 and "ham_scan_range(" not in amp
     assert "ham_scan_kernel" not in amp and "launch_scan" not in amp
     assert "__global__" in amp and "amp_count_kernel" in amp and "amp_emit_kernel" in amp
     assert "asm" not in re.sub(r"//.*", "", amp)

@@ -136,10 +136,10 @@ def test_refusals_are_the_familys_function():
     """No copy of the checks: both counting entry points go through one function that calls hamming_refusals once, which ends
     in the open-tickets check."""
     src = open(os.path.join(ROOT, "sassy_amd", "csrc", "hamming.hip")).read()
-    body = src[src.index("static int hamming_counts("):]
+    body = src[src.index("int hamming_count_call("):]
     body = body[:body.index("\n}\n")]
-    assert body.count("hamming_refusals(") == 1 and body.index("hamming_refusals(") < body.index("ensure_device")
-    assert src.count("static int hamming_counts(") == 1 and src.count("return hamming_counts(s, patterns,") == 2
+    assert body.count("hamming_refusals(") == 1 and body.index("hamming_refusals(") < body.index("hamming_call(")  # (hamming_call: the device)
+    assert src.count("int hamming_count_call(") == 1 and src.count("return hamming_count_call(s, patterns,") == 2
     assert src.count("only_best_match is not supported") == 1 and src.count("SASSY_NO_TICKETS") == 1
 
 

@@ -51,6 +51,14 @@ def test_step_header_is_free_of_hip():
     assert "__builtin_amdgcn" not in outside
 
 
+def test_plan_header_is_free_of_hip():
+    """csrc/hamming_plan.h, the host's decisions: no HIP header, no searcher, no device builtin, nothing but hamming_step.h."""
+    src = open(os.path.join(ROOT, "sassy_amd", "csrc", "hamming_plan.h")).read()
+    assert "#include <hip" not in src and "hipStream" not in src and "sassy_SearcherType" not in src
+    assert "__builtin_amdgcn" not in src and "__device__" not in src
+    assert re.findall(r'#include "([^"]+)"', src) == ["hamming_step.h"]
+
+
 def test_refusals_come_before_any_device_work(sassy):
     """Every refusal of the issue's table with its code and a message that names the reason, in a child that sees no device:
     a call that got as far as the device would say 'no usable HIP device' instead.  Then valid arguments: that message."""

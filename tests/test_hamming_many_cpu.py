@@ -141,10 +141,10 @@ def test_refusals_are_one_function():
     """The checks are factored out, not copied: the single-text entry point and the batch entry points call one refusals
     function, which ends in the open-tickets check (tests/test_gpu_hamming_many.py opens a ticket)."""
     src = open(os.path.join(ROOT, "sassy_amd", "csrc", "hamming.hip")).read()
-    body = src[src.index("static int hamming_refusals("):]
+    body = src[src.index("\nint hamming_refusals("):]
     body = body[:body.index("\n}\n")]
     assert "SASSY_NO_TICKETS(s);" in body and "only_best_match" in body and "overhang" in body
-    assert src.count("hamming_refusals(s, patterns, pattern_lens, n_patterns, k,") == 2  # the single-text call, the batch calls
+    assert src.count("hamming_refusals(s, patterns, pattern_lens, n_patterns, k,") == 3  # the single-text call, the two batch calls
     assert src.count("only_best_match is not supported") == 1 and src.count("SASSY_NO_TICKETS") == 1
 
 

@@ -70,9 +70,10 @@ def main():
                 kinds[name] = st["filtered"]
         shape = {"m": m, "k": k, "runs": {}}
         for name, v in scan.items():
-            med = statistics.median(v)
+            med = statistics.median(v)  # (0 where the run's route records no scan_ms: no spread, no rate)
             shape["runs"][name] = {"scan_ms": round(med, 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
-                                   "spread": round((max(v) - min(v)) / med, 4), "GB_per_s": round(n / med / 1e6, 1),
+                                   "spread": round((max(v) - min(v)) / med, 4) if med else None,
+                                   "GB_per_s": round(n / med / 1e6, 1) if med else None,
                                    "records": found[name], "filtered": kinds[name]}
             print(m, k, name, shape["runs"][name], flush=True)
         base = shape["runs"]["dp_streaming"]["scan_ms"]
