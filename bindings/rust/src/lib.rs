@@ -36,6 +36,17 @@ pub struct Amplicon {
     pub rev_cost: u8,
     _pad: u8,
 }
+/// One pair of `hamming_pairs` (include/sassy_hip.h: sassy_hip_HammingPair, 12 bytes): sequence `a_idx` of the first list and
+/// `b_idx` of the second differ in `cost` rows; `strand` 1: `b_idx` was taken as its reverse complement.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct HammingPair {
+    pub a_idx: u32,
+    pub b_idx: u32,
+    pub cost: u8,
+    pub strand: u8,
+    _pad: [u8; 2],
+}
 /// One record of an unwrapped FASTA chunk (include/sassy_hip.h: sassy_hip_FastaRecord, 32 bytes): the id in the raw bytes,
 /// the sequence in the device text.
 #[repr(C)]
@@ -108,6 +119,12 @@ extern "C" {
                                    rev_lens: *const usize, n_pairs: usize, text: *const u8, text_len: usize, k: usize, min_len: u64,
                                    max_len: u64, flags: u32, out: *mut *mut Amplicon, n_out: *mut usize) -> c_int;
     fn sassy_hip_amplicons_free(p: *mut Amplicon);
+    // ... without a text: two lists of sequences of one length all against all (b null and n_b 0: a against itself)
+    fn sassy_hip_hamming_pairs(s: *mut RawSearcher, a: *const u8, n_a: usize, b: *const u8, n_b: usize, m: usize, k: usize,
+                               flags: u32, out: *mut *mut HammingPair, n_out: *mut usize) -> c_int;
+    fn sassy_hip_hamming_pairs_free(p: *mut HammingPair);
+    fn sassy_hip_hamming_nearest(s: *mut RawSearcher, a: *const u8, n_a: usize, b: *const u8, n_b: usize, m: usize, k: usize,
+                                 flags: u32, out_cost: *mut u8, out_index: *mut u32, out_strand: *mut u8, out_ties: *mut u32) -> c_int;
     // FASTA unwrap on the device: raw bytes in, a device text per record and a host table out (flags: TEXT_ON_DEVICE)
     pub fn sassy_hip_fasta_unwrap(raw: *const u8, n: u64, flags: u32, hip_stream: *mut std::ffi::c_void, out: *mut *mut RawFasta) -> c_int;
     pub fn sassy_hip_fasta_n_records(f: *const RawFasta) -> u64;
@@ -431,6 +448,37 @@ impl<P: Profile> Searcher<P> {
         let v = if n == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(out, n) }.to_vec() };
         unsafe { sassy_hip_amplicons_free(out) };
         v
+    }
+
+    /// All-vs-all Hamming distances between two lists of sequences of `m` bytes each, stored back to back: every `(a_idx,
+    /// b_idx, strand)` with at most `k` mismatches, ordered by `(a_idx, b_idx, strand)`.  `b = None`: `a` against itself, every
+    /// unordered pair once (strand 0: `a_idx < b_idx`; strand 1: `a_idx <= b_idx`).  `m <= 128`, `k <= 254`.
+    pub fn hamming_pairs(&mut self, a: &[u8], b: Option<&[u8]>, m: usize, k: usize) -> Vec<HammingPair> {
+        assert!(m > 0 && a.len() % m == 0 && b.map_or(true, |b| b.len() % m == 0), "lists hold whole sequences of m bytes");
+        let (bp, nb) = b.map_or((std::ptr::null(), 0), |b| (b.as_ptr(), b.len() / m));
+        let mut out: *mut HammingPair = std::ptr::null_mut();
+        let mut n = 0usize;
+        let rc = unsafe { sassy_hip_hamming_pairs(self.raw, a.as_ptr(), a.len() / m, bp, nb, m, k, 0, &mut out, &mut n) };
+        assert_eq!(rc, 0, "{}", last_error());
+        let v = if n == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(out, n) }.to_vec() };
+        unsafe { sassy_hip_hamming_pairs_free(out) };
+        v
+    }
+
+    /// Per sequence of `a` its nearest sequence of `b` within `k` mismatches: `(cost, index, strand, ties)` -- the smallest
+    /// under `(cost, index, Fwd before Rc)` and how many candidates share that cost; `(NO_MATCH, u32::MAX, Fwd, 0)` where there
+    /// is none.  `b = None`: the nearest other sequence of `a` (only `(index == i, Fwd)` is no candidate).
+    pub fn hamming_nearest(&mut self, a: &[u8], b: Option<&[u8]>, m: usize, k: usize) -> Vec<(u8, u32, Strand, u32)> {
+        assert!(m > 0 && a.len() % m == 0 && b.map_or(true, |b| b.len() % m == 0), "lists hold whole sequences of m bytes");
+        let (bp, nb) = b.map_or((std::ptr::null(), 0), |b| (b.as_ptr(), b.len() / m));
+        let n = a.len() / m;
+        let (mut cost, mut index, mut strand, mut ties) = (vec![0u8; n], vec![0u32; n], vec![0u8; n], vec![0u32; n]);
+        let rc = unsafe {
+            sassy_hip_hamming_nearest(self.raw, a.as_ptr(), n, bp, nb, m, k, 0, cost.as_mut_ptr(), index.as_mut_ptr(), strand.as_mut_ptr(),
+                                      ties.as_mut_ptr())
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        (0..n).map(|i| (cost[i], index[i], if strand[i] != 0 { Strand::Rc } else { Strand::Fwd }, ties[i])).collect()
     }
 
     /// Per text the one best match over all patterns and strands as a complete record: lowest cost, then lowest pattern

@@ -93,7 +93,8 @@ typedef struct sassy_hip_Stats {
                             3: q-gram piece table (filter_table_kernel); 4: q-gram counting (filter_count_kernel);
                             5: the pattern-tiled scan of search_encoded (tiled_kernel: all patterns in one pass);
                             6: the seeded search of search_encoded (seed_kernels: seed table lookups, one lane per hit);
-                            7: the Hamming scan of sassy_hip_search_hamming (hamming.hip: no DP) */
+                            7: the Hamming scan of sassy_hip_search_hamming (hamming.hip: no DP);
+                            8: the all-vs-all walk of sassy_hip_hamming_pairs / _nearest (hamming_pairs.hip: no text) */
   double filter_ms;      /* HIP-event time of the prefilter kernel (part of scan_ms); a search in flight whose text pass
                             was served by several launches (see pass_patterns): the sum of their durations */
   uint64_t hit_blocks;   /* text blocks in which an exact pattern piece ends */
@@ -458,6 +459,51 @@ int sassy_hip_hamming_amplicons(sassy_SearcherType *s, const uint8_t *const *fwd
                                 size_t text_len, size_t k, uint64_t min_len, uint64_t max_len, uint32_t flags,
                                 sassy_hip_Amplicon **out, size_t *n_out);
 void sassy_hip_amplicons_free(sassy_hip_Amplicon *p);
+
+/* All-vs-all Hamming distances between two lists of sequences of ONE length m, 1 <= m <= 128: there is no text, every
+ * sequence of `a` meets every sequence of `b` at the one alignment there is (sassy_amd/csrc/hamming_pairs.hip; DESIGN.md
+ * 5.10 "Pairs").  `a` holds n_a sequences back to back, m bytes each, as sassy_hip_encode_patterns takes its patterns; so
+ * does `b`.  With match() the searcher's profile relation exactly as sassy_hip_search_hamming defines it,
+ *   H(x, y)  = #{ t < m : !match(x[t], y[t]) }   (strand 0),
+ *   H-(x, y) = H(x, reverse_complement(y))       (strand 1, an rc searcher only).
+ * Two-set mode: a pair is every (i, j, strand) with cost <= k, 0 <= i < n_a, 0 <= j < n_b.  Self mode (b == NULL and
+ * n_b == 0): b = a and every unordered pair once -- strand 0: i < j only; strand 1: i <= j (H- is symmetric in i and j);
+ * (i, i, 1) stays: a sequence within k of its own reverse complement is a real collision.  Barcode / UMI / guide set design,
+ * whitelist correction, collisions between two panels.
+ *  - sassy_hip_hamming_pairs: every pair as a record, in ascending (a_idx, b_idx, strand) order -- part of the contract;
+ *    *out = NULL and *n_out = 0 when there is none: a valid result; more than 2^32 - 1 records: SASSY_HIP_ENOMEM, the
+ *    message carries the count.  Free *out with sassy_hip_hamming_pairs_free.
+ *  - sassy_hip_hamming_nearest: per a_i the smallest candidate (j, strand), cost <= k, under (cost, b_idx, Fwd before Rc) --
+ *    the tie rule of sassy_hip_best_pattern and sassy_hip_hamming_best_pattern; out_ties[i] = the candidates at that cost
+ *    (a correction is unambiguous iff it is 1).  Self mode: the full square, only (j == i, strand 0) is no candidate.  An
+ *    entry without a candidate gets SASSY_HIP_NO_MATCH, UINT32_MAX, 0, 0.  out_index, out_strand and out_ties may be NULL.
+ *  - flags: none (the sequences are host bytes): anything else SASSY_HIP_EINVAL;
+ *  - refusals, before any device work: m == 0, m > 128, k > 254, n_a == 0, a non-NULL b with n_b == 0, a NULL b with
+ *    n_b > 0 and NULL out pointers SASSY_HIP_EINVAL; n_a or n_b > 2^31 - 1 and a searcher with max_n_frac (there is no
+ *    text span for it to apply to) SASSY_HIP_EUNSUPPORTED; then those of sassy_hip_search_hamming for each list as they stand,
+ *    a first, the message followed by "(<entry point>: list a)" or "(... list b)" and its "pattern N" counting inside that
+ *    list.  This includes the family's Ascii limit -- an ascii / ascii_ci sequence of more than 64 distinct (folded) bytes is
+ *    SASSY_HIP_EUNSUPPORTED -- which the bit planes here would not need: kept so that the family refuses one set of inputs;
+ *  - a host table or plane array that cannot be allocated: SASSY_HIP_ENOMEM (nothing throws across the C boundary);
+ *  - the host encodes the sequences into bit planes (Dna 2, Iupac 4, Ascii 8; ascii_ci folded first) and the reverse
+ *    complements of b as target records of their own; a lane owns one entry of a and walks the targets of its chunk, the
+ *    grid is strips of 256 entries x chunks of targets (option pairs_chunks: geometry only).  A survey pass leaves one cell
+ *    per entry and chunk; _nearest folds them in chunk order; _pairs scans the counts and a fill pass writes the records in
+ *    place -- no sort, no atomic;
+ *  - sassy_hip_get_stats afterwards: filtered = 8, chunks, grid = strips, candidates = the records (_pairs); at timing
+ *    level 2 filter_ms = the survey, trace_ms = the fill, scan_ms = all device passes. */
+typedef struct sassy_hip_HammingPair {
+  uint32_t a_idx, b_idx;
+  uint8_t cost;
+  uint8_t strand;   /* 0: H(a, b); 1: H(a, reverse_complement(b)) */
+  uint8_t pad_[2];  /* zero */
+} sassy_hip_HammingPair; /* 12 bytes */
+int sassy_hip_hamming_pairs(sassy_SearcherType *s, const uint8_t *a, size_t n_a, const uint8_t *b, size_t n_b, size_t m,
+                            size_t k, uint32_t flags, sassy_hip_HammingPair **out, size_t *n_out);
+void sassy_hip_hamming_pairs_free(sassy_hip_HammingPair *p);
+int sassy_hip_hamming_nearest(sassy_SearcherType *s, const uint8_t *a, size_t n_a, const uint8_t *b, size_t n_b, size_t m,
+                              size_t k, uint32_t flags, uint8_t *out_cost, uint32_t *out_index, uint8_t *out_strand,
+                              uint32_t *out_ties);
 
 /* FASTA unwrap on the device (sassy_amd/csrc/fasta_unwrap.hip): the raw bytes of a chunk of FASTA in, every
  * record's sequence out as a device-resident text that the one-text entry points take with SASSY_HIP_TEXT_ON_DEVICE, plus a

@@ -156,6 +156,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_search_hamming", "sassy_hip_search_hamming_many", "sassy_hip_hamming_best_pattern",
     "sassy_hip_hamming_counts", "sassy_hip_hamming_counts_many",
     "sassy_hip_hamming_amplicons", "sassy_hip_amplicons_free",
+    "sassy_hip_hamming_pairs", "sassy_hip_hamming_pairs_free", "sassy_hip_hamming_nearest",
     "sassy_hip_fasta_unwrap", "sassy_hip_fasta_n_records", "sassy_hip_fasta_records", "sassy_hip_fasta_text",
     "sassy_hip_fasta_text_bytes", "sassy_hip_fasta_free",
 ]
@@ -303,6 +304,12 @@ def lib():
                                               C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
     L.sassy_hip_amplicons_free.restype = None
     L.sassy_hip_amplicons_free.argtypes = [vp]
+    L.sassy_hip_hamming_pairs.restype = C.c_int
+    L.sassy_hip_hamming_pairs.argtypes = [vp, vp, sz, vp, sz, sz, sz, C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
+    L.sassy_hip_hamming_pairs_free.restype = None
+    L.sassy_hip_hamming_pairs_free.argtypes = [vp]
+    L.sassy_hip_hamming_nearest.restype = C.c_int
+    L.sassy_hip_hamming_nearest.argtypes = [vp, vp, sz, vp, sz, sz, sz, C.c_uint32, vp, vp, vp, vp]
     L.sassy_hip_class_cover.restype = C.c_long
     L.sassy_hip_class_cover.argtypes = [u8p, vp, vp, sz, C.POINTER(C.c_int)]
     L.sassy_hip_search_all_alignments.restype = C.c_int
@@ -435,6 +442,35 @@ def amplicon_dtype():
     import numpy as np
     return np.dtype([("start", "<u8"), ("end", "<u8"), ("pair_idx", "<u4"), ("strand", "u1"), ("fwd_cost", "u1"), ("rev_cost", "u1"),
                      ("pad_", "u1")])
+
+
+def hamming_pair_dtype():
+    """numpy view of include/sassy_hip.h: sassy_hip_HammingPair (12 bytes)."""
+    import numpy as np
+    return np.dtype([("a_idx", "<u4"), ("b_idx", "<u4"), ("cost", "u1"), ("strand", "u1"), ("pad_", "u1", (2,))])
+
+
+def pairs_sequences(seqs, who: str = "hamming_pairs"):
+    """One list of equal-length sequences for `Searcher.hamming_pairs` / `hamming_nearest` as the (n, m) uint8 array the C
+    call reads back to back: a C-contiguous uint8 array of shape (n, m) is used as it is (no copy per entry), a list of bytes
+    is joined -- unequal lengths raise SassyHipError naming the first offender.  ClassPattern entries are refused."""
+    import numpy as np
+    if isinstance(seqs, np.ndarray):
+        if seqs.dtype != np.uint8 or seqs.ndim != 2 or not seqs.flags["C_CONTIGUOUS"]:
+            raise SassyHipError(f"{who} takes a C-contiguous uint8 array of shape (n, m), or a list of equal-length bytes")
+        return seqs
+    if isinstance(seqs, ClassPattern) or isinstance(seqs, (bytes, bytearray, memoryview, str)):
+        raise SassyHipError(f"{who} takes a list of equal-length byte sequences: a ClassPattern is not supported"
+                            if isinstance(seqs, ClassPattern) else f"{who} takes a list of equal-length byte sequences, not one sequence")
+    seqs = list(seqs)
+    if any(isinstance(p, ClassPattern) for p in seqs):
+        raise SassyHipError(f"{who} takes byte sequences only: a ClassPattern is not supported")
+    seqs = [bytes(p) for p in seqs]
+    m = len(seqs[0]) if seqs else 0
+    for i, p in enumerate(seqs):
+        if len(p) != m:
+            raise SassyHipError(f"{who} takes sequences of one length: sequence {i} has {len(p)} bytes, sequence 0 has {m}")
+    return np.frombuffer(b"".join(seqs), dtype=np.uint8).reshape(len(seqs), m)
 
 
 def fasta_record_dtype():
@@ -1030,6 +1066,57 @@ class Searcher:
             return np.frombuffer(_bytes_at(out.value, n_out.value * dt.itemsize), dtype=dt).copy()
         finally:
             lib().sassy_hip_amplicons_free(out)
+
+    @staticmethod
+    def _pairs_lists(a, b, who: str):
+        a = pairs_sequences(a, who)
+        if len(a) == 0:
+            raise SassyHipError(f"{who} needs at least one sequence in a")
+        if b is not None:
+            b = pairs_sequences(b, who)
+            if len(b) == 0:
+                raise SassyHipError(f"{who}: b holds no sequence (b=None compares a with itself)")
+            if b.shape[1] != a.shape[1]:
+                raise SassyHipError(f"{who} takes sequences of one length: b has {b.shape[1]} bytes per sequence, a has {a.shape[1]}")
+        return a, b
+
+    def hamming_pairs(self, a, b=None, k: int = 0):
+        """All-vs-all Hamming distances (sassy_hip_hamming_pairs): every (a_idx, b_idx, strand) with at most k mismatches
+        between sequence a[a_idx] and b[b_idx] (strand 1, an rc searcher only: and reverse_complement(b[b_idx])) as a numpy
+        structured array of `hamming_pair_dtype()`, ordered by (a_idx, b_idx, strand).  All sequences share one length
+        m <= 128; `a`, `b`: a list of equal-length bytes or a C-contiguous uint8 array of shape (n, m).  b = None is self
+        mode: every unordered pair of `a` once -- strand 0: a_idx < b_idx; strand 1: a_idx <= b_idx, (i, i, 1) included.
+        Compared on the device as bit planes: no text, no records but the pairs.  k <= 254."""
+        import numpy as np
+        a, b = self._pairs_lists(a, b, "hamming_pairs")
+        out, n_out = C.c_void_p(), C.c_size_t()
+        _check(lib().sassy_hip_hamming_pairs(self._h, a.ctypes.data, len(a), None if b is None else b.ctypes.data,
+                                             0 if b is None else len(b), a.shape[1], k, 0, C.byref(out), C.byref(n_out)))
+        dt = hamming_pair_dtype()
+        if not n_out.value:
+            return np.zeros(0, dtype=dt)
+        try:
+            return np.frombuffer(_bytes_at(out.value, n_out.value * dt.itemsize), dtype=dt).copy()
+        finally:
+            lib().sassy_hip_hamming_pairs_free(out)
+
+    def hamming_nearest(self, a, b=None, k: int = 0):
+        """Per sequence of `a` its nearest sequence of `b` (sassy_hip_hamming_nearest): (cost uint8, index uint32, strand
+        uint8, ties uint32) arrays of len(a) entries -- of the candidates (b_idx, strand) with at most k mismatches the
+        smallest under (cost, b_idx, strand 0 before 1), and how many candidates share that cost (1: the correction is
+        unambiguous); NO_MATCH (255), 0xFFFFFFFF, 0, 0 where there is none.  b = None: the nearest OTHER entry of `a` -- the
+        full square, only (index == i, strand 0) is no candidate.  Inputs as for `hamming_pairs`.  k <= 254."""
+        import numpy as np
+        a, b = self._pairs_lists(a, b, "hamming_nearest")
+        n = len(a)
+        cost = np.empty(n, dtype=np.uint8)
+        index = np.empty(n, dtype=np.uint32)
+        strand = np.empty(n, dtype=np.uint8)
+        ties = np.empty(n, dtype=np.uint32)
+        _check(lib().sassy_hip_hamming_nearest(self._h, a.ctypes.data, n, None if b is None else b.ctypes.data,
+                                               0 if b is None else len(b), a.shape[1], k, 0, cost.ctypes.data, index.ctypes.data,
+                                               strand.ctypes.data, ties.ctypes.data))
+        return cost, index, strand, ties
 
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k

@@ -1,4 +1,4 @@
-"""`python -m sassy_amd search | filter | demux | count | amplicon ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
+"""`python -m sassy_amd search | filter | demux | count | amplicon | pairs ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
 
 Mirrors `sassy search` (reference: bin/grep.rs:30-157 arguments, :465-470 header, :623-660 pattern
 sources, :710-757 rows; FASTA/FASTQ records as bin/input_iterator.rs:125-137 reads them): every
@@ -51,6 +51,18 @@ every combination a row.  A header row, then rows by (record, pair, strand, star
     pair_id  text_id  strand  start  end  length  fwd_cost  rev_cost
 
 `--seq` appends the product's bytes, reverse-complemented for strand `-`.
+
+`pairs A [B] -k K [--rc] [--nearest] [-a dna|iupac|ascii|ascii_ci]` compares sets of equal-length sequences (barcodes, UMIs,
+guides) all against all, through `Searcher.hamming_pairs`: which sequence of A is within K mismatches of which sequence of B
+(`--rc`: or of its reverse complement, strand `-`); without B, A against itself, every unordered pair once.  A and B load as
+`count`'s PATTERNS.  A header row, then rows by (a, b, strand):
+
+    a_id  b_id  strand  cost
+
+`--nearest` writes one row per sequence of A through `Searcher.hamming_nearest` -- its nearest sequence of B (of A: its nearest
+other one), and `ties`, how many are that near; `*`, `*` and -1 where nothing is within K:
+
+    a_id  b_id  strand  cost  ties
 
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
@@ -369,6 +381,50 @@ def count_parser(sub):
     return cp
 
 
+def pairs_header(nearest: bool = False) -> str:
+    return "a_id\tb_id\tstrand\tcost" + ("\tties" if nearest else "") + "\n"
+
+
+def pairs_rows(a_seqs, b_seqs, records):
+    """The TSV rows of Searcher.hamming_pairs' records: a_id, b_id, strand, cost -- in the records' order."""
+    return [f"{a_seqs[int(r['a_idx'])][0]}\t{b_seqs[int(r['b_idx'])][0]}\t{'-' if r['strand'] else '+'}\t{int(r['cost'])}\n" for r in records]
+
+
+def nearest_rows(a_seqs, b_seqs, cost, index, strand, ties):
+    """The TSV rows of Searcher.hamming_nearest's columns, one per sequence of A: b_id and strand are `*` and cost is -1
+    where nothing is within k."""
+    rows = []
+    for i, (a_id, _) in enumerate(a_seqs):
+        if int(cost[i]) == NO_MATCH:
+            rows.append(f"{a_id}\t*\t*\t-1\t0\n")
+        else:
+            rows.append(f"{a_id}\t{b_seqs[int(index[i])][0]}\t{'-' if strand[i] else '+'}\t{int(cost[i])}\t{int(ties[i])}\n")
+    return rows
+
+
+def run_pairs(args, searcher, a_seqs, b_seqs, out) -> int:
+    a = [s for _, s in a_seqs]
+    b = None if b_seqs is None else [s for _, s in b_seqs]
+    out.write(pairs_header(args.nearest))
+    if args.nearest:
+        out.writelines(nearest_rows(a_seqs, a_seqs if b_seqs is None else b_seqs, *searcher.hamming_nearest(a, b, args.k)))
+    else:
+        out.writelines(pairs_rows(a_seqs, a_seqs if b_seqs is None else b_seqs, searcher.hamming_pairs(a, b, args.k)))
+    out.flush()
+    return 0
+
+
+def pairs_parser(sub):
+    cp = sub.add_parser("pairs", help="write which sequences of A and B (or of A alone) are within k mismatches of each other as TSV to stdout")
+    cp.add_argument("a", metavar="A", help="FASTA / FASTQ of equal-length sequences, or one sequence per line")
+    cp.add_argument("b", metavar="B", nargs="?", default=None, help="the second set (left out: A against itself, every unordered pair once)")
+    cp.add_argument("-k", type=int, required=True)
+    cp.add_argument("--rc", action="store_true", help="compare with the reverse complements of B as strand '-' as well")
+    cp.add_argument("--nearest", action="store_true", help="one row per sequence of A: its nearest sequence of B and how many tie with it")
+    cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac", "ascii", "ascii_ci"], default="dna")
+    return cp
+
+
 def load_primers(path: str) -> List[Tuple[str, bytes, bytes]]:
     """PRIMERS of `amplicon`: rows of name<TAB>fwd<TAB>rev (empty lines and lines from `#` on skipped)."""
     pairs = []
@@ -471,7 +527,24 @@ def main(argv=None) -> int:
     dp.add_argument("paths", nargs="+")
     count_parser(sub)
     amplicon_parser(sub)
+    pairs_parser(sub)
     args = ap.parse_args(argv)
+    if args.cmd == "pairs":
+        if not 0 <= args.k <= 254:
+            ap.error("pairs takes 0 <= k <= 254")
+        if args.rc and args.alphabet.startswith("ascii"):
+            ap.error("pairs --rc: there is no reverse complement of plain text")
+        a_seqs = load_count_patterns(args.a)
+        b_seqs = None if args.b is None else load_count_patterns(args.b)
+        m = len(a_seqs[0][1]) if a_seqs else 0
+        for path, seqs in ((args.a, a_seqs), (args.b, b_seqs)):
+            if seqs is not None and not seqs:
+                ap.error(f"pairs: {path} holds no sequence")
+            for i, (_, seq) in enumerate(seqs or ()):
+                if len(seq) != m:
+                    ap.error(f"pairs takes sequences of one length: {path}: sequence {i} has {len(seq)} bytes, the first of {args.a} has {m}")
+        searcher = Searcher(args.alphabet, rc=args.rc)
+        return run_pairs(args, searcher, a_seqs, b_seqs, sys.stdout)
     if args.cmd == "amplicon":
         if not 0 <= args.k <= 254:
             ap.error("amplicon takes 0 <= k <= 254")

@@ -697,6 +697,12 @@ struct sassy_SearcherType {
   DevBuf<uint32_t> d_amp_tab, d_amp_counts;
   DevBuf<uint64_t> d_amp_offs;
   DevBuf<sassy_hip_Amplicon> d_amp_out;
+  // all-vs-all Hamming (hamming_pairs.hip): the entries' and the target records' bit planes, the partials matrix (one
+  // PairsCell per chunk and entry), the row sums | their scan | its block sums, the records or the nearest columns
+  DevBuf<uint32_t> d_pairs_a, d_pairs_t;
+  DevBuf<uint4> d_pairs_cells;
+  DevBuf<unsigned long long> d_pairs_rows;
+  DevBuf<uint8_t> d_pairs_out;
   DevBuf<uint64_t> d_range;      // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
@@ -721,6 +727,7 @@ struct sassy_SearcherType {
     d_line_tiles.release(); d_line_prefix.release(); d_line_pos.release(); d_line_out.release();
     d_ham_tab.release(); d_ham_count.release(); d_ham_prefix.release(); d_ham_items.release(); d_ham_sorted.release(); d_ham_sort.release();
     d_ham_texts.release(); d_ham_rem.release(); d_ham_cells.release(); d_ham_bins.release();
+    d_pairs_a.release(); d_pairs_t.release(); d_pairs_cells.release(); d_pairs_rows.release(); d_pairs_out.release();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();
