@@ -41,9 +41,7 @@ def distances(profile: str, a, b, rc: bool) -> np.ndarray:
     return out
 
 
-def _candidates(profile, a, b, k, rc, square):
-    self_mode = b is None
-    h = distances(profile, a, a if self_mode else b, rc)
+def _records(h, k, rc, self_mode, square):
     keep = h <= k
     if self_mode:
         i = np.arange(h.shape[0])[:, None]
@@ -54,16 +52,22 @@ def _candidates(profile, a, b, k, rc, square):
             keep[:, :, 0] &= j > i
             if rc:
                 keep[:, :, 1] &= j >= i
-    return h, keep
-
-
-def expected_pairs(profile: str, a, b, k: int, rc: bool = False, square: bool = False) -> np.ndarray:
-    """The records in the contract's order (a_idx, b_idx, strand).  square: self mode as hamming_nearest sees it."""
-    h, keep = _candidates(profile, a, b, k, rc, square)
     i, j, s = np.nonzero(keep)  # (row-major: ascending (i, j, strand))
     out = np.zeros(len(i), dtype=PAIR)
     out["a_idx"], out["b_idx"], out["strand"], out["cost"] = i, j, s, h[i, j, s]
     return out
+
+
+def expected_pairs(profile: str, a, b, k: int, rc: bool = False, square: bool = False) -> np.ndarray:
+    """The records in the contract's order (a_idx, b_idx, strand).  square: self mode as hamming_nearest sees it."""
+    self_mode = b is None
+    return _records(distances(profile, a, a if self_mode else b, rc), k, rc, self_mode, square)
+
+
+def expected_self(profile: str, a, k: int, rc: bool = False):
+    """(expected_pairs(a, None), expected_pairs(a, None, square=True)) from one table of distances."""
+    h = distances(profile, a, a, rc)
+    return _records(h, k, rc, True, False), _records(h, k, rc, True, True)
 
 
 def nearest_of_pairs(pairs: np.ndarray, n_a: int):

@@ -2,9 +2,14 @@
 
 Every case compares the whole result: ids, lengths, starts (multiples of 64) and the device buffer byte for byte -- every
 record's sequence, the zero pads between them and the 64 spare bytes -- which is what fasta_ref.layout builds.  Inputs are a
-few MB in total.  Geometry the shapes aim at: 64 bytes per lane, 4 KiB per tile (a wavefront), 64 KiB per super-tile (a
-workgroup of the count pass); the record scan works in blocks of 1 024 records under one workgroup of 1 024 threads, so 70 000
-records are 69 blocks: block borders, more blocks than a wavefront has lanes, and the level above them."""
+few MB each, but for the three that exist for their size (tests/helpers/scan_levels.py: two of 64 MiB, one of a million
+records).  Geometry the shapes aim at: 64 bytes per lane, 4 KiB per tile (a wavefront), 64 KiB per super-tile (a workgroup of
+the count pass); the record scan works in blocks of 1 024 records under one workgroup of 1 024 threads, so 70 000 records are
+69 blocks: block borders, more blocks than a wavefront has lanes, and the level above them.  The upper levels: the scan of the
+super-tile summaries is one workgroup of 1 024 threads, each folding `per` = ceil(n_super / 1024) summaries in order -- 1 025
+super-tiles make per = 2; the compact pass runs at most 4 096 workgroups of one tile at a time -- 16 386 tiles make a
+workgroup reuse its LDS images; the scan of the record block sums gives each of 1 024 threads `per` blocks -- 1 026 blocks
+make per = 2.  Not reached: the record pass's grid cap of 2^20 workgroups (more than 16 GiB of input)."""
 import os
 import random
 import sys
@@ -16,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 
 import fasta_ref  # noqa: E402
+import scan_levels as lv  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -36,19 +42,35 @@ def first_diff(a: bytes, b: bytes) -> int:
     return int(x[0]) if x.size else n
 
 
-def compare(sassy, fa, raw: bytes, ctx):
-    want = fasta_ref.parse(raw)
-    assert len(fa) == len(want), (ctx, len(fa), len(want))
-    for name, col in (("id_starts", [r.id_start for r in want]), ("id_lens", [r.id_len for r in want]),
-                      ("seq_starts", [r.seq_start for r in want]), ("seq_lens", [r.seq_len for r in want])):
-        got = getattr(fa, name)
-        bad = np.flatnonzero(got != np.asarray(col, dtype=np.uint64))
-        assert not bad.size, (ctx, name, int(bad[0]), int(got[bad[0]]), col[int(bad[0])])
+def columns(want):
+    return {"id_starts": [r.id_start for r in want], "id_lens": [r.id_len for r in want],
+            "seq_starts": [r.seq_start for r in want], "seq_lens": [r.seq_len for r in want]}
+
+
+def compare_with(sassy, fa, cols, layout: bytes, ctx):
+    """the table, column by column, and the whole device buffer; a mismatch names the record, its block of the record scan
+    and the super-tile its '>' lies in"""
+    n_rec = len(cols["id_starts"])
+    assert len(fa) == n_rec, (ctx, len(fa), n_rec)
+    for name in ("id_starts", "id_lens", "seq_starts", "seq_lens"):
+        got, col = getattr(fa, name), np.asarray(cols[name], dtype=np.uint64)
+        bad = np.flatnonzero(got != col)
+        assert not bad.size, (ctx, name, "record", int(bad[0]), "record block", int(bad[0]) // 1024, "super-tile",
+                              int(cols["id_starts"][int(bad[0])]) // 65536, int(got[bad[0]]), int(col[bad[0]]))
     assert not (fa.seq_starts % 64).any(), ctx
-    layout = fasta_ref.layout(want)
     assert fa.text_bytes == len(layout) and fa.ptr, (ctx, fa.text_bytes, len(layout))
     got = sassy.DeviceText(fa.ptr, fa.text_bytes).download()
-    assert got == layout, (ctx, "first differing byte", first_diff(got, layout), len(layout))  # sequences, pads, spare bytes
+    if got != layout:  # sequences, pads, spare bytes
+        at = first_diff(got, layout)
+        rec = int(np.searchsorted(np.asarray(cols["seq_starts"], dtype=np.uint64), at, side="right")) - 1
+        raw_at = int(cols["id_starts"][rec]) + int(cols["id_lens"][rec]) + at - int(cols["seq_starts"][rec])  # (but for line ends)
+        pytest.fail(f"{ctx}: first differing byte {at} of {len(layout)}, in record {rec} (record block {rec // 1024}), near raw byte "
+                    f"{raw_at} (tile {raw_at // 4096}, super-tile {raw_at // 65536})")
+
+
+def compare(sassy, fa, raw: bytes, ctx, want=None, layout=None):
+    want = fasta_ref.parse(raw) if want is None else want
+    compare_with(sassy, fa, columns(want), fasta_ref.layout(want) if layout is None else layout, ctx)
     for i in sorted(set(list(range(min(3, len(want)))) + list(range(max(0, len(want) - 3), len(want))))):
         assert fa.download(i) == want[i].seq and fa.text(i).numel() == len(want[i].seq), (ctx, i)
         assert fa.text(i).data_ptr() % 64 == 0, (ctx, i)
@@ -168,6 +190,53 @@ def test_alignment_and_padding_of_neighbouring_records(sassy):
 def test_many_records_cross_the_record_scans_blocks(sassy):
     want = check(sassy, b">a\nA\n" * 70000, "70 000 records")
     assert len(want) == 70000 and want[-1].seq_start == 64 * 69999
+
+
+@pytest.mark.parametrize("variant", (0, 1))
+def test_more_than_1024_super_tiles(sassy, variant):
+    """64 MiB + 5000 bytes (scan_levels.fasta_big): n_super = 1025, so every thread of fasta_scan_kernel folds per = 2
+    super-tile summaries (thread 512 one, the threads behind it none), and n_tiles = 16 386 on 4096 workgroups of
+    fasta_compact_kernel, up to 5 tiles each.  Once from host bytes, once from a device-resident buffer."""
+    arr, at = lv.fasta_big(variant)
+    raw = arr.tobytes()
+    want = fasta_ref.parse(raw)
+    layout = fasta_ref.layout(want)
+    n_super, n_tiles = -(-len(raw) // lv.SUPER), -(-len(raw) // lv.TILE)
+    print(f"variant {variant}: {len(raw)} bytes, n_super={n_super} per={-(-n_super // 1024)} n_tiles={n_tiles} "
+          f"tiles of workgroup 0={len(range(0, n_tiles, 4096))} records={len(want)}")
+    assert n_super == 1025 and len(range(0, n_tiles, 4096)) == 5
+    host = sassy.DeviceFasta(raw)
+    try:
+        compare(sassy, host, raw, ("host", variant), want, layout)
+    finally:
+        host.free()
+    buf = sassy.DeviceBuffer((len(raw) + 63) // 64 * 64)
+    buf.upload(raw)
+    dev = sassy.DeviceFasta(sassy.DeviceText(buf.ptr, len(raw), owner=buf))
+    try:
+        compare(sassy, dev, raw, ("device", variant), want, layout)
+    finally:
+        dev.free()
+        buf.free()
+
+
+def test_more_than_1024_record_blocks(sassy):
+    """1 048 576 + 1030 records (scan_levels.fasta_many_records): n_blocks = 1026 blocks of the record scan, so
+    fasta_rec_top_kernel runs with per = 2 -- thread 512 owns the last full block and the one of 6 records, the threads
+    behind it nothing.  The expectation is the closed form, which test_scan_levels_cpu compares with the line-by-line parse
+    around every planted border."""
+    raw, cols, layout = lv.fasta_many_records()
+    n_blocks = -(-lv.FASTA_MANY_RECORDS // lv.REC_BLOCK)
+    print(f"{len(raw)} bytes, records={lv.FASTA_MANY_RECORDS} n_blocks={n_blocks} per={-(-n_blocks // 1024)} layout={len(layout)}")
+    assert n_blocks == 1026
+    fa = sassy.DeviceFasta(raw)
+    try:
+        compare_with(sassy, fa, cols, layout, "1 049 606 records")
+        for r in (0, 1023 * 1024 + 1, 1024 * 1024 - 1, lv.FASTA_MANY_RECORDS - 1):
+            a, n = int(cols["seq_starts"][r]), int(cols["seq_lens"][r])
+            assert fa.download(r) == layout[a:a + n] and fa.text(r).data_ptr() % 64 == 0, r
+    finally:
+        fa.free()
 
 
 def test_host_and_device_resident_input_agree(sassy):

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import oracle  # noqa: E402
 import hamming_ref as href  # noqa: E402
 import hamming_pairs_ref as pref  # noqa: E402
+from scan_levels import LETTERS, near_copy, random_rows  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +24,6 @@ MS = (1, 16, 31, 32, 33, 64, 65, 128)
 ALPHABETS = (("dna", False), ("dna", True), ("iupac", False), ("iupac", True), ("ascii", False), ("ascii_ci", False))
 KS = (0, 1, 3)
 CHUNKS = (0, 1, 2, 3, 7)
-LETTERS = {"dna": b"ACGT", "iupac": b"ACGTACGTACGTNRYKMX", "ascii": b"ACGTacgt xyzXYZ@[`{", "ascii_ci": b"ACGTacgt xyzXYZ@[`{"}
 
 
 @pytest.fixture(scope="module")
@@ -47,20 +47,6 @@ def check_pairs(got, want):
 def check_nearest(got, want):
     for g, w, name in zip(got, want, ("cost", "index", "strand", "ties")):
         assert g.dtype == w.dtype and g.tolist() == w.tolist(), name
-
-
-def random_rows(rng, profile, n, m):
-    letters = np.frombuffer(LETTERS[profile], dtype=np.uint8)
-    return letters[rng.integers(0, len(letters), size=(n, m))]
-
-
-def near_copy(rng, profile, base, d):
-    """base with d rows changed to another letter (under Dna and Ascii: exactly d mismatches)."""
-    out = base.copy()
-    letters = LETTERS[profile][:4]
-    for t in rng.choice(len(base), size=min(d, len(base)), replace=False):
-        out[t] = next(c for c in letters if c != base[t] and (c | 0x20) != (base[t] | 0x20))
-    return out
 
 
 def seams(n, chunk=None):

@@ -13,6 +13,7 @@ import oracle
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from helpers import line_spans_ref as ref  # noqa: E402
+from helpers import scan_levels as lv  # noqa: E402
 from helpers.prose_text import fold, on_device, prose  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -59,13 +60,20 @@ def random_spans(rng, n, count, tile):
     return first, np.minimum(first + width, n).astype(np.uint64)
 
 
+def first_bad(got, want, first, last):
+    """the first differing span: its index, its ends and the super-tiles (64 KiB) they lie in, what came and what was due"""
+    i = int(np.flatnonzero(got != want)[0])
+    return ("span", i, int(first[i]), int(last[i]), "super-tiles", int(first[i]) >> 16, int(last[i]) >> 16, "got", got[i], "want", want[i])
+
+
 def check(sassy, s, text, first, last, dev=None):
     want = want_spans(sassy, text, first, last)
     got = s.line_spans(text, first, last)
-    assert got.dtype == sassy.line_span_dtype() and (got == want).all(), (np.flatnonzero(got != want)[:5], got[:3], want[:3])
+    assert got.dtype == sassy.line_span_dtype()
+    assert (got == want).all(), (np.flatnonzero(got != want)[:5], first_bad(got, want, first, last))
     if dev is not None:
         got = s.line_spans(dev, first, last)
-        assert (got == want).all(), ("device text", np.flatnonzero(got != want)[:5])
+        assert (got == want).all(), ("device text", np.flatnonzero(got != want)[:5], first_bad(got, want, first, last))
 
 
 def test_random_texts_and_densities(sassy):
@@ -115,6 +123,24 @@ def test_tile_borders_and_a_long_line(sassy):
     assert all(tuple(int(x) for x in g) == (3, 3, 13, 13 + long_line) for g in got)
     first, last = random_spans(rng, n, 300, tile)
     check(sassy, s, text, first, last)
+
+
+def test_more_than_1024_super_tiles(sassy):
+    """64 MiB + 4096 + 17 bytes (helpers/scan_levels.py: lines_big): n_super = 1025, so every thread of line_scan_kernel sums
+    per = 2 super-tile counts (thread 512 one, the threads behind it none); the counts are very uneven -- 0, 65 536, about
+    820 and 1150 -- so that a prefix shifted by one super-tile shows in every span behind it."""
+    rng = random.Random(1025)
+    s = sassy.Searcher("ascii", rc=False)
+    text = lv.lines_big()
+    n = len(text)
+    n_super = -(-n // lv.SUPER)
+    print(f"{n} bytes, n_super={n_super} per={-(-n_super // 1024)}")
+    assert n_super == 1025
+    first, last = lv.lines_spans()
+    more_first, more_last = random_spans(rng, n, 300, sassy.line_tile())
+    buf, dev = on_device(sassy, text)
+    check(sassy, s, text, np.concatenate([first, more_first]), np.concatenate([last, more_last]), dev)
+    buf.free()
 
 
 @pytest.mark.parametrize("count", [1, 63, 64, 65, 100_000])
