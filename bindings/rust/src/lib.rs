@@ -125,6 +125,12 @@ extern "C" {
     fn sassy_hip_hamming_pairs_free(p: *mut HammingPair);
     fn sassy_hip_hamming_nearest(s: *mut RawSearcher, a: *const u8, n_a: usize, b: *const u8, n_b: usize, m: usize, k: usize,
                                  flags: u32, out_cost: *mut u8, out_index: *mut u32, out_strand: *mut u8, out_ties: *mut u32) -> c_int;
+    // ... and under the edit distance: a length per list (sassy_hip_EditPair is sassy_hip_HammingPair, cost = E)
+    fn sassy_hip_edit_pairs(s: *mut RawSearcher, a: *const u8, n_a: usize, m_a: usize, b: *const u8, n_b: usize, m_b: usize, k: usize,
+                            flags: u32, out: *mut *mut HammingPair, n_out: *mut usize) -> c_int;
+    fn sassy_hip_edit_pairs_free(p: *mut HammingPair);
+    fn sassy_hip_edit_nearest(s: *mut RawSearcher, a: *const u8, n_a: usize, m_a: usize, b: *const u8, n_b: usize, m_b: usize, k: usize,
+                              flags: u32, out_cost: *mut u8, out_index: *mut u32, out_strand: *mut u8, out_ties: *mut u32) -> c_int;
     // FASTA unwrap on the device: raw bytes in, a device text per record and a host table out (flags: TEXT_ON_DEVICE)
     pub fn sassy_hip_fasta_unwrap(raw: *const u8, n: u64, flags: u32, hip_stream: *mut std::ffi::c_void, out: *mut *mut RawFasta) -> c_int;
     pub fn sassy_hip_fasta_n_records(f: *const RawFasta) -> u64;
@@ -476,6 +482,36 @@ impl<P: Profile> Searcher<P> {
         let rc = unsafe {
             sassy_hip_hamming_nearest(self.raw, a.as_ptr(), n, bp, nb, m, k, 0, cost.as_mut_ptr(), index.as_mut_ptr(), strand.as_mut_ptr(),
                                       ties.as_mut_ptr())
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        (0..n).map(|i| (cost[i], index[i], if strand[i] != 0 { Strand::Rc } else { Strand::Fwd }, ties[i])).collect()
+    }
+
+    /// All-vs-all edit (Levenshtein) distances: `hamming_pairs` with substitutions, insertions and deletions at 1 each, both
+    /// sequences consumed whole.  `a` holds sequences of `m_a` bytes, `b` of `m_b` bytes (`(list, m_b)`), both `<= 64`;
+    /// `b = None`: `a` against itself.  Records and order as `hamming_pairs`; `cost` is the edit distance.  `k <= 254`.
+    pub fn edit_pairs(&mut self, a: &[u8], m_a: usize, b: Option<(&[u8], usize)>, k: usize) -> Vec<HammingPair> {
+        assert!(m_a > 0 && a.len() % m_a == 0 && b.map_or(true, |(b, m_b)| m_b > 0 && b.len() % m_b == 0), "lists hold whole sequences");
+        let (bp, nb, m_b) = b.map_or((std::ptr::null(), 0, 0), |(b, m_b)| (b.as_ptr(), b.len() / m_b, m_b));
+        let mut out: *mut HammingPair = std::ptr::null_mut();
+        let mut n = 0usize;
+        let rc = unsafe { sassy_hip_edit_pairs(self.raw, a.as_ptr(), a.len() / m_a, m_a, bp, nb, m_b, k, 0, &mut out, &mut n) };
+        assert_eq!(rc, 0, "{}", last_error());
+        let v = if n == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(out, n) }.to_vec() };
+        unsafe { sassy_hip_edit_pairs_free(out) };
+        v
+    }
+
+    /// Per sequence of `a` its nearest sequence of `b` within `k` edits: `(cost, index, strand, ties)` as `hamming_nearest`
+    /// gives them.  Lists as for `edit_pairs`.
+    pub fn edit_nearest(&mut self, a: &[u8], m_a: usize, b: Option<(&[u8], usize)>, k: usize) -> Vec<(u8, u32, Strand, u32)> {
+        assert!(m_a > 0 && a.len() % m_a == 0 && b.map_or(true, |(b, m_b)| m_b > 0 && b.len() % m_b == 0), "lists hold whole sequences");
+        let (bp, nb, m_b) = b.map_or((std::ptr::null(), 0, 0), |(b, m_b)| (b.as_ptr(), b.len() / m_b, m_b));
+        let n = a.len() / m_a;
+        let (mut cost, mut index, mut strand, mut ties) = (vec![0u8; n], vec![0u32; n], vec![0u8; n], vec![0u32; n]);
+        let rc = unsafe {
+            sassy_hip_edit_nearest(self.raw, a.as_ptr(), n, m_a, bp, nb, m_b, k, 0, cost.as_mut_ptr(), index.as_mut_ptr(), strand.as_mut_ptr(),
+                                   ties.as_mut_ptr())
         };
         assert_eq!(rc, 0, "{}", last_error());
         (0..n).map(|i| (cost[i], index[i], if strand[i] != 0 { Strand::Rc } else { Strand::Fwd }, ties[i])).collect()

@@ -94,7 +94,9 @@ typedef struct sassy_hip_Stats {
                             5: the pattern-tiled scan of search_encoded (tiled_kernel: all patterns in one pass);
                             6: the seeded search of search_encoded (seed_kernels: seed table lookups, one lane per hit);
                             7: the Hamming scan of sassy_hip_search_hamming (hamming.hip: no DP);
-                            8: the all-vs-all walk of sassy_hip_hamming_pairs / _nearest (hamming_pairs.hip: no text) */
+                            8: the all-vs-all walk of sassy_hip_hamming_pairs / _nearest (hamming_pairs.hip: no text);
+                            9: the all-vs-all walk of sassy_hip_edit_pairs / _nearest (edit_pairs.hip: no text; also
+                               where |m_a - m_b| > k and nothing was launched) */
   double filter_ms;      /* HIP-event time of the prefilter kernel (part of scan_ms); a search in flight whose text pass
                             was served by several launches (see pass_patterns): the sum of their durations */
   uint64_t hit_blocks;   /* text blocks in which an exact pattern piece ends */
@@ -504,6 +506,42 @@ void sassy_hip_hamming_pairs_free(sassy_hip_HammingPair *p);
 int sassy_hip_hamming_nearest(sassy_SearcherType *s, const uint8_t *a, size_t n_a, const uint8_t *b, size_t n_b, size_t m,
                               size_t k, uint32_t flags, uint8_t *out_cost, uint32_t *out_index, uint8_t *out_strand,
                               uint32_t *out_ties);
+
+/* All-vs-all edit distances between two lists of sequences: sassy_hip_hamming_pairs / _nearest with the Levenshtein distance
+ * in place of H, so that a sequence that lost or gained a base is near its origin (sassy_amd/csrc/edit_pairs.hip; DESIGN.md
+ * 5.10 "Edit pairs").  `a` holds n_a sequences of m_a bytes back to back, `b` holds n_b sequences of m_b bytes,
+ * 1 <= m_a, m_b <= 64; the two lengths may differ.  With match() the searcher's profile relation exactly as
+ * sassy_hip_search_hamming defines it,
+ *   E(x, y)  = the fewest substitutions, insertions and deletions (1 each) that turn x into y under match(): both
+ *              sequences are consumed whole, D[0][j] = j and D[i][0] = i                         (strand 0),
+ *   E-(x, y) = E(x, reverse_complement(y))                                                       (strand 1, an rc searcher only).
+ * Everything else is the Hamming pair calls' contract word for word: two-set mode and self mode (b == NULL and n_b == 0;
+ * m_b is then 0 or m_a), the self-mode triangle -- strand 0: i < j, strand 1: i <= j, (i, i, 1) stays --, records in
+ * ascending (a_idx, b_idx, strand) order, _nearest under (cost, b_idx, Fwd before Rc) with out_ties over the full square
+ * without (i, i, 0) in self mode, SASSY_HIP_NO_MATCH, UINT32_MAX, 0, 0 for an entry without a candidate, *out = NULL and
+ * *n_out = 0 for no record, more than 2^32 - 1 records SASSY_HIP_ENOMEM with the count.  Free *out with
+ * sassy_hip_edit_pairs_free.  out_index, out_strand and out_ties may be NULL.
+ *  - flags: none: anything else SASSY_HIP_EINVAL;
+ *  - refusals, before any device work: m_a or m_b == 0 or > 64, k > 254, n_a == 0, a non-NULL b with n_b == 0, a NULL b
+ *    with n_b > 0, a NULL b with m_b neither 0 nor m_a and NULL out pointers SASSY_HIP_EINVAL; n_a or n_b > 2^31 - 1 and a
+ *    searcher with max_n_frac SASSY_HIP_EUNSUPPORTED; then those of sassy_hip_search_hamming for each list as they stand,
+ *    named as the Hamming pair calls name them ("(<entry point>: list a)");
+ *  - |m_a - m_b| > k is a valid call with an empty answer (E >= |m_a - m_b|): the device is acquired -- a machine without
+ *    one still fails -- and nothing is launched;
+ *  - a host table that cannot be allocated: SASSY_HIP_ENOMEM;
+ *  - the host encodes the entries of a into the bit planes of the Hamming pair calls and the targets into one row code per
+ *    column; a lane owns one entry and steps a bit-vector column (Myers / Hyyro, global boundary) per target column, several
+ *    targets side by side; grid, survey, scan and fill are those of sassy_hip_hamming_pairs (option pairs_chunks: geometry
+ *    only);
+ *  - sassy_hip_get_stats afterwards: filtered = 9, chunks, grid = strips, candidates = the records (_pairs); at timing
+ *    level 2 filter_ms = the survey, trace_ms = the fill, scan_ms = all device passes. */
+typedef sassy_hip_HammingPair sassy_hip_EditPair; /* the same 12 bytes; cost = E */
+int sassy_hip_edit_pairs(sassy_SearcherType *s, const uint8_t *a, size_t n_a, size_t m_a, const uint8_t *b, size_t n_b,
+                         size_t m_b, size_t k, uint32_t flags, sassy_hip_EditPair **out, size_t *n_out);
+void sassy_hip_edit_pairs_free(sassy_hip_EditPair *p);
+int sassy_hip_edit_nearest(sassy_SearcherType *s, const uint8_t *a, size_t n_a, size_t m_a, const uint8_t *b, size_t n_b,
+                           size_t m_b, size_t k, uint32_t flags, uint8_t *out_cost, uint32_t *out_index, uint8_t *out_strand,
+                           uint32_t *out_ties);
 
 /* FASTA unwrap on the device (sassy_amd/csrc/fasta_unwrap.hip): the raw bytes of a chunk of FASTA in, every
  * record's sequence out as a device-resident text that the one-text entry points take with SASSY_HIP_TEXT_ON_DEVICE, plus a

@@ -157,6 +157,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_hamming_counts", "sassy_hip_hamming_counts_many",
     "sassy_hip_hamming_amplicons", "sassy_hip_amplicons_free",
     "sassy_hip_hamming_pairs", "sassy_hip_hamming_pairs_free", "sassy_hip_hamming_nearest",
+    "sassy_hip_edit_pairs", "sassy_hip_edit_pairs_free", "sassy_hip_edit_nearest",
     "sassy_hip_fasta_unwrap", "sassy_hip_fasta_n_records", "sassy_hip_fasta_records", "sassy_hip_fasta_text",
     "sassy_hip_fasta_text_bytes", "sassy_hip_fasta_free",
 ]
@@ -310,6 +311,12 @@ def lib():
     L.sassy_hip_hamming_pairs_free.argtypes = [vp]
     L.sassy_hip_hamming_nearest.restype = C.c_int
     L.sassy_hip_hamming_nearest.argtypes = [vp, vp, sz, vp, sz, sz, sz, C.c_uint32, vp, vp, vp, vp]
+    L.sassy_hip_edit_pairs.restype = C.c_int
+    L.sassy_hip_edit_pairs.argtypes = [vp, vp, sz, sz, vp, sz, sz, sz, C.c_uint32, C.POINTER(vp), C.POINTER(sz)]
+    L.sassy_hip_edit_pairs_free.restype = None
+    L.sassy_hip_edit_pairs_free.argtypes = [vp]
+    L.sassy_hip_edit_nearest.restype = C.c_int
+    L.sassy_hip_edit_nearest.argtypes = [vp, vp, sz, sz, vp, sz, sz, sz, C.c_uint32, vp, vp, vp, vp]
     L.sassy_hip_class_cover.restype = C.c_long
     L.sassy_hip_class_cover.argtypes = [u8p, vp, vp, sz, C.POINTER(C.c_int)]
     L.sassy_hip_search_all_alignments.restype = C.c_int
@@ -1068,7 +1075,7 @@ class Searcher:
             lib().sassy_hip_amplicons_free(out)
 
     @staticmethod
-    def _pairs_lists(a, b, who: str):
+    def _pairs_lists(a, b, who: str, one_length: bool = True):
         a = pairs_sequences(a, who)
         if len(a) == 0:
             raise SassyHipError(f"{who} needs at least one sequence in a")
@@ -1076,7 +1083,7 @@ class Searcher:
             b = pairs_sequences(b, who)
             if len(b) == 0:
                 raise SassyHipError(f"{who}: b holds no sequence (b=None compares a with itself)")
-            if b.shape[1] != a.shape[1]:
+            if one_length and b.shape[1] != a.shape[1]:
                 raise SassyHipError(f"{who} takes sequences of one length: b has {b.shape[1]} bytes per sequence, a has {a.shape[1]}")
         return a, b
 
@@ -1116,6 +1123,43 @@ class Searcher:
         _check(lib().sassy_hip_hamming_nearest(self._h, a.ctypes.data, n, None if b is None else b.ctypes.data,
                                                0 if b is None else len(b), a.shape[1], k, 0, cost.ctypes.data, index.ctypes.data,
                                                strand.ctypes.data, ties.ctypes.data))
+        return cost, index, strand, ties
+
+    def edit_pairs(self, a, b=None, k: int = 0):
+        """All-vs-all edit distances (sassy_hip_edit_pairs): `hamming_pairs` with the Levenshtein distance E in place of
+        H -- substitution, insertion and deletion cost 1 each and both sequences are consumed whole --, so a sequence that
+        lost or gained a base is at cost 1 from its origin.  Every (a_idx, b_idx, strand) with E <= k as a structured
+        array of `hamming_pair_dtype()`, ordered by (a_idx, b_idx, strand); strand 1 (an rc searcher only) is
+        E(a, reverse_complement(b)).  The sequences of `a` share one length m_a <= 64 and those of `b` one length
+        m_b <= 64; the two may differ (|m_a - m_b| > k: no record).  Inputs, self mode (b = None) and its triangle as for
+        `hamming_pairs`.  k <= 254."""
+        import numpy as np
+        a, b = self._pairs_lists(a, b, "edit_pairs", one_length=False)
+        out, n_out = C.c_void_p(), C.c_size_t()
+        _check(lib().sassy_hip_edit_pairs(self._h, a.ctypes.data, len(a), a.shape[1], None if b is None else b.ctypes.data,
+                                          0 if b is None else len(b), 0 if b is None else b.shape[1], k, 0, C.byref(out), C.byref(n_out)))
+        dt = hamming_pair_dtype()
+        if not n_out.value:
+            return np.zeros(0, dtype=dt)
+        try:
+            return np.frombuffer(_bytes_at(out.value, n_out.value * dt.itemsize), dtype=dt).copy()
+        finally:
+            lib().sassy_hip_edit_pairs_free(out)
+
+    def edit_nearest(self, a, b=None, k: int = 0):
+        """Per sequence of `a` its nearest sequence of `b` under the edit distance (sassy_hip_edit_nearest): (cost uint8,
+        index uint32, strand uint8, ties uint32) arrays exactly as `hamming_nearest` returns them, with E in place of H.
+        Inputs as for `edit_pairs`.  k <= 254."""
+        import numpy as np
+        a, b = self._pairs_lists(a, b, "edit_nearest", one_length=False)
+        n = len(a)
+        cost = np.empty(n, dtype=np.uint8)
+        index = np.empty(n, dtype=np.uint32)
+        strand = np.empty(n, dtype=np.uint8)
+        ties = np.empty(n, dtype=np.uint32)
+        _check(lib().sassy_hip_edit_nearest(self._h, a.ctypes.data, n, a.shape[1], None if b is None else b.ctypes.data,
+                                            0 if b is None else len(b), 0 if b is None else b.shape[1], k, 0, cost.ctypes.data,
+                                            index.ctypes.data, strand.ctypes.data, ties.ctypes.data))
         return cost, index, strand, ties
 
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:

@@ -64,6 +64,10 @@ other one), and `ties`, how many are that near; `*`, `*` and -1 where nothing is
 
     a_id  b_id  strand  cost  ties
 
+`--edit` counts K edits (substitutions, insertions and deletions; `Searcher.edit_pairs` / `edit_nearest`) where the rows above
+count K mismatches: a barcode that lost or gained a base is then one edit from its origin.  The sequences of B may have a
+length of their own; both lengths are at most 64.  Same rows.
+
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
 one block per match, sorted by (start, end): `PATH:LINE:COL:COST:` and the line(s) the match lies in -- LINE and the line's
@@ -406,10 +410,13 @@ def run_pairs(args, searcher, a_seqs, b_seqs, out) -> int:
     a = [s for _, s in a_seqs]
     b = None if b_seqs is None else [s for _, s in b_seqs]
     out.write(pairs_header(args.nearest))
+    edit = getattr(args, "edit", False)
     if args.nearest:
-        out.writelines(nearest_rows(a_seqs, a_seqs if b_seqs is None else b_seqs, *searcher.hamming_nearest(a, b, args.k)))
+        nearest = searcher.edit_nearest if edit else searcher.hamming_nearest
+        out.writelines(nearest_rows(a_seqs, a_seqs if b_seqs is None else b_seqs, *nearest(a, b, args.k)))
     else:
-        out.writelines(pairs_rows(a_seqs, a_seqs if b_seqs is None else b_seqs, searcher.hamming_pairs(a, b, args.k)))
+        pairs = searcher.edit_pairs if edit else searcher.hamming_pairs
+        out.writelines(pairs_rows(a_seqs, a_seqs if b_seqs is None else b_seqs, pairs(a, b, args.k)))
     out.flush()
     return 0
 
@@ -422,6 +429,8 @@ def pairs_parser(sub):
     cp.add_argument("--rc", action="store_true", help="compare with the reverse complements of B as strand '-' as well")
     cp.add_argument("--nearest", action="store_true", help="one row per sequence of A: its nearest sequence of B and how many tie with it")
     cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac", "ascii", "ascii_ci"], default="dna")
+    cp.add_argument("--edit", action="store_true",
+                    help="k edits (substitutions, insertions, deletions) instead of k mismatches; B may have a length of its own, both at most 64")
     return cp
 
 
@@ -536,13 +545,15 @@ def main(argv=None) -> int:
             ap.error("pairs --rc: there is no reverse complement of plain text")
         a_seqs = load_count_patterns(args.a)
         b_seqs = None if args.b is None else load_count_patterns(args.b)
-        m = len(a_seqs[0][1]) if a_seqs else 0
         for path, seqs in ((args.a, a_seqs), (args.b, b_seqs)):
             if seqs is not None and not seqs:
                 ap.error(f"pairs: {path} holds no sequence")
+            # one length for both sets; under --edit one length per set
+            first, of = (path, seqs) if args.edit and seqs else (args.a, a_seqs)
+            m = len(of[0][1])
             for i, (_, seq) in enumerate(seqs or ()):
                 if len(seq) != m:
-                    ap.error(f"pairs takes sequences of one length: {path}: sequence {i} has {len(seq)} bytes, the first of {args.a} has {m}")
+                    ap.error(f"pairs takes sequences of one length: {path}: sequence {i} has {len(seq)} bytes, the first of {first} has {m}")
         searcher = Searcher(args.alphabet, rc=args.rc)
         return run_pairs(args, searcher, a_seqs, b_seqs, sys.stdout)
     if args.cmd == "amplicon":

@@ -20,10 +20,13 @@
 //   pairs_fill_kernel     walks again the tiles (wavefront x chunk) that hold a candidate and writes the records: a lane
 //                         walks its targets in order and the cells are placed in (entry, chunk) order, so the records come
 //                         out in the contract's order (a_idx, b_idx, strand)
+// The passes between survey and fill know nothing of the distance: the host code around them (pairs_place_rows,
+// pairs_take_records, pairs_fold_nearest; host_internal.h) also serves edit_pairs.hip, which has a walk of its own.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <new>
 #include <stdexcept>
@@ -280,17 +283,7 @@ void encode_list(Profile pr, const uint8_t* list, size_t n, uint32_t m, uint32_t
       }
     }
   };
-  const size_t workers = n < (1u << 16) ? 1 : std::min<size_t>(8, std::max(1u, std::thread::hardware_concurrency()));
-  if (workers == 1) return slice(0, n);
-  std::vector<std::thread> pool;
-  pool.reserve(workers);
-  size_t w = 0;
-  try {
-    for (; w + 1 < workers; ++w) pool.emplace_back(slice, n * w / workers, n * (w + 1) / workers);
-  } catch (const std::system_error&) {  // (no more threads to be had: this one does the rest)
-  }
-  slice(n * w / workers, n);
-  for (std::thread& t : pool) t.join();
+  pairs_for_slices(n, slice);
 }
 
 // What both entry points refuse, before any device work; self: b == NULL && n_b == 0.
@@ -320,19 +313,6 @@ int pairs_refusals(sassy_SearcherType* s, bool have_out, const uint8_t* a, size_
   };
   if (int rc = family(a, n_a, "a")) return rc;
   return b ? family(b, n_b, "b") : 0;
-}
-
-// An entry point's body: what throws for want of host memory (the lists' tables and planes are sized by the caller's n)
-// comes back as SASSY_HIP_ENOMEM.
-template <typename Body>
-int pairs_guarded(const char* who, Body&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return fail(SASSY_HIP_ENOMEM, std::string(who) + ": out of host memory");
-  } catch (const std::length_error&) {
-    return fail(SASSY_HIP_ENOMEM, std::string(who) + ": out of host memory (a list too long for a host table)");
-  }
 }
 
 // The survey of a call behind its refusals: both lists encoded and uploaded, the partials matrix filled.
@@ -375,6 +355,23 @@ int pairs_survey(sassy_SearcherType* s, const uint8_t* a, size_t n_a, const uint
   s->stats.text_bytes = (uint64_t)(n_a + nb) * m;
   return 0;
 }
+}  // namespace
+
+// ---- what edit_pairs.hip shares (host_internal.h): the passes behind a survey that do not depend on the distance ----
+// slice(i0, i1) over [0, n) in up to 8 host threads (a list of a million sequences is encoded in a fraction of the time)
+void pairs_for_slices(size_t n, const std::function<void(size_t, size_t)>& slice) {
+  const size_t workers = n < (1u << 16) ? 1 : std::min<size_t>(8, std::max(1u, std::thread::hardware_concurrency()));
+  if (workers == 1) return slice(0, n);
+  std::vector<std::thread> pool;
+  pool.reserve(workers);
+  size_t w = 0;
+  try {
+    for (; w + 1 < workers; ++w) pool.emplace_back(slice, n * w / workers, n * (w + 1) / workers);
+  } catch (const std::system_error&) {  // (no more threads to be had: this one does the rest)
+  }
+  slice(n * w / workers, n);
+  for (std::thread& t : pool) t.join();
+}
 // timing level 2: filter_ms the survey, trace_ms the last pass (fill or reduce), scan_ms all of it -- the scan between them
 void pairs_times(sassy_SearcherType* s, bool has_last) {
   if (s->timing < 2) return;
@@ -386,8 +383,61 @@ void pairs_times(sassy_SearcherType* s, bool has_last) {
   s->stats.trace_ms = last;
   s->stats.scan_ms = (double)survey + mid + last;
 }
+// the rows' sums, their exclusive scan, the total: every cell's place in its row, *row_first the device's table of rows
+int pairs_place_rows(sassy_SearcherType* s, uint4* cells, uint64_t n_a, uint32_t n_chunks, const unsigned long long** row_first_out,
+                     unsigned long long* total_out) {
+  hipStream_t st = s->stream;
+  const uint64_t n_blocks = (n_a + kScanBlock - 1) / kScanBlock;
+  if (int rc = s->d_pairs_rows.reserve(2 * n_a + n_blocks + 1)) return rc;
+  unsigned long long *row_sum = s->d_pairs_rows.p, *row_first = row_sum + n_a, *block_sum = row_first + n_a;
+  const uint32_t row_grid = (uint32_t)((n_a + 255) / 256);
+  hipLaunchKernelGGL(pairs_rows_kernel, dim3(row_grid), dim3(256), 0, st, cells, n_a, n_chunks, row_sum);
+  hipLaunchKernelGGL(pairs_scan_sums_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, row_sum, n_a, block_sum);
+  hipLaunchKernelGGL(pairs_scan_top_kernel, dim3(1), dim3(1024), 0, st, block_sum, n_blocks);
+  hipLaunchKernelGGL(pairs_scan_rows_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, row_sum, n_a, block_sum, row_first);
+  HIP_TRY(hipGetLastError());
+  if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[2], st));
+  unsigned long long total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, block_sum + n_blocks, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  s->stats.candidates = total;
+  *row_first_out = row_first;
+  *total_out = total;
+  return 0;
+}
+// the `total` records a fill pass left in d_pairs_out, as the caller's malloc'd array
+int pairs_take_records(sassy_SearcherType* s, unsigned long long total, sassy_hip_HammingPair** out, size_t* n_out) {
+  hipStream_t st = s->stream;
+  sassy_hip_HammingPair* p = static_cast<sassy_hip_HammingPair*>(malloc((size_t)total * sizeof(sassy_hip_HammingPair)));
+  if (!p) return fail(SASSY_HIP_ENOMEM, "out of host memory (pair records)");
+  std::unique_ptr<sassy_hip_HammingPair, decltype(&free)> hold(p, &free);
+  HIP_TRY(hipMemcpyAsync(p, s->d_pairs_out.p, (size_t)total * sizeof(sassy_hip_HammingPair), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  pairs_times(s, true);
+  *out = hold.release();
+  *n_out = (size_t)total;
+  return 0;
+}
+// nearest: every entry's cells folded on the device, the four columns (index | ties | cost | strand) to the caller's arrays
+int pairs_fold_nearest(sassy_SearcherType* s, const uint4* cells, uint64_t n_a, uint32_t n_chunks, uint32_t S, uint8_t* out_cost, uint32_t* out_index,
+                       uint8_t* out_strand, uint32_t* out_ties) {
+  hipStream_t st = s->stream;
+  if (int rc = s->d_pairs_out.reserve(n_a * 10)) return rc;
+  uint32_t *d_index = reinterpret_cast<uint32_t*>(s->d_pairs_out.p), *d_ties = d_index + n_a;
+  uint8_t *d_cost = reinterpret_cast<uint8_t*>(d_ties + n_a), *d_strand = d_cost + n_a;
+  hipLaunchKernelGGL(pairs_nearest_kernel, dim3((uint32_t)((n_a + 255) / 256)), dim3(256), 0, st, cells, n_a, n_chunks, S, d_cost, d_index, d_strand,
+                     d_ties);
+  HIP_TRY(hipGetLastError());
+  if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[2], st));
+  HIP_TRY(hipMemcpyAsync(out_cost, d_cost, n_a, hipMemcpyDeviceToHost, st));
+  if (out_index) HIP_TRY(hipMemcpyAsync(out_index, d_index, n_a * 4, hipMemcpyDeviceToHost, st));
+  if (out_strand) HIP_TRY(hipMemcpyAsync(out_strand, d_strand, n_a, hipMemcpyDeviceToHost, st));
+  if (out_ties) HIP_TRY(hipMemcpyAsync(out_ties, d_ties, n_a * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  pairs_times(s, false);
+  return 0;
+}
 
-}  // namespace
 }  // namespace sassy_hip
 
 using namespace sassy_hip;
@@ -406,21 +456,9 @@ int sassy_hip_hamming_pairs(sassy_SearcherType* s, const uint8_t* a, size_t n_a,
     hipStream_t st = s->stream;
     PairsRun R;
     if (int rc = pairs_survey(s, a, n_a, b, n_b, (uint32_t)m, kk, kPairsSelfPairs, R)) return rc;
-    // the rows' sums, their exclusive scan, the total
-    const uint64_t n_blocks = (n_a + kScanBlock - 1) / kScanBlock;
-    if (int rc = s->d_pairs_rows.reserve(2 * n_a + n_blocks + 1)) return rc;
-    unsigned long long *row_sum = s->d_pairs_rows.p, *row_first = row_sum + n_a, *block_sum = row_first + n_a;
-    const uint32_t row_grid = (uint32_t)((n_a + 255) / 256);
-    hipLaunchKernelGGL(pairs_rows_kernel, dim3(row_grid), dim3(256), 0, st, R.args.cells, (uint64_t)n_a, R.plan.n_chunks, row_sum);
-    hipLaunchKernelGGL(pairs_scan_sums_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, row_sum, (uint64_t)n_a, block_sum);
-    hipLaunchKernelGGL(pairs_scan_top_kernel, dim3(1), dim3(1024), 0, st, block_sum, n_blocks);
-    hipLaunchKernelGGL(pairs_scan_rows_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, row_sum, (uint64_t)n_a, block_sum, row_first);
-    HIP_TRY(hipGetLastError());
-    if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[2], st));
+    const unsigned long long* row_first = nullptr;
     unsigned long long total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, block_sum + n_blocks, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    s->stats.candidates = total;
+    if (int rc = pairs_place_rows(s, R.args.cells, n_a, R.plan.n_chunks, &row_first, &total)) return rc;
     if (total > 0xFFFFFFFFull) return fail(SASSY_HIP_ENOMEM, "hamming_pairs: more than 2^32 - 1 records (" + std::to_string(total) + ")");
     if (total == 0) {
       pairs_times(s, false);
@@ -432,15 +470,7 @@ int sassy_hip_hamming_pairs(sassy_SearcherType* s, const uint8_t* a, size_t n_a,
     HIP_TRY(launch_walk_profile(s->profile, true, R.W, R.args, R.grid, st));
     if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[3], st));
     s->stats.scan_launches = 2;
-    sassy_hip_HammingPair* p = static_cast<sassy_hip_HammingPair*>(malloc((size_t)total * sizeof(sassy_hip_HammingPair)));
-    if (!p) return fail(SASSY_HIP_ENOMEM, "out of host memory (pair records)");
-    std::unique_ptr<sassy_hip_HammingPair, decltype(&free)> hold(p, &free);
-    HIP_TRY(hipMemcpyAsync(p, s->d_pairs_out.p, (size_t)total * sizeof(sassy_hip_HammingPair), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    pairs_times(s, true);
-    *out = hold.release();
-    *n_out = (size_t)total;
-    return 0;
+    return pairs_take_records(s, total, out, n_out);
   });
   });
 }
@@ -454,24 +484,9 @@ int sassy_hip_hamming_nearest(sassy_SearcherType* s, const uint8_t* a, size_t n_
   if (int rc = pairs_refusals(s, out_cost != nullptr, a, n_a, b, n_b, m, k, flags, who)) return rc;
   const size_t lens[1] = {m};
   return hamming_call(s, lens, 1, k, [&](uint32_t kk) {
-    hipStream_t st = s->stream;
     PairsRun R;
     if (int rc = pairs_survey(s, a, n_a, b, n_b, (uint32_t)m, kk, kPairsSelfNearest, R)) return rc;
-    // the four columns on the device: index | ties | cost | strand
-    if (int rc = s->d_pairs_out.reserve(n_a * 10)) return rc;
-    uint32_t *d_index = reinterpret_cast<uint32_t*>(s->d_pairs_out.p), *d_ties = d_index + n_a;
-    uint8_t *d_cost = reinterpret_cast<uint8_t*>(d_ties + n_a), *d_strand = d_cost + n_a;
-    hipLaunchKernelGGL(pairs_nearest_kernel, dim3((uint32_t)((n_a + 255) / 256)), dim3(256), 0, st, (const uint4*)R.args.cells, (uint64_t)n_a,
-                       R.plan.n_chunks, R.args.S, d_cost, d_index, d_strand, d_ties);
-    HIP_TRY(hipGetLastError());
-    if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[2], st));
-    HIP_TRY(hipMemcpyAsync(out_cost, d_cost, n_a, hipMemcpyDeviceToHost, st));
-    if (out_index) HIP_TRY(hipMemcpyAsync(out_index, d_index, n_a * 4, hipMemcpyDeviceToHost, st));
-    if (out_strand) HIP_TRY(hipMemcpyAsync(out_strand, d_strand, n_a, hipMemcpyDeviceToHost, st));
-    if (out_ties) HIP_TRY(hipMemcpyAsync(out_ties, d_ties, n_a * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    pairs_times(s, false);
-    return 0;
+    return pairs_fold_nearest(s, R.args.cells, n_a, R.plan.n_chunks, R.args.S, out_cost, out_index, out_strand, out_ties);
   });
   });
 }

@@ -1242,6 +1242,28 @@ int hamming_call(sassy_SearcherType* s, const size_t* lens, size_t n_pats, size_
   s->stats.total_ms = now_ms() - t0;
   return 0;
 }
+// hamming_pairs.hip, shared with edit_pairs.hip: what a pair call does behind its survey (one PairsCell per chunk and entry,
+// cells[chunk][entry]) whatever the distance -- the rows' places and their 64-bit scan, the records' way back, the nearest
+// fold, the pass times.  The kernels exist once, in hamming_pairs.hip.
+int pairs_place_rows(sassy_SearcherType* s, uint4* cells, uint64_t n_a, uint32_t n_chunks, const unsigned long long** row_first_out,
+                     unsigned long long* total_out);
+int pairs_take_records(sassy_SearcherType* s, unsigned long long total, sassy_hip_HammingPair** out, size_t* n_out);
+int pairs_fold_nearest(sassy_SearcherType* s, const uint4* cells, uint64_t n_a, uint32_t n_chunks, uint32_t S, uint8_t* out_cost, uint32_t* out_index,
+                       uint8_t* out_strand, uint32_t* out_ties);
+void pairs_times(sassy_SearcherType* s, bool has_last);
+void pairs_for_slices(size_t n, const std::function<void(size_t, size_t)>& slice);  // the lists' encoding, in host threads
+// A pair entry point's body: what throws for want of host memory (the lists' tables and planes are sized by the caller's n)
+// comes back as SASSY_HIP_ENOMEM.
+template <typename Body>
+int pairs_guarded(const char* who, Body&& body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc&) {
+    return fail(SASSY_HIP_ENOMEM, std::string(who) + ": out of host memory");
+  } catch (const std::length_error&) {
+    return fail(SASSY_HIP_ENOMEM, std::string(who) + ": out of host memory (a list too long for a host table)");
+  }
+}
 // The one text of search_hamming, hamming_counts and hamming_amplicons on the device: the caller's device pointer, or an upload.
 inline int ham_one_text(sassy_SearcherType* s, const void* text, size_t text_len, uint32_t flags, HamText* out) {
   const uint8_t* d_text = static_cast<const uint8_t*>(text);
