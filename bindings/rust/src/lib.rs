@@ -131,6 +131,11 @@ extern "C" {
     fn sassy_hip_edit_pairs_free(p: *mut HammingPair);
     fn sassy_hip_edit_nearest(s: *mut RawSearcher, a: *const u8, n_a: usize, m_a: usize, b: *const u8, n_b: usize, m_b: usize, k: usize,
                               flags: u32, out_cost: *mut u8, out_index: *mut u32, out_strand: *mut u8, out_ties: *mut u32) -> c_int;
+    // ... and the groups one list forms: per sequence the smallest index of its connected component within k, and its size
+    fn sassy_hip_hamming_clusters(s: *mut RawSearcher, a: *const u8, n: usize, m: usize, k: usize, flags: u32, out_label: *mut u32,
+                                  out_size: *mut u32, n_clusters: *mut usize) -> c_int;
+    fn sassy_hip_edit_clusters(s: *mut RawSearcher, a: *const u8, n: usize, m: usize, k: usize, flags: u32, out_label: *mut u32,
+                               out_size: *mut u32, n_clusters: *mut usize) -> c_int;
     // FASTA unwrap on the device: raw bytes in, a device text per record and a host table out (flags: TEXT_ON_DEVICE)
     pub fn sassy_hip_fasta_unwrap(raw: *const u8, n: u64, flags: u32, hip_stream: *mut std::ffi::c_void, out: *mut *mut RawFasta) -> c_int;
     pub fn sassy_hip_fasta_n_records(f: *const RawFasta) -> u64;
@@ -515,6 +520,29 @@ impl<P: Profile> Searcher<P> {
         };
         assert_eq!(rc, 0, "{}", last_error());
         (0..n).map(|i| (cost[i], index[i], if strand[i] != 0 { Strand::Rc } else { Strand::Fwd }, ties[i])).collect()
+    }
+
+    /// The groups the sequences of `a` (`m` bytes each, `m <= 128`) form: the connected components of the graph that joins
+    /// two sequences within `k` mismatches of each other (an rc searcher: or of each other's reverse complement).
+    /// `(labels, sizes, n_clusters)`: `labels[i]` is the smallest index of `i`'s component, `sizes[i]` its size.  `k <= 254`.
+    pub fn hamming_clusters(&mut self, a: &[u8], m: usize, k: usize) -> (Vec<u32>, Vec<u32>, usize) {
+        assert!(m > 0 && a.len() % m == 0, "the list holds whole sequences of m bytes");
+        let n = a.len() / m;
+        let (mut labels, mut sizes, mut count) = (vec![0u32; n], vec![0u32; n], 0usize);
+        let rc = unsafe { sassy_hip_hamming_clusters(self.raw, a.as_ptr(), n, m, k, 0, labels.as_mut_ptr(), sizes.as_mut_ptr(), &mut count) };
+        assert_eq!(rc, 0, "{}", last_error());
+        (labels, sizes, count)
+    }
+
+    /// `hamming_clusters` under the edit distance: an edge where at most `k` substitutions, insertions and deletions turn one
+    /// sequence into the other.  `m <= 64`.
+    pub fn edit_clusters(&mut self, a: &[u8], m: usize, k: usize) -> (Vec<u32>, Vec<u32>, usize) {
+        assert!(m > 0 && a.len() % m == 0, "the list holds whole sequences of m bytes");
+        let n = a.len() / m;
+        let (mut labels, mut sizes, mut count) = (vec![0u32; n], vec![0u32; n], 0usize);
+        let rc = unsafe { sassy_hip_edit_clusters(self.raw, a.as_ptr(), n, m, k, 0, labels.as_mut_ptr(), sizes.as_mut_ptr(), &mut count) };
+        assert_eq!(rc, 0, "{}", last_error());
+        (labels, sizes, count)
     }
 
     /// Per text the one best match over all patterns and strands as a complete record: lowest cost, then lowest pattern

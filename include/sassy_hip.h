@@ -96,7 +96,9 @@ typedef struct sassy_hip_Stats {
                             7: the Hamming scan of sassy_hip_search_hamming (hamming.hip: no DP);
                             8: the all-vs-all walk of sassy_hip_hamming_pairs / _nearest (hamming_pairs.hip: no text);
                             9: the all-vs-all walk of sassy_hip_edit_pairs / _nearest (edit_pairs.hip: no text; also
-                               where |m_a - m_b| > k and nothing was launched) */
+                               where |m_a - m_b| > k and nothing was launched);
+                            10: the link walk of sassy_hip_hamming_clusters (hamming_pairs.hip + clusters.hip: no text);
+                            11: the link walk of sassy_hip_edit_clusters (edit_pairs.hip + clusters.hip: no text) */
   double filter_ms;      /* HIP-event time of the prefilter kernel (part of scan_ms); a search in flight whose text pass
                             was served by several launches (see pass_patterns): the sum of their durations */
   uint64_t hit_blocks;   /* text blocks in which an exact pattern piece ends */
@@ -542,6 +544,29 @@ void sassy_hip_edit_pairs_free(sassy_hip_EditPair *p);
 int sassy_hip_edit_nearest(sassy_SearcherType *s, const uint8_t *a, size_t n_a, size_t m_a, const uint8_t *b, size_t n_b,
                            size_t m_b, size_t k, uint32_t flags, uint8_t *out_cost, uint32_t *out_index, uint8_t *out_strand,
                            uint32_t *out_ties);
+
+/* Sequence clustering (sassy_amd/csrc/clusters.hip; DESIGN.md 5.10 "Clusters"): the connected components of the within-k
+ * graph of ONE list -- UMI deduplication, collapsing barcodes onto their origins, collision groups of a panel -- without
+ * the pair records.  a: n sequences of m bytes each, laid out as the pair calls take them; m <= 128 (_hamming_) or <= 64
+ * (_edit_).  The graph has an edge {i, j}, i != j, where H(a_i, a_j) <= k (E(a_i, a_j) <= k) under the family's relation
+ * and, for an rc searcher, also where the distance of a_i to reverse_complement(a_j) is <= k: exactly the records (i, j,
+ * strand) of the self-mode pair call, (i, i, 1) left out.  The Iupac relation is not transitive (N meets everything);
+ * components are well defined all the same.
+ *  - out_label[i] (n entries, required): the SMALLEST index of i's connected component -- one fixed array, whatever the
+ *    device's schedule; out_size[i] (n entries, may be NULL): the size of that component; *n_clusters (may be NULL): the
+ *    number of i with out_label[i] == i;
+ *  - refused before any device work, as the self-mode pair call of the same distance refuses: NULL s, a or out_label, any
+ *    flag, m == 0, m over the limit, k > 254, n == 0 (SASSY_HIP_EINVAL); n > 2^31 - 1, a searcher with max_n_frac, and what
+ *    the Hamming family refuses (SASSY_HIP_EUNSUPPORTED / _EINVAL); k >= m: one cluster;
+ *  - the device walks the self-mode triangle of the pair call once (option pairs_chunks: geometry only) and joins the two
+ *    trees of every candidate pair in one array of n indices, lock-free (parent[x] <= x, roots linked larger under smaller
+ *    by compare-and-swap); no cell matrix, no scan, no fill, no record.  Device memory: the encoded list and 8 n bytes;
+ *  - sassy_hip_get_stats afterwards: filtered = 10 (_hamming_) or 11 (_edit_), chunks, grid = strips, text_bytes; at timing
+ *    level 2 filter_ms = the link pass, scan_ms = link + flatten. */
+int sassy_hip_hamming_clusters(sassy_SearcherType *s, const uint8_t *a, size_t n, size_t m, size_t k, uint32_t flags,
+                               uint32_t *out_label, uint32_t *out_size, size_t *n_clusters);
+int sassy_hip_edit_clusters(sassy_SearcherType *s, const uint8_t *a, size_t n, size_t m, size_t k, uint32_t flags,
+                            uint32_t *out_label, uint32_t *out_size, size_t *n_clusters);
 
 /* FASTA unwrap on the device (sassy_amd/csrc/fasta_unwrap.hip): the raw bytes of a chunk of FASTA in, every
  * record's sequence out as a device-resident text that the one-text entry points take with SASSY_HIP_TEXT_ON_DEVICE, plus a

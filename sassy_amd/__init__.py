@@ -158,6 +158,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_hamming_amplicons", "sassy_hip_amplicons_free",
     "sassy_hip_hamming_pairs", "sassy_hip_hamming_pairs_free", "sassy_hip_hamming_nearest",
     "sassy_hip_edit_pairs", "sassy_hip_edit_pairs_free", "sassy_hip_edit_nearest",
+    "sassy_hip_hamming_clusters", "sassy_hip_edit_clusters",
     "sassy_hip_fasta_unwrap", "sassy_hip_fasta_n_records", "sassy_hip_fasta_records", "sassy_hip_fasta_text",
     "sassy_hip_fasta_text_bytes", "sassy_hip_fasta_free",
 ]
@@ -317,6 +318,10 @@ def lib():
     L.sassy_hip_edit_pairs_free.argtypes = [vp]
     L.sassy_hip_edit_nearest.restype = C.c_int
     L.sassy_hip_edit_nearest.argtypes = [vp, vp, sz, sz, vp, sz, sz, sz, C.c_uint32, vp, vp, vp, vp]
+    L.sassy_hip_hamming_clusters.restype = C.c_int
+    L.sassy_hip_hamming_clusters.argtypes = [vp, vp, sz, sz, sz, C.c_uint32, vp, vp, C.POINTER(sz)]
+    L.sassy_hip_edit_clusters.restype = C.c_int
+    L.sassy_hip_edit_clusters.argtypes = [vp, vp, sz, sz, sz, C.c_uint32, vp, vp, C.POINTER(sz)]
     L.sassy_hip_class_cover.restype = C.c_long
     L.sassy_hip_class_cover.argtypes = [u8p, vp, vp, sz, C.POINTER(C.c_int)]
     L.sassy_hip_search_all_alignments.restype = C.c_int
@@ -1161,6 +1166,30 @@ class Searcher:
                                             0 if b is None else len(b), 0 if b is None else b.shape[1], k, 0, cost.ctypes.data,
                                             index.ctypes.data, strand.ctypes.data, ties.ctypes.data))
         return cost, index, strand, ties
+
+    def _clusters(self, entry, a, k: int, who: str):
+        import numpy as np
+        a, _ = self._pairs_lists(a, None, who)
+        n = len(a)
+        labels = np.empty(n, dtype=np.uint32)
+        sizes = np.empty(n, dtype=np.uint32)
+        _check(entry(self._h, a.ctypes.data, n, a.shape[1], k, 0, labels.ctypes.data, sizes.ctypes.data, None))
+        return labels, sizes
+
+    def hamming_clusters(self, a, k: int = 0):
+        """The groups a set of sequences forms (sassy_hip_hamming_clusters): the connected components of the graph with an
+        edge between two sequences of `a` that are within k mismatches of each other (an rc searcher: or of each other's
+        reverse complement) -- the self-mode records of `hamming_pairs`, never made.  Returns (labels, sizes), uint32 arrays
+        of len(a) entries: labels[i] is the smallest index of i's component (so labels[i] == i marks one sequence per
+        cluster, and the array is the same on every run), sizes[i] the size of that component.  One length m <= 128; `a` as
+        for `hamming_pairs`.  k <= 254; k >= m is one cluster.  Components, not a UMI rule: two sequences that are far apart
+        share a cluster where a chain of near ones joins them, and Iupac's N joins whatever it meets."""
+        return self._clusters(lib().sassy_hip_hamming_clusters, a, k, "hamming_clusters")
+
+    def edit_clusters(self, a, k: int = 0):
+        """`hamming_clusters` under the edit distance (sassy_hip_edit_clusters): an edge where E <= k, so a sequence that lost
+        or gained a base joins its origin at k = 1.  One length m <= 64.  Returns (labels, sizes) as `hamming_clusters`."""
+        return self._clusters(lib().sassy_hip_edit_clusters, a, k, "edit_clusters")
 
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k

@@ -1,4 +1,4 @@
-"""`python -m sassy_amd search | filter | demux | count | amplicon | pairs ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
+"""`python -m sassy_amd search | filter | demux | count | amplicon | pairs | cluster ...` -- the match-table and the record-filter front ends of the reference CLI on the GPU path.
 
 Mirrors `sassy search` (reference: bin/grep.rs:30-157 arguments, :465-470 header, :623-660 pattern
 sources, :710-757 rows; FASTA/FASTQ records as bin/input_iterator.rs:125-137 reads them): every
@@ -67,6 +67,14 @@ other one), and `ties`, how many are that near; `*`, `*` and -1 where nothing is
 `--edit` counts K edits (substitutions, insertions and deletions; `Searcher.edit_pairs` / `edit_nearest`) where the rows above
 count K mismatches: a barcode that lost or gained a base is then one edit from its origin.  The sequences of B may have a
 length of their own; both lengths are at most 64.  Same rows.
+
+`cluster A -k K [--edit] [--rc] [-a dna|iupac|ascii|ascii_ci]` writes which groups the sequences of A form, through
+`Searcher.hamming_clusters` (`--edit`: `edit_clusters`): the connected components of the graph that joins two sequences within
+K of each other (`--rc`: or of each other's reverse complement) -- what `pairs A` lists as records, without the records.  A
+loads as `pairs` loads it.  A header row, then one row per sequence in input order; `cluster_id` is the id of the cluster's
+first sequence:
+
+    id  cluster_id  cluster_size
 
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
@@ -434,6 +442,34 @@ def pairs_parser(sub):
     return cp
 
 
+def cluster_header() -> str:
+    return "id\tcluster_id\tcluster_size\n"
+
+
+def cluster_rows(seqs, labels, sizes):
+    """The TSV rows of Searcher.hamming_clusters' arrays, one per sequence in input order: its id, the id of its cluster's
+    first sequence, the cluster's size."""
+    return [f"{seq_id}\t{seqs[int(labels[i])][0]}\t{int(sizes[i])}\n" for i, (seq_id, _) in enumerate(seqs)]
+
+
+def run_cluster(args, searcher, seqs, out) -> int:
+    clusters = searcher.edit_clusters if args.edit else searcher.hamming_clusters
+    out.write(cluster_header())
+    out.writelines(cluster_rows(seqs, *clusters([s for _, s in seqs], args.k)))
+    out.flush()
+    return 0
+
+
+def cluster_parser(sub):
+    cp = sub.add_parser("cluster", help="write the groups a set of sequences forms (connected components within k) as TSV to stdout")
+    cp.add_argument("a", metavar="A", help="FASTA / FASTQ of equal-length sequences, or one sequence per line")
+    cp.add_argument("-k", type=int, required=True)
+    cp.add_argument("--rc", action="store_true", help="a sequence also joins one whose reverse complement is within k")
+    cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac", "ascii", "ascii_ci"], default="dna")
+    cp.add_argument("--edit", action="store_true", help="k edits (substitutions, insertions, deletions) instead of k mismatches; sequences of at most 64")
+    return cp
+
+
 def load_primers(path: str) -> List[Tuple[str, bytes, bytes]]:
     """PRIMERS of `amplicon`: rows of name<TAB>fwd<TAB>rev (empty lines and lines from `#` on skipped)."""
     pairs = []
@@ -537,7 +573,21 @@ def main(argv=None) -> int:
     count_parser(sub)
     amplicon_parser(sub)
     pairs_parser(sub)
+    cluster_parser(sub)
     args = ap.parse_args(argv)
+    if args.cmd == "cluster":
+        if not 0 <= args.k <= 254:
+            ap.error("cluster takes 0 <= k <= 254")
+        if args.rc and args.alphabet.startswith("ascii"):
+            ap.error("cluster --rc: there is no reverse complement of plain text")
+        seqs = load_count_patterns(args.a)
+        if not seqs:
+            ap.error(f"cluster: {args.a} holds no sequence")
+        m = len(seqs[0][1])
+        for i, (_, seq) in enumerate(seqs):
+            if len(seq) != m:
+                ap.error(f"cluster takes sequences of one length: {args.a}: sequence {i} has {len(seq)} bytes, the first has {m}")
+        return run_cluster(args, Searcher(args.alphabet, rc=args.rc), seqs, sys.stdout)
     if args.cmd == "pairs":
         if not 0 <= args.k <= 254:
             ap.error("pairs takes 0 <= k <= 254")

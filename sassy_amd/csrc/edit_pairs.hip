@@ -14,6 +14,8 @@
 // Launches, grid = strips of 256 entries x chunks of targets (pairs_plan; pairs_chunks forces the chunk count):
 //   edit_survey_kernel   per (entry, chunk) one PairsCell into the partials matrix [chunk][entry]
 //   edit_fill_kernel     edit_pairs: walks again the tiles (wavefront x chunk) that hold a candidate and writes the records
+//   edit_cluster_kernel  edit_clusters (clusters.hip): the survey's walk of the self-mode triangle, a union step per
+//                        candidate (cluster_step.h) in place of the cell
 // and between them the passes that know nothing of the distance, which exist once, in hamming_pairs.hip (pairs_fold_nearest;
 // pairs_place_rows, pairs_take_records).
 #include <hip/hip_runtime.h>
@@ -22,6 +24,7 @@
 #include <cstring>
 #include <vector>
 
+#include "cluster_step.h"
 #include "edit_pairs_step.h"
 #include "host_internal.h"
 
@@ -40,6 +43,7 @@ struct EditArgs {
   uint4* cells;          // [n_chunks][n_a] PairsCell
   const unsigned long long* row_first;  // fill: per entry the index of its first record
   sassy_hip_EditPair* out;
+  uint32_t* parent;      // clusters: the forest of cluster_step.h, [n_a]
 };
 
 constexpr uint32_t kEditTileWords = 2048;  // the staged tile: 8 KiB of records, 8 words per thread; a record is at most 16 words
@@ -171,22 +175,110 @@ __global__ __launch_bounds__(kPairsStrip) void edit_fill_kernel(EditArgs A) {
   });
 }
 
+// edit_clusters: the survey's walk over the self-mode triangle with a union step in place of the cell (cluster_step.h).  j is
+// the same for the whole wavefront, so the look at parent[j] that comes first is one broadcast load; a lane whose register
+// already names j's parent goes on without a chase or a write.
+template <int P, int W, bool IUPAC>
+__global__ __launch_bounds__(kPairsStrip) void edit_cluster_kernel(EditArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * kPairsStrip + threadIdx.x;
+  const uint64_t c = blockIdx.y;
+  const bool valid = i < A.n_a;
+  EditWord<W> a[P];
+  edit_load_entry<P, W>(A, i, valid, a);
+  ClusterDeviceMem mem{A.parent};
+  uint32_t root = (uint32_t)i;
+  edit_walk<P, W, IUPAC>(A, i, valid, true, c, a, [&](uint32_t, uint64_t j, uint32_t, uint32_t) {
+    if (j != i) cluster_join(mem, (uint32_t)i, (uint32_t)j, root);  // ((i, i, 1) is no edge)
+  });
+}
+
+// which kernel walks: the survey, the fill pass of edit_pairs, the link pass of edit_clusters
+enum : int { kWalkSurvey = 0, kWalkFill = 1, kWalkCluster = 2 };
 template <int P, bool IUPAC>
-hipError_t launch_walk(bool fill, uint32_t W, const EditArgs& A, dim3 grid, hipStream_t st) {
+hipError_t launch_walk(int kind, uint32_t W, const EditArgs& A, dim3 grid, hipStream_t st) {
   if (W == 1) {
-    if (fill) hipLaunchKernelGGL((edit_fill_kernel<P, 1, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+    if (kind == kWalkCluster) hipLaunchKernelGGL((edit_cluster_kernel<P, 1, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+    else if (kind == kWalkFill) hipLaunchKernelGGL((edit_fill_kernel<P, 1, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
     else hipLaunchKernelGGL((edit_survey_kernel<P, 1, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
   } else {
-    if (fill) hipLaunchKernelGGL((edit_fill_kernel<P, 2, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+    if (kind == kWalkCluster) hipLaunchKernelGGL((edit_cluster_kernel<P, 2, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+    else if (kind == kWalkFill) hipLaunchKernelGGL((edit_fill_kernel<P, 2, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
     else hipLaunchKernelGGL((edit_survey_kernel<P, 2, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
   }
   return hipGetLastError();
 }
-hipError_t launch_walk_profile(Profile pr, bool fill, uint32_t W, const EditArgs& A, dim3 grid, hipStream_t st) {
-  if (pr == PROFILE_DNA) return launch_walk<2, false>(fill, W, A, grid, st);
-  if (pr == PROFILE_IUPAC) return launch_walk<4, true>(fill, W, A, grid, st);
-  return launch_walk<8, false>(fill, W, A, grid, st);
+hipError_t launch_walk_profile(Profile pr, int kind, uint32_t W, const EditArgs& A, dim3 grid, hipStream_t st) {
+  if (pr == PROFILE_DNA) return launch_walk<2, false>(kind, W, A, grid, st);
+  if (pr == PROFILE_IUPAC) return launch_walk<4, true>(kind, W, A, grid, st);
+  return launch_walk<8, false>(kind, W, A, grid, st);
 }
+
+// A call behind its refusals: the plan, the walk's arguments, its grid.
+struct EditRun {
+  PairsPlan plan;
+  EditArgs args{};
+  uint32_t W = 1;
+  dim3 grid;
+};
+// The first half of a call behind its refusals: the plan, both lists encoded and uploaded, the walk's arguments and grid, the
+// stats' geometry.  want_cells: the partials matrix too (the clustering walk has none).
+int edit_stage(sassy_SearcherType* s, const uint8_t* a, size_t n_a, uint32_t m_a, const uint8_t* b, size_t n_b, uint32_t m_b, uint32_t k, uint32_t self_mode,
+               bool want_cells, EditRun& R) {
+  hipStream_t st = s->stream;
+  const bool self = b == nullptr;
+  const uint32_t S = s->rc ? 2u : 1u, P = pairs_planes(s->profile), W = pairs_words(m_a), PW = P * W, rw = edit_record_words(P, m_b);
+  const size_t nb = self ? n_a : n_b;
+  const uint8_t* targets = self ? a : b;
+  R.W = W;
+  R.plan = pairs_plan(n_a, nb, self ? self_mode : kPairsCross, s->sw.pairs_chunks, self_mode == kPairsSelfPairs ? kEditFineChunk : 0);
+  std::vector<uint32_t> ha(n_a * PW), ht(nb * S * rw);
+  pairs_for_slices(n_a, [&](size_t i0, size_t i1) {
+    for (size_t i = i0; i < i1; ++i) pairs_encode(s->profile, a + i * m_a, m_a, W, ha.data() + i * PW);
+  });
+  pairs_for_slices(nb, [&](size_t j0, size_t j1) {
+    uint8_t rev[kEditMaxRows];
+    for (size_t j = j0; j < j1; ++j) {
+      edit_encode_record(s->profile, targets + j * m_b, m_b, ht.data() + j * S * rw);
+      if (S == 2) {
+        pairs_reverse_complement(targets + j * m_b, m_b, [&](uint8_t c) { return complement_char(s->profile, c); }, rev);
+        edit_encode_record(s->profile, rev, m_b, ht.data() + (j * S + 1) * rw);
+      }
+    }
+  });
+  if (int rc = s->d_pairs_a.reserve(ha.size())) return rc;
+  if (int rc = s->d_pairs_t.reserve(ht.size())) return rc;
+  if (want_cells)
+    if (int rc = s->d_pairs_cells.reserve((size_t)R.plan.n_chunks * n_a)) return rc;
+  HIP_TRY(hipMemcpyAsync(s->d_pairs_a.p, ha.data(), ha.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->d_pairs_t.p, ht.data(), ht.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the host vectors go away)
+  EditArgs& A = R.args;
+  A.a = s->d_pairs_a.p; A.t = s->d_pairs_t.p;
+  A.n_a = n_a; A.n_b = nb; A.chunk = R.plan.chunk;
+  A.S = S; A.m_a = m_a; A.m_b = m_b; A.rw = rw; A.k = k; A.mode = R.plan.mode;
+  A.cells = want_cells ? s->d_pairs_cells.p : nullptr;
+  R.grid = dim3((uint32_t)R.plan.n_strips, R.plan.n_chunks);
+  s->stats.scan_launches = 1;
+  s->stats.chunks = R.plan.n_chunks;
+  s->stats.grid = (uint32_t)R.plan.n_strips;
+  s->stats.blocks_per_chunk = (uint32_t)std::min<uint64_t>(R.plan.chunk, 0xFFFFFFFFull);
+  s->stats.text_bytes = (uint64_t)n_a * m_a + (uint64_t)nb * m_b;
+  return 0;
+}
+// The survey: the partials matrix filled.
+int edit_survey(sassy_SearcherType* s, const uint8_t* a, size_t n_a, uint32_t m_a, const uint8_t* b, size_t n_b, uint32_t m_b, uint32_t k, uint32_t self_mode,
+                EditRun& R) {
+  hipStream_t st = s->stream;
+  if (int rc = edit_stage(s, a, n_a, m_a, b, n_b, m_b, k, self_mode, true, R)) return rc;
+  if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[0], st));
+  HIP_TRY(launch_walk_profile(s->profile, kWalkSurvey, R.W, R.args, R.grid, st));
+  if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[1], st));
+  return 0;
+}
+// E >= |m_a - m_b|: beyond k no pair is a candidate and nothing is launched
+bool edit_lengths_too_far(size_t m_a, size_t m_b, size_t k) { return (m_a > m_b ? m_a - m_b : m_b - m_a) > k; }
+
+}  // namespace
 
 // What both entry points refuse, before any device work; self: b == NULL && n_b == 0, where m_b is 0 or m_a.
 int edit_refusals(sassy_SearcherType* s, bool have_out, const uint8_t* a, size_t n_a, size_t m_a, const uint8_t* b, size_t n_b, size_t m_b, size_t k,
@@ -221,62 +313,18 @@ int edit_refusals(sassy_SearcherType* s, bool have_out, const uint8_t* a, size_t
   return b ? family(b, n_b, m_b, "b") : 0;
 }
 
-// The survey of a call behind its refusals: both lists encoded and uploaded, the partials matrix filled.
-struct EditRun {
-  PairsPlan plan;
-  EditArgs args{};
-  uint32_t W = 1;
-  dim3 grid;
-};
-int edit_survey(sassy_SearcherType* s, const uint8_t* a, size_t n_a, uint32_t m_a, const uint8_t* b, size_t n_b, uint32_t m_b, uint32_t k, uint32_t self_mode,
-                EditRun& R) {
+// edit_clusters (clusters.hip): the list staged as a self-mode pairs call stages it, one launch of the link kernel
+int edit_link_components(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent) {
   hipStream_t st = s->stream;
-  const bool self = b == nullptr;
-  const uint32_t S = s->rc ? 2u : 1u, P = pairs_planes(s->profile), W = pairs_words(m_a), PW = P * W, rw = edit_record_words(P, m_b);
-  const size_t nb = self ? n_a : n_b;
-  const uint8_t* targets = self ? a : b;
-  R.W = W;
-  R.plan = pairs_plan(n_a, nb, self ? self_mode : kPairsCross, s->sw.pairs_chunks, self_mode == kPairsSelfPairs ? kEditFineChunk : 0);
-  std::vector<uint32_t> ha(n_a * PW), ht(nb * S * rw);
-  pairs_for_slices(n_a, [&](size_t i0, size_t i1) {
-    for (size_t i = i0; i < i1; ++i) pairs_encode(s->profile, a + i * m_a, m_a, W, ha.data() + i * PW);
-  });
-  pairs_for_slices(nb, [&](size_t j0, size_t j1) {
-    uint8_t rev[kEditMaxRows];
-    for (size_t j = j0; j < j1; ++j) {
-      edit_encode_record(s->profile, targets + j * m_b, m_b, ht.data() + j * S * rw);
-      if (S == 2) {
-        pairs_reverse_complement(targets + j * m_b, m_b, [&](uint8_t c) { return complement_char(s->profile, c); }, rev);
-        edit_encode_record(s->profile, rev, m_b, ht.data() + (j * S + 1) * rw);
-      }
-    }
-  });
-  if (int rc = s->d_pairs_a.reserve(ha.size())) return rc;
-  if (int rc = s->d_pairs_t.reserve(ht.size())) return rc;
-  if (int rc = s->d_pairs_cells.reserve((size_t)R.plan.n_chunks * n_a)) return rc;
-  HIP_TRY(hipMemcpyAsync(s->d_pairs_a.p, ha.data(), ha.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->d_pairs_t.p, ht.data(), ht.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));  // (the host vectors go away)
-  EditArgs& A = R.args;
-  A.a = s->d_pairs_a.p; A.t = s->d_pairs_t.p;
-  A.n_a = n_a; A.n_b = nb; A.chunk = R.plan.chunk;
-  A.S = S; A.m_a = m_a; A.m_b = m_b; A.rw = rw; A.k = k; A.mode = R.plan.mode;
-  A.cells = s->d_pairs_cells.p;
-  R.grid = dim3((uint32_t)R.plan.n_strips, R.plan.n_chunks);
+  EditRun R;
+  if (int rc = edit_stage(s, a, n, m, nullptr, 0, m, k, kPairsSelfPairs, false, R)) return rc;
+  R.args.parent = d_parent;
   if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[0], st));
-  HIP_TRY(launch_walk_profile(s->profile, false, W, A, R.grid, st));
+  HIP_TRY(launch_walk_profile(s->profile, kWalkCluster, R.W, R.args, R.grid, st));
   if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[1], st));
-  s->stats.scan_launches = 1;
-  s->stats.chunks = R.plan.n_chunks;
-  s->stats.grid = (uint32_t)R.plan.n_strips;
-  s->stats.blocks_per_chunk = (uint32_t)std::min<uint64_t>(R.plan.chunk, 0xFFFFFFFFull);
-  s->stats.text_bytes = (uint64_t)n_a * m_a + (uint64_t)nb * m_b;
   return 0;
 }
-// E >= |m_a - m_b|: beyond k no pair is a candidate and nothing is launched
-bool edit_lengths_too_far(size_t m_a, size_t m_b, size_t k) { return (m_a > m_b ? m_a - m_b : m_b - m_a) > k; }
 
-}  // namespace
 }  // namespace sassy_hip
 
 using namespace sassy_hip;
@@ -309,7 +357,7 @@ int sassy_hip_edit_pairs(sassy_SearcherType* s, const uint8_t* a, size_t n_a, si
     if (int rc = s->d_pairs_out.reserve((size_t)total * sizeof(sassy_hip_EditPair))) return rc;
     R.args.row_first = row_first;
     R.args.out = reinterpret_cast<sassy_hip_EditPair*>(s->d_pairs_out.p);
-    HIP_TRY(launch_walk_profile(s->profile, true, R.W, R.args, R.grid, st));
+    HIP_TRY(launch_walk_profile(s->profile, kWalkFill, R.W, R.args, R.grid, st));
     if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[3], st));
     s->stats.scan_launches = 2;
     return pairs_take_records(s, total, out, n_out);

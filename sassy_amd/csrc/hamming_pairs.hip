@@ -20,6 +20,8 @@
 //   pairs_fill_kernel     walks again the tiles (wavefront x chunk) that hold a candidate and writes the records: a lane
 //                         walks its targets in order and the cells are placed in (entry, chunk) order, so the records come
 //                         out in the contract's order (a_idx, b_idx, strand)
+//   pairs_cluster_kernel  hamming_clusters (clusters.hip): the survey's walk of the self-mode triangle, a union step per
+//                         candidate (cluster_step.h) in place of the cell -- no matrix, no pass behind it here
 // The passes between survey and fill know nothing of the distance: the host code around them (pairs_place_rows,
 // pairs_take_records, pairs_fold_nearest; host_internal.h) also serves edit_pairs.hip, which has a walk of its own.
 #include <hip/hip_runtime.h>
@@ -34,6 +36,7 @@
 #include <thread>
 #include <vector>
 
+#include "cluster_step.h"
 #include "host_internal.h"
 #include "pairs_step.h"
 
@@ -52,6 +55,7 @@ struct PairsArgs {
   uint4* cells;          // [n_chunks][n_a] PairsCell
   const unsigned long long* row_first;  // fill: per entry the index of its first record
   sassy_hip_HammingPair* out;
+  uint32_t* parent;      // clusters: the forest of cluster_step.h, [n_a]
 };
 
 constexpr uint32_t kPairsTileWords = 2048;  // the staged tile: 8 KiB of records, 8 words per thread
@@ -155,6 +159,23 @@ __global__ __launch_bounds__(kPairsStrip) void pairs_fill_kernel(PairsArgs A) {
   });
 }
 
+// hamming_clusters: the survey's walk over the self-mode triangle with a union step in place of the cell (cluster_step.h).
+// j is the same for the whole wavefront, so the look at parent[j] that comes first is one broadcast load; a lane whose
+// register already names j's parent goes on without a chase or a write.
+template <int P, int W, bool IUPAC>
+__global__ __launch_bounds__(kPairsStrip) void pairs_cluster_kernel(PairsArgs A) {
+  const uint64_t i = (uint64_t)blockIdx.x * kPairsStrip + threadIdx.x;
+  const uint64_t c = blockIdx.y;
+  const bool valid = i < A.n_a;
+  uint32_t a[P * W];
+  pairs_load_entry<P, W>(A, i, valid, a);
+  ClusterDeviceMem mem{A.parent};
+  uint32_t root = (uint32_t)i;
+  pairs_walk<P, W, IUPAC>(A, i, valid, true, c, a, [&](uint32_t, uint64_t j, uint32_t, uint32_t) {
+    if (j != i) cluster_join(mem, (uint32_t)i, (uint32_t)j, root);  // ((i, i, 1) is no edge)
+  });
+}
+
 // hamming_nearest: an entry's cells folded in chunk order -- the answer of one sequential walk
 __global__ __launch_bounds__(256) void pairs_nearest_kernel(const uint4* cells, uint64_t n_a, uint32_t n_chunks, uint32_t S, uint8_t* out_cost,
                                                             uint32_t* out_index, uint8_t* out_strand, uint32_t* out_ties) {
@@ -246,28 +267,33 @@ __global__ __launch_bounds__(256) void pairs_scan_rows_kernel(const unsigned lon
   }
 }
 
+// which kernel walks: the survey, the fill pass of hamming_pairs, the link pass of hamming_clusters
+enum : int { kWalkSurvey = 0, kWalkFill = 1, kWalkCluster = 2 };
 template <int P, bool IUPAC>
-hipError_t launch_walk(bool fill, uint32_t W, const PairsArgs& A, dim3 grid, hipStream_t st) {
+hipError_t launch_walk(int kind, uint32_t W, const PairsArgs& A, dim3 grid, hipStream_t st) {
   switch (W) {
     case 1:
-      if (fill) hipLaunchKernelGGL((pairs_fill_kernel<P, 1, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+      if (kind == kWalkCluster) hipLaunchKernelGGL((pairs_cluster_kernel<P, 1, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+      else if (kind == kWalkFill) hipLaunchKernelGGL((pairs_fill_kernel<P, 1, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
       else hipLaunchKernelGGL((pairs_survey_kernel<P, 1, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
       break;
     case 2:
-      if (fill) hipLaunchKernelGGL((pairs_fill_kernel<P, 2, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+      if (kind == kWalkCluster) hipLaunchKernelGGL((pairs_cluster_kernel<P, 2, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+      else if (kind == kWalkFill) hipLaunchKernelGGL((pairs_fill_kernel<P, 2, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
       else hipLaunchKernelGGL((pairs_survey_kernel<P, 2, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
       break;
     default:
-      if (fill) hipLaunchKernelGGL((pairs_fill_kernel<P, 4, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+      if (kind == kWalkCluster) hipLaunchKernelGGL((pairs_cluster_kernel<P, 4, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
+      else if (kind == kWalkFill) hipLaunchKernelGGL((pairs_fill_kernel<P, 4, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
       else hipLaunchKernelGGL((pairs_survey_kernel<P, 4, IUPAC>), grid, dim3(kPairsStrip), 0, st, A);
       break;
   }
   return hipGetLastError();
 }
-hipError_t launch_walk_profile(Profile pr, bool fill, uint32_t W, const PairsArgs& A, dim3 grid, hipStream_t st) {
-  if (pr == PROFILE_DNA) return launch_walk<2, false>(fill, W, A, grid, st);
-  if (pr == PROFILE_IUPAC) return launch_walk<4, true>(fill, W, A, grid, st);
-  return launch_walk<8, false>(fill, W, A, grid, st);
+hipError_t launch_walk_profile(Profile pr, int kind, uint32_t W, const PairsArgs& A, dim3 grid, hipStream_t st) {
+  if (pr == PROFILE_DNA) return launch_walk<2, false>(kind, W, A, grid, st);
+  if (pr == PROFILE_IUPAC) return launch_walk<4, true>(kind, W, A, grid, st);
+  return launch_walk<8, false>(kind, W, A, grid, st);
 }
 
 // list[0 .. n) x m bytes -> planes, [n][S][P W] words: strand 1 of an entry (S = 2) is its reverse complement
@@ -285,6 +311,58 @@ void encode_list(Profile pr, const uint8_t* list, size_t n, uint32_t m, uint32_t
   };
   pairs_for_slices(n, slice);
 }
+
+// A call behind its refusals: the plan, the walk's arguments, its grid.
+struct PairsRun {
+  PairsPlan plan;
+  PairsArgs args{};
+  uint32_t W = 1;
+  dim3 grid;
+};
+// The first half of a call behind its refusals: the plan, both lists encoded and uploaded, the walk's arguments and grid, the
+// stats' geometry.  want_cells: the partials matrix too (the clustering walk has none).
+int pairs_stage(sassy_SearcherType* s, const uint8_t* a, size_t n_a, const uint8_t* b, size_t n_b, uint32_t m, uint32_t k, uint32_t self_mode, bool want_cells,
+                PairsRun& R) {
+  hipStream_t st = s->stream;
+  const bool self = b == nullptr;
+  const uint32_t S = s->rc ? 2u : 1u, W = pairs_words(m), PW = pairs_planes(s->profile) * W;
+  const size_t nb = self ? n_a : n_b;
+  R.W = W;
+  R.plan = pairs_plan(n_a, nb, self ? self_mode : kPairsCross, s->sw.pairs_chunks, self_mode == kPairsSelfPairs ? kPairsFineChunk : 0);
+  std::vector<uint32_t> ha(n_a * PW), ht(nb * S * PW);
+  encode_list(s->profile, a, n_a, m, W, 1, ha.data());
+  encode_list(s->profile, self ? a : b, nb, m, W, S, ht.data());
+  if (int rc = s->d_pairs_a.reserve(ha.size())) return rc;
+  if (int rc = s->d_pairs_t.reserve(ht.size())) return rc;
+  if (want_cells)
+    if (int rc = s->d_pairs_cells.reserve((size_t)R.plan.n_chunks * n_a)) return rc;
+  HIP_TRY(hipMemcpyAsync(s->d_pairs_a.p, ha.data(), ha.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->d_pairs_t.p, ht.data(), ht.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the host vectors go away)
+  PairsArgs& A = R.args;
+  A.a = s->d_pairs_a.p; A.t = s->d_pairs_t.p;
+  A.n_a = n_a; A.n_b = nb; A.chunk = R.plan.chunk;
+  A.S = S; A.m = m; A.k = k; A.mode = R.plan.mode;
+  A.cells = want_cells ? s->d_pairs_cells.p : nullptr;
+  R.grid = dim3((uint32_t)R.plan.n_strips, R.plan.n_chunks);
+  s->stats.scan_launches = 1;
+  s->stats.chunks = R.plan.n_chunks;
+  s->stats.grid = (uint32_t)R.plan.n_strips;
+  s->stats.blocks_per_chunk = (uint32_t)std::min<uint64_t>(R.plan.chunk, 0xFFFFFFFFull);
+  s->stats.text_bytes = (uint64_t)(n_a + nb) * m;
+  return 0;
+}
+// The survey: the partials matrix filled.
+int pairs_survey(sassy_SearcherType* s, const uint8_t* a, size_t n_a, const uint8_t* b, size_t n_b, uint32_t m, uint32_t k, uint32_t self_mode, PairsRun& R) {
+  hipStream_t st = s->stream;
+  if (int rc = pairs_stage(s, a, n_a, b, n_b, m, k, self_mode, true, R)) return rc;
+  if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[0], st));
+  HIP_TRY(launch_walk_profile(s->profile, kWalkSurvey, R.W, R.args, R.grid, st));
+  if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[1], st));
+  s->stats.filtered = 8;
+  return 0;
+}
+}  // namespace
 
 // What both entry points refuse, before any device work; self: b == NULL && n_b == 0.
 int pairs_refusals(sassy_SearcherType* s, bool have_out, const uint8_t* a, size_t n_a, const uint8_t* b, size_t n_b, size_t m, size_t k, uint32_t flags,
@@ -315,47 +393,17 @@ int pairs_refusals(sassy_SearcherType* s, bool have_out, const uint8_t* a, size_
   return b ? family(b, n_b, "b") : 0;
 }
 
-// The survey of a call behind its refusals: both lists encoded and uploaded, the partials matrix filled.
-struct PairsRun {
-  PairsPlan plan;
-  PairsArgs args{};
-  uint32_t W = 1;
-  dim3 grid;
-};
-int pairs_survey(sassy_SearcherType* s, const uint8_t* a, size_t n_a, const uint8_t* b, size_t n_b, uint32_t m, uint32_t k, uint32_t self_mode, PairsRun& R) {
+// hamming_clusters (clusters.hip): the list staged as a self-mode pairs call stages it, one launch of the link kernel
+int pairs_link_components(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent) {
   hipStream_t st = s->stream;
-  const bool self = b == nullptr;
-  const uint32_t S = s->rc ? 2u : 1u, W = pairs_words(m), PW = pairs_planes(s->profile) * W;
-  const size_t nb = self ? n_a : n_b;
-  R.W = W;
-  R.plan = pairs_plan(n_a, nb, self ? self_mode : kPairsCross, s->sw.pairs_chunks, self_mode == kPairsSelfPairs ? kPairsFineChunk : 0);
-  std::vector<uint32_t> ha(n_a * PW), ht(nb * S * PW);
-  encode_list(s->profile, a, n_a, m, W, 1, ha.data());
-  encode_list(s->profile, self ? a : b, nb, m, W, S, ht.data());
-  if (int rc = s->d_pairs_a.reserve(ha.size())) return rc;
-  if (int rc = s->d_pairs_t.reserve(ht.size())) return rc;
-  if (int rc = s->d_pairs_cells.reserve((size_t)R.plan.n_chunks * n_a)) return rc;
-  HIP_TRY(hipMemcpyAsync(s->d_pairs_a.p, ha.data(), ha.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->d_pairs_t.p, ht.data(), ht.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));  // (the host vectors go away)
-  PairsArgs& A = R.args;
-  A.a = s->d_pairs_a.p; A.t = s->d_pairs_t.p;
-  A.n_a = n_a; A.n_b = nb; A.chunk = R.plan.chunk;
-  A.S = S; A.m = m; A.k = k; A.mode = R.plan.mode;
-  A.cells = s->d_pairs_cells.p;
-  R.grid = dim3((uint32_t)R.plan.n_strips, R.plan.n_chunks);
+  PairsRun R;
+  if (int rc = pairs_stage(s, a, n, nullptr, 0, m, k, kPairsSelfPairs, false, R)) return rc;
+  R.args.parent = d_parent;
   if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[0], st));
-  HIP_TRY(launch_walk_profile(s->profile, false, W, A, R.grid, st));
+  HIP_TRY(launch_walk_profile(s->profile, kWalkCluster, R.W, R.args, R.grid, st));
   if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[1], st));
-  s->stats.scan_launches = 1;
-  s->stats.chunks = R.plan.n_chunks;
-  s->stats.grid = (uint32_t)R.plan.n_strips;
-  s->stats.blocks_per_chunk = (uint32_t)std::min<uint64_t>(R.plan.chunk, 0xFFFFFFFFull);
-  s->stats.filtered = 8;
-  s->stats.text_bytes = (uint64_t)(n_a + nb) * m;
   return 0;
 }
-}  // namespace
 
 // ---- what edit_pairs.hip shares (host_internal.h): the passes behind a survey that do not depend on the distance ----
 // slice(i0, i1) over [0, n) in up to 8 host threads (a list of a million sequences is encoded in a fraction of the time)
@@ -467,7 +515,7 @@ int sassy_hip_hamming_pairs(sassy_SearcherType* s, const uint8_t* a, size_t n_a,
     if (int rc = s->d_pairs_out.reserve((size_t)total * sizeof(sassy_hip_HammingPair))) return rc;
     R.args.row_first = row_first;
     R.args.out = reinterpret_cast<sassy_hip_HammingPair*>(s->d_pairs_out.p);
-    HIP_TRY(launch_walk_profile(s->profile, true, R.W, R.args, R.grid, st));
+    HIP_TRY(launch_walk_profile(s->profile, kWalkFill, R.W, R.args, R.grid, st));
     if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[3], st));
     s->stats.scan_launches = 2;
     return pairs_take_records(s, total, out, n_out);

@@ -1264,6 +1264,24 @@ int pairs_guarded(const char* who, Body&& body) {
     return fail(SASSY_HIP_ENOMEM, std::string(who) + ": out of host memory (a list too long for a host table)");
   }
 }
+// The clustering calls (clusters.hip; DESIGN.md 5.10 "Clusters").  Their refusals are the self-mode pair calls' own (b == NULL),
+// defined next to those calls; each pair unit has one launcher that encodes and uploads the list, plans as its pair call
+// does and links {i, j} in `d_parent` (device, n entries, parent[i] = i) for every pair of its walk's self-mode triangle --
+// the events ev_line[0] and [1] around the link kernel, the stats' geometry filled in.
+int pairs_refusals(sassy_SearcherType* s, bool have_out, const uint8_t* a, size_t n_a, const uint8_t* b, size_t n_b, size_t m, size_t k, uint32_t flags,
+                   const char* who);
+int edit_refusals(sassy_SearcherType* s, bool have_out, const uint8_t* a, size_t n_a, size_t m_a, const uint8_t* b, size_t n_b, size_t m_b, size_t k,
+                  uint32_t flags, const char* who);
+int pairs_link_components(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent);
+int edit_link_components(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent);
+// cluster_step.h's memory policy on the device: relaxed, agent scope, vector memory operations
+struct ClusterDeviceMem {
+  uint32_t* parent;
+  __device__ __forceinline__ uint32_t load(uint32_t x) const { return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  __device__ __forceinline__ bool cas(uint32_t x, uint32_t expect, uint32_t desired) const {
+    return __hip_atomic_compare_exchange_strong(parent + x, &expect, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
 // The one text of search_hamming, hamming_counts and hamming_amplicons on the device: the caller's device pointer, or an upload.
 inline int ham_one_text(sassy_SearcherType* s, const void* text, size_t text_len, uint32_t flags, HamText* out) {
   const uint8_t* d_text = static_cast<const uint8_t*>(text);
