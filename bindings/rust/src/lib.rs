@@ -61,6 +61,22 @@ pub struct FastaRecord {
 pub struct RawFasta {
     _p: [u8; 0],
 }
+/// One read of a FASTQ chunk parsed on the device (include/sassy_hip.h: sassy_hip_ReadRecord, 48 bytes): id and quality in
+/// the raw bytes, the sequence in the device text.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct ReadRecord {
+    pub id_start: u64,
+    pub id_len: u64,
+    pub seq_start: u64,
+    pub seq_len: u64,
+    pub qual_start: u64,
+    pub qual_len: u64,
+}
+#[repr(C)]
+pub struct RawReads {
+    _p: [u8; 0],
+}
 #[repr(C)]
 struct RawSearcher {
     _p: [u8; 0],
@@ -143,6 +159,23 @@ extern "C" {
     pub fn sassy_hip_fasta_text(f: *const RawFasta) -> *mut std::ffi::c_void;
     pub fn sassy_hip_fasta_text_bytes(f: *const RawFasta) -> u64;
     pub fn sassy_hip_fasta_free(f: *mut RawFasta);
+    // FASTQ parse on the device: raw bytes in, a resident read batch and a host table out (flags: TEXT_ON_DEVICE) ...
+    pub fn sassy_hip_fastq_parse(raw: *const u8, n: u64, flags: u32, hip_stream: *mut std::ffi::c_void, out: *mut *mut RawReads) -> c_int;
+    pub fn sassy_hip_reads_n(r: *const RawReads) -> u64;
+    pub fn sassy_hip_reads_records(r: *const RawReads) -> *const ReadRecord;
+    pub fn sassy_hip_reads_text(r: *const RawReads) -> *mut std::ffi::c_void;
+    pub fn sassy_hip_reads_text_bytes(r: *const RawReads) -> u64;
+    pub fn sassy_hip_reads_longest(r: *const RawReads) -> u64;
+    pub fn sassy_hip_reads_rem(r: *const RawReads) -> *const u32;
+    pub fn sassy_hip_reads_free(r: *mut RawReads);
+    // ... and the Hamming batch calls over it: the handle where the _many sibling takes texts, text_lens, n_texts
+    fn sassy_hip_search_hamming_reads(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                      reads: *const RawReads, k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
+    fn sassy_hip_hamming_best_pattern_reads(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                            reads: *const RawReads, k: usize, flags: u32, out_cost: *mut u8, out_pattern: *mut u32,
+                                            out_strand: *mut u8, out_start: *mut u64) -> c_int;
+    fn sassy_hip_hamming_counts_reads(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                      reads: *const RawReads, k: usize, flags: u32, out_counts: *mut u64) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

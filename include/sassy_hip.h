@@ -599,6 +599,68 @@ void *sassy_hip_fasta_text(const sassy_hip_Fasta *f);                           
 uint64_t sassy_hip_fasta_text_bytes(const sassy_hip_Fasta *f);
 void sassy_hip_fasta_free(sassy_hip_Fasta *f);
 
+/* FASTQ parse on the device (sassy_amd/csrc/fastq_reads.hip): the raw bytes of a chunk of FASTQ in, a read
+ * batch out that stays on the device in the layout the Hamming batch kernels scan, plus a small host table.  `raw` holds n
+ * bytes, is empty or begins with '@', and holds whole records.  The definition is strict four-line FASTQ: split at '\n' (a
+ * final empty piece is no line), strip one trailing '\r' from each line; with L lines, record r is lines 4r .. 4r + 3: line 4r
+ * begins with '@' and the id is the rest of it, line 4r + 1 is the sequence, line 4r + 2 begins with '+' and its content is
+ * ignored, line 4r + 3 is the quality, whose length is reported and not compared.  Nothing else is touched (case, N, an '@'
+ * or '+' that opens a quality line, a '\r' elsewhere).  Empty input is valid: 0 records.
+ *  - malformed input is SASSY_HIP_EINVAL, and the message names the smallest malformed record and the rule it breaks: a
+ *    line 4r without its '@', a line 4r + 2 without its '+', or, where L is no multiple of 4, the last record (index L / 4),
+ *    which lacks lines.  Multi-line FASTQ is malformed input;
+ *  - the text: one device buffer of sassy_hip_reads_text_bytes bytes; read r's sequence lies at [seq_start, seq_start +
+ *    seq_len), seq_start a multiple of 64; the bytes between the sequences are 0 and 64 zero bytes follow the last one (they
+ *    are counted in text_bytes); an empty sequence takes no block and shares its start with the next read, trailing empty
+ *    reads start at the layout's size (text_bytes - 64);
+ *  - the table: one sassy_hip_ReadRecord per record in file order; id_start / id_len (the id without '@' and without the
+ *    line's trailing '\r') and qual_start / qual_len index `raw`, seq_start / seq_len the text; sassy_hip_reads_longest is
+ *    the longest seq_len;
+ *  - flags: SASSY_HIP_TEXT_ON_DEVICE: `raw` is a device pointer, 16-byte aligned and readable up to the next multiple of 64
+ *    behind n; 0: host bytes, uploaded once.  Takes no searcher: it runs on the calling thread's current device, on
+ *    `hip_stream` (NULL: the default stream), and returns when the table is on the host;
+ *  - refused before any device work: null arguments with n > 0, an unknown flag bit, a device pointer that is not 16-byte
+ *    aligned, a first byte that is not '@' (SASSY_HIP_EINVAL; a device-resident first byte is read back first); more than
+ *    2^31 - 1 super-tiles of 64 KiB, i.e. n > 2^47 - 65536 (SASSY_HIP_EUNSUPPORTED); no device SASSY_HIP_ENODEVICE.  More
+ *    than 2^32 - 1 records is SASSY_HIP_EUNSUPPORTED as well, known once the count pass has run.
+ * The handle owns the text, the device copies of the starts and the lengths (uint64 each, n starts, then n lengths), the
+ * table of the bytes left in its own read per 64-byte block of the text (uint32; sassy_hip_reads_rem is its device pointer,
+ * (text_bytes - 64) / 64 entries) and the number of the device it was made on: sassy_hip_reads_free releases all of it. */
+typedef struct sassy_hip_ReadRecord {
+  uint64_t id_start, id_len;     /* in raw: the id without '@' and without the '\r' */
+  uint64_t seq_start, seq_len;   /* in the device text; seq_start a multiple of 64 */
+  uint64_t qual_start, qual_len; /* in raw */
+} sassy_hip_ReadRecord;
+typedef struct sassy_hip_Reads sassy_hip_Reads;
+int sassy_hip_fastq_parse(const void *raw, uint64_t n, uint32_t flags, void *hip_stream, sassy_hip_Reads **out);
+uint64_t sassy_hip_reads_n(const sassy_hip_Reads *r);
+const sassy_hip_ReadRecord *sassy_hip_reads_records(const sassy_hip_Reads *r); /* NULL without records */
+void *sassy_hip_reads_text(const sassy_hip_Reads *r);                          /* the device pointer */
+uint64_t sassy_hip_reads_text_bytes(const sassy_hip_Reads *r);
+uint64_t sassy_hip_reads_longest(const sassy_hip_Reads *r);
+const uint32_t *sassy_hip_reads_rem(const sassy_hip_Reads *r); /* the device pointer */
+void sassy_hip_reads_free(sassy_hip_Reads *r);
+
+/* The Hamming batch calls over a resident read batch: each returns exactly what its _many sibling (sassy_hip_search_hamming_many,
+ * sassy_hip_hamming_best_pattern, sassy_hip_hamming_counts_many) returns for the host list of the handle's sequences in file
+ * order -- fields, order, tie rule and limits are the sibling's -- with `reads` in the place of texts, text_lens, n_texts.
+ *  - the sibling's refusals, with the same codes, before any device work (a read of 2^32 bytes or more for best_pattern);
+ *    reads == NULL SASSY_HIP_EINVAL; a handle made on another device than the searcher's SASSY_HIP_EINVAL;
+ *  - flags: sassy_hip_search_hamming_reads takes SASSY_HIP_WITHOUT_TRACE, the other two none; anything else SASSY_HIP_EINVAL;
+ *  - the handle is scanned whole, as one batch whose first text has index 0: no upload, no layout and no table is built in
+ *    these calls, and option hamming_many_batch has no meaning here; hamming_batch, hamming_items, hamming_records and
+ *    hamming_count_copies keep theirs;
+ *  - the handle is only read: it serves any number of calls, of any searcher on its device, one call at a time. */
+int sassy_hip_search_hamming_reads(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                                   size_t n_patterns, const sassy_hip_Reads *reads, size_t k, uint32_t flags,
+                                   sassy_hip_Result **out);
+int sassy_hip_hamming_best_pattern_reads(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                                         size_t n_patterns, const sassy_hip_Reads *reads, size_t k, uint32_t flags,
+                                         uint8_t *out_cost, uint32_t *out_pattern, uint8_t *out_strand, uint64_t *out_start);
+int sassy_hip_hamming_counts_reads(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                                   size_t n_patterns, const sassy_hip_Reads *reads, size_t k, uint32_t flags,
+                                   uint64_t *out_counts /* n_patterns * 2 * (k + 1) */);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is

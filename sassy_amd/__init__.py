@@ -161,6 +161,9 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_hamming_clusters", "sassy_hip_edit_clusters",
     "sassy_hip_fasta_unwrap", "sassy_hip_fasta_n_records", "sassy_hip_fasta_records", "sassy_hip_fasta_text",
     "sassy_hip_fasta_text_bytes", "sassy_hip_fasta_free",
+    "sassy_hip_fastq_parse", "sassy_hip_reads_n", "sassy_hip_reads_records", "sassy_hip_reads_text", "sassy_hip_reads_text_bytes",
+    "sassy_hip_reads_longest", "sassy_hip_reads_rem", "sassy_hip_reads_free",
+    "sassy_hip_search_hamming_reads", "sassy_hip_hamming_best_pattern_reads", "sassy_hip_hamming_counts_reads",
 ]
 
 _lib = None
@@ -395,6 +398,20 @@ def lib():
     L.sassy_hip_fasta_text_bytes.argtypes = [vp]
     L.sassy_hip_fasta_free.restype = None
     L.sassy_hip_fasta_free.argtypes = [vp]
+    L.sassy_hip_fastq_parse.restype = C.c_int
+    L.sassy_hip_fastq_parse.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.POINTER(vp)]
+    for name, res in (("n", C.c_uint64), ("records", vp), ("text", vp), ("text_bytes", C.c_uint64), ("longest", C.c_uint64), ("rem", vp),
+                      ("free", None)):
+        fn = getattr(L, "sassy_hip_reads_" + name)
+        fn.restype, fn.argtypes = res, [vp]
+    # the _reads calls: a handle where the _many sibling takes texts, text_lens, n_texts
+    pats = [vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, vp, sz, C.c_uint32]
+    L.sassy_hip_search_hamming_reads.restype = C.c_int
+    L.sassy_hip_search_hamming_reads.argtypes = pats + [C.POINTER(vp)]
+    L.sassy_hip_hamming_best_pattern_reads.restype = C.c_int
+    L.sassy_hip_hamming_best_pattern_reads.argtypes = pats + [vp, vp, vp, vp]
+    L.sassy_hip_hamming_counts_reads.restype = C.c_int
+    L.sassy_hip_hamming_counts_reads.argtypes = pats + [vp]
     L.sassy_hip_malloc.restype = vp
     L.sassy_hip_malloc.argtypes = [sz]
     L.sassy_hip_free.restype = None
@@ -489,6 +506,13 @@ def fasta_record_dtype():
     """numpy view of include/sassy_hip.h: sassy_hip_FastaRecord (32 bytes)."""
     import numpy as np
     return np.dtype([("id_start", "<u8"), ("id_len", "<u8"), ("seq_start", "<u8"), ("seq_len", "<u8")])
+
+
+def read_record_dtype():
+    """numpy view of include/sassy_hip.h: sassy_hip_ReadRecord (48 bytes)."""
+    import numpy as np
+    return np.dtype([("id_start", "<u8"), ("id_len", "<u8"), ("seq_start", "<u8"), ("seq_len", "<u8"), ("qual_start", "<u8"),
+                     ("qual_len", "<u8")])
 
 
 def line_tile() -> int:
@@ -982,12 +1006,24 @@ class Searcher:
             patterns = [patterns]
         return [bytes(p) for p in patterns]
 
+    @staticmethod
+    def _pattern_arrays(patterns):
+        return (C.c_char_p * max(1, len(patterns)))(*patterns), (C.c_size_t * max(1, len(patterns)))(*[len(p) for p in patterns])
+
     def search_hamming_many(self, patterns, texts: Sequence, k: int, without_trace: bool = False, as_result: bool = False):
         """search_hamming over a batch of texts (reads) in one call (sassy_hip_search_hamming_many): the records of
         search_hamming(patterns, texts[t], k) for every t, each with text_idx = t and coordinates relative to its text,
         ordered by (pattern_idx, '+' before '-', text_idx, text_start).  `texts`: a list of host texts or a TextBatch, as
-        search_many (host texts only).  without_trace: the same records without cigar.  as_result: the Result."""
+        search_many (host texts only), or a DeviceReads -- a read batch parsed on the device, scanned where it lies
+        (sassy_hip_search_hamming_reads; hamming_best_pattern and hamming_counts_many take one likewise).  without_trace: the same records without cigar.  as_result: the Result."""
         patterns = self._hamming_patterns(patterns, "search_hamming_many")
+        if isinstance(texts, DeviceReads):  # a resident read batch: sassy_hip_search_hamming_reads
+            pp, pl = self._pattern_arrays(patterns)
+            out = C.c_void_p()
+            _check(lib().sassy_hip_search_hamming_reads(self._h, pp, pl, len(patterns), texts._handle(), k,
+                                                        WITHOUT_TRACE if without_trace else 0, C.byref(out)))
+            r = Result(out)
+            return r if as_result else r.matches
         pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
         if on_device:
             raise SassyHipError("search_hamming_many takes host texts only")
@@ -1005,6 +1041,14 @@ class Searcher:
         cigars.  k <= 254.  Demultiplexing by mismatch count."""
         import numpy as np
         patterns = self._hamming_patterns(patterns, "hamming_best_pattern")
+        if isinstance(texts, DeviceReads):  # a resident read batch: sassy_hip_hamming_best_pattern_reads
+            pp, pl = self._pattern_arrays(patterns)
+            n = len(texts)
+            cost, pattern = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32)
+            strand, start = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint64)
+            _check(lib().sassy_hip_hamming_best_pattern_reads(self._h, pp, pl, len(patterns), texts._handle(), k, 0, cost.ctypes.data,
+                                                              pattern.ctypes.data, strand.ctypes.data, start.ctypes.data))
+            return cost, pattern, strand, start
         pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
         if on_device:
             raise SassyHipError("hamming_best_pattern takes host texts only")
@@ -1041,6 +1085,11 @@ class Searcher:
         `texts`: a list of host texts or a TextBatch (host texts only)."""
         import numpy as np
         patterns = self._hamming_patterns(patterns, "hamming_counts_many")
+        if isinstance(texts, DeviceReads):  # a resident read batch: sassy_hip_hamming_counts_reads
+            pp, pl = self._pattern_arrays(patterns)
+            counts = np.zeros((len(patterns), 2, max(0, min(int(k), 254)) + 1), dtype=np.uint64)
+            _check(lib().sassy_hip_hamming_counts_reads(self._h, pp, pl, len(patterns), texts._handle(), k, 0, counts.ctypes.data))
+            return counts
         pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
         if on_device:
             raise SassyHipError("hamming_counts_many takes host texts only")
@@ -1795,6 +1844,102 @@ class DeviceFasta:
         if getattr(self, "_h", None) is not None:
             try:
                 lib().sassy_hip_fasta_free(self._h)
+            except Exception:  # interpreter shutdown
+                pass
+            self._h = None
+            self.ptr = 0
+
+    def __del__(self):
+        self.free()
+
+
+class DeviceReads:
+    """A chunk of FASTQ parsed on the device (sassy_hip_fastq_parse): `raw` -- bytes, a numpy uint8 array, or a device text
+    (DeviceText, a torch tensor) -- holds whole records of strict four-line FASTQ and is empty or begins with '@'.  The
+    sequences stay on the device in the layout the Hamming batch kernels scan: `search_hamming_many`, `hamming_best_pattern`
+    and `hamming_counts_many` take the object as `texts`, any number of times, without an upload.  Only the record table
+    comes back: `id_starts` / `id_lens` and `qual_starts` / `qual_lens` index `raw`, `seq_starts` (multiples of 64) /
+    `seq_lens` the device buffer.  Malformed input raises SassyHipError and names the first bad record.  The definition is
+    tests/helpers/fastq_ref.py."""
+
+    def __init__(self, raw, stream: int = 0):
+        import numpy as np
+        addr, n, keep, on_dev = _ptr_len(raw)
+        self._raw, self._raw_on_device = keep, on_dev
+        self._h = None
+        out = C.c_void_p()
+        _check(lib().sassy_hip_fastq_parse(addr, n, TEXT_ON_DEVICE if on_dev else 0, stream or None, C.byref(out)))
+        self._h = out
+        count = int(lib().sassy_hip_reads_n(out))
+        dt = read_record_dtype()
+        # (a view of the handle's own table: the columns below are its only copy -- millions of reads are 48 bytes each)
+        table = (np.frombuffer((C.c_char * (count * dt.itemsize)).from_address(lib().sassy_hip_reads_records(out)), dtype=dt) if count
+                 else np.zeros(0, dtype=dt))
+        self.id_starts, self.id_lens = table["id_start"].copy(), table["id_len"].copy()
+        self.seq_starts, self.seq_lens = table["seq_start"].copy(), table["seq_len"].copy()
+        self.qual_starts, self.qual_lens = table["qual_start"].copy(), table["qual_len"].copy()
+        self.ptr = int(lib().sassy_hip_reads_text(out) or 0)
+        self.text_bytes = int(lib().sassy_hip_reads_text_bytes(out))
+        self.longest = int(lib().sassy_hip_reads_longest(out))
+
+    def __len__(self) -> int:
+        return len(self.id_starts)
+
+    def _live(self):
+        if self._h is None:
+            raise SassyHipError("DeviceReads: freed")
+
+    def _handle(self):
+        self._live()
+        return self._h
+
+    def _raw_bytes(self, a: int, n: int) -> bytes:
+        if self._raw is None:
+            raise SassyHipError("DeviceReads: the raw bytes were let go (ids and qualities are with whoever released them)")
+        if self._raw_on_device:
+            return DeviceText(self._raw.data_ptr() + a, n).download()
+        if isinstance(self._raw, bytes):
+            return self._raw[a:a + n]
+        return self._raw[a:a + n].tobytes()
+
+    def id(self, i: int) -> str:
+        return self._raw_bytes(int(self.id_starts[i]), int(self.id_lens[i])).decode()
+
+    def quality(self, i: int) -> bytes:
+        return self._raw_bytes(int(self.qual_starts[i]), int(self.qual_lens[i]))
+
+    def text(self, i: int) -> DeviceText:
+        """Read i's sequence on the device."""
+        self._live()
+        return DeviceText(self.ptr + int(self.seq_starts[i]), int(self.seq_lens[i]), owner=self)
+
+    def download(self, i: int, start: int = 0, end: Optional[int] = None) -> bytes:
+        """Read i's sequence, or its bytes [start, end), on the host."""
+        self._live()
+        n = int(self.seq_lens[i])
+        end = n if end is None else min(int(end), n)
+        start = max(0, int(start))
+        if end <= start:
+            return b""
+        return DeviceText(self.ptr + int(self.seq_starts[i]) + start, end - start).download()
+
+    def download_text(self) -> bytes:
+        """The whole device buffer: the layout, pads and the 64 spare bytes included."""
+        self._live()
+        return DeviceText(self.ptr, self.text_bytes).download()
+
+    def download_rem(self):
+        """The per-block table the scan masks by (bytes left in the block's own read), as a numpy uint32 array."""
+        import numpy as np
+        self._live()
+        n_blocks = (self.text_bytes - 64) // 64
+        raw = DeviceText(int(lib().sassy_hip_reads_rem(self._h) or 0), 4 * n_blocks).download()
+        return np.frombuffer(raw, dtype=np.uint32).copy()
+
+    def free(self):
+        if getattr(self, "_h", None) is not None:
+            try:
+                lib().sassy_hip_reads_free(self._h)
             except Exception:  # interpreter shutdown
                 pass
             self._h = None

@@ -41,6 +41,9 @@ FASTA / FASTQ file or a file with one pattern per line (ids 1, 2, ...).  Forward
 `--per-record` writes the rows per record instead (one call per record: the per-chromosome table), `text_id` in front.
 `--device-unwrap` (with `--per-record`, and on `amplicon`; FASTA only) reads the records through `read_fasta_device_batches`:
 the file's bytes go up once, kernels drop headers and line ends, every call gets a device-resident text; the output is the same.
+`--device-parse` (on `demux`, and on `count` without `--per-record`; FASTQ only) reads the records through
+`read_fastq_device_batches`: a batch's bytes go up once, kernels find and check the reads and lay them out, and the batch call
+scans them where they lie (`sassy_amd.DeviceReads`); the output is the same.
 
 `amplicon PRIMERS FASTX ... -k K --min-len A --max-len B [--no-rc] [-a dna|iupac] [--max-n-frac X] [--seq]` writes which
 products primer pairs make (in-silico PCR) through `Searcher.hamming_amplicons`, one call per FASTX record.  PRIMERS is a TSV
@@ -99,7 +102,7 @@ BATCH_BYTES = 64 << 20  # input bytes per search_many call (a longer record is a
 
 
 # (the reader: sassy_amd/fastx.py -- batches of whole records as one buffer + offsets, numpy over an mmap)
-from .fastx import read_fasta_device_batches, read_fastx, read_fastx_batches  # noqa: E402,F401
+from .fastx import first_byte, read_fasta_device_batches, read_fastq_device_batches, read_fastx, read_fastx_batches  # noqa: E402,F401
 
 
 def load_patterns(args) -> List[Tuple[str, bytes]]:
@@ -315,12 +318,15 @@ def demux_rows(patterns, ids, best):
 def run_demux(args, searcher, patterns, out) -> int:
     out.write(DEMUX_HEADER)
     pats = [p for _, p in patterns]
+    device_parse = getattr(args, "device_parse", False)  # the reads of a batch are parsed, laid out and scanned on the device
     for path in args.paths:
-        for batch in read_fastx_batches(path, BATCH_BYTES):
+        for batch in (read_fastq_device_batches if device_parse else read_fastx_batches)(path, BATCH_BYTES):
             if not len(batch):
                 continue
             best = searcher.hamming_best_pattern(pats, batch.texts, args.k)
             out.writelines(demux_rows(patterns, [batch.id(i) for i in range(len(batch))], best))
+            if device_parse:
+                batch.free()
     out.flush()
     return 0
 
@@ -364,6 +370,12 @@ def run_count(args, searcher, patterns, out) -> int:
                                               text_id=batch.id(i)))
                 batch.free()
             continue
+        if getattr(args, "device_parse", False):  # (without --per-record: the batch call scans the reads where they lie)
+            for batch in read_fastq_device_batches(path, BATCH_BYTES):
+                if len(batch):
+                    total += searcher.hamming_counts_many(pats, batch.texts, args.k)
+                batch.free()
+            continue
         for batch in read_fastx_batches(path, BATCH_BYTES):
             if not len(batch):
                 continue
@@ -390,6 +402,8 @@ def count_parser(sub):
     cp.add_argument("--per-record", action="store_true", help="rows per record (text_id in front) instead of summed over all records")
     cp.add_argument("--device-unwrap", action="store_true",
                     help="with --per-record, FASTA only: upload the file's bytes and drop headers and line ends on the device")
+    cp.add_argument("--device-parse", action="store_true",
+                    help="without --per-record, FASTQ only: upload the file's bytes, find and lay out the reads on the device")
     return cp
 
 
@@ -570,11 +584,19 @@ def main(argv=None) -> int:
     dp = sub.add_parser("demux", help="write per record the pattern (barcode) with the fewest mismatches as TSV to stdout")
     add_search_arguments(dp)
     dp.add_argument("paths", nargs="+")
+    dp.add_argument("--device-parse", action="store_true",
+                    help="FASTQ only: upload the file's bytes, find and lay out the reads on the device, scan them where they lie")
     count_parser(sub)
     amplicon_parser(sub)
     pairs_parser(sub)
     cluster_parser(sub)
     args = ap.parse_args(argv)
+    if getattr(args, "device_parse", False):
+        if args.cmd == "count" and args.per_record:
+            ap.error("count --device-parse serves the summed table: --per-record takes --device-unwrap (FASTA) or no flag")
+        for path in args.paths:
+            if first_byte(path) not in (b"@", b""):
+                ap.error(f"{args.cmd} --device-parse takes FASTQ only: {path} does not begin with '@'")
     if args.cmd == "cluster":
         if not 0 <= args.k <= 254:
             ap.error("cluster takes 0 <= k <= 254")

@@ -25,6 +25,8 @@
 //                    one device text or one laid-out batch
 //   ham_for_text_batches   the _many calls: one loop over text batches that calls one of the three
 //   hamming_refusals, hamming_count_call and the five entry points, each behind hamming_call (host_internal.h)
+//   hamming_reads_records / _cells / _counts   the three drivers over a batch that is already resident and laid out (the
+//                    handle of fastq_reads.hip, whose entry points call them)
 #include "host_internal.h"
 #include "profile_masks.h"
 #include "hamming_step.h"
@@ -675,6 +677,52 @@ int hamming_refusals(sassy_SearcherType* s, const uint8_t* const* patterns, cons
   }
   SASSY_NO_TICKETS(s);
   return 0;
+}
+
+// ---- a resident read batch (fastq_reads.hip): the three drivers over one HamText that is already laid out on the device,
+// behind the caller's pointer and flag checks.  No upload, no layout, no ham_rem_kernel; `device`: where the batch was made.
+namespace {
+int same_device(const sassy_SearcherType* s, int device, const char* who) {
+  if (s->device == device) return 0;
+  return fail(SASSY_HIP_EINVAL, std::string(who) + ": the reads were made on device " + std::to_string(device) + ", the searcher is on device " +
+                                    std::to_string(s->device));
+}
+}  // namespace
+// records into R, in the contract's order; the caller has called hamming_refusals
+int hamming_reads_records(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, const HamText& reads, int device,
+                          size_t k, bool without_trace, sassy_hip_Result* R) {
+  return hamming_call(s, lens, n_pats, k, [&](uint32_t kk) {
+    if (int rc = same_device(s, device, "search_hamming_reads")) return rc;
+    if (reads.n == 0) return 0;  // (only empty reads: no hits)
+    if (int rc = hamming_records(s, pats, lens, n_pats, reads, kk, without_trace, R)) return rc;
+    // pattern groups and ranges each came in the contract's order: a stable sort on (pattern, strand) restores it for the call
+    if (!std::is_sorted(R->matches.begin(), R->matches.end(), by_pattern)) std::stable_sort(R->matches.begin(), R->matches.end(), by_pattern);
+    return 0;
+  });
+}
+// per read its best-pattern cell, on the host (all ones: no hit); the caller has called hamming_refusals
+int hamming_reads_cells(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, const HamText& reads, int device,
+                        size_t k, unsigned long long* cells) {
+  return hamming_call(s, lens, n_pats, k, [&](uint32_t kk) {
+    if (int rc = same_device(s, device, "hamming_best_pattern_reads")) return rc;
+    if (reads.n == 0) return 0;
+    const size_t nt = reads.n_texts;
+    if (int rc = s->d_ham_cells.reserve(nt)) return rc;
+    HIP_TRY(hipMemsetAsync(s->d_ham_cells.p, 0xFF, nt * 8, s->stream));
+    if (int rc = hamming_cells(s, pats, lens, n_pats, reads, kk, s->d_ham_cells.p)) return rc;
+    HIP_TRY(hipMemcpyAsync(cells, s->d_ham_cells.p, nt * 8, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+  });
+}
+// the counts table; the refusals are hamming_count_call's
+int hamming_reads_counts(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, const HamText& reads, int device,
+                         size_t k, const char* who, uint64_t* out_counts) {
+  return hamming_count_call(s, pats, lens, n_pats, k, who, reads.n_texts == 0, out_counts, [&](uint32_t kk, const HamCounts& C) {
+    if (int rc = same_device(s, device, who)) return rc;
+    if (reads.n == 0) return 0;
+    return hamming_add_counts(s, pats, lens, n_pats, reads, kk, C);
+  });
 }
 
 }  // namespace sassy_hip

@@ -7,6 +7,7 @@
 //                     the device side of their one driver (ham_prepare, ham_scan_range; records / cells / counts) and the entry points
 //   hamming_plan.h    that driver's decisions that need no device (patterns as scanned, groups, tables, overflow step, text batches), free of HIP
 //   amplicons.hip     sassy_hip_hamming_amplicons: primer pairs joined on the sorted items of the Hamming scan (ham_walk_ranges, below)
+//   fastq_reads.hip   sassy_hip_fastq_parse: FASTQ into a resident read batch; sassy_hip_*_reads, the Hamming batch calls over it
 //   c_abi.hip         the C-ABI of include/sassy.h + sassy_hip.h, the switch table, synthetic inputs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1193,6 +1194,15 @@ int ham_prepare(sassy_SearcherType* S, const HamJob& J, HamPrepared& P);
 int ham_scan_range(sassy_SearcherType* S, const HamJob& J, HamPrepared& P, uint64_t tile0, HamRangeOut& out);
 // what every Hamming entry point refuses, before any device work; `who` names the entry point
 int hamming_refusals(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, size_t k, const char* who);
+// The drivers over a read batch that is resident and laid out (fastq_reads.hip's handle as one HamText with text0 = 0; `device`:
+// where it was made, another one than the searcher's is SASSY_HIP_EINVAL): records in the contract's order, the best-pattern
+// cells on the host, the counts table.  The first two stand behind the caller's hamming_refusals, the third calls it.
+int hamming_reads_records(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, const HamText& reads, int device,
+                          size_t k, bool without_trace, sassy_hip_Result* R);
+int hamming_reads_cells(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, const HamText& reads, int device,
+                        size_t k, unsigned long long* cells);
+int hamming_reads_counts(sassy_SearcherType* s, const uint8_t* const* pats, const size_t* lens, size_t n_pats, const HamText& reads, int device,
+                         size_t k, const char* who, uint64_t* out_counts);
 // A group's tiles in ranges, for the callers that list records: every range asks for all that is left and ham_scan_range cuts
 // it to what the item list holds.  per_range(range, t1, last, &next) makes the records of tiles [.., t1) and may move `next`,
 // the tile the next range starts at (t1 as it comes).  Each range's records come in the contract's order and the ranges

@@ -16,6 +16,9 @@ only the records with a match are printed.
 
 `read_fasta_device_batches` is the same stream of chunks with the unwrap on the device (`sassy_amd.DeviceFasta`): the raw bytes
 of a chunk are uploaded once, and every record comes back as a device-resident text for the one-text calls.  FASTA only.
+
+`read_fastq_device_batches` is that for FASTQ (`sassy_amd.DeviceReads`): a chunk's raw bytes go up once, kernels find and check
+the records and lay the sequences out, and the batch is what the Hamming batch calls take as `texts`.
 """
 from __future__ import annotations
 
@@ -432,6 +435,96 @@ def read_fasta_device_batches(path: str, batch_bytes: int = 256 << 20) -> Iterat
             yield DeviceRecordBatch(fasta, ids)
             if eof and carry == 0:
                 return
+    finally:
+        if path not in ("", "-"):
+            fh.close()
+
+
+class DeviceReadBatch:
+    """Records of one FASTQ chunk, parsed on the device (sassy_amd.DeviceReads): `texts` is the resident read batch that
+    search_hamming_many, hamming_best_pattern and hamming_counts_many scan where it lies; `sequence(i)` downloads a read.
+    The ids are gathered out of the reader's reused buffer into one array when the batch is made (one numpy gather, no loop
+    over the reads); qualities are not kept."""
+
+    def __init__(self, reads, chunk: np.ndarray):
+        self.texts = reads
+        lens = reads.id_lens.astype(np.int64)
+        self._id_at = np.cumsum(lens) - lens
+        self._id_lens = lens
+        total = int(lens.sum())
+        self._ids = chunk[np.repeat(reads.id_starts.astype(np.int64) - self._id_at, lens) + np.arange(total, dtype=np.int64)] if total else chunk[:0]
+
+    def __len__(self) -> int:
+        return len(self.texts)
+
+    def id(self, i: int) -> str:
+        a, n = int(self._id_at[i]), int(self._id_lens[i])
+        return self._ids[a:a + n].tobytes().decode()
+
+    def sequence(self, i: int, start: int = 0, end: Optional[int] = None) -> bytes:
+        return self.texts.download(i, start, end)
+
+    def free(self):
+        self.texts.free()
+
+
+def read_fastq_device_batches(path: str, batch_bytes: int = 256 << 20) -> Iterator[DeviceReadBatch]:
+    """read_fastx_batches for FASTQ with the parse on the device: the same chunks, cut at the same record boundaries; the raw
+    bytes of a chunk are uploaded once and kernels find the records and lay the sequences out (sassy_hip_fastq_parse).
+    FASTA is refused: read_fasta_device_batches unwraps it."""
+    from . import DeviceReads
+    # (read_fastx_batches' own loop over chunks, FASTQ only: that function stays as it is, so the loop is written out here)
+    work = _Work()
+    fill, fh = _sources(path)
+    try:
+        carry = 0
+        eof = False
+        first = True
+        while True:
+            want = batch_bytes
+            m, raw = work.raw_buffer(carry + want, carry)
+            have = carry
+            while True:
+                while have < carry + want and not eof:
+                    got = fill(memoryview(m)[have:carry + want])
+                    if got == 0:
+                        eof = True
+                    have += got
+                if have == 0:
+                    return
+                if first:
+                    head = bytes(raw[:1])
+                    if head != b"@":
+                        raise ValueError(f"{path}: not FASTQ (first byte {head!r}): the parse on the device takes FASTQ only")
+                    first = False
+                end = _cut(m, 0, have, True, eof)
+                if end > 0:
+                    break
+                want *= 2  # a record longer than the batch: read on
+                m, raw = work.raw_buffer(carry + want, have)
+            chunk = raw[:end]
+            reads = DeviceReads(chunk)
+            batch = DeviceReadBatch(reads, chunk)
+            reads._raw = None  # (the reader's buffer is reused: the batch keeps the ids, not the chunk)
+            rest = have - end
+            work.turn ^= 1
+            m2, raw2 = work.raw_buffer(rest + batch_bytes, 0)
+            raw2[:rest] = raw[end:have]
+            carry = rest
+            yield batch
+            if eof and carry == 0:
+                return
+    finally:
+        if path not in ("", "-"):
+            fh.close()
+
+
+def first_byte(path: str) -> bytes:
+    """The first byte of a file's contents (behind gzip), b"" for an empty one."""
+    fill, fh = _sources(path)
+    try:
+        one = bytearray(1)
+        return bytes(one) if fill(memoryview(one)) else b""
     finally:
         if path not in ("", "-"):
             fh.close()
