@@ -176,6 +176,18 @@ extern "C" {
                                             out_strand: *mut u8, out_start: *mut u64) -> c_int;
     fn sassy_hip_hamming_counts_reads(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
                                       reads: *const RawReads, k: usize, flags: u32, out_counts: *mut u64) -> c_int;
+    // ... and the edit-distance batch calls: the resident reads are laid out for the scan by a kernel, no upload
+    pub fn sassy_hip_search_many_reads(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                       reads: *const RawReads, k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
+    pub fn sassy_hip_min_costs_reads(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                     reads: *const RawReads, k: usize, flags: u32, out_cost: *mut u8, out_strand: *mut u8) -> c_int;
+    pub fn sassy_hip_best_pattern_reads(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                        reads: *const RawReads, k: usize, flags: u32, out_cost: *mut u8, out_pattern: *mut u32,
+                                        out_strand: *mut u8) -> c_int;
+    pub fn sassy_hip_best_matches_reads(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
+                                        reads: *const RawReads, k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
+    pub fn sassy_hip_reads_relayout(reads: *const RawReads, first: u64, count: u64, dst_starts: *const u64, total: u64, pad: u8,
+                                    d_dst: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

@@ -661,6 +661,42 @@ int sassy_hip_hamming_counts_reads(sassy_SearcherType *s, const uint8_t *const *
                                    size_t n_patterns, const sassy_hip_Reads *reads, size_t k, uint32_t flags,
                                    uint64_t *out_counts /* n_patterns * 2 * (k + 1) */);
 
+/* The edit-distance batch calls over a resident read batch: each returns exactly what its sibling
+ * (sassy_hip_search_many, sassy_hip_min_costs, sassy_hip_best_pattern, sassy_hip_best_matches) returns for the host list of
+ * the handle's sequences in file order -- fields, order, tie rules, limits and refusals are the sibling's -- with `reads` in
+ * the place of texts, text_lens, n_texts.
+ *  - where the sibling lays a batch of host texts out on the host and uploads it (its one-pass paths), a kernel lays the
+ *    resident reads out into the same buffer, byte for byte the same (sassy_hip_reads_relayout): no host layout, no upload;
+ *    everything behind the layout is the sibling's code.  A Dna searcher's "plain A, C, G, T only" look at the texts is made
+ *    on the device, over the sequences alone (the zeros between them do not count);
+ *  - where the one-pass paths decline (fewer than 2 reads, a Dna batch with other letters that the per-text path does not
+ *    take either, patterns of mixed lengths on a filterable shape, 2^24 reads or more, ...) the call runs the sibling's
+ *    general path on the reads where they lie, as device texts;
+ *  - additional refusals: reads == NULL SASSY_HIP_EINVAL; a handle made on another device than the searcher's
+ *    SASSY_HIP_EINVAL; SASSY_HIP_TEXT_ON_DEVICE in flags SASSY_HIP_EINVAL (it has no meaning here); searches in flight on
+ *    the searcher are refused as elsewhere;
+ *  - the handle is only read: it serves any number of calls, the Hamming ones included, one call at a time. */
+int sassy_hip_search_many_reads(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                                size_t n_patterns, const sassy_hip_Reads *reads, size_t k, uint32_t flags,
+                                sassy_hip_Result **out);
+int sassy_hip_min_costs_reads(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                              size_t n_patterns, const sassy_hip_Reads *reads, size_t k, uint32_t flags, uint8_t *out_cost,
+                              uint8_t *out_strand);
+int sassy_hip_best_pattern_reads(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                                 size_t n_patterns, const sassy_hip_Reads *reads, size_t k, uint32_t flags, uint8_t *out_cost,
+                                 uint32_t *out_pattern, uint8_t *out_strand);
+int sassy_hip_best_matches_reads(sassy_SearcherType *s, const uint8_t *const *patterns, const size_t *pattern_lens,
+                                 size_t n_patterns, const sassy_hip_Reads *reads, size_t k, uint32_t flags,
+                                 sassy_hip_Result **out);
+/* The relayout itself, for a host that builds a batch of its own: reads first .. first + count of the handle into d_dst (device
+ * memory of at least `total` bytes, 16-byte aligned), read first + i at [dst_starts[i], dst_starts[i] + seq_len) -- dst_starts
+ * is a host table, ascending, no read over the next one's start or over `total` --, every other byte of [0, total) = pad;
+ * bytes behind `total` are not written.  Runs on the handle's device, on hip_stream (NULL: the default stream), and returns
+ * when the buffer is written.  Null arguments, a range outside the handle, a destination that is not 16-byte aligned and a
+ * table the reads do not fit are SASSY_HIP_EINVAL. */
+int sassy_hip_reads_relayout(const sassy_hip_Reads *reads, uint64_t first, uint64_t count, const uint64_t *dst_starts,
+                             uint64_t total, uint8_t pad, void *d_dst, void *hip_stream);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is

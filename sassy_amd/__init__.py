@@ -164,6 +164,8 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_fastq_parse", "sassy_hip_reads_n", "sassy_hip_reads_records", "sassy_hip_reads_text", "sassy_hip_reads_text_bytes",
     "sassy_hip_reads_longest", "sassy_hip_reads_rem", "sassy_hip_reads_free",
     "sassy_hip_search_hamming_reads", "sassy_hip_hamming_best_pattern_reads", "sassy_hip_hamming_counts_reads",
+    "sassy_hip_search_many_reads", "sassy_hip_min_costs_reads", "sassy_hip_best_pattern_reads", "sassy_hip_best_matches_reads",
+    "sassy_hip_reads_relayout",
 ]
 
 _lib = None
@@ -412,6 +414,16 @@ def lib():
     L.sassy_hip_hamming_best_pattern_reads.argtypes = pats + [vp, vp, vp, vp]
     L.sassy_hip_hamming_counts_reads.restype = C.c_int
     L.sassy_hip_hamming_counts_reads.argtypes = pats + [vp]
+    L.sassy_hip_search_many_reads.restype = C.c_int
+    L.sassy_hip_search_many_reads.argtypes = pats + [C.POINTER(vp)]
+    L.sassy_hip_min_costs_reads.restype = C.c_int
+    L.sassy_hip_min_costs_reads.argtypes = pats + [vp, vp]
+    L.sassy_hip_best_pattern_reads.restype = C.c_int
+    L.sassy_hip_best_pattern_reads.argtypes = pats + [vp, vp, vp]
+    L.sassy_hip_best_matches_reads.restype = C.c_int
+    L.sassy_hip_best_matches_reads.argtypes = pats + [C.POINTER(vp)]
+    L.sassy_hip_reads_relayout.restype = C.c_int
+    L.sassy_hip_reads_relayout.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint8, vp, vp]
     L.sassy_hip_malloc.restype = vp
     L.sassy_hip_malloc.argtypes = [sz]
     L.sassy_hip_free.restype = None
@@ -1316,12 +1328,28 @@ class Searcher:
             held = infos
         return pp, pl, len(patterns), tp, tl, n_texts, on_device, (patterns, texts, held, tp, tl)
 
-    def search_many(self, patterns: Sequence[bytes], texts: Sequence, k: int, all_minima: bool = False, as_result: bool = False):
+    @staticmethod
+    def _marshal_patterns(patterns: Sequence[bytes]):
+        """(pattern pointers, pattern lengths, n_patterns, what must stay alive) for the calls over a DeviceReads"""
+        patterns = [_byte_pattern(p) for p in patterns]
+        return (C.c_char_p * len(patterns))(*patterns), (C.c_size_t * len(patterns))(*[len(p) for p in patterns]), len(patterns), patterns
+
+    def search_many(self, patterns: Sequence[bytes], texts: Sequence, k: int, all_minima: bool = False, as_result: bool = False,
+                    without_trace: bool = False):
         """Searcher::search_many in SearchMode::Single order (src/search.rs:531-560): every pattern in
         every text, pattern-major; matches carry pattern_idx and text_idx.  as_result: the Result itself (numpy `.array`,
-        `.lazy_matches`) instead of a list of Match objects."""
+        `.lazy_matches`) instead of a list of Match objects.  `texts`: a list, a TextBatch, or a DeviceReads -- a read batch
+        parsed on the device and laid out for the scan there, without a host layout or an upload (sassy_hip_search_many_reads;
+        min_costs, best_pattern, best_matches and search_texts take one likewise)."""
+        if isinstance(texts, DeviceReads):
+            pp, pl, n_patterns, _alive = self._marshal_patterns(patterns)
+            out = C.c_void_p()
+            _check(lib().sassy_hip_search_many_reads(self._h, pp, pl, n_patterns, texts._handle(), k,
+                                                     (ALL_MINIMA if all_minima else 0) | (WITHOUT_TRACE if without_trace else 0), C.byref(out)))
+            r = Result(out)
+            return r if as_result else r.matches
         pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
-        flags = (ALL_MINIMA if all_minima else 0) | (TEXT_ON_DEVICE if on_device else 0)
+        flags = (ALL_MINIMA if all_minima else 0) | (TEXT_ON_DEVICE if on_device else 0) | (WITHOUT_TRACE if without_trace else 0)
         out = C.c_void_p()
         _check(lib().sassy_hip_search_many(self._h, pp, pl, n_patterns, tp, tl, n_texts, k, flags, C.byref(out)))
         r = Result(out)
@@ -1333,6 +1361,13 @@ class Searcher:
         (costs, strands) -- the strand of each minimum, 0 Fwd / 1 Rc, Fwd on a tie.  A batch of host texts is reduced on
         the device from the scan's own list: no records, no traceback.  `texts` a list or a TextBatch, as search_many."""
         import numpy as np
+        if isinstance(texts, DeviceReads):  # a resident read batch: sassy_hip_min_costs_reads
+            pp, pl, n_patterns, _alive = self._marshal_patterns(patterns)
+            cost = np.empty((n_patterns, len(texts)), dtype=np.uint8)
+            strand = np.empty((n_patterns, len(texts)), dtype=np.uint8) if strands else None
+            _check(lib().sassy_hip_min_costs_reads(self._h, pp, pl, n_patterns, texts._handle(), k, 0, cost.ctypes.data,
+                                                   strand.ctypes.data if strands else None))
+            return (cost, strand) if strands else cost
         pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
         cost = np.empty((n_patterns, n_texts), dtype=np.uint8)
         strand = np.empty((n_patterns, n_texts), dtype=np.uint8) if strands else None
@@ -1346,6 +1381,12 @@ class Searcher:
         index on a tie, then Fwd before Rc; 0xFFFFFFFF where there is no match) and its strand.  Demultiplexing, and
         `filter`: a record is kept when its cost is not NO_MATCH."""
         import numpy as np
+        if isinstance(texts, DeviceReads):  # a resident read batch: sassy_hip_best_pattern_reads
+            pp, pl, n_patterns, _alive = self._marshal_patterns(patterns)
+            cost, pattern, strand = np.empty(len(texts), dtype=np.uint8), np.empty(len(texts), dtype=np.uint32), np.empty(len(texts), dtype=np.uint8)
+            _check(lib().sassy_hip_best_pattern_reads(self._h, pp, pl, n_patterns, texts._handle(), k, 0, cost.ctypes.data, pattern.ctypes.data,
+                                                      strand.ctypes.data))
+            return cost, pattern, strand
         pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
         cost = np.empty(n_texts, dtype=np.uint8)
         pattern = np.empty(n_texts, dtype=np.uint32)
@@ -1361,7 +1402,14 @@ class Searcher:
         direction (largest text_end for Fwd, smallest text_start for Rc).  At most one Match per text, ascending text_idx;
         a text without a match of cost <= k has none.  A batch of host texts is reduced and traced on the device: one
         traceback per text.  without_trace: end and cost only.  as_result: the Result itself.  `texts` a list or a
-        TextBatch, as search_many."""
+        TextBatch, as search_many, or a DeviceReads."""
+        if isinstance(texts, DeviceReads):  # a resident read batch: sassy_hip_best_matches_reads
+            pp, pl, n_patterns, _alive = self._marshal_patterns(patterns)
+            out = C.c_void_p()
+            _check(lib().sassy_hip_best_matches_reads(self._h, pp, pl, n_patterns, texts._handle(), k, WITHOUT_TRACE if without_trace else 0,
+                                                      C.byref(out)))
+            r = Result(out)
+            return r if as_result else r.matches
         pp, pl, n_patterns, tp, tl, n_texts, on_device, _alive = self._marshal_many(patterns, texts)
         flags = (WITHOUT_TRACE if without_trace else 0) | (TEXT_ON_DEVICE if on_device else 0)
         out = C.c_void_p()

@@ -165,9 +165,11 @@ bool better_match(const sassy_hip_Match& a, const sassy_hip_Match& b) {
   return a.pattern_end < b.pattern_end;
 }
 
-int best_matches(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
-                 const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags, sassy_hip_Result** out) {
-  if (!s || !out || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!texts || !text_lens)))
+int best_matches(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, TextSource& src,
+                 size_t k, uint32_t flags, sassy_hip_Result** out) {
+  const size_t* text_lens = src.lens;
+  const size_t n_texts = src.n;
+  if (!s || !out || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!src.texts || !text_lens)))
     return fail(SASSY_HIP_EINVAL, "null argument");
   SASSY_NO_LINE_SPANS(flags);
   if (flags & ~(SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_WITHOUT_TRACE))
@@ -178,7 +180,7 @@ int best_matches(sassy_SearcherType* s, const uint8_t* const* patterns, const si
     return fail(SASSY_HIP_EUNSUPPORTED, "reverse complement is not defined for the ascii alphabet");
   const double t0 = now_ms();
   // ---- the device path: where best_pattern's device reduction takes the call, without the N filter, texts < 2^31 ----
-  bool device = s->sw.best_match_device != 0 && n_texts >= 2 && n_patterns > 0 && !(flags & SASSY_HIP_TEXT_ON_DEVICE) &&
+  bool device = s->sw.best_match_device != 0 && n_texts >= 2 && n_patterns > 0 && (!(flags & SASSY_HIP_TEXT_ON_DEVICE) || src.reads) &&
                 !is_ascii(s->profile) && pattern_lens[0] <= 64 && 2 * k + 3 <= 64 && n_patterns < (1u << 24) &&
                 std::isnan(s->max_n_frac);
   for (size_t pi = 1; device && pi < n_patterns; ++pi) device = pattern_lens[pi] == pattern_lens[0];
@@ -206,7 +208,7 @@ int best_matches(sassy_SearcherType* s, const uint8_t* const* patterns, const si
   } restore{s, s->only_best};
   s->only_best = false;
   sassy_hip_Result* R = nullptr;
-  if (int rc = sassy_hip_search_many(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, &R)) return rc;
+  if (int rc = search_many_source(s, patterns, pattern_lens, n_patterns, src, k, flags, &R)) return rc;
   std::unique_ptr<sassy_hip_Result> all(R);
   if (sink.located) {  // (records the host made -- without trace -- went through search_many's pattern-major sort)
     std::sort(all->matches.begin(), all->matches.end(),
@@ -252,7 +254,21 @@ int sassy_hip_best_matches(sassy_SearcherType* s, const uint8_t* const* patterns
                            const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
                            sassy_hip_Result** out) {
   try {
-    return best_matches(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, out);
+    TextSource src{texts, text_lens, n_texts};
+    return best_matches(s, patterns, pattern_lens, n_patterns, src, k, flags, out);
+  } catch (const std::bad_alloc&) {
+    if (s) s->min_sink = nullptr;
+    return fail(SASSY_HIP_ENOMEM, "best_matches: out of host memory");
+  }
+}
+
+int sassy_hip_best_matches_reads(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                                 const sassy_hip_Reads* reads, size_t k, uint32_t flags, sassy_hip_Result** out) {
+  try {
+    if (out) *out = nullptr;
+    ReadsTexts rt;
+    if (int rc = reads_as_source(s, reads, flags, "best_matches_reads", &rt)) return rc;
+    return best_matches(s, patterns, pattern_lens, n_patterns, rt.src, k, flags | SASSY_HIP_TEXT_ON_DEVICE, out);
   } catch (const std::bad_alloc&) {
     if (s) s->min_sink = nullptr;
     return fail(SASSY_HIP_ENOMEM, "best_matches: out of host memory");

@@ -271,6 +271,27 @@ int sassy_hip_search_many(sassy_SearcherType* s, const uint8_t* const* patterns,
                           size_t k, uint32_t flags, sassy_hip_Result** out) {
   if (!s || !out || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!texts || !text_lens)))
     return fail(SASSY_HIP_EINVAL, "null argument");
+  TextSource src{texts, text_lens, n_texts};
+  return search_many_source(s, patterns, pattern_lens, n_patterns, src, k, flags, out);
+}
+
+int sassy_hip_search_many_reads(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                                const sassy_hip_Reads* reads, size_t k, uint32_t flags, sassy_hip_Result** out) {
+  if (out) *out = nullptr;
+  if (!s || !out || !reads || (n_patterns && (!patterns || !pattern_lens))) return fail(SASSY_HIP_EINVAL, "null argument");
+  ReadsTexts rt;
+  if (int rc = reads_as_source(s, reads, flags, "search_many_reads", &rt)) return rc;
+  return search_many_source(s, patterns, pattern_lens, n_patterns, rt.src, k, flags | SASSY_HIP_TEXT_ON_DEVICE, out);
+}
+
+}  // extern "C"
+
+// sassy_hip_search_many behind its null checks; src: host texts, the caller's device texts, or a resident read batch
+int sassy_hip::search_many_source(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                                  TextSource& src, size_t k, uint32_t flags, sassy_hip_Result** out) {
+  const uint8_t* const* texts = src.texts;
+  const size_t* text_lens = src.lens;
+  const size_t n_texts = src.n;
   SASSY_NO_LINE_SPANS(flags);
   SASSY_NO_TICKETS(s);
   DeviceGuard on_device(s);
@@ -285,15 +306,12 @@ int sassy_hip_search_many(sassy_SearcherType* s, const uint8_t* const* patterns,
     uint64_t sum = 0;
     for (size_t ti = 0; ti < n_texts; ++ti) sum += text_lens[ti];
     if (n_texts >= 2 && many_tiled_wanted(s, pattern_lens, n_patterns, sum, k))
-      if (int rc = search_many_batched(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, R.get(),
-                                       handled, true)) return rc;
+      if (int rc = search_many_batched(s, patterns, pattern_lens, n_patterns, src, k, flags, R.get(), handled, true)) return rc;
   }
   if (!handled)
-    if (int rc = search_many_pertext(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, R.get(), handled))
-      return rc;
+    if (int rc = search_many_pertext(s, patterns, pattern_lens, n_patterns, src, k, flags, R.get(), handled)) return rc;
   if (!handled)
-    if (int rc = search_many_batched(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, R.get(), handled))
-      return rc;
+    if (int rc = search_many_batched(s, patterns, pattern_lens, n_patterns, src, k, flags, R.get(), handled)) return rc;
   // Device-resident texts, forward strand: every (pattern, text) pair is one scan job; several are in flight
   // on the searcher's lanes (ScanQueue), so the latency-bound tail of one pair runs next to the filter of the
   // next instead of the host waiting for each pair in turn (reference: search_many spreads the pairs over
@@ -359,6 +377,8 @@ int sassy_hip_search_many(sassy_SearcherType* s, const uint8_t* const* patterns,
   *out = R.release();
   return 0;
 }
+
+extern "C" {
 
 const char* sassy_hip_tsv_header(void) {
   return "pat_id\ttext_id\tcost\tstrand\tstart\tend\tmatch_region\tcigar\n";  // bin/grep.rs:465-470

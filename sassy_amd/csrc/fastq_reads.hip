@@ -21,22 +21,7 @@
 #include "fastq_step.h"
 #include "hamming_step.h"
 
-struct sassy_hip_Reads {
-  std::unique_ptr<sassy_hip_ReadRecord[]> records;  // n_records of them, not cleared before the device's copy lands: a
-  uint64_t n_records = 0;                           // table of millions of reads is touched once
-  uint8_t* d_text = nullptr;
-  uint64_t text_bytes = 0;      // the layout and the 64 spare bytes behind it
-  uint64_t* d_table = nullptr;  // starts[n], then lens[n]: the order d_ham_texts has
-  uint32_t* d_rem = nullptr;    // per block of the layout
-  uint64_t longest = 0;
-  int device = -1;
-  void release() {
-    if (d_text) (void)hipFree(d_text);
-    if (d_table) (void)hipFree(d_table);
-    if (d_rem) (void)hipFree(d_rem);
-    d_text = nullptr; d_table = nullptr; d_rem = nullptr;
-  }
-};
+// (struct sassy_hip_Reads: host_internal.h -- reads_relayout.hip reads it too)
 
 namespace sassy_hip {
 

@@ -562,6 +562,24 @@ struct GeoTuner {
   }
 };
 
+// A read batch resident on the device (fastq_reads.hip makes it; reads_relayout.hip lays it out anew for search_many).
+struct sassy_hip_Reads {
+  std::unique_ptr<sassy_hip_ReadRecord[]> records;  // n_records of them, not cleared before the device's copy lands: a
+  uint64_t n_records = 0;                           // table of millions of reads is touched once
+  uint8_t* d_text = nullptr;
+  uint64_t text_bytes = 0;      // the layout and the 64 spare bytes behind it
+  uint64_t* d_table = nullptr;  // starts[n], then lens[n]: the order d_ham_texts has
+  uint32_t* d_rem = nullptr;    // per block of the layout
+  uint64_t longest = 0;
+  int device = -1;
+  void release() {
+    if (d_text) (void)hipFree(d_text);
+    if (d_table) (void)hipFree(d_table);
+    if (d_rem) (void)hipFree(d_rem);
+    d_text = nullptr; d_table = nullptr; d_rem = nullptr;
+  }
+};
+
 struct sassy_SearcherType {
   // every path-forcing / tuning switch (switches.h): defaults + the environment, read ONCE, here, when the searcher is
   // made; sassy_hip_set_option changes an entry afterwards.  apply_switches() copies the entries that have setters of
@@ -1311,15 +1329,43 @@ int line_spans_on_device(sassy_SearcherType* S, const uint8_t* d_text, uint64_t 
 struct TiledPerText;  // (many_patterns.hip)
 // c_abi.hip
 bool parse_alphabet(const char* alphabet, Profile& pr);
+// Where the texts of a search_many call come from: the caller's pointers -- host memory, or device memory under
+// SASSY_HIP_TEXT_ON_DEVICE --, or a read batch resident on the device (`reads`; then texts[r] = its d_text + seq_start[r],
+// device pointers for the general path, lens[r] = seq_len[r] from its record table, and the flag is set).  The one-pass
+// paths lay a batch of host texts out on the host and upload it (layout_and_upload); a resident batch is laid out by
+// reads_relayout.hip's kernel into the same buffer, byte for byte the same.
+struct TextSource {
+  const uint8_t* const* texts = nullptr;
+  const size_t* lens = nullptr;
+  size_t n = 0;
+  const sassy_hip_Reads* reads = nullptr;
+  int plain = -1;  // reads: does every sequence hold A, C, G, T only?  (-1: not looked at yet -- reads_plain)
+};
+// reads_relayout.hip
+// Reads first .. first + count of the handle to d_dst + d_dst_start[i] (a device table), every other byte of [0, total) = pad.
+int reads_relayout(const sassy_hip_Reads* reads, uint64_t first, uint64_t count, const uint64_t* d_dst_start, uint64_t total, uint8_t pad,
+                   uint8_t* d_dst, hipStream_t stream);
+// acgt_only over every sequence of the handle, on the device, once per source
+int reads_plain(sassy_SearcherType* s, TextSource& src, bool* plain);
+// The handle as a text source: what every *_reads sibling of the search_many family refuses (reads == NULL, the flag
+// SASSY_HIP_TEXT_ON_DEVICE, open tickets, another device than the searcher's), then the pointers and lengths.
+struct ReadsTexts {
+  std::vector<const uint8_t*> ptr;
+  std::vector<size_t> len;
+  TextSource src;
+};
+int reads_as_source(sassy_SearcherType* s, const sassy_hip_Reads* reads, uint32_t flags, const char* who, ReadsTexts* out);
+// c_abi.hip: sassy_hip_search_many behind its null checks
+int search_many_source(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, TextSource& src,
+                       size_t k, uint32_t flags, sassy_hip_Result** out);
 // many_patterns.hip
 int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens,
-                               size_t n_patterns, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts,
-                               size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled, bool tiled_only = false);
+                               size_t n_patterns, TextSource& src, size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled,
+                               bool tiled_only = false);
 double seeded_hit_rate(size_t m, size_t k);
 double seeded_estimate(size_t m, size_t k, size_t n_patterns, uint64_t text_len);
 int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens,
-                               size_t n_patterns, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts,
-                               size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled);
+                               size_t n_patterns, TextSource& src, size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled);
 int search_encoded_tiled(sassy_SearcherType* s, const sassy_hip_Encoded* e, const uint8_t* tptr,
                                 const uint8_t* h_text, uint64_t text_len, uint32_t k, bool all, bool wo,
                                 sassy_hip_Result* R, bool* done, const TextTable* tt = nullptr,

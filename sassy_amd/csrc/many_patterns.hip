@@ -1,6 +1,7 @@
 // many_patterns.hip -- search_encoded_patterns / search_many: every pattern against the text(s) in one pass (pattern-tiled
 // scan, seeded search, per-text tiled scan for overhang), the list -> report rule -> traceback -> records tail, and the
-// batch layouts of many host texts.  Reference: src/pattern_tiling/*, src/search.rs:404-423, 548-683.
+// batch layouts of many host texts -- or of a read batch resident on the device (TextSource; reads_relayout.hip lays it out).
+// Reference: src/pattern_tiling/*, src/search.rs:404-423, 548-683.
 #include "host_internal.h"
 
 namespace sassy_hip {
@@ -1061,6 +1062,9 @@ double seeded_estimate(size_t m, size_t k, size_t n_patterns, uint64_t text_len)
   return 3e-4 + (double)text_len / 3e11 + hits * (m <= 32 ? 8e-12 : 16e-12);
 }
 
+// A laid-out batch of search_many is at most this many bytes (switch many_batch; a longer text is a batch of its own).
+static uint64_t many_batch_bytes(const sassy_SearcherType* s) { return s->sw.many_batch > 0 ? (uint64_t)s->sw.many_batch : (1ull << 30); }
+
 bool many_tiled_wanted(const sassy_SearcherType* s, const size_t* pattern_lens, size_t n_patterns, uint64_t total, size_t k) {
   if (n_patterns == 0 || pattern_lens[0] > 64 || 2 * k + 3 > 64 || n_patterns >= (1u << 24)) return false;
   for (size_t pi = 1; pi < n_patterns; ++pi)
@@ -1240,10 +1244,14 @@ static int finish_best_matches(sassy_SearcherType* s, const uint8_t* const* patt
 }
 
 int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens,
-                               size_t n_patterns, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts,
-                               size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled, bool tiled_only) {
+                               size_t n_patterns, TextSource& src, size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled,
+                               bool tiled_only) {
   handled = false;
-  if (n_texts < 2 || n_patterns == 0 || (flags & SASSY_HIP_TEXT_ON_DEVICE) || is_ascii(s->profile)) return 0;
+  const uint8_t* const* texts = src.texts;
+  const size_t* text_lens = src.lens;
+  const size_t n_texts = src.n;
+  // (device pointers of the caller's: not here; a resident read batch is laid out on the device -- reads_relayout)
+  if (n_texts < 2 || n_patterns == 0 || ((flags & SASSY_HIP_TEXT_ON_DEVICE) && !src.reads) || is_ascii(s->profile)) return 0;
   if (!std::isnan(s->alpha)) return 0;  // overhang gives every text its own special edges: pair by pair
   if (n_texts >= (1u << (32 - kCandTextShift))) return 0;
   size_t max_m = 0;
@@ -1252,7 +1260,13 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
     max_m = std::max(max_m, pattern_lens[pi]);
     if (s->profile == PROFILE_DNA && !acgt_only(patterns[pi], pattern_lens[pi])) return 0;
   }
-  for (size_t ti = 0; ti < n_texts; ++ti) {
+  if (src.reads) {  // (the same decision, made where the sequences are)
+    bool plain = true;
+    if (s->profile == PROFILE_DNA)
+      if (int rc = reads_plain(s, src, &plain)) return rc;
+    if (!plain) return 0;
+  }
+  for (size_t ti = 0; !src.reads && ti < n_texts; ++ti) {
     if (!texts[ti] && text_lens[ti]) return fail(SASSY_HIP_EINVAL, "null text");
     if (s->profile == PROFILE_DNA && !acgt_only(texts[ti], text_lens[ti])) return 0;
   }
@@ -1267,8 +1281,8 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
   const bool all = (flags & SASSY_HIP_ALL_MINIMA) != 0;
   const bool wo = (flags & SASSY_HIP_WITHOUT_TRACE) != 0;
   const uint64_t pad = ((uint64_t)max_m + k + 1 + 15) / 16 * 16;
-  const uint64_t batch_cap = 1ull << 30;  // bytes of device buffer per batch
-  uint8_t* hbuf = nullptr;  // the batch in pinned host memory (s->h_stage)
+  const uint64_t batch_cap = many_batch_bytes(s);  // bytes of device buffer per batch
+  uint8_t* hbuf = nullptr;  // the batch in pinned host memory (s->h_stage); a resident read batch has no host copy
   HostTexts ht, ht_rev;
   size_t t0 = 0;
   while (t0 < n_texts) {
@@ -1285,16 +1299,21 @@ int search_many_batched(sassy_SearcherType* s, const uint8_t* const* patterns, c
     }
     const size_t nt = t1 - t0;
     if (total > 0) {
-      if (int rc = s->reserve_stage(total + 64)) return rc;
-      hbuf = s->h_stage;
-      if (ht.start[0] > 0) memset(hbuf, 'X', ht.start[0]);
+      if (!src.reads) {
+        if (int rc = s->reserve_stage(total + 64)) return rc;
+        hbuf = s->h_stage;
+        if (ht.start[0] > 0) memset(hbuf, 'X', ht.start[0]);
+      }
       if (int rc = s->d_text.reserve(total + 64)) return rc;
       if (int rc = s->d_tables.reserve(4 * nt)) return rc;
-      if (int rc = layout_and_upload(hbuf, s->d_text.p, texts + t0, text_lens + t0, ht.start.data(), nt, total, (uint8_t)'X',
-                                     s->stream)) return rc;
+      if (!src.reads)
+        if (int rc = layout_and_upload(hbuf, s->d_text.p, texts + t0, text_lens + t0, ht.start.data(), nt, total, (uint8_t)'X',
+                                       s->stream)) return rc;
       uint64_t* d_tab = s->d_tables.p;
       HIP_TRY(hipMemcpyAsync(d_tab, ht.start.data(), nt * 8, hipMemcpyHostToDevice, s->stream));
       HIP_TRY(hipMemcpyAsync(d_tab + nt, ht.len.data(), nt * 8, hipMemcpyHostToDevice, s->stream));
+      if (src.reads)  // (the kernel finds its reads in the start table just uploaded)
+        if (int rc = reads_relayout(src.reads, t0, nt, d_tab, total, (uint8_t)'X', s->d_text.p, s->stream)) return rc;
       TextTable tt{d_tab, d_tab + nt, (uint32_t)nt, all ? 1u : 0u}, tt_rev{};
       if (s->rc) {
         // the reversed buffer holds the texts in reverse order, each one reversed
@@ -1521,10 +1540,12 @@ int search_encoded_overhang(sassy_SearcherType* s, const sassy_hip_Encoded* e, c
 }
 
 int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens,
-                               size_t n_patterns, const uint8_t* const* texts, const size_t* text_lens, size_t n_texts,
-                               size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled) {
+                               size_t n_patterns, TextSource& src, size_t k, uint32_t flags, sassy_hip_Result* R, bool& handled) {
   handled = false;
-  if (n_texts < 2 || n_patterns == 0 || (flags & SASSY_HIP_TEXT_ON_DEVICE)) return 0;
+  const uint8_t* const* texts = src.texts;
+  const size_t* text_lens = src.lens;
+  const size_t n_texts = src.n;
+  if (n_texts < 2 || n_patterns == 0 || ((flags & SASSY_HIP_TEXT_ON_DEVICE) && !src.reads)) return 0;
   if (n_texts >= (1u << (32 - kCandTextShift))) return 0;
   const bool overhang = !std::isnan(s->alpha);
   size_t max_m = 0;
@@ -1575,8 +1596,8 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
     const bool env_off = s->sw.overhang_seeded == 0;
     seed_ov = !env_off;
   }
-  const uint64_t batch_cap = 1ull << 30;
-  uint8_t* hbuf = nullptr;  // the batch in pinned host memory (s->h_stage)
+  const uint64_t batch_cap = many_batch_bytes(s);
+  uint8_t* hbuf = nullptr;  // the batch in pinned host memory (s->h_stage); a resident read batch has no host copy
   HostTexts ht;
   std::vector<uint32_t> blk2text;
   std::vector<ChunkDesc> desc;
@@ -1597,13 +1618,16 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
     }
     const size_t nt = t1 - t0;
     if (total > 0) {
-      if (int rc = s->reserve_stage(total + 64)) return rc;
-      hbuf = s->h_stage;
+      if (!src.reads) {
+        if (int rc = s->reserve_stage(total + 64)) return rc;
+        hbuf = s->h_stage;
+      }
       uint8_t pad_b = seed_ov ? (uint8_t)'X' : pad;
       // (the upload rides along: the copy of a 32 MB segment runs while the next one is laid out, and the tables below
-      // are built while the last copies are in flight)
+      // are built while the last copies are in flight; a resident read batch is laid out by a kernel once its starts are up)
       if (int rc = s->d_text.reserve(total + 64)) return rc;
-      if (int rc = layout_and_upload(hbuf, s->d_text.p, texts + t0, text_lens + t0, ht.start.data(), nt, total, pad_b, s->stream)) return rc;
+      if (!src.reads)
+        if (int rc = layout_and_upload(hbuf, s->d_text.p, texts + t0, text_lens + t0, ht.start.data(), nt, total, pad_b, s->stream)) return rc;
       blk2text.assign(total / 64, 0u);
       for (size_t i = 0; i < nt; ++i) {
         const uint64_t b0 = ht.start[i] / 64, b1 = (i + 1 < nt ? ht.start[i + 1] : total) / 64;
@@ -1637,6 +1661,8 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
       HIP_TRY(hipMemcpyAsync(d_tab, ht.start.data(), nt * 8, hipMemcpyHostToDevice, s->stream));
       HIP_TRY(hipMemcpyAsync(d_tab + nt, ht.len.data(), nt * 8, hipMemcpyHostToDevice, s->stream));
       HIP_TRY(hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice, s->stream));
+      if (src.reads)
+        if (int rc = reads_relayout(src.reads, t0, nt, d_tab, total, pad_b, s->d_text.p, s->stream)) return rc;
       TextTable tt{d_tab, d_tab + nt, (uint32_t)nt, all ? 1u : 0u, 1u};
       if (s->rc) {
         HIP_TRY(hipMemcpyAsync(d_b2t, blk2text.data(), blk2text.size() * 4, hipMemcpyHostToDevice, s->stream));
@@ -1714,8 +1740,12 @@ int search_many_pertext(sassy_SearcherType* s, const uint8_t* const* patterns, c
         R->pool.resize(pool_first);
         if (pad_b != pad) {  // ... whose DP reads the virtual columns from the buffer: pad it with 'N' after all
           pad_b = pad;
-          layout_texts(hbuf, texts + t0, text_lens + t0, ht.start.data(), nt, total, pad_b);
-          HIP_TRY(hipMemcpyAsync(s->d_text.p, hbuf, total, hipMemcpyHostToDevice, s->stream));
+          if (src.reads) {
+            if (int rc = reads_relayout(src.reads, t0, nt, d_tab, total, pad_b, s->d_text.p, s->stream)) return rc;
+          } else {
+            layout_texts(hbuf, texts + t0, text_lens + t0, ht.start.data(), nt, total, pad_b);
+            HIP_TRY(hipMemcpyAsync(s->d_text.p, hbuf, total, hipMemcpyHostToDevice, s->stream));
+          }
           if (s->rc) {
             hipError_t le = launch_reverse_texts(s->d_text.p, s->d_rev.p, total, d_b2t, d_tab, d_tab + nt, pad_b, s->stream);
             if (le != hipSuccess) return hip_fail(le, "reverse kernel launch");

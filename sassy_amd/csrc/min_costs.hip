@@ -135,10 +135,10 @@ namespace {
 
 // out_pattern == nullptr: the pair matrix (sassy_hip_min_costs); else one row per text (sassy_hip_best_pattern; the caller
 // passes buffers of its own for the outputs its caller left out).
-int best_costs(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
-               const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags, bool per_text,
-               uint8_t* out_cost, uint32_t* out_pattern, uint8_t* out_strand) {
-  if (!s || !out_cost || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!texts || !text_lens)))
+int best_costs(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, TextSource& src,
+               size_t k, uint32_t flags, bool per_text, uint8_t* out_cost, uint32_t* out_pattern, uint8_t* out_strand) {
+  const size_t n_texts = src.n;
+  if (!s || !out_cost || (n_patterns && (!patterns || !pattern_lens)) || (n_texts && (!src.texts || !src.lens)))
     return fail(SASSY_HIP_EINVAL, "null argument");
   SASSY_NO_LINE_SPANS(flags);
   if (flags & ~SASSY_HIP_TEXT_ON_DEVICE) return fail(SASSY_HIP_EINVAL, "best-cost search takes SASSY_HIP_TEXT_ON_DEVICE only");
@@ -146,8 +146,9 @@ int best_costs(sassy_SearcherType* s, const uint8_t* const* patterns, const size
   SASSY_NO_TICKETS(s);
   const double t0 = now_ms();
   const size_t n_out = per_text ? n_texts : n_patterns * n_texts;
-  // ---- the device path: a batch of host texts, patterns of one length (what the one-pass paths of search_many take) ----
-  bool device = s->sw.min_cost_device != 0 && n_texts >= 2 && n_patterns > 0 && !(flags & SASSY_HIP_TEXT_ON_DEVICE) &&
+  // ---- the device path: a batch of host texts or a resident read batch, patterns of one length (what the one-pass paths of
+  // search_many take) ----
+  bool device = s->sw.min_cost_device != 0 && n_texts >= 2 && n_patterns > 0 && (!(flags & SASSY_HIP_TEXT_ON_DEVICE) || src.reads) &&
                 !is_ascii(s->profile) && pattern_lens[0] <= 64 && 2 * k + 3 <= 64 &&
                 (per_text ? n_patterns < (1u << 24) : (uint64_t)n_patterns * n_texts <= 0xFFFFFF00ull);
   for (size_t pi = 1; device && pi < n_patterns; ++pi) device = pattern_lens[pi] == pattern_lens[0];
@@ -170,7 +171,7 @@ int best_costs(sassy_SearcherType* s, const uint8_t* const* patterns, const size
   // (the traced span decides the N filter: only without it can the traceback be left out)
   const uint32_t many_flags = flags | (std::isnan(s->max_n_frac) ? SASSY_HIP_WITHOUT_TRACE : 0u);
   sassy_hip_Result* R = nullptr;
-  const int rc_many = sassy_hip_search_many(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, many_flags, &R);
+  const int rc_many = search_many_source(s, patterns, pattern_lens, n_patterns, src, k, many_flags, &R);
   s->min_sink = nullptr;
   if (rc_many) return rc_many;
   std::unique_ptr<sassy_hip_Result> owned(R);
@@ -256,7 +257,20 @@ int sassy_hip_min_costs(sassy_SearcherType* s, const uint8_t* const* patterns, c
                         const uint8_t* const* texts, const size_t* text_lens, size_t n_texts, size_t k, uint32_t flags,
                         uint8_t* out_cost, uint8_t* out_strand) {
   try {
-    return best_costs(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, false, out_cost, nullptr, out_strand);
+    TextSource src{texts, text_lens, n_texts};
+    return best_costs(s, patterns, pattern_lens, n_patterns, src, k, flags, false, out_cost, nullptr, out_strand);
+  } catch (const std::bad_alloc&) {
+    if (s) s->min_sink = nullptr;
+    return fail(SASSY_HIP_ENOMEM, "best-cost search: out of host memory");
+  }
+}
+
+int sassy_hip_min_costs_reads(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                              const sassy_hip_Reads* reads, size_t k, uint32_t flags, uint8_t* out_cost, uint8_t* out_strand) {
+  try {
+    ReadsTexts rt;
+    if (int rc = reads_as_source(s, reads, flags, "min_costs_reads", &rt)) return rc;
+    return best_costs(s, patterns, pattern_lens, n_patterns, rt.src, k, flags | SASSY_HIP_TEXT_ON_DEVICE, false, out_cost, nullptr, out_strand);
   } catch (const std::bad_alloc&) {
     if (s) s->min_sink = nullptr;
     return fail(SASSY_HIP_ENOMEM, "best-cost search: out of host memory");
@@ -272,7 +286,26 @@ int sassy_hip_best_pattern(sassy_SearcherType* s, const uint8_t* const* patterns
     std::vector<uint8_t> strand_tmp;
     if (!out_pattern) { pat_tmp.resize(n_texts + 1); out_pattern = pat_tmp.data(); }
     if (!out_strand) { strand_tmp.resize(n_texts + 1); out_strand = strand_tmp.data(); }
-    return best_costs(s, patterns, pattern_lens, n_patterns, texts, text_lens, n_texts, k, flags, true, out_cost, out_pattern, out_strand);
+    TextSource src{texts, text_lens, n_texts};
+    return best_costs(s, patterns, pattern_lens, n_patterns, src, k, flags, true, out_cost, out_pattern, out_strand);
+  } catch (const std::bad_alloc&) {
+    if (s) s->min_sink = nullptr;
+    return fail(SASSY_HIP_ENOMEM, "best-cost search: out of host memory");
+  }
+}
+
+int sassy_hip_best_pattern_reads(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns,
+                                 const sassy_hip_Reads* reads, size_t k, uint32_t flags, uint8_t* out_cost, uint32_t* out_pattern,
+                                 uint8_t* out_strand) {
+  try {
+    ReadsTexts rt;
+    if (int rc = reads_as_source(s, reads, flags, "best_pattern_reads", &rt)) return rc;
+    const size_t n_texts = rt.src.n;
+    std::vector<uint32_t> pat_tmp;
+    std::vector<uint8_t> strand_tmp;
+    if (!out_pattern) { pat_tmp.resize(n_texts + 1); out_pattern = pat_tmp.data(); }
+    if (!out_strand) { strand_tmp.resize(n_texts + 1); out_strand = strand_tmp.data(); }
+    return best_costs(s, patterns, pattern_lens, n_patterns, rt.src, k, flags | SASSY_HIP_TEXT_ON_DEVICE, true, out_cost, out_pattern, out_strand);
   } catch (const std::bad_alloc&) {
     if (s) s->min_sink = nullptr;
     return fail(SASSY_HIP_ENOMEM, "best-cost search: out of host memory");

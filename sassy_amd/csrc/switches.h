@@ -48,6 +48,7 @@ namespace sassy_hip {
   X(many_tiled, -1, "search_many: 1 force / 0 forbid the one-pass paths (-1: by size)")                                     \
   X(many_seeded, -1, "search_many: 1 force / 0 forbid the seeded search inside the one-pass path")                          \
   X(many_assemble, 1, "0: search_many's records ordered by the host")                                                       \
+  X(many_batch, 0, "> 0: a laid-out batch of search_many is at most this many bytes (a longer text is a batch of its own) (0: 1 GiB)") \
   X(overhang_tiled, 1, "0: overhang with many patterns as one launch per pattern and strand")                               \
   X(overhang_seeded, 1, "0: overhang with many patterns through the per-text tiled scan over everything")                   \
   X(multi_min_text, 16 << 20, "search_encoded: smallest text (bytes) for the multi-pattern prefilter")                       \

@@ -14,6 +14,15 @@ whole call from Python over a TextBatch, warmed, --reps repetitions, median and 
 --best-matches: Searcher.best_matches (default shape: 330 000 reads) next to the two ways to the same answer without it --
 search_many followed by the host's reduction of its records, and search_many on an only_best_match searcher followed by
 the same reduction -- and to best_pattern, the lower bound; --out defaults to profiles/best_matches_bench.json.
+
+--device-parse: the same reads as FASTQ bytes in host memory, and per call (search_many as a numpy result, best_pattern,
+best_matches), alternating inside one repetition loop after a warm-up that compares the results:
+  (a) the call on the host texts (a TextBatch), against (b) the same call on the resident batch (sassy_amd.DeviceReads);
+  (c) raw bytes -> results by the host reader (fastx's line table over the bytes) plus the call on its host texts, against
+  (d) DeviceReads(raw) plus the call on it and the handle's release;
+and the relayout alone: sassy_hip_reads_relayout of the whole batch into the separator layout between two device events (the
+call uploads its start table and waits, so this bounds the kernel from above), bytes written per second.  Every timed leg ends
+with a device synchronise.  One JSON line; --out defaults to profiles/reads_edit_resident.json.
 """
 import argparse
 import json
@@ -159,6 +168,114 @@ def bench_best_matches(args, pats, texts, total):
             fh.write("\n")
 
 
+def bench_device_parse(args, pats, texts, total):
+    import ctypes as C
+    from sassy_amd import fastx
+    hip = C.CDLL("libamdhip64.so")
+    n, L = len(texts), args.read_len
+    head = 2 + 9 + 1
+    row = head + L + 3 + L + 1
+    grid = np.empty((n, row), dtype=np.uint8)
+    grid[:, :2] = np.frombuffer(b"@r", dtype=np.uint8)
+    digits = np.arange(n, dtype=np.int64)
+    for d in range(9):
+        grid[:, 2 + 8 - d] = ord("0") + digits % 10
+        digits //= 10
+    grid[:, head - 1] = 10
+    grid[:, head:head + L] = np.frombuffer(b"".join(texts), dtype=np.uint8).reshape(n, L)
+    grid[:, head + L:head + L + 3] = np.frombuffer(b"\n+\n", dtype=np.uint8)
+    grid[:, head + L + 3:row - 1] = ord("I")
+    grid[:, row - 1] = 10
+    raw = grid.reshape(-1)
+    mk = lambda: sassy_amd.Searcher(args.profile, rc=not args.fwd, alpha=args.overhang)
+    s_host, s_dev = mk(), mk()
+    sync = lambda: hip.hipDeviceSynchronize()
+    calls = {"search_many": lambda s, t: s.search_many(pats, t, args.k, as_result=True).array,
+             "best_pattern": lambda s, t: s.best_pattern(pats, t, args.k),
+             "best_matches": lambda s, t: s.best_matches(pats, t, args.k, as_result=True).array}
+    host_batch = fastx._parse_single_line_records(raw, 4).texts
+    reads = sassy_amd.DeviceReads(raw)
+    assert len(reads) == n and len(host_batch) == n
+
+    def timed(f):
+        sync()
+        t0 = time.perf_counter()
+        r = f()
+        sync()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def leg_c(call):
+        return call(s_host, fastx._parse_single_line_records(raw, 4).texts)
+
+    def leg_d(call):
+        r = sassy_amd.DeviceReads(raw)
+        out = call(s_dev, r)
+        r.free()
+        return out
+
+    def same(x, y):
+        if isinstance(x, tuple):
+            return all(np.array_equal(a, b) for a, b in zip(x, y))
+        return len(x) == len(y) and all(np.array_equal(x[f], y[f]) for f in ("pattern_idx", "text_idx", "text_start", "text_end", "cost", "strand", "cigar_len"))
+
+    summary = lambda v: {"median_ms": round(float(np.median(v)), 3), "min_ms": round(float(np.min(v)), 3), "max_ms": round(float(np.max(v)), 3),
+                         "spread": round(float((np.max(v) - np.min(v)) / np.median(v)), 4), "reps": len(v)}
+    res = {}
+    for name, call in calls.items():
+        for _ in range(2):  # warm-up: kernels loaded, buffers grown; and the check
+            a, b, c, d = call(s_host, host_batch), call(s_dev, reads), leg_c(call), leg_d(call)
+        assert same(a, b) and same(a, c) and same(a, d), name
+        st_host, st_dev = None, None
+        ms = {"a_host_texts": [], "b_resident": [], "c_raw_host_reader": [], "d_raw_device_parse": []}
+        for _ in range(args.reps):
+            ms["a_host_texts"].append(timed(lambda: call(s_host, host_batch))[0])
+            st_host = s_host.stats()
+            ms["b_resident"].append(timed(lambda: call(s_dev, reads))[0])
+            st_dev = s_dev.stats()
+            ms["c_raw_host_reader"].append(timed(lambda: leg_c(call))[0])
+            ms["d_raw_device_parse"].append(timed(lambda: leg_d(call))[0])
+        res[name] = {k: summary(v) for k, v in ms.items()}
+        res[name]["c_abi_total_ms_last_rep"] = {"a": round(st_host["total_ms"], 3), "b": round(st_dev["total_ms"], 3)}
+        res[name]["path"] = {"filtered": [st_host["filtered"], st_dev["filtered"]], "scan_launches": [st_host["scan_launches"], st_dev["scan_launches"]]}
+        print(name, json.dumps(res[name]), flush=True)
+    # the relayout alone: the whole batch into the separator layout search_many_batched scans
+    gap = (args.pattern_len + args.k + 1 + 15) // 16 * 16
+    starts = np.arange(n, dtype=np.uint64) * np.uint64(L + gap)
+    out_total = n * (L + gap) - gap
+    buf = sassy_amd.DeviceBuffer(out_total + 64)
+    ev = [C.c_void_p(), C.c_void_p()]
+    for e in ev:
+        assert hip.hipEventCreate(C.byref(e)) == 0
+    rl = []
+    for rep in range(args.reps + 2):
+        assert hip.hipEventRecord(ev[0], None) == 0
+        sassy_amd._check(sassy_amd.lib().sassy_hip_reads_relayout(reads._handle(), 0, n, starts.ctypes.data, out_total, ord("X"), buf.ptr, None))
+        assert hip.hipEventRecord(ev[1], None) == 0 and hip.hipEventSynchronize(ev[1]) == 0
+        t = C.c_float()
+        assert hip.hipEventElapsedTime(C.byref(t), ev[0], ev[1]) == 0
+        if rep >= 2:
+            rl.append(float(t.value))
+    buf.free()
+    reads.free()
+    med = float(np.median(rl))
+    doc = {"workload": f"{args.patterns} x {args.pattern_len} bp patterns, {n} reads x {L} bp ({total / 1e6:.0f} MB of sequence, {raw.size / 1e6:.0f} MB of FASTQ), "
+                       f"k={args.k}, {args.profile}, {'forward strand' if args.fwd else 'both strands'}",
+           "what": "wall ms of whole Python calls, a device synchronise at the end of each, legs alternating in one loop, warmed",
+           "calls": res,
+           "relayout_call": dict(summary(rl), bytes_written=int(out_total), bytes_read=int(total),
+                                 written_gb_per_s=round(out_total / 1e9 / (med / 1e3), 1), moved_gb_per_s=round((out_total + total) / 1e9 / (med / 1e3), 1),
+                                 what="device events around sassy_hip_reads_relayout (start table upload, kernel, wait)")}
+    print(json.dumps(doc))
+    if args.out:
+        prev = []
+        if os.path.exists(args.out):
+            with open(args.out) as fh:
+                prev = json.load(fh)
+        with open(args.out, "w") as fh:
+            json.dump(prev + [doc], fh, indent=1)
+            fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=None, help="default 100 000; 330 000 with --best-matches")
@@ -172,6 +289,7 @@ def main():
     ap.add_argument("--min-costs", action="store_true", help="time Searcher.min_costs next to search_many")
     ap.add_argument("--best-pattern", action="store_true", help="time Searcher.best_pattern next to search_many")
     ap.add_argument("--best-matches", action="store_true", help="time Searcher.best_matches next to search_many + host reduction")
+    ap.add_argument("--device-parse", action="store_true", help="the calls on host texts against the same calls on a resident read batch (DeviceReads)")
     ap.add_argument("--only-new", action="store_true", help="with --min-costs / --best-pattern / --best-matches: only these calls' device path (a kernel trace of it alone)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None, help="default profiles/min_costs_bench.json; profiles/best_matches_bench.json with --best-matches")
@@ -179,7 +297,8 @@ def main():
     if args.reads is None:
         args.reads = 330_000 if args.best_matches else 100_000
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "best_matches_bench.json" if args.best_matches else "min_costs_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "reads_edit_resident.json" if args.device_parse else
+                                "best_matches_bench.json" if args.best_matches else "min_costs_bench.json")
     rng = np.random.default_rng(7)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
     pats = [bytes(acgt[rng.integers(0, 4, args.pattern_len)]) for _ in range(args.patterns)]
@@ -191,6 +310,8 @@ def main():
         flat[r, at[r]:at[r] + args.pattern_len] = p
     texts = [flat[r].tobytes() for r in range(args.reads)]
     total = args.reads * args.read_len
+    if args.device_parse:
+        return bench_device_parse(args, pats, texts, total)
     if args.best_matches:
         return bench_best_matches(args, pats, texts, total)
     if args.min_costs or args.best_pattern:
