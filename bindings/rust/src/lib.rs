@@ -152,6 +152,9 @@ extern "C" {
                                   out_size: *mut u32, n_clusters: *mut usize) -> c_int;
     fn sassy_hip_edit_clusters(s: *mut RawSearcher, a: *const u8, n: usize, m: usize, k: usize, flags: u32, out_label: *mut u32,
                                out_size: *mut u32, n_clusters: *mut usize) -> c_int;
+    // ... and UMI groups: duplicates collapsed, then method 0 unique / 1 cluster / 2 directional over the distinct sequences
+    fn sassy_hip_umi_groups(s: *mut RawSearcher, a: *const u8, n: usize, m: usize, k: usize, method: u32, flags: u32, out_label: *mut u32,
+                            out_size: *mut u32, out_rep: *mut u32, out_count: *mut u32, n_unique: *mut usize, n_groups: *mut usize) -> c_int;
     // FASTA unwrap on the device: raw bytes in, a device text per record and a host table out (flags: TEXT_ON_DEVICE)
     pub fn sassy_hip_fasta_unwrap(raw: *const u8, n: u64, flags: u32, hip_stream: *mut std::ffi::c_void, out: *mut *mut RawFasta) -> c_int;
     pub fn sassy_hip_fasta_n_records(f: *const RawFasta) -> u64;
@@ -588,6 +591,24 @@ impl<P: Profile> Searcher<P> {
         let rc = unsafe { sassy_hip_edit_clusters(self.raw, a.as_ptr(), n, m, k, 0, labels.as_mut_ptr(), sizes.as_mut_ptr(), &mut count) };
         assert_eq!(rc, 0, "{}", last_error());
         (labels, sizes, count)
+    }
+
+    /// UMI grouping of the sequences of `a` (`m` bytes each, `m <= 128`): identical reads collapsed, the distinct sequences
+    /// grouped by `method` -- 0 unique (collapse only), 1 cluster (connected components within `k` mismatches), 2 directional
+    /// (a neighbour of count `c_u >= 2 c_v - 1` absorbs `v`; UMI-tools' rule with the tie order fixed).
+    /// `(labels, sizes, reps, counts, n_unique, n_groups)`: `reps[i]` is the first duplicate of `i`, `counts[i]` the number
+    /// of its duplicates, `labels[i]` the first index of its group's opener, `sizes[i]` the reads of that group.  `k <= 254`.
+    pub fn umi_groups(&mut self, a: &[u8], m: usize, k: usize, method: u32) -> (Vec<u32>, Vec<u32>, Vec<u32>, Vec<u32>, usize, usize) {
+        assert!(m > 0 && a.len() % m == 0, "the list holds whole sequences of m bytes");
+        let n = a.len() / m;
+        let (mut labels, mut sizes, mut reps, mut counts) = (vec![0u32; n], vec![0u32; n], vec![0u32; n], vec![0u32; n]);
+        let (mut n_unique, mut n_groups) = (0usize, 0usize);
+        let rc = unsafe {
+            sassy_hip_umi_groups(self.raw, a.as_ptr(), n, m, k, method, 0, labels.as_mut_ptr(), sizes.as_mut_ptr(), reps.as_mut_ptr(),
+                                 counts.as_mut_ptr(), &mut n_unique, &mut n_groups)
+        };
+        assert_eq!(rc, 0, "{}", last_error());
+        (labels, sizes, reps, counts, n_unique, n_groups)
     }
 
     /// Per text the one best match over all patterns and strands as a complete record: lowest cost, then lowest pattern

@@ -98,7 +98,9 @@ typedef struct sassy_hip_Stats {
                             9: the all-vs-all walk of sassy_hip_edit_pairs / _nearest (edit_pairs.hip: no text; also
                                where |m_a - m_b| > k and nothing was launched);
                             10: the link walk of sassy_hip_hamming_clusters (hamming_pairs.hip + clusters.hip: no text);
-                            11: the link walk of sassy_hip_edit_clusters (edit_pairs.hip + clusters.hip: no text) */
+                            11: the link walk of sassy_hip_edit_clusters (edit_pairs.hip + clusters.hip: no text);
+                            12: sassy_hip_umi_groups (umi_groups.hip: the collapse, then hamming_pairs.hip's walk over the
+                                distinct sequences: no text) */
   double filter_ms;      /* HIP-event time of the prefilter kernel (part of scan_ms); a search in flight whose text pass
                             was served by several launches (see pass_patterns): the sum of their durations */
   uint64_t hit_blocks;   /* text blocks in which an exact pattern piece ends */
@@ -567,6 +569,50 @@ int sassy_hip_hamming_clusters(sassy_SearcherType *s, const uint8_t *a, size_t n
                                uint32_t *out_label, uint32_t *out_size, size_t *n_clusters);
 int sassy_hip_edit_clusters(sassy_SearcherType *s, const uint8_t *a, size_t n, size_t m, size_t k, uint32_t flags,
                             uint32_t *out_label, uint32_t *out_size, size_t *n_clusters);
+
+/* UMI grouping (sassy_amd/csrc/umi_groups.hip; DESIGN.md 5.10 "UMI groups"): identical reads counted and collapsed, the
+ * distinct sequences compared with each other only, and an abundant sequence absorbing its rare neighbours -- UMI-tools'
+ * `directional` method with the tie order fixed.  a, n, m as sassy_hip_hamming_clusters takes them (m <= 128); Hamming only.
+ *  - duplicates: two sequences whose bit planes (the pair family's encoding) are equal.  Dna: the planes hold (c >> 1) & 3 per
+ *    row, so upper and lower case fold and so do all bytes that share that code (A / a, C / c, T / t / U / u, G / g -- and N
+ *    with G's code: Dna has no N of its own).  Iupac: the planes hold the letter's set of bases, so case folds and letters
+ *    with one set are one (T / U); N and A MATCH but are no duplicates.  Ascii: the byte itself, nothing folds; ascii_ci: the
+ *    folded byte, A-Z onto a-z only.  out_rep[i] (may be NULL): the smallest j that is a duplicate of i -- out_rep[i] == i
+ *    marks the distinct sequences; out_count[i] (may be NULL): the duplicates of i, itself included; *n_unique (may be NULL):
+ *    the number of i with out_rep[i] == i;
+ *  - groups are formed over the distinct sequences, each named by its first index u and carrying its count c_u.  u and v are
+ *    neighbours where the self-mode pair call on the distinct sequences has a record (u, v, strand), u != v -- H <= k on
+ *    either strand for an rc searcher; (u, u, 1) is no edge.  SASSY_HIP_UMI_UNIQUE: label = rep, k is ignored.
+ *    SASSY_HIP_UMI_CLUSTER: the connected components; out_label and out_size are exactly sassy_hip_hamming_clusters' on the
+ *    full list.  SASSY_HIP_UMI_DIRECTIONAL: an edge u -> v where u and v are neighbours and c_u >= 2 c_v - 1 (two sequences of
+ *    count 1 point at each other); the distinct sequences ordered by (count descending, first index ascending) and gone
+ *    through in that order, one that is in no group yet opens a group and takes every sequence reachable from it along edges
+ *    that is in no group yet; the label of v is the opener of its group -- the first in the order among all u from which v
+ *    is reachable, v included;
+ *  - out_label[i] (n entries, required): the label of out_rep[i], an index into a; out_size[i] (may be NULL): the READS, not
+ *    the distinct sequences, that share that label; *n_groups (may be NULL): the number of i with out_label[i] == i.  The
+ *    arrays are the same on every run, whatever the device's schedule and whatever the table's hash;
+ *  - refused before any device work: what sassy_hip_hamming_clusters refuses, by the same function; an unknown method
+ *    SASSY_HIP_EINVAL.  More than 2^32 - 1 pair records among the distinct sequences (DIRECTIONAL): SASSY_HIP_ENOMEM with
+ *    the count, as the pair call fails, once the survey has counted them.  k >= m is cut to m;
+ *  - the device: an open-addressing table of 32-bit slots keyed by a hash of the plane words (option collapse_slots:
+ *    geometry only), a scan of the flags rep[i] == i for the distinct sequences' numbering, a gather of their planes, the pair
+ *    call's passes over those (CLUSTER: its link pass; DIRECTIONAL: survey, scan, fill -- the records stay on the device),
+ *    DIRECTIONAL: a relaxation of 64-bit labels over the records, launched until nothing falls (at most n_unique + 1
+ *    launches), then one pass per distinct sequence for the groups' sizes and one per read for the columns;
+ *  - sassy_hip_get_stats afterwards: filtered = 12, candidates = the records among the distinct sequences (DIRECTIONAL; else
+ *    0), chunks, grid = strips of that walk, hit_blocks = n_unique, blocks = the relaxation's launches; at timing level 2
+ *    (the events ev_line[0 .. 3] of the searcher) filter_ms = the walk passes over the distinct sequences ([1] -> [2]),
+ *    trace_ms = the relaxation (CLUSTER: the flatten) with the size and expand passes ([2] -> [3]), scan_ms = those and the
+ *    collapse -- table, lookup, scan, gather ([0] -> [1]) --, so the collapse alone is scan_ms - filter_ms - trace_ms. */
+#define SASSY_HIP_UMI_UNIQUE      0u  /* collapse only: a group is a set of identical sequences; k is ignored */
+#define SASSY_HIP_UMI_CLUSTER     1u  /* connected components within k, on the distinct sequences */
+#define SASSY_HIP_UMI_DIRECTIONAL 2u  /* the count-aware rule above */
+int sassy_hip_umi_groups(sassy_SearcherType *s, const uint8_t *a, size_t n, size_t m, size_t k,
+                         uint32_t method, uint32_t flags,
+                         uint32_t *out_label, uint32_t *out_size,   /* n entries; out_size may be NULL */
+                         uint32_t *out_rep, uint32_t *out_count,    /* n entries; either may be NULL */
+                         size_t *n_unique, size_t *n_groups);       /* may be NULL */
 
 /* FASTA unwrap on the device (sassy_amd/csrc/fasta_unwrap.hip): the raw bytes of a chunk of FASTA in, every
  * record's sequence out as a device-resident text that the one-text entry points take with SASSY_HIP_TEXT_ON_DEVICE, plus a

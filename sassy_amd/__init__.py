@@ -37,6 +37,7 @@ TEXT_UNCHANGED = 8
 CLASS_MAX_CUBES = 256  # SASSY_HIP_CLASS_MAX_CUBES: cubes of one class pattern, all distinct sets together
 LINE_SPANS = 16  # sassy_hip_search only: resolve the matches to their lines (Result.line_spans)
 UINT64_MAX = (1 << 64) - 1
+UMI_METHODS = {"unique": 0, "cluster": 1, "directional": 2}  # SASSY_HIP_UMI_*: Searcher.umi_groups
 
 
 class SassyHipError(RuntimeError):
@@ -158,7 +159,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_hamming_amplicons", "sassy_hip_amplicons_free",
     "sassy_hip_hamming_pairs", "sassy_hip_hamming_pairs_free", "sassy_hip_hamming_nearest",
     "sassy_hip_edit_pairs", "sassy_hip_edit_pairs_free", "sassy_hip_edit_nearest",
-    "sassy_hip_hamming_clusters", "sassy_hip_edit_clusters",
+    "sassy_hip_hamming_clusters", "sassy_hip_edit_clusters", "sassy_hip_umi_groups",
     "sassy_hip_fasta_unwrap", "sassy_hip_fasta_n_records", "sassy_hip_fasta_records", "sassy_hip_fasta_text",
     "sassy_hip_fasta_text_bytes", "sassy_hip_fasta_free",
     "sassy_hip_fastq_parse", "sassy_hip_reads_n", "sassy_hip_reads_records", "sassy_hip_reads_text", "sassy_hip_reads_text_bytes",
@@ -327,6 +328,8 @@ def lib():
     L.sassy_hip_hamming_clusters.argtypes = [vp, vp, sz, sz, sz, C.c_uint32, vp, vp, C.POINTER(sz)]
     L.sassy_hip_edit_clusters.restype = C.c_int
     L.sassy_hip_edit_clusters.argtypes = [vp, vp, sz, sz, sz, C.c_uint32, vp, vp, C.POINTER(sz)]
+    L.sassy_hip_umi_groups.restype = C.c_int
+    L.sassy_hip_umi_groups.argtypes = [vp, vp, sz, sz, sz, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(sz)]
     L.sassy_hip_class_cover.restype = C.c_long
     L.sassy_hip_class_cover.argtypes = [u8p, vp, vp, sz, C.POINTER(C.c_int)]
     L.sassy_hip_search_all_alignments.restype = C.c_int
@@ -1251,6 +1254,27 @@ class Searcher:
         """`hamming_clusters` under the edit distance (sassy_hip_edit_clusters): an edge where E <= k, so a sequence that lost
         or gained a base joins its origin at k = 1.  One length m <= 64.  Returns (labels, sizes) as `hamming_clusters`."""
         return self._clusters(lib().sassy_hip_edit_clusters, a, k, "edit_clusters")
+
+    def umi_groups(self, a, k: int = 1, method: str = "directional"):
+        """UMI grouping of a list of reads' UMIs (sassy_hip_umi_groups): identical sequences are counted and collapsed on the
+        device, only the distinct ones are compared, and `method` makes the groups -- "unique": a group is a set of identical
+        sequences (k is ignored); "cluster": the connected components within k mismatches, exactly `hamming_clusters`' labels
+        and sizes; "directional": UMI-tools' rule -- a sequence of count c_u absorbs a neighbour of count c_v where
+        c_u >= 2 c_v - 1, the sequences gone through by (count descending, first index ascending), so two abundant neighbours
+        stay apart.  Returns (labels, sizes, reps, counts), uint32 arrays of len(a) entries: reps[i] the smallest index with
+        i's sequence (reps[i] == i marks the distinct ones; what counts as identical is the pair calls' encoding: case folds
+        under dna, iupac and ascii_ci, and Iupac's N is no duplicate of A), counts[i] how many reads carry it, labels[i] the
+        first index of the sequence that opened i's group, sizes[i] the READS in that group.  The arrays are the same on every
+        run.  One length m <= 128; `a` as for `hamming_pairs`; k <= 254."""
+        import numpy as np
+        if method not in UMI_METHODS:
+            raise SassyHipError(f"umi_groups: method must be one of {', '.join(UMI_METHODS)} (got {method!r})")
+        a, _ = self._pairs_lists(a, None, "umi_groups")
+        n = len(a)
+        labels, sizes, reps, counts = (np.empty(n, dtype=np.uint32) for _ in range(4))
+        _check(lib().sassy_hip_umi_groups(self._h, a.ctypes.data, n, a.shape[1], k, UMI_METHODS[method], 0, labels.ctypes.data,
+                                          sizes.ctypes.data, reps.ctypes.data, counts.ctypes.data, None, None))
+        return labels, sizes, reps, counts
 
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k

@@ -71,13 +71,20 @@ other one), and `ties`, how many are that near; `*`, `*` and -1 where nothing is
 count K mismatches: a barcode that lost or gained a base is then one edit from its origin.  The sequences of B may have a
 length of their own; both lengths are at most 64.  Same rows.
 
-`cluster A -k K [--edit] [--rc] [-a dna|iupac|ascii|ascii_ci]` writes which groups the sequences of A form, through
+`cluster A -k K [--edit] [--rc] [-a dna|iupac|ascii|ascii_ci] [--umi unique|cluster|directional]` writes which groups the sequences of A form, through
 `Searcher.hamming_clusters` (`--edit`: `edit_clusters`): the connected components of the graph that joins two sequences within
 K of each other (`--rc`: or of each other's reverse complement) -- what `pairs A` lists as records, without the records.  A
 loads as `pairs` loads it.  A header row, then one row per sequence in input order; `cluster_id` is the id of the cluster's
 first sequence:
 
     id  cluster_id  cluster_size
+
+`--umi METHOD` groups UMIs through `Searcher.umi_groups` instead (mismatches only): identical sequences are collapsed and
+counted, then `unique` stops there, `cluster` takes the components of the distinct sequences and `directional` lets a
+sequence absorb a neighbour of at most half its reads (count(a) >= 2 count(b) - 1, UMI-tools' rule).  `rep_id` is the id of
+the first sequence identical to the row's, `group_id` the id of the sequence that opened its group, `group_size` in reads:
+
+    id  rep_id  count  group_id  group_size
 
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
@@ -466,7 +473,22 @@ def cluster_rows(seqs, labels, sizes):
     return [f"{seq_id}\t{seqs[int(labels[i])][0]}\t{int(sizes[i])}\n" for i, (seq_id, _) in enumerate(seqs)]
 
 
+def umi_header() -> str:
+    return "id\trep_id\tcount\tgroup_id\tgroup_size\n"
+
+
+def umi_rows(seqs, labels, sizes, reps, counts):
+    """The TSV rows of Searcher.umi_groups' arrays, one per sequence in input order: its id, the id of the first sequence
+    identical to it, how many are, the id of the sequence that opened its group, the reads in that group."""
+    return [f"{seq_id}\t{seqs[int(reps[i])][0]}\t{int(counts[i])}\t{seqs[int(labels[i])][0]}\t{int(sizes[i])}\n" for i, (seq_id, _) in enumerate(seqs)]
+
+
 def run_cluster(args, searcher, seqs, out) -> int:
+    if args.umi:
+        out.write(umi_header())
+        out.writelines(umi_rows(seqs, *searcher.umi_groups([s for _, s in seqs], args.k, args.umi)))
+        out.flush()
+        return 0
     clusters = searcher.edit_clusters if args.edit else searcher.hamming_clusters
     out.write(cluster_header())
     out.writelines(cluster_rows(seqs, *clusters([s for _, s in seqs], args.k)))
@@ -481,6 +503,10 @@ def cluster_parser(sub):
     cp.add_argument("--rc", action="store_true", help="a sequence also joins one whose reverse complement is within k")
     cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac", "ascii", "ascii_ci"], default="dna")
     cp.add_argument("--edit", action="store_true", help="k edits (substitutions, insertions, deletions) instead of k mismatches; sequences of at most 64")
+    cp.add_argument("--umi", choices=["unique", "cluster", "directional"], default=None,
+                    help="UMI grouping: identical sequences collapsed and counted first; unique: no more than that; cluster: the components of the "
+                         "distinct sequences; directional: a sequence absorbs a neighbour of at most (its count + 1) / 2 reads.  Rows: id, rep_id, "
+                         "count, group_id, group_size")
     return cp
 
 
@@ -602,6 +628,8 @@ def main(argv=None) -> int:
             ap.error("cluster takes 0 <= k <= 254")
         if args.rc and args.alphabet.startswith("ascii"):
             ap.error("cluster --rc: there is no reverse complement of plain text")
+        if args.umi and args.edit:
+            ap.error("cluster --umi groups by mismatches only: it does not take --edit")
         seqs = load_count_patterns(args.a)
         if not seqs:
             ap.error(f"cluster: {args.a} holds no sequence")

@@ -24,6 +24,9 @@
 //                         candidate (cluster_step.h) in place of the cell -- no matrix, no pass behind it here
 // The passes between survey and fill know nothing of the distance: the host code around them (pairs_place_rows,
 // pairs_take_records, pairs_fold_nearest; host_internal.h) also serves edit_pairs.hip, which has a walk of its own.
+// Staging is two halves -- pairs_upload (encode, upload) and pairs_stage_resident (plan, arguments, grid) -- so that the walks
+// also run over arrays a kernel made: umi_groups.hip gathers the distinct sequences of a list on the device and calls
+// pairs_resident_link / pairs_resident_records on them, and scans its flags with pairs_scan_u64.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -319,38 +322,50 @@ struct PairsRun {
   uint32_t W = 1;
   dim3 grid;
 };
-// The first half of a call behind its refusals: the plan, both lists encoded and uploaded, the walk's arguments and grid, the
-// stats' geometry.  want_cells: the partials matrix too (the clustering walk has none).
-int pairs_stage(sassy_SearcherType* s, const uint8_t* a, size_t n_a, const uint8_t* b, size_t n_b, uint32_t m, uint32_t k, uint32_t self_mode, bool want_cells,
-                PairsRun& R) {
-  hipStream_t st = s->stream;
-  const bool self = b == nullptr;
-  const uint32_t S = s->rc ? 2u : 1u, W = pairs_words(m), PW = pairs_planes(s->profile) * W;
-  const size_t nb = self ? n_a : n_b;
-  R.W = W;
-  R.plan = pairs_plan(n_a, nb, self ? self_mode : kPairsCross, s->sw.pairs_chunks, self_mode == kPairsSelfPairs ? kPairsFineChunk : 0);
-  std::vector<uint32_t> ha(n_a * PW), ht(nb * S * PW);
-  encode_list(s->profile, a, n_a, m, W, 1, ha.data());
-  encode_list(s->profile, self ? a : b, nb, m, W, S, ht.data());
-  if (int rc = s->d_pairs_a.reserve(ha.size())) return rc;
-  if (int rc = s->d_pairs_t.reserve(ht.size())) return rc;
+// The second half of staging, for planes that lie on the device already (the lists a call uploaded, or arrays a kernel
+// made: umi_groups.hip): the plan, the walk's arguments and grid, the stats' geometry.  d_a: [n_a][P W]; d_t: [S n_b][P W].
+// want_cells: the partials matrix too (the clustering walk has none).
+int pairs_stage_resident(sassy_SearcherType* s, const uint32_t* d_a, size_t n_a, const uint32_t* d_t, size_t n_b, bool self, uint32_t m, uint32_t k,
+                         uint32_t self_mode, bool want_cells, PairsRun& R) {
+  R.W = pairs_words(m);
+  R.plan = pairs_plan(n_a, n_b, self ? self_mode : kPairsCross, s->sw.pairs_chunks, self_mode == kPairsSelfPairs ? kPairsFineChunk : 0);
   if (want_cells)
     if (int rc = s->d_pairs_cells.reserve((size_t)R.plan.n_chunks * n_a)) return rc;
-  HIP_TRY(hipMemcpyAsync(s->d_pairs_a.p, ha.data(), ha.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(s->d_pairs_t.p, ht.data(), ht.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));  // (the host vectors go away)
   PairsArgs& A = R.args;
-  A.a = s->d_pairs_a.p; A.t = s->d_pairs_t.p;
-  A.n_a = n_a; A.n_b = nb; A.chunk = R.plan.chunk;
-  A.S = S; A.m = m; A.k = k; A.mode = R.plan.mode;
+  A.a = d_a; A.t = d_t;
+  A.n_a = n_a; A.n_b = n_b; A.chunk = R.plan.chunk;
+  A.S = s->rc ? 2u : 1u; A.m = m; A.k = k; A.mode = R.plan.mode;
   A.cells = want_cells ? s->d_pairs_cells.p : nullptr;
   R.grid = dim3((uint32_t)R.plan.n_strips, R.plan.n_chunks);
   s->stats.scan_launches = 1;
   s->stats.chunks = R.plan.n_chunks;
   s->stats.grid = (uint32_t)R.plan.n_strips;
   s->stats.blocks_per_chunk = (uint32_t)std::min<uint64_t>(R.plan.chunk, 0xFFFFFFFFull);
-  s->stats.text_bytes = (uint64_t)(n_a + nb) * m;
+  s->stats.text_bytes = (uint64_t)(n_a + n_b) * m;
   return 0;
+}
+// The first half: both lists encoded and uploaded (d_pairs_a: the entries; d_pairs_t: the target records, both strands of
+// an rc searcher's).
+int pairs_upload(sassy_SearcherType* s, const uint8_t* a, size_t n_a, const uint8_t* b, size_t n_b, uint32_t m) {
+  hipStream_t st = s->stream;
+  const bool self = b == nullptr;
+  const uint32_t S = s->rc ? 2u : 1u, W = pairs_words(m), PW = pairs_planes(s->profile) * W;
+  const size_t nb = self ? n_a : n_b;
+  std::vector<uint32_t> ha(n_a * PW), ht(nb * S * PW);
+  encode_list(s->profile, a, n_a, m, W, 1, ha.data());
+  encode_list(s->profile, self ? a : b, nb, m, W, S, ht.data());
+  if (int rc = s->d_pairs_a.reserve(ha.size())) return rc;
+  if (int rc = s->d_pairs_t.reserve(ht.size())) return rc;
+  HIP_TRY(hipMemcpyAsync(s->d_pairs_a.p, ha.data(), ha.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->d_pairs_t.p, ht.data(), ht.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the host vectors go away)
+  return 0;
+}
+// A call behind its refusals, staged: upload, then the plan over what was uploaded.
+int pairs_stage(sassy_SearcherType* s, const uint8_t* a, size_t n_a, const uint8_t* b, size_t n_b, uint32_t m, uint32_t k, uint32_t self_mode, bool want_cells,
+                PairsRun& R) {
+  if (int rc = pairs_upload(s, a, n_a, b, n_b, m)) return rc;
+  return pairs_stage_resident(s, s->d_pairs_a.p, n_a, s->d_pairs_t.p, b ? n_b : n_a, b == nullptr, m, k, self_mode, want_cells, R);
 }
 // The survey: the partials matrix filled.
 int pairs_survey(sassy_SearcherType* s, const uint8_t* a, size_t n_a, const uint8_t* b, size_t n_b, uint32_t m, uint32_t k, uint32_t self_mode, PairsRun& R) {
@@ -360,6 +375,20 @@ int pairs_survey(sassy_SearcherType* s, const uint8_t* a, size_t n_a, const uint
   HIP_TRY(launch_walk_profile(s->profile, kWalkSurvey, R.W, R.args, R.grid, st));
   if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[1], st));
   s->stats.filtered = 8;
+  return 0;
+}
+// Behind a survey: the rows placed, the total checked, the records written into d_pairs_out in the contract's order
+// (*total == 0: none, and no fill pass).
+int pairs_fill_records(sassy_SearcherType* s, PairsRun& R, const char* who, unsigned long long* total) {
+  const unsigned long long* row_first = nullptr;
+  if (int rc = pairs_place_rows(s, R.args.cells, R.args.n_a, R.plan.n_chunks, &row_first, total)) return rc;
+  if (*total > 0xFFFFFFFFull) return fail(SASSY_HIP_ENOMEM, std::string(who) + ": more than 2^32 - 1 records (" + std::to_string(*total) + ")");
+  if (*total == 0) return 0;
+  if (int rc = s->d_pairs_out.reserve((size_t)*total * sizeof(sassy_hip_HammingPair))) return rc;
+  R.args.row_first = row_first;
+  R.args.out = reinterpret_cast<sassy_hip_HammingPair*>(s->d_pairs_out.p);
+  HIP_TRY(launch_walk_profile(s->profile, kWalkFill, R.W, R.args, R.grid, s->stream));
+  if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[3], s->stream));
   return 0;
 }
 }  // namespace
@@ -405,6 +434,34 @@ int pairs_link_components(sassy_SearcherType* s, const uint8_t* a, size_t n, uin
   return 0;
 }
 
+// ---- what umi_groups.hip uses (host_internal.h): the list's upload alone, then the walks over arrays that a kernel made ----
+// The list as a self-mode call stages it: *d_a [n][P W], *d_t [S n][P W] (d_pairs_a, d_pairs_t).
+int pairs_upload_self(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, const uint32_t** d_a, const uint32_t** d_t) {
+  if (int rc = pairs_upload(s, a, n, nullptr, 0, m)) return rc;
+  *d_a = s->d_pairs_a.p;
+  *d_t = s->d_pairs_t.p;
+  return 0;
+}
+// The link pass of the clustering call over n device-resident entries and their target records: no event, no copy.
+int pairs_resident_link(sassy_SearcherType* s, const uint32_t* d_a, const uint32_t* d_t, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent) {
+  PairsRun R;
+  if (int rc = pairs_stage_resident(s, d_a, n, d_t, n, true, m, k, kPairsSelfPairs, false, R)) return rc;
+  R.args.parent = d_parent;
+  HIP_TRY(launch_walk_profile(s->profile, kWalkCluster, R.W, R.args, R.grid, s->stream));
+  return 0;
+}
+// The self-mode records of n device-resident entries: survey, rows, scan, fill.  They stay in d_pairs_out, *total of them
+// (stats.candidates too); more than 2^32 - 1: SASSY_HIP_ENOMEM with the count, as the pair call fails.
+int pairs_resident_records(sassy_SearcherType* s, const uint32_t* d_a, const uint32_t* d_t, size_t n, uint32_t m, uint32_t k, const char* who,
+                           unsigned long long* total) {
+  PairsRun R;
+  if (int rc = pairs_stage_resident(s, d_a, n, d_t, n, true, m, k, kPairsSelfPairs, true, R)) return rc;
+  HIP_TRY(launch_walk_profile(s->profile, kWalkSurvey, R.W, R.args, R.grid, s->stream));
+  if (int rc = pairs_fill_records(s, R, who, total)) return rc;
+  s->stats.scan_launches = *total ? 2 : 1;
+  return 0;
+}
+
 // ---- what edit_pairs.hip shares (host_internal.h): the passes behind a survey that do not depend on the distance ----
 // slice(i0, i1) over [0, n) in up to 8 host threads (a list of a million sequences is encoded in a fraction of the time)
 void pairs_for_slices(size_t n, const std::function<void(size_t, size_t)>& slice) {
@@ -431,19 +488,28 @@ void pairs_times(sassy_SearcherType* s, bool has_last) {
   s->stats.trace_ms = last;
   s->stats.scan_ms = (double)survey + mid + last;
 }
+// The 64-bit exclusive scan of in[0 .. n) into out, on the searcher's stream: block sums, their scan by one workgroup, the
+// items.  block_sum: pairs_scan_blocks(n) + 1 entries of the caller's; the total is left in its last one.
+uint64_t pairs_scan_blocks(uint64_t n) { return (n + kScanBlock - 1) / kScanBlock; }
+int pairs_scan_u64(sassy_SearcherType* s, const unsigned long long* in, uint64_t n, unsigned long long* block_sum, unsigned long long* out) {
+  hipStream_t st = s->stream;
+  const uint64_t n_blocks = pairs_scan_blocks(n);
+  hipLaunchKernelGGL(pairs_scan_sums_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, in, n, block_sum);
+  hipLaunchKernelGGL(pairs_scan_top_kernel, dim3(1), dim3(1024), 0, st, block_sum, n_blocks);
+  hipLaunchKernelGGL(pairs_scan_rows_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, in, n, block_sum, out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 // the rows' sums, their exclusive scan, the total: every cell's place in its row, *row_first the device's table of rows
 int pairs_place_rows(sassy_SearcherType* s, uint4* cells, uint64_t n_a, uint32_t n_chunks, const unsigned long long** row_first_out,
                      unsigned long long* total_out) {
   hipStream_t st = s->stream;
-  const uint64_t n_blocks = (n_a + kScanBlock - 1) / kScanBlock;
+  const uint64_t n_blocks = pairs_scan_blocks(n_a);
   if (int rc = s->d_pairs_rows.reserve(2 * n_a + n_blocks + 1)) return rc;
   unsigned long long *row_sum = s->d_pairs_rows.p, *row_first = row_sum + n_a, *block_sum = row_first + n_a;
   const uint32_t row_grid = (uint32_t)((n_a + 255) / 256);
   hipLaunchKernelGGL(pairs_rows_kernel, dim3(row_grid), dim3(256), 0, st, cells, n_a, n_chunks, row_sum);
-  hipLaunchKernelGGL(pairs_scan_sums_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, row_sum, n_a, block_sum);
-  hipLaunchKernelGGL(pairs_scan_top_kernel, dim3(1), dim3(1024), 0, st, block_sum, n_blocks);
-  hipLaunchKernelGGL(pairs_scan_rows_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, row_sum, n_a, block_sum, row_first);
-  HIP_TRY(hipGetLastError());
+  if (int rc = pairs_scan_u64(s, row_sum, n_a, block_sum, row_first)) return rc;
   if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[2], st));
   unsigned long long total = 0;
   HIP_TRY(hipMemcpyAsync(&total, block_sum + n_blocks, 8, hipMemcpyDeviceToHost, st));
@@ -501,22 +567,14 @@ int sassy_hip_hamming_pairs(sassy_SearcherType* s, const uint8_t* a, size_t n_a,
   *n_out = 0;
   const size_t lens[1] = {m};
   return hamming_call(s, lens, 1, k, [&](uint32_t kk) {  // (k >= m: every pair is a record)
-    hipStream_t st = s->stream;
     PairsRun R;
     if (int rc = pairs_survey(s, a, n_a, b, n_b, (uint32_t)m, kk, kPairsSelfPairs, R)) return rc;
-    const unsigned long long* row_first = nullptr;
     unsigned long long total = 0;
-    if (int rc = pairs_place_rows(s, R.args.cells, n_a, R.plan.n_chunks, &row_first, &total)) return rc;
-    if (total > 0xFFFFFFFFull) return fail(SASSY_HIP_ENOMEM, "hamming_pairs: more than 2^32 - 1 records (" + std::to_string(total) + ")");
+    if (int rc = pairs_fill_records(s, R, who, &total)) return rc;
     if (total == 0) {
       pairs_times(s, false);
       return 0;
     }
-    if (int rc = s->d_pairs_out.reserve((size_t)total * sizeof(sassy_hip_HammingPair))) return rc;
-    R.args.row_first = row_first;
-    R.args.out = reinterpret_cast<sassy_hip_HammingPair*>(s->d_pairs_out.p);
-    HIP_TRY(launch_walk_profile(s->profile, kWalkFill, R.W, R.args, R.grid, st));
-    if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[3], st));
     s->stats.scan_launches = 2;
     return pairs_take_records(s, total, out, n_out);
   });

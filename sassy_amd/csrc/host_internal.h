@@ -722,6 +722,9 @@ struct sassy_SearcherType {
   DevBuf<uint4> d_pairs_cells;
   DevBuf<unsigned long long> d_pairs_rows;
   DevBuf<uint8_t> d_pairs_out;
+  // UMI groups (umi_groups.hip): what is sized by the reads (the table, rep, count, the flags and their scan, the output
+  // columns) and what is sized by the distinct sequences (their planes, counts, labels)
+  DevBuf<uint8_t> d_umi_reads, d_umi_distinct;
   DevBuf<uint64_t> d_range;      // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
@@ -747,6 +750,7 @@ struct sassy_SearcherType {
     d_ham_tab.release(); d_ham_count.release(); d_ham_prefix.release(); d_ham_items.release(); d_ham_sorted.release(); d_ham_sort.release();
     d_ham_texts.release(); d_ham_rem.release(); d_ham_cells.release(); d_ham_bins.release();
     d_pairs_a.release(); d_pairs_t.release(); d_pairs_cells.release(); d_pairs_rows.release(); d_pairs_out.release();
+    d_umi_reads.release(); d_umi_distinct.release();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();
@@ -1301,6 +1305,15 @@ int pairs_refusals(sassy_SearcherType* s, bool have_out, const uint8_t* a, size_
 int edit_refusals(sassy_SearcherType* s, bool have_out, const uint8_t* a, size_t n_a, size_t m_a, const uint8_t* b, size_t n_b, size_t m_b, size_t k,
                   uint32_t flags, const char* who);
 int pairs_link_components(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent);
+// The UMI grouping call (umi_groups.hip; DESIGN.md 5.10 "UMI groups") walks device-resident arrays of the distinct sequences:
+// the list's upload alone (*d_a [n][P W], *d_t [S n][P W]), the link pass and the record passes (survey, rows, scan, fill;
+// the records stay in d_pairs_out) over such arrays, and the 64-bit exclusive scan the record passes use.
+int pairs_upload_self(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, const uint32_t** d_a, const uint32_t** d_t);
+int pairs_resident_link(sassy_SearcherType* s, const uint32_t* d_a, const uint32_t* d_t, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent);
+int pairs_resident_records(sassy_SearcherType* s, const uint32_t* d_a, const uint32_t* d_t, size_t n, uint32_t m, uint32_t k, const char* who,
+                           unsigned long long* total);
+uint64_t pairs_scan_blocks(uint64_t n);
+int pairs_scan_u64(sassy_SearcherType* s, const unsigned long long* in, uint64_t n, unsigned long long* block_sum, unsigned long long* out);
 int edit_link_components(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent);
 // cluster_step.h's memory policy on the device: relaxed, agent scope, vector memory operations
 struct ClusterDeviceMem {

@@ -65,7 +65,8 @@ namespace sassy_hip {
   X(hamming_batch, 0, "search_hamming: > 0: at most this many scanned patterns (a strand counts as one) share a launch of the scan kernel (0: 512)") \
   X(hamming_many_batch, 0, "search_hamming_many / hamming_best_pattern: > 0: a batch of texts is at most this many bytes laid out (each text from a multiple of 64 on; a longer text is a batch of its own) (0: 1 GiB)") \
   X(hamming_count_copies, 0, "hamming_counts / hamming_counts_many: > 0: this many copies of the counts table -- a workgroup adds into copy blockIdx & (copies - 1), the host sums them (rounded down to a power of two, at most 1024) (0: 32 while 32 tables are at most 65536 counters, fewer for a larger table)") \
-  X(pairs_chunks, 0, "hamming_pairs / hamming_nearest: > 0: the targets are cut into this many chunks (at most one per target, at most 65535) -- the grid is strips of 256 entries x chunks; geometry only (0: enough chunks of at least 256 targets that 2048 workgroups are in flight; hamming_pairs: also chunks of at most 16384 targets, within 2^24 partial cells)")
+  X(pairs_chunks, 0, "hamming_pairs / hamming_nearest: > 0: the targets are cut into this many chunks (at most one per target, at most 65535) -- the grid is strips of 256 entries x chunks; geometry only (0: enough chunks of at least 256 targets that 2048 workgroups are in flight; hamming_pairs: also chunks of at most 16384 targets, within 2^24 partial cells)") \
+  X(collapse_slots, 0, "umi_groups: > 0: the duplicate table holds this many slots, but at least one per read -- geometry only: at exactly one per read the table runs full and the probes wrap round (0: the power of two that is at least twice the reads)")
 
 struct Switches {
 #define SASSY_HIP_SWITCH_FIELD(name, dflt, doc) long name = (dflt);
