@@ -77,6 +77,16 @@ pub struct ReadRecord {
 pub struct RawReads {
     _p: [u8; 0],
 }
+/// The best overlap of one read pair (include/sassy_hip.h: sassy_hip_ReadOverlap, 16 bytes); n_accepted == 0: no overlap, every
+/// field is 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct ReadOverlap {
+    pub offset: i32,
+    pub overlap: u32,
+    pub mismatches: u32,
+    pub n_accepted: u32,
+}
 #[repr(C)]
 struct RawSearcher {
     _p: [u8; 0],
@@ -191,6 +201,9 @@ extern "C" {
                                         reads: *const RawReads, k: usize, flags: u32, out: *mut *mut RawResult) -> c_int;
     pub fn sassy_hip_reads_relayout(reads: *const RawReads, first: u64, count: u64, dst_starts: *const u64, total: u64, pad: u8,
                                     d_dst: *mut std::ffi::c_void, hip_stream: *mut std::ffi::c_void) -> c_int;
+    // paired-end overlap: read r of r1 against the reverse complement of read r of r2, `out` holds sassy_hip_reads_n(r1) records
+    pub fn sassy_hip_read_overlaps(s: *mut RawSearcher, r1: *const RawReads, r2: *const RawReads, min_overlap: u32, k: usize,
+                                   max_permille: u32, flags: u32, out: *mut ReadOverlap) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

@@ -743,6 +743,43 @@ int sassy_hip_best_matches_reads(sassy_SearcherType *s, const uint8_t *const *pa
 int sassy_hip_reads_relayout(const sassy_hip_Reads *reads, uint64_t first, uint64_t count, const uint64_t *dst_starts,
                              uint64_t total, uint8_t pad, void *d_dst, void *hip_stream);
 
+/* Paired-end read overlap (sassy_amd/csrc/read_overlaps.hip, arithmetic in overlap_step.h): the best overlap
+ * of the two reads of every pair, both read batches resident on the device.  The definition is
+ * tests/helpers/read_overlaps_ref.py.  Pair r: a = read r of r1 (la bytes), b = the reverse complement of read r of r2 (lb
+ * bytes; the profile's complement, byte by byte).  The offset d, -(lb - 1) <= d <= la - 1, places b[0] under a[d]:
+ * lo = max(0, d), hi = min(la, d + lb), the overlap is ov = hi - lo rows and
+ *   mm(d) = #{ i in [lo, hi) : !match(a[i], b[i - d]) },   match: the searcher's profile relation, a on the pattern side.
+ *  - an offset is ACCEPTED when ov >= min_overlap, mm <= k and mm * 1000 <= max_permille * ov (integers, no floats);
+ *  - the BEST accepted offset is the one of the lowest mismatch density (mm1 * ov2 < mm2 * ov1), at equal density of the
+ *    larger ov, at equal ov of the larger d (FLASH's rule with the ties fixed: a non-read-through alignment beats its mirror
+ *    image); the order is total, so the record is the same on every run;
+ *  - out[r], 16 bytes: the best offset, its overlap and mismatches, and n_accepted, the number of accepted offsets (above 1:
+ *    repeats, low-complexity reads).  No accepted offset, or an empty read on either side: all four fields zero;
+ *  - derived on the host: d >= 0: insert = max(la, d + lb), both reads are kept whole; d < 0 (read-through: the insert is
+ *    shorter than the reads and their tails are adapter): insert = ov, keep min(la, d + lb) bytes of read 1 and lb + d of
+ *    read 2; no overlap: insert 0 (Python: sassy_amd.overlap_trims);
+ *  - Iupac: R2's bytes are complemented as the reference's profile does it (U is its own complement and matches as T; what
+ *    is no letter stays as it is and matches as N; X matches nothing).  Dna: both batches must hold A, C, G, T only (looked
+ *    at on the device once per call and handle, in either case, as the _reads calls look; a lower-case letter keeps its
+ *    2-bit code and, as in the reference's profile, is not complemented) -- anything else is SASSY_HIP_EINVAL and the message
+ *    points to an iupac searcher: the 2-bit codes would let N match G, and N has no complement there;
+ *  - k is not capped at 254: mismatches are 32-bit here; k beyond the longest read accepts what k = 512 accepts;
+ *  - refused before any device work, SASSY_HIP_EINVAL unless noted: s == NULL; any flag; min_overlap == 0;
+ *    max_permille > 1000; an Ascii searcher (no complement); overhang, only_best_match, max_n_frac set
+ *    (SASSY_HIP_EUNSUPPORTED, as the Hamming family refuses them); r1 or r2 NULL; different record counts; a handle made on
+ *    another device than the searcher's; a read longer than SASSY_HIP_OVERLAP_MAX_LEN in either handle (such a pair is never
+ *    launched); out == NULL with pairs to write; searches in flight on the searcher.  Zero pairs: success, nothing written;
+ *  - both handles are only read.  One launch, one wavefront per pair; option-free. */
+#define SASSY_HIP_OVERLAP_MAX_LEN 512u
+typedef struct sassy_hip_ReadOverlap {
+  int32_t offset;      /* d of the best accepted offset */
+  uint32_t overlap;    /* its ov */
+  uint32_t mismatches; /* its mm */
+  uint32_t n_accepted; /* accepted offsets of the pair; 0: no overlap, every field is 0 */
+} sassy_hip_ReadOverlap;
+int sassy_hip_read_overlaps(sassy_SearcherType *s, const sassy_hip_Reads *r1, const sassy_hip_Reads *r2, uint32_t min_overlap,
+                            size_t k, uint32_t max_permille, uint32_t flags, sassy_hip_ReadOverlap *out /* sassy_hip_reads_n(r1) */);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is

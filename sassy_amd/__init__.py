@@ -166,7 +166,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_reads_longest", "sassy_hip_reads_rem", "sassy_hip_reads_free",
     "sassy_hip_search_hamming_reads", "sassy_hip_hamming_best_pattern_reads", "sassy_hip_hamming_counts_reads",
     "sassy_hip_search_many_reads", "sassy_hip_min_costs_reads", "sassy_hip_best_pattern_reads", "sassy_hip_best_matches_reads",
-    "sassy_hip_reads_relayout",
+    "sassy_hip_reads_relayout", "sassy_hip_read_overlaps",
 ]
 
 _lib = None
@@ -427,6 +427,8 @@ def lib():
     L.sassy_hip_best_matches_reads.argtypes = pats + [C.POINTER(vp)]
     L.sassy_hip_reads_relayout.restype = C.c_int
     L.sassy_hip_reads_relayout.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint8, vp, vp]
+    L.sassy_hip_read_overlaps.restype = C.c_int
+    L.sassy_hip_read_overlaps.argtypes = [vp, vp, vp, C.c_uint32, sz, C.c_uint32, C.c_uint32, vp]
     L.sassy_hip_malloc.restype = vp
     L.sassy_hip_malloc.argtypes = [sz]
     L.sassy_hip_free.restype = None
@@ -528,6 +530,43 @@ def read_record_dtype():
     import numpy as np
     return np.dtype([("id_start", "<u8"), ("id_len", "<u8"), ("seq_start", "<u8"), ("seq_len", "<u8"), ("qual_start", "<u8"),
                      ("qual_len", "<u8")])
+
+
+def read_overlap_dtype():
+    """numpy view of include/sassy_hip.h: sassy_hip_ReadOverlap (16 bytes)."""
+    import numpy as np
+    return np.dtype([("offset", "<i4"), ("overlap", "<u4"), ("mismatches", "<u4"), ("n_accepted", "<u4")])
+
+
+OVERLAP_MAX_LEN = 512  # SASSY_HIP_OVERLAP_MAX_LEN
+
+
+def overlap_trims(rec, la: int, lb: int):
+    """(insert, keep1, keep2) of one record of `Searcher.read_overlaps` for reads of la and lb bytes: the fragment length and
+    how many bytes of each read belong to it.  d >= 0: insert = max(la, d + lb), both reads are kept whole; d < 0
+    (read-through: the tails are adapter): insert = ov, keep1 = min(la, d + lb), keep2 = lb + d; no overlap (n_accepted == 0):
+    insert = 0 and both reads whole.  Pure arithmetic on the host."""
+    d, ov, n = int(rec["offset"]), int(rec["overlap"]), int(rec["n_accepted"])
+    la, lb = int(la), int(lb)
+    if n == 0:
+        return 0, la, lb
+    if d >= 0:
+        return max(la, d + lb), la, lb
+    return ov, min(la, d + lb), lb + d
+
+
+def fastq_from_sequences(seqs) -> bytes:
+    """Minimal four-line FASTQ of a list of byte sequences, an empty id and an empty quality each: b"@\\n" + seq + b"\\n+\\n\\n".
+    A sequence that holds a line end would change the record structure and is refused."""
+    out = []
+    for i, s in enumerate(seqs):
+        if isinstance(s, str):
+            s = s.encode()
+        s = bytes(s)
+        if b"\n" in s or b"\r" in s:
+            raise SassyHipError(f"from_sequences: sequence {i} holds a line end (\\n or \\r)")
+        out.append(b"@\n" + s + b"\n+\n\n")
+    return b"".join(out)
 
 
 def line_tile() -> int:
@@ -1276,6 +1315,36 @@ class Searcher:
                                           sizes.ctypes.data, reps.ctypes.data, counts.ctypes.data, None, None))
         return labels, sizes, reps, counts
 
+    def read_overlaps(self, r1, r2, min_overlap: int = 10, k: int = OVERLAP_MAX_LEN, max_permille: int = 200):
+        """The best overlap of the two reads of every pair (sassy_hip_read_overlaps): pair r is read r of `r1` against the
+        reverse complement of read r of `r2`, every end-to-end offset d (b[0] under a[d]) tried on the device.  An offset is
+        accepted when it overlaps in at least `min_overlap` rows with at most `k` mismatches and at most `max_permille` per
+        thousand of them; the best one has the lowest mismatch density, then the longer overlap, then the larger d.  Returns
+        a numpy array of `read_overlap_dtype()` (offset, overlap, mismatches, n_accepted), all zero where nothing is accepted
+        or a read is empty; `overlap_trims` derives insert length and trim points.  `r1` and `r2` are DeviceReads of equal
+        length (reads of at most 512 bytes), or lists of byte sequences, which go through DeviceReads.from_sequences.  dna
+        (A, C, G, T only) or iupac; the defaults accept up to 20 % mismatches and leave k open."""
+        import numpy as np
+        made = []
+        # (lists: both are wrapped, and refused for a line end, before either is parsed)
+        sources = [r if isinstance(r, DeviceReads) else fastq_from_sequences(r) for r in (r1, r2)]
+        try:
+            handles = []
+            for r in sources:
+                if not isinstance(r, DeviceReads):
+                    r = DeviceReads(r)
+                    made.append(r)
+                handles.append(r)
+            if not 0 <= int(min_overlap) < (1 << 32) or not 0 <= int(max_permille) < (1 << 32) or int(k) < 0:
+                raise SassyHipError("read_overlaps: min_overlap, k and max_permille must not be negative")
+            out = np.zeros(len(handles[0]), dtype=read_overlap_dtype())
+            _check(lib().sassy_hip_read_overlaps(self._h, handles[0]._handle(), handles[1]._handle(), int(min_overlap), int(k), int(max_permille), 0,
+                                                 out.ctypes.data if len(out) else None))
+            return out
+        finally:
+            for r in made:
+                r.free()
+
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k
         at every end position of search_all, grouped: one list per (strand, anchor) -- the anchor is text_end for
@@ -1953,6 +2022,12 @@ class DeviceReads:
         self.ptr = int(lib().sassy_hip_reads_text(out) or 0)
         self.text_bytes = int(lib().sassy_hip_reads_text_bytes(out))
         self.longest = int(lib().sassy_hip_reads_longest(out))
+
+    @classmethod
+    def from_sequences(cls, seqs, stream: int = 0):
+        """A read batch of a list of byte sequences: they are wrapped into minimal four-line FASTQ (fastq_from_sequences: an
+        empty id and an empty quality each) and parsed like any chunk.  A sequence that holds '\\n' or '\\r' is refused."""
+        return cls(fastq_from_sequences(seqs), stream)
 
     def __len__(self) -> int:
         return len(self.id_starts)

@@ -86,6 +86,16 @@ the first sequence identical to the row's, `group_id` the id of the sequence tha
 
     id  rep_id  count  group_id  group_size
 
+`overlap R1 R2 [--min-overlap N] [-k K] [--max-permille P] [--alphabet dna|iupac]` writes how the two reads of every pair of
+two FASTQ files overlap, through `Searcher.read_overlaps`: read r of R1 against the reverse complement of read r of R2 at
+every end-to-end offset; both files are parsed on the device and cut at the same records.  An offset is accepted with at
+least N rows of overlap (default 10), at most K mismatches (default: no limit) and at most P per thousand of them (default
+200); the best one has the lowest mismatch density.  `accepted` counts the accepted offsets (above 1: repeats); `insert` is
+the fragment length and `keep1` / `keep2` what of each read belongs to it (less than the read where the pair reads through
+into adapter); all zero offsets and insert 0 where nothing is accepted.  A header row, then one row per pair, the id R1's:
+
+    id  offset  overlap  mismatches  accepted  insert  keep1  keep2
+
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
 one block per match, sorted by (start, end): `PATH:LINE:COL:COST:` and the line(s) the match lies in -- LINE and the line's
@@ -510,6 +520,42 @@ def cluster_parser(sub):
     return cp
 
 
+OVERLAP_HEADER = "id\toffset\toverlap\tmismatches\taccepted\tinsert\tkeep1\tkeep2\n"
+
+
+def overlap_rows(ids, records, lens1, lens2):
+    """The TSV rows of Searcher.read_overlaps' array, one per pair: R1's id, the record, and overlap_trims of it."""
+    from . import overlap_trims
+    rows = []
+    for i, rec in enumerate(records):
+        insert, keep1, keep2 = overlap_trims(rec, int(lens1[i]), int(lens2[i]))
+        rows.append(f"{ids[i]}\t{int(rec['offset'])}\t{int(rec['overlap'])}\t{int(rec['mismatches'])}\t{int(rec['n_accepted'])}\t{insert}\t{keep1}\t{keep2}\n")
+    return rows
+
+
+def run_overlap(args, searcher, out) -> int:
+    from .fastx import read_fastq_pair_device_batches
+    out.write(OVERLAP_HEADER)
+    for b1, b2 in read_fastq_pair_device_batches(args.r1, args.r2, BATCH_BYTES):
+        records = searcher.read_overlaps(b1.texts, b2.texts, args.min_overlap, args.k, args.max_permille)
+        out.writelines(overlap_rows([b1.id(i) for i in range(len(b1))], records, b1.texts.seq_lens, b2.texts.seq_lens))
+        b1.free()
+        b2.free()
+    out.flush()
+    return 0
+
+
+def overlap_parser(sub):
+    cp = sub.add_parser("overlap", help="write the best overlap of the two reads of every pair (paired-end FASTQ) as TSV to stdout")
+    cp.add_argument("r1", metavar="R1", help="FASTQ of the first reads")
+    cp.add_argument("r2", metavar="R2", help="FASTQ of the second reads, in the same order")
+    cp.add_argument("--min-overlap", type=int, default=10, help="rows an accepted overlap has at least (default 10)")
+    cp.add_argument("-k", type=int, default=512, help="mismatches an accepted overlap has at most (default: no limit)")
+    cp.add_argument("--max-permille", type=int, default=200, help="mismatches per thousand rows an accepted overlap has at most (default 200)")
+    cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac"], default="dna")
+    return cp
+
+
 def load_primers(path: str) -> List[Tuple[str, bytes, bytes]]:
     """PRIMERS of `amplicon`: rows of name<TAB>fwd<TAB>rev (empty lines and lines from `#` on skipped)."""
     pairs = []
@@ -616,7 +662,12 @@ def main(argv=None) -> int:
     amplicon_parser(sub)
     pairs_parser(sub)
     cluster_parser(sub)
+    overlap_parser(sub)
     args = ap.parse_args(argv)
+    if args.cmd == "overlap":
+        if args.min_overlap < 1 or args.k < 0 or not 0 <= args.max_permille <= 1000:
+            ap.error("overlap takes --min-overlap >= 1, -k >= 0 and 0 <= --max-permille <= 1000")
+        return run_overlap(args, Searcher(args.alphabet, rc=False), sys.stdout)
     if getattr(args, "device_parse", False):
         if args.cmd == "count" and args.per_record:
             ap.error("count --device-parse serves the summed table: --per-record takes --device-unwrap (FASTA) or no flag")

@@ -8,6 +8,7 @@
 //   hamming_plan.h    that driver's decisions that need no device (patterns as scanned, groups, tables, overflow step, text batches), free of HIP
 //   amplicons.hip     sassy_hip_hamming_amplicons: primer pairs joined on the sorted items of the Hamming scan (ham_walk_ranges, below)
 //   fastq_reads.hip   sassy_hip_fastq_parse: FASTQ into a resident read batch; sassy_hip_*_reads, the Hamming batch calls over it
+//   read_overlaps.hip sassy_hip_read_overlaps: the best overlap of read r of one resident batch with the reverse complement of read r of another
 //   c_abi.hip         the C-ABI of include/sassy.h + sassy_hip.h, the switch table, synthetic inputs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -725,7 +726,8 @@ struct sassy_SearcherType {
   // UMI groups (umi_groups.hip): what is sized by the reads (the table, rep, count, the flags and their scan, the output
   // columns) and what is sized by the distinct sequences (their planes, counts, labels)
   DevBuf<uint8_t> d_umi_reads, d_umi_distinct;
-  DevBuf<uint64_t> d_range;      // N counting on device-resident text
+  DevBuf<sassy_hip_ReadOverlap> d_overlaps;  // read overlaps (read_overlaps.hip): one record per pair
+  DevBuf<uint64_t> d_range;     // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
   // scan; default), 2 every phase.  Each event record costs a few microseconds of stream idle time.
@@ -750,7 +752,7 @@ struct sassy_SearcherType {
     d_ham_tab.release(); d_ham_count.release(); d_ham_prefix.release(); d_ham_items.release(); d_ham_sorted.release(); d_ham_sort.release();
     d_ham_texts.release(); d_ham_rem.release(); d_ham_cells.release(); d_ham_bins.release();
     d_pairs_a.release(); d_pairs_t.release(); d_pairs_cells.release(); d_pairs_rows.release(); d_pairs_out.release();
-    d_umi_reads.release(); d_umi_distinct.release();
+    d_umi_reads.release(); d_umi_distinct.release(); d_overlaps.release();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();

@@ -519,6 +519,90 @@ def read_fastq_device_batches(path: str, batch_bytes: int = 256 << 20) -> Iterat
             fh.close()
 
 
+# ---- two FASTQ files read in step (paired-end: record r of both files is one pair) ----
+def whole_records(newlines: int, tail_bytes: int, at_eof: bool) -> int:
+    """The whole four-line records in a buffer that holds `newlines` line ends and `tail_bytes` bytes behind the last one: a
+    last line without its line end counts only once the file has ended."""
+    return (newlines + (1 if at_eof and tail_bytes else 0)) // 4
+
+
+def pair_cut(records1: int, records2: int) -> int:
+    """Where both files of a pair are cut: at the smaller count of whole records of the two buffers; what is behind it is
+    carried into the next chunk."""
+    return min(records1, records2)
+
+
+def records_end(nl: np.ndarray, records: int, have: int) -> int:
+    """The buffer offset behind record `records` - 1: behind line end 4 * records - 1 of `nl` (the line ends' offsets), or
+    `have`, the buffer's end, where the file ended without it."""
+    if records == 0:
+        return 0
+    last = 4 * records - 1
+    return int(nl[last]) + 1 if last < nl.size else have
+
+
+def fastq_pair_chunks(fill1, fill2, batch_bytes: int, names=("R1", "R2")):
+    """Pairs of byte chunks (numpy uint8, copies) of two FASTQ streams with equal record counts: both buffers take up to
+    batch_bytes more bytes, both are cut at pair_cut of their whole records, the rest is carried.  fill(view) -> bytes
+    written, 0 at the end.  Raises ValueError when the streams end with different record counts or inside a record."""
+    fills, bufs, eofs = (fill1, fill2), [bytearray(), bytearray()], [False, False]
+    want = batch_bytes
+    while True:
+        for i in range(2):
+            room = bytearray(want)
+            while not eofs[i] and len(bufs[i]) < want:
+                got = fills[i](memoryview(room)[:want - len(bufs[i])])
+                if got == 0:
+                    eofs[i] = True
+                bufs[i] += room[:got]
+        views = [np.frombuffer(bytes(b), dtype=np.uint8) for b in bufs]
+        nls = [np.flatnonzero(v == NL) for v in views]
+        counts = [whole_records(nl.size, v.size - (int(nl[-1]) + 1 if nl.size else 0), eof) for nl, v, eof in zip(nls, views, eofs)]
+        n = pair_cut(*counts)
+        if n == 0:
+            if all(eofs):
+                rest = [v.size - records_end(nl, c, v.size) for nl, v, c in zip(nls, views, counts)]
+                if counts[0] != counts[1]:
+                    raise ValueError(f"{names[0]} and {names[1]} end with different record counts ({max(counts)} more in "
+                                     f"{names[0] if counts[0] > counts[1] else names[1]})")
+                if any(rest):
+                    raise ValueError(f"{names[0 if rest[0] else 1]} ends inside a FASTQ record")
+                return
+            if any(eof and c == 0 for eof, c in zip(eofs, counts)) and any(counts):
+                raise ValueError(f"{names[0]} and {names[1]} end with different record counts")
+            want *= 2  # a record longer than the batch: read on
+            continue
+        ends = [records_end(nl, n, v.size) for nl, v in zip(nls, views)]
+        yield views[0][:ends[0]], views[1][:ends[1]]
+        for i in range(2):
+            del bufs[i][:ends[i]]
+        want = batch_bytes
+
+
+def read_fastq_pair_device_batches(path1: str, path2: str, batch_bytes: int = 256 << 20):
+    """Pairs of DeviceReadBatch of two FASTQ files (R1, R2) with equal record counts, both parsed on the device: what
+    Searcher.read_overlaps takes as batch1.texts, batch2.texts.  Both files are cut at the same record number
+    (fastq_pair_chunks); files that end with different record counts raise ValueError."""
+    from . import DeviceReads
+    (fill1, fh1), (fill2, fh2) = _sources(path1), _sources(path2)
+    try:
+        for c1, c2 in fastq_pair_chunks(fill1, fill2, batch_bytes, (path1, path2)):
+            batches = []
+            for path, chunk in ((path1, c1), (path2, c2)):
+                if chunk[:1].tobytes() != b"@":
+                    raise ValueError(f"{path}: not FASTQ (first byte {chunk[:1].tobytes()!r}): the parse on the device takes FASTQ only")
+                reads = DeviceReads(chunk)
+                batches.append(DeviceReadBatch(reads, chunk))
+                reads._raw = None
+            if len(batches[0]) != len(batches[1]):
+                raise ValueError(f"{path1} and {path2}: a chunk parsed into {len(batches[0])} and {len(batches[1])} records (blank lines?)")
+            yield batches[0], batches[1]
+    finally:
+        for path, fh in ((path1, fh1), (path2, fh2)):
+            if path not in ("", "-"):
+                fh.close()
+
+
 def first_byte(path: str) -> bytes:
     """The first byte of a file's contents (behind gzip), b"" for an empty one."""
     fill, fh = _sources(path)
