@@ -2,6 +2,7 @@
 // traceback on one lane), the reference-lane mode, both strands, the report filters.
 // Mirror of the reference's Searcher<P>::search path (src/search.rs:510-937).
 #include "host_internal.h"
+#include "pass_lds.h"
 
 PinPool g_pin_pool;
 
@@ -357,7 +358,7 @@ int ScanJob::prepare() {
       // chunks per wave between two chunk-DP passes: a wave runs a pass when more than cap - 128 are queued (a full
       // batch of 64 lanes), so the queue never overflows; + the count (16 bytes);
       // 4 workgroups per CU still fit the LDS: 4 x 4 x (8192 + 1536 + 16) = 155 904 bytes
-      F.fuse_queue_cap = 192u;
+      F.fuse_queue_cap = kPassLdsQueueCap;
       F.lds_per_wave += F.fuse_queue_cap * 8u + 16u;
       const int env_press = (int)sw.fused_press;
       F.fuse_press = F.fuse_queue_cap - 128u;
@@ -677,13 +678,18 @@ int ScanJob::enqueue_pass(ScanJob* other, uint32_t g0, uint32_t g1, PassSlot& sl
     }
     for (hipEvent_t e : kept->wait)  // (a reader: behind the launch that wrote its half)
       if (e) HIP_TRY(hipStreamWaitEvent(L.stream, e, 0));
+    // A reader stages no text: the DP's masks and carries, the segment state, the queue -- no tile behind them and no
+    // pipelining pad (pass_lds.h).  Four workgroups per CU, as its 127 VGPRs allow, instead of the padded launch's two.
+    if (src == kPlaneRead) GP.lds_per_wave = pass_lds_per_wave(1, src, F.fuse_queue_cap);
   }
   if (other) {
     const ScanJob& B = *other;
     // The tile and both members' queues and counts, WITHOUT the pipelining pad of prepare(): 4 x (8192 + 2 x 1552) =
     // 45 184 bytes per workgroup, so three workgroups per CU stream the text instead of two (the kernel's VGPRs allow
-    // three waves per SIMD).  The pass keeps the members' geometry (the pad, the geometry and why).
-    GP.lds_per_wave = kTileBytes + 2u * (F.fuse_queue_cap * 8u + 16u);
+    // three waves per SIMD).  The pass keeps the members' geometry (the pad, the geometry and why).  On kept
+    // planes nothing is staged and the queues follow the segment state: 4 x (6912 + 2 x 1552) = 40 064 bytes, four
+    // workgroups per CU at the reader's 128 VGPRs (pass_lds.h owns both layouts).
+    GP.lds_per_wave = pass_lds_per_wave(2, src, F.fuse_queue_cap);
     const uint32_t na = F.n_pieces, nb = B.F.n_pieces;
     GP.piece_member = 0;
     for (uint32_t pp = 0; pp < 8; ++pp) {  // (slots behind both repeat member 0's first piece)

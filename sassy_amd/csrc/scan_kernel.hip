@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "pass_lds.h"
 #include "profile_masks.h"
 #include "piece_pair_step.h"
 
@@ -1711,7 +1712,8 @@ __device__ __forceinline__ bool other_letters16(const uint4 v) { return other_le
 // its iterations into ScanParams::plane_store, indexed by the kernel's own iteration space [workgroup of the whole grid]
 // [wave][iteration][lane] -- one 16-byte vector store, 1 KiB contiguous per wave and iteration.  kPlaneRead: no staging,
 // no tile reads, no bit_plane: the lane loads its 16 bytes back (a few iterations ahead, in registers) and goes on from
-// b0 / b1 as ever; the tile is only the chunk DP's.  A reader sees what the writer computed, tail bytes included, so
+// b0 / b1 as ever; the tile is only the chunk DP's, so a reader has none: its wave's LDS is the DP's 4 KiB, the segment
+// state behind them and the queues behind the state (pass_lds.h).  A reader sees what the writer computed, tail bytes included, so
 // `interior` plays no part; a wave with nothing to do neither writes nor reads.
 // The pair step takes the rows of 0 / ~0 words of every piece slot from a table the workgroup writes once (Q * 64 bytes of
 // static LDS in front of the launch's own -- in the G = 2 instantiations only, which are the ones that call this); the piece
@@ -1723,8 +1725,9 @@ __device__ __forceinline__ uint32_t* piece_row_table_lds() {
   return tab;
 }
 template <int Q, int NPG, bool FUSED, bool CHECK = false, bool PAIR = false, int DPNS = 4, int G = 1, int SRC = kPlaneRaw>
-// (CHECK: four waves per SIMD are asked for -- left to itself the compiler settles for three, 0.59 instead of 0.52 ms)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || PAIR) ? 4 : 1))) void filter_dna_kernel(const ScanParams P) {
+// (CHECK: four waves per SIMD are asked for -- left to itself the compiler settles for three, 0.59 instead of 0.52 ms.  The
+// two-member plane reader: 129 VGPRs left to itself, 128 asked; its LDS allows four workgroups per CU -- pass_lds.h)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || PAIR || (G == 2 && SRC == kPlaneRead)) ? 4 : 1))) void filter_dna_kernel(const ScanParams P) {
   static_assert(!CHECK || FUSED, "the text check exists in the fused launch only");
   static_assert(!PAIR || (FUSED && 2 * Q + 2 <= 31), "the paired filter exists in the fused launch only; its look-back stays inside one plane half");
   static_assert(G == 1 || (G == 2 && FUSED && !CHECK && !PAIR && NPG == 2), "the grouped pass: two members, fused Dna bit planes, eight piece slots");
@@ -1741,7 +1744,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   // of the detection column, like the characters in front of a B (one v_alignbit by the column index fetches either)
   constexpr int DL = Q + 2;
   constexpr int ND = PAIR ? Q + DL : Q;      // shift distances the piece rows are taken at
-  constexpr uint32_t kTile = 64u * kRowBytes;
+  // the wave's LDS (pass_lds.h): the queues lie behind the staging tile, or -- kPlaneRead stages nothing -- behind the state
+  constexpr uint32_t kTile = pass_lds_queues(G, SRC);
+  static_assert(SRC == kPlaneRead || kTile == 64u * kRowBytes, "a staging launch's queues lie behind its text tile");
+  static_assert(kPassLdsTile == kTileBytes && kPassLdsMaxWords == kFuseGroupMaxWords && kPassLdsWaves == kWavesPerGroup, "pass_lds.h restates common.h");
+  static_assert(pass_lds_dp(G, SRC).end >= (DPNS + kFuseGroupMaxWords) * 512u && pass_lds_dp(G, SRC).end == pass_lds_state(G, SRC).begin,
+                "the DP's masks and the carries of kFuseGroupMaxWords words end where the segment state begins");
+  static_assert(!(G == 2 || SRC == kPlaneRead) || pass_lds_dp(G, SRC).end == (DPNS + kFuseGroupMaxWords) * 512u, "... exactly, in the shared pass's layouts");
+  static_assert(SRC != kPlaneRead || Q > 12 || pass_lds_per_group(G, SRC, kPassLdsQueueCap, Q) <= kPassLdsCuBytes / 4u,
+                "four workgroups of the plane reader, table included, share a CU's LDS");
   typedef const ScanParams __attribute__((address_space(4)))* kparams_ptr;
 
   // FUSED: the wave streams its text range in SEGMENTS.  A segment ends when the range is done or when the wave's chunk
@@ -1754,7 +1765,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   // masks and carries, at most eight pattern words, leave free -- and the lane index comes from v_mbcnt, the wave index
   // from a scalar: kept in vector registers across the DP they were spilled to scratch memory, and a kernel that owns a
   // scratch segment starts its waves slower.)
-  constexpr uint32_t kSegState = G == 2 ? 4096u : 6144u;  // tile offset of the saved state: [7][64] u32 (G = 2: [11][64])
+  // tile offset of the saved state: [7][64] u32 (G = 2: [11][64]) -- 6144, or 4096 where the DP's masks and carries end there
+  constexpr uint32_t kSegState = pass_lds_state(G, SRC).begin;
+  static_assert(kSegState + (G == 2 ? 11u : 7u) * 256u == pass_lds_state(G, SRC).end && pass_lds_state(G, SRC).end <= kTile, "the state lies in front of the queues");
   uint32_t seg_it = 0;                             // wave-uniform, even
   bool first_segment = true;
   const uint32_t wave_s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1776,6 +1789,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   uint2* queue = reinterpret_cast<uint2*>(tile + kTile);
   uint32_t* qcount = reinterpret_cast<uint32_t*>(tile + kTile + (size_t)Pk->fuse_queue_cap * 8u);
   // (G = 2: member 1's queue and count behind member 0's)
+  static_assert(pass_lds_queue(G, SRC, kPassLdsQueueCap, 0).begin == kTile && pass_lds_count(G, SRC, kPassLdsQueueCap, 0).begin == kTile + kPassLdsQueueCap * 8u &&
+                    pass_lds_queue(G, SRC, kPassLdsQueueCap, 1).begin == kTile + kPassLdsQueueCap * 8u + 16u && pass_lds_count(G, SRC, kPassLdsQueueCap, 1).begin == kTile + kPassLdsQueueCap * 16u + 16u,
+                "the queue addresses below are pass_lds.h's");
   uint2* queue1 = reinterpret_cast<uint2*>(tile + kTile + (size_t)Pk->fuse_queue_cap * 8u + 16u);
   uint32_t* qcount1 = reinterpret_cast<uint32_t*>(tile + kTile + (size_t)Pk->fuse_queue_cap * 16u + 16u);
   const uint64_t group = (uint64_t)blockIdx.x + Pk->group_offset;

@@ -12,10 +12,10 @@ for line in sys.stdin:
     if m: cur={'name':m.group(1)}; rows.append(cur); continue
     for key in ('VGPRs','ScratchSize \[bytes/lane\]','Occupancy \[waves/SIMD\]','SGPRs Spill','VGPRs Spill'):
         m=re.search(r'    '+key+r': (\d+)',line)
-        if m and cur is not None: cur[key.split()[0]]=int(m.group(1))
+        if m and cur is not None: cur[key.replace(' Spill','Spill').split()[0]]=int(m.group(1))
 names=subprocess.run(['c++filt']+[r['name'] for r in rows],capture_output=True,text=True).stdout.split('\n')
 for r,n in zip(rows,names):
-    print(f\"$u  {n[:90]:90s} vgpr {r.get('VGPRs')} scratch {r.get('ScratchSize')} occ {r.get('Occupancy')} sspill {r.get('SGPRs')}\")
+    print(f\"$u  {n[:90]:90s} vgpr {r.get('VGPRs')} scratch {r.get('ScratchSize')} occ {r.get('Occupancy')} sspill {r.get('SGPRsSpill')} vspill {r.get('VGPRsSpill')}\")
 "
 done
 rm -f /tmp/kr_$$.o

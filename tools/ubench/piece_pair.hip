@@ -2,7 +2,10 @@
 //   1. explicit-register rows: v_bitop3_b32 with a scalar third source against three vector sources, a scalar constant's
 //      way into a vector register (v_mov_b32, v_bfe_i32), and s_bfe_i32 read by the very next vector instruction;
 //   2. the kernel's block in its own shape, three waves per SIMD (45 184 B of LDS per workgroup and at most 168 VGPRs,
-//      as the kernel has them): today's per-block form against the block-pair form with its constants in vector registers.
+//      as the kernel has them): today's per-block form against the block-pair form with its constants in vector registers;
+//   3. the LDS-table body at three waves per SIMD and 45 184 + Q x 64 B of LDS per workgroup against four waves and
+//      40 064 + Q x 64 B (the plane reader's own layout, csrc/pass_lds.h; profiles/r13_reader_occupancy.txt): each alone and
+//      as two launches side by side on two streams, the rows alternating three times.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -o piece_pair piece_pair.hip
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -97,8 +100,8 @@ constexpr uint32_t kStoreIters = 256; // the plane store every wave reads, over 
 // lane's 16 plane bytes (asked for four iterations ahead), the piece test of eight slots, the OR of the masks and a rare
 // branch.  FORM: today's block with scalar constants, or the block pair with the constants in vector registers -- moved
 // there from s_bfe_i32's result, made by v_bfe_i32 from the scalar piece word, or read from an LDS table by broadcast.
-template <int Q, int FORM>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void piece_body(const uint8_t* planes, const uint32_t* piece_bits, uint32_t* out, uint32_t n_iter) {
+template <int Q, int FORM, int W = 3>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, W))) void piece_body(const uint8_t* planes, const uint32_t* piece_bits, uint32_t* out, uint32_t n_iter) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int kAhead = 4;
   const uint32_t lane = threadIdx.x & 63u;
@@ -275,6 +278,55 @@ template <int Q> void bodies(const uint8_t* planes, const uint32_t* pieces, uint
          t_a2 / t_a, same ? "equal" : "DIFFER");
 }
 
+// ---- section 3: the LDS-table body at three and at four waves per SIMD ----
+// W = 3: 45 184 B + the table (three workgroups per CU); W = 4: 40 064 B + the table (four).  `streams` launches of 509
+// workgroups side by side, ten in a row on each stream; returns ms per launch.
+template <int Q, int W> float run_occ(int streams, const uint8_t* planes, const uint32_t* pieces, uint32_t* out, hipStream_t* st, uint32_t* checksum) {
+  const uint32_t grid = 509, n_iter = 182, lds = (W == 4 ? 40064u : kBodyLds) + (uint32_t)Q * 64u;
+  hipEvent_t a, b, j; hipEventCreate(&a); hipEventCreate(&b); hipEventCreate(&j);
+  for (int s = 0; s < streams; ++s) hipLaunchKernelGGL((piece_body<Q, kPairLds, W>), dim3(grid), dim3(256), lds, st[s], planes, pieces, out + s * grid * 256u, n_iter);
+  hipDeviceSynchronize();
+  hipEventRecord(a, st[0]);
+  if (streams == 2) hipStreamWaitEvent(st[1], a, 0);
+  for (int r = 0; r < 10; ++r)
+    for (int s = 0; s < streams; ++s) hipLaunchKernelGGL((piece_body<Q, kPairLds, W>), dim3(grid), dim3(256), lds, st[s], planes, pieces, out + s * grid * 256u, n_iter);
+  if (streams == 2) { hipEventRecord(j, st[1]); hipStreamWaitEvent(st[0], j, 0); }
+  hipEventRecord(b, st[0]); hipEventSynchronize(b);
+  float ms; hipEventElapsedTime(&ms, a, b);
+  ms /= 10.f * (float)streams;
+  std::vector<uint32_t> h(grid * 256u);
+  hipMemcpy(h.data(), out, h.size() * 4, hipMemcpyDeviceToHost);
+  uint32_t sum = 0;
+  for (uint32_t v : h) sum += v;
+  *checksum = sum;
+  const double per = ms * 1e6 / ((double)grid * 4 * n_iter / 1024.0);
+  printf("occ  Q=%-2d %d waves/SIMD %6u B LDS  %s  %7.4f ms per launch  %7.1f ns per wave-block and SIMD (%6.0f cyc @2.4GHz)  checksum %08x\n", Q, W, lds,
+         streams == 2 ? "two side by side" : "alone           ", ms, per, per * 2.4, sum);
+  hipEventDestroy(a); hipEventDestroy(b); hipEventDestroy(j);
+  return ms;
+}
+template <int Q> bool occupancy_rows(const uint8_t* planes, const uint32_t* pieces, uint32_t* out, hipStream_t* st) {
+  bool gate = true, same = true;
+  uint32_t first = 0, sum = 0;
+  for (int streams = 1; streams <= 2; ++streams) {
+    float worst4 = 0.f, best3 = 1e9f;
+    for (int rep = 0; rep < 3; ++rep) {  // the rows alternate: a drift of the box hits both
+      const float t3 = run_occ<Q, 3>(streams, planes, pieces, out, st, &sum);
+      if (streams == 1 && rep == 0) first = sum;
+      same = same && sum == first;
+      const float t4 = run_occ<Q, 4>(streams, planes, pieces, out, st, &sum);
+      same = same && sum == first;
+      best3 = t3 < best3 ? t3 : best3;
+      worst4 = t4 > worst4 ? t4 : worst4;
+    }
+    printf("occ  Q=%-2d %s: slowest four-wave run %.4f ms, fastest three-wave run %.4f ms: %.3f\n", Q, streams == 2 ? "two side by side" : "alone", worst4, best3,
+           worst4 / best3);
+    gate = gate && worst4 < best3;
+  }
+  printf("occ  Q=%-2d gate (every four-wave run faster than every three-wave run) %s; checksums %s\n\n", Q, gate ? "passed" : "FAILED", same ? "equal" : "DIFFER");
+  return gate && same;
+}
+
 int main() {
   unsigned* d; hipMalloc(&d, 256 * 8 * 256 * 4);
   for (int w : {1, 2, 3, 4}) {
@@ -304,5 +356,11 @@ int main() {
   bodies<8>(planes, pieces, out);
   bodies<7>(planes, pieces, out);
   bodies<12>(planes, pieces, out);
+  uint32_t* out2; hipMalloc(&out2, 2 * 509 * 256 * 4);
+  hipStream_t st[2]; hipStreamCreate(&st[0]); hipStreamCreate(&st[1]);
+  bool gate = occupancy_rows<7>(planes, pieces, out2, st);
+  gate = occupancy_rows<8>(planes, pieces, out2, st) && gate;
+  gate = occupancy_rows<12>(planes, pieces, out2, st) && gate;
+  printf("occ  gate over Q = 7, 8, 12: %s\n", gate ? "passed" : "FAILED");
   return 0;
 }
