@@ -111,6 +111,8 @@ struct RawTicket {
 pub const ALL_MINIMA: u32 = 1;
 pub const WITHOUT_TRACE: u32 = 2;
 pub const TEXT_ON_DEVICE: u32 = 4;
+/// sassy_hip_fastq_parse only: keep the base qualities on the device (sassy_hip_reads_quality)
+pub const KEEP_QUALITY: u32 = 32;
 /// `min_costs` / `best_pattern`: no match of cost <= k.
 pub const NO_MATCH: u8 = 255;
 
@@ -180,6 +182,8 @@ extern "C" {
     pub fn sassy_hip_reads_text_bytes(r: *const RawReads) -> u64;
     pub fn sassy_hip_reads_longest(r: *const RawReads) -> u64;
     pub fn sassy_hip_reads_rem(r: *const RawReads) -> *const u32;
+    /// the device pointer of the qualities in the text's layout; null unless the batch was parsed with KEEP_QUALITY (32)
+    pub fn sassy_hip_reads_quality(r: *const RawReads) -> *const u8;
     pub fn sassy_hip_reads_free(r: *mut RawReads);
     // ... and the Hamming batch calls over it: the handle where the _many sibling takes texts, text_lens, n_texts
     fn sassy_hip_search_hamming_reads(s: *mut RawSearcher, patterns: *const *const u8, pattern_lens: *const usize, n_patterns: usize,
@@ -204,6 +208,9 @@ extern "C" {
     // paired-end overlap: read r of r1 against the reverse complement of read r of r2, `out` holds sassy_hip_reads_n(r1) records
     pub fn sassy_hip_read_overlaps(s: *mut RawSearcher, r1: *const RawReads, r2: *const RawReads, min_overlap: u32, k: usize,
                                    max_permille: u32, flags: u32, out: *mut ReadOverlap) -> c_int;
+    /// every pair with an accepted overlap merged into a new resident batch (one record per pair; free it with sassy_hip_reads_free)
+    pub fn sassy_hip_merge_pairs(s: *mut RawSearcher, r1: *const RawReads, r2: *const RawReads, min_overlap: u32, k: usize,
+                                 max_permille: u32, flags: u32, out_overlaps: *mut ReadOverlap, out_merged: *mut *mut RawReads) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

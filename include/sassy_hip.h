@@ -37,6 +37,8 @@ extern "C" {
                                        is still resident (sassy_hip_result_line_spans); every other call that takes flags
                                        refuses the bit with SASSY_HIP_EUNSUPPORTED, and so does sassy_hip_search together with
                                        SASSY_HIP_WITHOUT_TRACE (no match start to resolve) */
+#define SASSY_HIP_KEEP_QUALITY 32u  /* sassy_hip_fastq_parse only: the handle also keeps the base qualities on the device, in
+                                       the layout of its text (sassy_hip_reads_quality) */
 
 /* Full match record = reference Match (src/search.rs:35-62).  cigar is the SAM text the
  * reference's Cigar::to_string gives ("3=1X"), stored in the result's string pool.
@@ -664,7 +666,11 @@ void sassy_hip_fasta_free(sassy_hip_Fasta *f);
  *    the longest seq_len;
  *  - flags: SASSY_HIP_TEXT_ON_DEVICE: `raw` is a device pointer, 16-byte aligned and readable up to the next multiple of 64
  *    behind n; 0: host bytes, uploaded once.  Takes no searcher: it runs on the calling thread's current device, on
- *    `hip_stream` (NULL: the default stream), and returns when the table is on the host;
+ *    `hip_stream` (NULL: the default stream), and returns when the table is on the host.  SASSY_HIP_KEEP_QUALITY: the handle
+ *    also owns a quality buffer of text_bytes bytes in the layout of the text (sassy_hip_reads_quality): the quality of read
+ *    r lies at [seq_start, seq_start + seq_len), the pads and the 64 spare bytes are 0.  Only under this flag a record whose
+ *    quality is not as long as its sequence is SASSY_HIP_EINVAL (the message names the smallest such record; a file that is
+ *    malformed as well gets the verdict above).  Without the flag nothing is kept and sassy_hip_reads_quality is NULL;
  *  - refused before any device work: null arguments with n > 0, an unknown flag bit, a device pointer that is not 16-byte
  *    aligned, a first byte that is not '@' (SASSY_HIP_EINVAL; a device-resident first byte is read back first); more than
  *    2^31 - 1 super-tiles of 64 KiB, i.e. n > 2^47 - 65536 (SASSY_HIP_EUNSUPPORTED); no device SASSY_HIP_ENODEVICE.  More
@@ -675,7 +681,8 @@ void sassy_hip_fasta_free(sassy_hip_Fasta *f);
 typedef struct sassy_hip_ReadRecord {
   uint64_t id_start, id_len;     /* in raw: the id without '@' and without the '\r' */
   uint64_t seq_start, seq_len;   /* in the device text; seq_start a multiple of 64 */
-  uint64_t qual_start, qual_len; /* in raw */
+  uint64_t qual_start, qual_len; /* in raw; in a handle made by sassy_hip_merge_pairs: in the handle's own quality buffer
+                                    (qual_start == seq_start), and id_start == id_len == 0 there */
 } sassy_hip_ReadRecord;
 typedef struct sassy_hip_Reads sassy_hip_Reads;
 int sassy_hip_fastq_parse(const void *raw, uint64_t n, uint32_t flags, void *hip_stream, sassy_hip_Reads **out);
@@ -685,6 +692,7 @@ void *sassy_hip_reads_text(const sassy_hip_Reads *r);                          /
 uint64_t sassy_hip_reads_text_bytes(const sassy_hip_Reads *r);
 uint64_t sassy_hip_reads_longest(const sassy_hip_Reads *r);
 const uint32_t *sassy_hip_reads_rem(const sassy_hip_Reads *r); /* the device pointer */
+const uint8_t *sassy_hip_reads_quality(const sassy_hip_Reads *r); /* the device pointer; NULL where qualities were not kept */
 void sassy_hip_reads_free(sassy_hip_Reads *r);
 
 /* The Hamming batch calls over a resident read batch: each returns exactly what its _many sibling (sassy_hip_search_hamming_many,
@@ -779,6 +787,38 @@ typedef struct sassy_hip_ReadOverlap {
 } sassy_hip_ReadOverlap;
 int sassy_hip_read_overlaps(sassy_SearcherType *s, const sassy_hip_Reads *r1, const sassy_hip_Reads *r2, uint32_t min_overlap,
                             size_t k, uint32_t max_permille, uint32_t flags, sassy_hip_ReadOverlap *out /* sassy_hip_reads_n(r1) */);
+
+/* Paired-end merge (sassy_amd/csrc/merge_pairs.hip, arithmetic in merge_step.h): every pair with an accepted
+ * overlap becomes one merged read with consensus sequence and consensus quality, in a NEW read batch resident on the device
+ * that every _reads entry point takes.  The definition is tests/helpers/merge_pairs_ref.py.  Pair r: a = read r of r1 with
+ * qualities qa, b = the reverse complement of read r of r2 with r2's qualities reversed, qb; (d, ov, mm, n_accepted) = the
+ * pair's sassy_hip_read_overlaps record under min_overlap, k, max_permille.
+ *  - n_accepted == 0 (an empty read included): the pair is not merged, its merged read is empty;
+ *  - otherwise the merged read has L = max(la, d + lb) columns for d >= 0 and L = ov for d < 0 (read-through: r2's head and
+ *    r1's tail beyond the overlap are adapter and are dropped).  Column p is row p of a where p < la and row p - d of b where
+ *    0 <= p - d < lb;
+ *  - a column that one read covers takes its byte and quality; where both cover it and the bytes are equal (as bytes), that
+ *    byte with the higher quality; where they differ -- whether or not the profile's relation calls them a match --, the byte
+ *    of the higher quality, a's on a tie, with quality min(126, 33 + max(2, |qa - qb|)) (FLASH's rule with the tie fixed).  No
+ *    quality byte is validated;
+ *  - *out_merged: an ordinary sassy_hip_Reads on the searcher's device with qualities kept, ONE RECORD PER PAIR: record r is
+ *    empty iff pair r was not merged.  id_start = id_len = 0 (the ids are r1's), qual_start = seq_start and qual_len = seq_len
+ *    index the handle's own quality buffer.  Zero pairs, or no pair merged: text_bytes == 64.  The caller frees it with
+ *    sassy_hip_reads_free;
+ *  - out_overlaps, where given, receives exactly what sassy_hip_read_overlaps writes (sassy_hip_reads_n(r1) records);
+ *  - refused before any device work, in this order: everything sassy_hip_read_overlaps refuses, with its codes (out_overlaps
+ *    may be NULL); a handle that was parsed without SASSY_HIP_KEEP_QUALITY (SASSY_HIP_EINVAL); out_merged == NULL
+ *    (SASSY_HIP_EINVAL).  A Dna batch with other bytes than A, C, G, T is refused as there.  *out_merged is NULL after every
+ *    refusal;
+ *  - both input handles are only read.  Device work on the searcher's stream: the overlap kernel, the layout scan of the
+ *    parse over the merged lengths, one host wait for the layout's size, one write kernel indexed by 64-byte block of the
+ *    output.  Stats as sassy_hip_read_overlaps leaves them, with candidates = the number of merged pairs and scan_launches = 5
+ *    (the overlap kernel, the three kernels of the layout scan, the write kernel; the Dna look is not counted, as there).  Zero
+ *    pairs launch no kernel: scan_launches = 0. */
+int sassy_hip_merge_pairs(sassy_SearcherType *s, const sassy_hip_Reads *r1, const sassy_hip_Reads *r2, uint32_t min_overlap,
+                          size_t k, uint32_t max_permille, uint32_t flags,
+                          sassy_hip_ReadOverlap *out_overlaps /* may be NULL; sassy_hip_reads_n(r1) */,
+                          sassy_hip_Reads **out_merged);
 
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar

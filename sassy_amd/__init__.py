@@ -36,6 +36,7 @@ NO_MATCH = 255  # min_costs / best_pattern: no match of cost <= k
 TEXT_UNCHANGED = 8
 CLASS_MAX_CUBES = 256  # SASSY_HIP_CLASS_MAX_CUBES: cubes of one class pattern, all distinct sets together
 LINE_SPANS = 16  # sassy_hip_search only: resolve the matches to their lines (Result.line_spans)
+KEEP_QUALITY = 32  # sassy_hip_fastq_parse only: the handle keeps the base qualities on the device (DeviceReads(keep_quality=True))
 UINT64_MAX = (1 << 64) - 1
 UMI_METHODS = {"unique": 0, "cluster": 1, "directional": 2}  # SASSY_HIP_UMI_*: Searcher.umi_groups
 
@@ -167,6 +168,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_search_hamming_reads", "sassy_hip_hamming_best_pattern_reads", "sassy_hip_hamming_counts_reads",
     "sassy_hip_search_many_reads", "sassy_hip_min_costs_reads", "sassy_hip_best_pattern_reads", "sassy_hip_best_matches_reads",
     "sassy_hip_reads_relayout", "sassy_hip_read_overlaps",
+    "sassy_hip_reads_quality", "sassy_hip_merge_pairs",
 ]
 
 _lib = None
@@ -406,7 +408,7 @@ def lib():
     L.sassy_hip_fastq_parse.restype = C.c_int
     L.sassy_hip_fastq_parse.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.POINTER(vp)]
     for name, res in (("n", C.c_uint64), ("records", vp), ("text", vp), ("text_bytes", C.c_uint64), ("longest", C.c_uint64), ("rem", vp),
-                      ("free", None)):
+                      ("quality", vp), ("free", None)):
         fn = getattr(L, "sassy_hip_reads_" + name)
         fn.restype, fn.argtypes = res, [vp]
     # the _reads calls: a handle where the _many sibling takes texts, text_lens, n_texts
@@ -429,6 +431,8 @@ def lib():
     L.sassy_hip_reads_relayout.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint8, vp, vp]
     L.sassy_hip_read_overlaps.restype = C.c_int
     L.sassy_hip_read_overlaps.argtypes = [vp, vp, vp, C.c_uint32, sz, C.c_uint32, C.c_uint32, vp]
+    L.sassy_hip_merge_pairs.restype = C.c_int
+    L.sassy_hip_merge_pairs.argtypes = [vp, vp, vp, C.c_uint32, sz, C.c_uint32, C.c_uint32, vp, C.POINTER(vp)]
     L.sassy_hip_malloc.restype = vp
     L.sassy_hip_malloc.argtypes = [sz]
     L.sassy_hip_free.restype = None
@@ -555,9 +559,12 @@ def overlap_trims(rec, la: int, lb: int):
     return ov, min(la, d + lb), lb + d
 
 
-def fastq_from_sequences(seqs) -> bytes:
+def fastq_from_sequences(seqs, quals=None) -> bytes:
     """Minimal four-line FASTQ of a list of byte sequences, an empty id and an empty quality each: b"@\\n" + seq + b"\\n+\\n\\n".
-    A sequence that holds a line end would change the record structure and is refused."""
+    A sequence that holds a line end would change the record structure and is refused.  `quals`: a list of as many quality
+    strings, each as long as its sequence and free of line ends, which take the place of the empty quality lines."""
+    if quals is not None and len(quals) != len(seqs):
+        raise SassyHipError(f"from_sequences: {len(seqs)} sequences and {len(quals)} qualities")
     out = []
     for i, s in enumerate(seqs):
         if isinstance(s, str):
@@ -565,8 +572,47 @@ def fastq_from_sequences(seqs) -> bytes:
         s = bytes(s)
         if b"\n" in s or b"\r" in s:
             raise SassyHipError(f"from_sequences: sequence {i} holds a line end (\\n or \\r)")
-        out.append(b"@\n" + s + b"\n+\n\n")
+        q = b""
+        if quals is not None:
+            q = quals[i].encode() if isinstance(quals[i], str) else bytes(quals[i])
+            if b"\n" in q or b"\r" in q:
+                raise SassyHipError(f"from_sequences: quality {i} holds a line end (\\n or \\r)")
+            if len(q) != len(s):
+                raise SassyHipError(f"from_sequences: quality {i} has {len(q)} bytes, its sequence {len(s)}")
+        out.append(b"@\n" + s + b"\n+\n" + q + b"\n")
     return b"".join(out)
+
+
+def reads_to_fastq(reads, ids) -> bytes:
+    """FASTQ of a DeviceReads with kept qualities (a merged batch of `Searcher.merge_pairs`, say): record r is written under
+    ids[r] (str or bytes, without the '@'), empty records are skipped.  Two downloads -- the text and the quality buffer --
+    sliced with numpy on the host."""
+    import numpy as np
+    if len(ids) != len(reads):
+        raise SassyHipError(f"reads_to_fastq: {len(reads)} reads and {len(ids)} ids")
+    text = np.frombuffer(reads.download_text(), dtype=np.uint8)
+    qual = np.frombuffer(reads.download_quality_text(), dtype=np.uint8)
+    keep = np.flatnonzero(reads.seq_lens)
+    if not keep.size:
+        return b""
+    lens = reads.seq_lens[keep].astype(np.int64)
+    starts = reads.seq_starts[keep].astype(np.int64)
+    heads = [b"@" + (i.encode() if isinstance(i, str) else bytes(i)) + b"\n" for i in (ids[r] for r in keep.tolist())]
+    head_lens = np.array([len(h) for h in heads], dtype=np.int64)
+    rec_lens = head_lens + 2 * lens + 4  # '@id\n' seq '\n+\n' qual '\n'
+    at = np.concatenate([[0], np.cumsum(rec_lens)[:-1]])
+    out = np.empty(int(rec_lens.sum()), dtype=np.uint8)
+    # the bytes of every sequence (and quality) as one gather: source index = start + the position within its read
+    within = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+    src = np.repeat(starts, lens) + within
+    seq_at = at + head_lens
+    out[np.repeat(seq_at, lens) + within] = text[src]
+    out[np.repeat(seq_at + lens + 3, lens) + within] = qual[src]
+    out[np.repeat(at, head_lens) + (np.arange(int(head_lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(head_lens) - head_lens, head_lens))] = \
+        np.frombuffer(b"".join(heads), dtype=np.uint8)
+    mid = seq_at + lens  # '\n+\n' between the sequence and the quality, '\n' behind the quality
+    out[mid], out[mid + 1], out[mid + 2], out[mid + 3 + lens] = 10, 43, 10, 10
+    return out.tobytes()
 
 
 def line_tile() -> int:
@@ -1345,6 +1391,37 @@ class Searcher:
             for r in made:
                 r.free()
 
+    def merge_pairs(self, r1, r2, min_overlap: int = 10, k: int = OVERLAP_MAX_LEN, max_permille: int = 200, with_overlaps: bool = False):
+        """Every pair with an accepted overlap merged on the device (sassy_hip_merge_pairs): the overlap is `read_overlaps`'
+        under the same `min_overlap`, `k`, `max_permille`; the merged read is a up to the overlap, the consensus inside it
+        and b = reverse_complement(read of r2) behind it (a read-through pair: the overlap alone), with consensus qualities --
+        equal bytes take the higher quality, different bytes the byte of the higher quality (a's on a tie) and
+        min(126, 33 + max(2, |qa - qb|)).  Returns a new DeviceReads with kept qualities, ONE RECORD PER PAIR, empty where the
+        pair was not merged, which every call that takes a DeviceReads takes; with `with_overlaps` also `read_overlaps`'
+        array.  `r1`, `r2`: DeviceReads made with keep_quality=True, or lists of (sequence, quality) tuples.  The definition
+        is tests/helpers/merge_pairs_ref.py."""
+        import numpy as np
+        made = []
+        sources = [r if isinstance(r, DeviceReads) else fastq_from_sequences([x[0] for x in r], [x[1] for x in r]) for r in (r1, r2)]
+        try:
+            handles = []
+            for r in sources:
+                if not isinstance(r, DeviceReads):
+                    r = DeviceReads(r, keep_quality=True)
+                    made.append(r)
+                handles.append(r)
+            if not 0 <= int(min_overlap) < (1 << 32) or not 0 <= int(max_permille) < (1 << 32) or int(k) < 0:
+                raise SassyHipError("merge_pairs: min_overlap, k and max_permille must not be negative")
+            records = np.zeros(len(handles[0]), dtype=read_overlap_dtype()) if with_overlaps else None
+            out = C.c_void_p()
+            _check(lib().sassy_hip_merge_pairs(self._h, handles[0]._handle(), handles[1]._handle(), int(min_overlap), int(k), int(max_permille), 0,
+                                               records.ctypes.data if with_overlaps and len(records) else None, C.byref(out)))
+            merged = DeviceReads._adopt(out)
+            return (merged, records) if with_overlaps else merged
+        finally:
+            for r in made:
+                r.free()
+
     def search_all_alignments(self, pattern: bytes, text, k: int) -> List[List[Match]]:
         """Searcher::search_all_alignments (src/python.rs:117-135, src/search.rs:702-760): every alignment of cost <= k
         at every end position of search_all, grouped: one list per (strand, anchor) -- the anchor is text_end for
@@ -2003,13 +2080,25 @@ class DeviceReads:
     `seq_lens` the device buffer.  Malformed input raises SassyHipError and names the first bad record.  The definition is
     tests/helpers/fastq_ref.py."""
 
-    def __init__(self, raw, stream: int = 0):
-        import numpy as np
+    def __init__(self, raw, stream: int = 0, keep_quality: bool = False):
         addr, n, keep, on_dev = _ptr_len(raw)
-        self._raw, self._raw_on_device = keep, on_dev
+        self._raw, self._raw_on_device, self._adopted = keep, on_dev, False
         self._h = None
         out = C.c_void_p()
-        _check(lib().sassy_hip_fastq_parse(addr, n, TEXT_ON_DEVICE if on_dev else 0, stream or None, C.byref(out)))
+        _check(lib().sassy_hip_fastq_parse(addr, n, (TEXT_ON_DEVICE if on_dev else 0) | (KEEP_QUALITY if keep_quality else 0), stream or None,
+                                           C.byref(out)))
+        self._take(out)
+
+    @classmethod
+    def _adopt(cls, handle):
+        """A handle that another call made (Searcher.merge_pairs): no raw bytes, so no ids; the qualities are on the device."""
+        self = cls.__new__(cls)
+        self._raw, self._raw_on_device, self._adopted = None, False, True
+        self._take(handle)
+        return self
+
+    def _take(self, out):
+        import numpy as np
         self._h = out
         count = int(lib().sassy_hip_reads_n(out))
         dt = read_record_dtype()
@@ -2022,12 +2111,14 @@ class DeviceReads:
         self.ptr = int(lib().sassy_hip_reads_text(out) or 0)
         self.text_bytes = int(lib().sassy_hip_reads_text_bytes(out))
         self.longest = int(lib().sassy_hip_reads_longest(out))
+        self.qual_ptr = int(lib().sassy_hip_reads_quality(out) or 0)  # 0: the qualities were not kept
 
     @classmethod
-    def from_sequences(cls, seqs, stream: int = 0):
+    def from_sequences(cls, seqs, quals=None, stream: int = 0, keep_quality: Optional[bool] = None):
         """A read batch of a list of byte sequences: they are wrapped into minimal four-line FASTQ (fastq_from_sequences: an
-        empty id and an empty quality each) and parsed like any chunk.  A sequence that holds '\\n' or '\\r' is refused."""
-        return cls(fastq_from_sequences(seqs), stream)
+        empty id and an empty quality each) and parsed like any chunk.  A sequence that holds '\\n' or '\\r' is refused.
+        `quals`: a list of as many qualities of equal lengths; they are kept on the device unless keep_quality=False."""
+        return cls(fastq_from_sequences(seqs, quals), stream, keep_quality=(quals is not None) if keep_quality is None else keep_quality)
 
     def __len__(self) -> int:
         return len(self.id_starts)
@@ -2050,10 +2141,24 @@ class DeviceReads:
         return self._raw[a:a + n].tobytes()
 
     def id(self, i: int) -> str:
+        if self._adopted:
+            raise SassyHipError("DeviceReads: a merged batch has no ids of its own: record r is pair r, and the ids are R1's")
         return self._raw_bytes(int(self.id_starts[i]), int(self.id_lens[i])).decode()
 
     def quality(self, i: int) -> bytes:
+        """Read i's quality: from the device buffer where the handle keeps one, else out of the raw bytes."""
+        if self.qual_ptr:
+            self._live()
+            n = int(self.seq_lens[i])
+            return DeviceText(self.qual_ptr + int(self.seq_starts[i]), n).download() if n else b""
         return self._raw_bytes(int(self.qual_starts[i]), int(self.qual_lens[i]))
+
+    def download_quality_text(self) -> bytes:
+        """The whole quality buffer, the twin of download_text: the text's layout, pads and the 64 spare bytes included."""
+        self._live()
+        if not self.qual_ptr:
+            raise SassyHipError("DeviceReads: the qualities were not kept (keep_quality=True keeps them on the device)")
+        return DeviceText(self.qual_ptr, self.text_bytes).download()
 
     def text(self, i: int) -> DeviceText:
         """Read i's sequence on the device."""
@@ -2091,6 +2196,7 @@ class DeviceReads:
                 pass
             self._h = None
             self.ptr = 0
+            self.qual_ptr = 0
 
     def __del__(self):
         self.free()

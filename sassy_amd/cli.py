@@ -96,6 +96,14 @@ into adapter); all zero offsets and insert 0 where nothing is accepted.  A heade
 
     id  offset  overlap  mismatches  accepted  insert  keep1  keep2
 
+`merge R1 R2 [-o MERGED.fq] [--unmerged1 U1.fq --unmerged2 U2.fq] [--min-overlap N] [-k K] [--max-permille P] [--alphabet
+dna|iupac] [--tsv]` merges the two reads of every pair that `overlap` finds an accepted offset for, through
+`Searcher.merge_pairs`, on the device: the merged read is R1 up to the overlap, the consensus inside it (equal bases take the
+higher quality; of different ones the base of the higher quality wins, R1's on a tie, with quality
+min(126, 33 + max(2, |q1 - q2|))) and the reverse complement of R2 behind it; a pair that reads through keeps its overlap
+alone.  Merged records go to `-o` (default stdout) under R1's id; pairs without an accepted offset are copied unchanged to
+`--unmerged1` / `--unmerged2` where these are given; `--tsv` writes `overlap`'s rows to MERGED.fq.tsv.
+
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
 one block per match, sorted by (start, end): `PATH:LINE:COL:COST:` and the line(s) the match lies in -- LINE and the line's
@@ -556,6 +564,58 @@ def overlap_parser(sub):
     return cp
 
 
+def run_merge(args, searcher, out) -> int:
+    """`merge`: every pair with an accepted overlap as one FASTQ record under R1's id (Searcher.merge_pairs; out: a binary
+    stream); the pairs without one go, unchanged, to --unmerged1 / --unmerged2 where these are given."""
+    from . import reads_to_fastq
+    from .fastx import read_fastq_pair_device_batches
+    u1 = open(args.unmerged1, "wb") if args.unmerged1 else None
+    u2 = open(args.unmerged2, "wb") if args.unmerged2 else None
+    tsv = open(args.tsv_path, "w") if args.tsv_path else None
+    try:
+        if tsv:
+            tsv.write(OVERLAP_HEADER)
+        for b1, b2 in read_fastq_pair_device_batches(args.r1, args.r2, BATCH_BYTES, keep_quality=True):
+            merged = None
+            try:  # (a refused batch -- a read over 512 bases, another letter under dna -- lets go of its device memory as well)
+                merged, records = searcher.merge_pairs(b1.texts, b2.texts, args.min_overlap, args.k, args.max_permille, with_overlaps=True)
+                ids = [b1.id(i) for i in range(len(b1))]
+                out.write(reads_to_fastq(merged, ids))
+                if tsv:
+                    tsv.writelines(overlap_rows(ids, records, b1.texts.seq_lens, b2.texts.seq_lens))
+                for r in (merged.seq_lens == 0).nonzero()[0].tolist():
+                    if u1:
+                        u1.write(b1.record(r))
+                    if u2:
+                        u2.write(b2.record(r))
+            finally:
+                if merged is not None:
+                    merged.free()
+                b1.free()
+                b2.free()
+        out.flush()
+    finally:
+        for fh in (u1, u2, tsv):
+            if fh:
+                fh.close()
+    return 0
+
+
+def merge_parser(sub):
+    cp = sub.add_parser("merge", help="merge the two reads of every pair that overlap (paired-end FASTQ) into one FASTQ record")
+    cp.add_argument("r1", metavar="R1", help="FASTQ of the first reads")
+    cp.add_argument("r2", metavar="R2", help="FASTQ of the second reads, in the same order")
+    cp.add_argument("-o", "--output", default="", help="the merged FASTQ, under R1's ids (default: stdout)")
+    cp.add_argument("--unmerged1", default="", help="R1's records of the pairs that were not merged, unchanged")
+    cp.add_argument("--unmerged2", default="", help="R2's records of the pairs that were not merged, unchanged")
+    cp.add_argument("--min-overlap", type=int, default=10, help="rows an accepted overlap has at least (default 10)")
+    cp.add_argument("-k", type=int, default=512, help="mismatches an accepted overlap has at most (default: no limit)")
+    cp.add_argument("--max-permille", type=int, default=200, help="mismatches per thousand rows an accepted overlap has at most (default 200)")
+    cp.add_argument("-a", "--alphabet", type=str.lower, choices=["dna", "iupac"], default="dna")
+    cp.add_argument("--tsv", action="store_true", help="also write `overlap`'s rows, to MERGED.fq.tsv beside -o (needs -o)")
+    return cp
+
+
 def load_primers(path: str) -> List[Tuple[str, bytes, bytes]]:
     """PRIMERS of `amplicon`: rows of name<TAB>fwd<TAB>rev (empty lines and lines from `#` on skipped)."""
     pairs = []
@@ -663,7 +723,19 @@ def main(argv=None) -> int:
     pairs_parser(sub)
     cluster_parser(sub)
     overlap_parser(sub)
+    merge_parser(sub)
     args = ap.parse_args(argv)
+    if args.cmd == "merge":
+        if args.min_overlap < 1 or args.k < 0 or not 0 <= args.max_permille <= 1000:
+            ap.error("merge takes --min-overlap >= 1, -k >= 0 and 0 <= --max-permille <= 1000")
+        if args.tsv and not args.output:
+            ap.error("merge --tsv writes beside the merged file: it needs -o")
+        args.tsv_path = args.output + ".tsv" if args.tsv else ""
+        searcher = Searcher(args.alphabet, rc=False)
+        if args.output:
+            with open(args.output, "wb") as fh:
+                return run_merge(args, searcher, fh)
+        return run_merge(args, searcher, sys.stdout.buffer)
     if args.cmd == "overlap":
         if args.min_overlap < 1 or args.k < 0 or not 0 <= args.max_permille <= 1000:
             ap.error("overlap takes --min-overlap >= 1, -k >= 0 and 0 <= --max-permille <= 1000")

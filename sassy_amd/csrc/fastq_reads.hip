@@ -15,11 +15,15 @@
 //                        lengths rounded up to 64 in blocks of 1024 records and one workgroup over the block sums
 //   fastq_rec_write_kernel  the record table, starts[] and lens[] of the batch, the longest read; the layout's size  -> host
 //   fastq_copy_kernel    a lane per 64-byte block of the OUTPUT: its read by ham_text_of, its bytes from the unaligned source
-//                        with 16-byte loads and stores, zeros behind the read's end and in the 64 spare bytes, rem[block]
+//                        with 16-byte loads and stores, zeros behind the read's end and in the 64 spare bytes, rem[block].
+//                        Under SASSY_HIP_KEEP_QUALITY it runs once more, over line 4t + 3, into the handle's quality buffer
 // Two host waits size what cannot be sized before: the line table (L) and the text (layout bytes).
+// The record kernels take their lengths from a source: the lines of a file (the parse) or the overlap records of a batch of
+// pairs (reads_layout_merged, for merge_pairs.hip), so the layout rule and its two-level scan have one owner.
 #include "host_internal.h"
 #include "fastq_step.h"
 #include "hamming_step.h"
+#include "merge_step.h"
 
 // (struct sassy_hip_Reads: host_internal.h -- reads_relayout.hip reads it too)
 
@@ -40,6 +44,8 @@ struct FastqTotals {
   unsigned long long bad_line;  // the smallest line that lacks its marker
   unsigned long long layout;    // bytes of the layout
   unsigned long long longest;   // the longest sequence
+  unsigned long long bad_qual;  // the smallest record whose quality is not as long as its sequence (looked at on request)
+  unsigned long long filled;    // records that are not empty (counted for the sources that ask for it)
 };
 
 // The lane's 64 bytes of a tile as words.  raw is 16-byte aligned and readable up to the next multiple of 64 behind n, so a
@@ -189,14 +195,51 @@ __device__ __forceinline__ uint64_t block_scan256(uint64_t v, unsigned long long
   return sh[threadIdx.x] - v;
 }
 
-// The layout bytes of every block of kRecBlock records.  (n_lines = 4 n_rec here and below.)
-__global__ __launch_bounds__(256) void fastq_rec_sum_kernel(const uint64_t* line_start, const uint8_t* line_cr, uint64_t n_rec, uint64_t virt,
-                                                            unsigned long long* block_sum) {
+// Where the record kernels take the lengths from, and what a record says besides.  The lines of a file ...
+struct LineSource {
+  const uint64_t* line_start;
+  const uint8_t* line_cr;
+  uint64_t n_rec, virt;
+  bool check_qual;  // report the smallest record with qual_len != seq_len
+  static constexpr bool kCountFilled = false;
+  __device__ __forceinline__ uint64_t len(uint64_t r) const { return line_len(line_start, line_cr, 4 * r + 1, 4 * n_rec, virt); }
+  __device__ __forceinline__ sassy_hip_ReadRecord record(uint64_t r, uint64_t at, uint64_t seq_len) const {
+    sassy_hip_ReadRecord R;
+    R.id_start = line_start[4 * r] + 1;
+    R.id_len = line_len(line_start, line_cr, 4 * r, 4 * n_rec, virt) - 1;  // (the line begins with '@': checked before the table is used)
+    R.seq_start = at;
+    R.seq_len = seq_len;
+    R.qual_start = line_start[4 * r + 3];
+    R.qual_len = line_len(line_start, line_cr, 4 * r + 3, 4 * n_rec, virt);
+    return R;
+  }
+};
+// ... or the overlap records of a batch of pairs: read r is the merged read of pair r (merge_step.h), empty where the pair
+// has no accepted overlap.  No ids; the quality lies in the handle's own buffer, where the sequence lies in the text.
+struct MergedSource {
+  const sassy_hip_ReadOverlap* rec;
+  const uint64_t *len1, *len2;
+  static constexpr bool check_qual = false;
+  static constexpr bool kCountFilled = true;
+  __device__ __forceinline__ uint64_t len(uint64_t r) const {
+    const sassy_hip_ReadOverlap o = rec[r];
+    // (a record with an accepted offset comes from reads of at most kOvlMaxLen bytes; the clamp keeps a length sane whatever it holds)
+    const uint32_t la = (uint32_t)min(len1[r], (uint64_t)kOvlMaxLen), lb = (uint32_t)min(len2[r], (uint64_t)kOvlMaxLen);
+    return min(mrg_length(la, lb, OvlBest{o.offset, o.overlap, o.mismatches, o.n_accepted}), 2u * kOvlMaxLen);
+  }
+  __device__ __forceinline__ sassy_hip_ReadRecord record(uint64_t, uint64_t at, uint64_t seq_len) const {
+    return sassy_hip_ReadRecord{0, 0, at, seq_len, at, seq_len};
+  }
+};
+
+// The layout bytes of every block of kRecBlock records.
+template <typename Src>
+__global__ __launch_bounds__(256) void fastq_rec_sum_kernel(Src S, uint64_t n_rec, unsigned long long* block_sum) {
   __shared__ unsigned long long sh[256];
   const uint64_t r0 = (uint64_t)blockIdx.x * kRecBlock + (uint64_t)threadIdx.x * kRecPerThread;
   uint64_t mine = 0;
   for (uint32_t j = 0; j < kRecPerThread; ++j)
-    if (r0 + j < n_rec) mine += fq_round64(line_len(line_start, line_cr, 4 * (r0 + j) + 1, 4 * n_rec, virt));
+    if (r0 + j < n_rec) mine += fq_round64(S.len(r0 + j));
   uint64_t total;
   (void)block_scan256(mine, sh, &total);
   if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
@@ -230,48 +273,52 @@ __global__ __launch_bounds__(1024) void fastq_rec_top_kernel(unsigned long long*
 }
 
 // The record table, the batch's starts[] and lens[] (table: starts first), the longest read.
-__global__ __launch_bounds__(256) void fastq_rec_write_kernel(const uint64_t* line_start, const uint8_t* line_cr, uint64_t n_rec, uint64_t virt,
-                                                              const unsigned long long* block_off, sassy_hip_ReadRecord* rec, uint64_t* table,
-                                                              FastqTotals* totals) {
+template <typename Src>
+__global__ __launch_bounds__(256) void fastq_rec_write_kernel(Src S, uint64_t n_rec, const unsigned long long* block_off, sassy_hip_ReadRecord* rec,
+                                                              uint64_t* table, FastqTotals* totals) {
   __shared__ unsigned long long sh[256];
-  const uint64_t r0 = (uint64_t)blockIdx.x * kRecBlock + (uint64_t)threadIdx.x * kRecPerThread, n_lines = 4 * n_rec;
+  const uint64_t r0 = (uint64_t)blockIdx.x * kRecBlock + (uint64_t)threadIdx.x * kRecPerThread;
   uint64_t lens[kRecPerThread], mine = 0, longest = 0;
+  uint32_t filled = 0;
 #pragma unroll
   for (uint32_t j = 0; j < kRecPerThread; ++j) {
-    lens[j] = r0 + j < n_rec ? line_len(line_start, line_cr, 4 * (r0 + j) + 1, n_lines, virt) : 0;
+    lens[j] = r0 + j < n_rec ? S.len(r0 + j) : 0;
     mine += fq_round64(lens[j]);
     longest = max(longest, lens[j]);
+    filled += lens[j] != 0;
   }
   uint64_t total;
   uint64_t at = block_off[blockIdx.x] + block_scan256(mine, sh, &total);
+  unsigned long long bad = kNoBadLine;
 #pragma unroll
   for (uint32_t j = 0; j < kRecPerThread; ++j) {
     const uint64_t r = r0 + j;
     if (r >= n_rec) break;
-    sassy_hip_ReadRecord R;
-    R.id_start = line_start[4 * r] + 1;
-    R.id_len = line_len(line_start, line_cr, 4 * r, n_lines, virt) - 1;  // (the line begins with '@': checked before the table is used)
-    R.seq_start = at;
-    R.seq_len = lens[j];
-    R.qual_start = line_start[4 * r + 3];
-    R.qual_len = line_len(line_start, line_cr, 4 * r + 3, n_lines, virt);
+    const sassy_hip_ReadRecord R = S.record(r, at, lens[j]);
+    if (S.check_qual && R.qual_len != R.seq_len && r < bad) bad = r;
     rec[r] = R;
     table[r] = at;
     table[n_rec + r] = lens[j];
     at += fq_round64(lens[j]);
   }
+  if (bad != kNoBadLine) atomicMin(&totals->bad_qual, bad);  // (well-formed input never comes here)
   // one atomic per wavefront at the most, and none once the maximum stands: reads of one length would otherwise queue
   // every thread of the grid on one address
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) longest = max(longest, (uint64_t)__shfl_xor((unsigned long long)longest, o, 64));
   if ((threadIdx.x & 63u) == 0 && longest > __hip_atomic_load(&totals->longest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
     atomicMax(&totals->longest, (unsigned long long)longest);
+  if constexpr (Src::kCountFilled) {
+    filled = wave_sum(filled);
+    if ((threadIdx.x & 63u) == 0 && filled) atomicAdd(&totals->filled, (unsigned long long)filled);
+  }
 }
 
 // Pass three: a lane per 64-byte block of the layout, and one more for the spare bytes behind it.  n_pad: up to where raw is
-// readable (the next multiple of 64 behind n).
-__global__ __launch_bounds__(256) void fastq_copy_kernel(const uint8_t* raw, uint64_t n_pad, const uint64_t* line_start, const uint64_t* table,
-                                                         uint32_t n_rec, uint64_t n_blocks, uint8_t* text, uint32_t* rem) {
+// readable (the next multiple of 64 behind n).  `line`: which line of a record is copied -- 1, the sequence, into the text, or
+// 3, the quality, into a buffer of the same layout (rem: null then, it is the text's).
+__global__ __launch_bounds__(256) void fastq_copy_kernel(const uint8_t* raw, uint64_t n_pad, const uint64_t* line_start, uint32_t line,
+                                                         const uint64_t* table, uint32_t n_rec, uint64_t n_blocks, uint8_t* text, uint32_t* rem) {
   const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b > n_blocks) return;
   uint32_t out[16];
@@ -282,8 +329,8 @@ __global__ __launch_bounds__(256) void fastq_copy_kernel(const uint8_t* raw, uin
     const uint32_t t = ham_text_of([&](uint32_t i) { return table[i]; }, n_rec, b * 64);
     const uint64_t start = table[t];
     const uint32_t left = ham_rem(b, start, table[(uint64_t)n_rec + t]);
-    rem[b] = left;
-    const uint64_t src = line_start[4ull * t + 1] + (b * 64 - start), a = src & ~15ull;
+    if (rem) rem[b] = left;
+    const uint64_t src = line_start[4ull * t + line] + (b * 64 - start), a = src & ~15ull;
     uint32_t w[20];
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
@@ -298,9 +345,11 @@ __global__ __launch_bounds__(256) void fastq_copy_kernel(const uint8_t* raw, uin
   for (int j = 0; j < 4; ++j) dst[j] = make_uint4(out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]);
 }
 
-// device memory of one call
+// device memory of one call; who: the call's name, for its messages
 struct Temps {
+  const char* who;
   std::vector<void*> p;
+  explicit Temps(const char* who_) : who(who_) {}
   ~Temps() {
     for (void* x : p) (void)hipFree(x);
   }
@@ -310,7 +359,7 @@ struct Temps {
     const hipError_t e = hipMalloc(&x, std::max<uint64_t>(count, 1) * sizeof(T));
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      return fail(SASSY_HIP_ENOMEM, "fastq_parse: out of device memory (" + std::to_string(count * sizeof(T)) + " bytes)");
+      return fail(SASSY_HIP_ENOMEM, std::string(who) + ": out of device memory (" + std::to_string(count * sizeof(T)) + " bytes)");
     }
     p.push_back(x);
     *out = static_cast<T*>(x);
@@ -319,11 +368,11 @@ struct Temps {
 };
 
 template <typename T>
-int own(T** out, uint64_t count, const char* what) {
+int own(T** out, uint64_t count, const char* what, const char* who) {
   if (hipMalloc(reinterpret_cast<void**>(out), std::max<uint64_t>(count, 1) * sizeof(T)) != hipSuccess) {
     (void)hipGetLastError();
     *out = nullptr;
-    return fail(SASSY_HIP_ENOMEM, "fastq_parse: out of device memory (" + std::to_string(count * sizeof(T)) + " bytes of " + what + ")");
+    return fail(SASSY_HIP_ENOMEM, std::string(who) + ": out of device memory (" + std::to_string(count * sizeof(T)) + " bytes of " + what + ")");
   }
   return 0;
 }
@@ -336,10 +385,55 @@ int malformed(uint64_t n_lines, uint64_t bad_line) {
   return fail(SASSY_HIP_EINVAL, rec + ": it has " + std::to_string(n_lines - 4 * v.record) + " of its four lines (strict four-line FASTQ)");
 }
 
+// The record kernels over a source of n_rec lengths: the handle's device table, the records on the device (*d_rec, T's) and the
+// totals on the host.  d_totals is initialised by the caller; the one host wait of the layout is here.
+template <typename Src>
+int layout_records(const Src& S, uint64_t n_rec, hipStream_t st, Temps& T, sassy_hip_Reads* F, FastqTotals* d_totals, FastqTotals* tot,
+                   sassy_hip_ReadRecord** d_rec) {
+  const uint64_t n_blocks = (n_rec + kRecBlock - 1) / kRecBlock;
+  unsigned long long* block_sum = nullptr;
+  if (int rc = T.get(&block_sum, n_blocks + 1)) return rc;
+  if (int rc = T.get(d_rec, n_rec)) return rc;
+  if (int rc = own(&F->d_table, 2 * n_rec, "read table", T.who)) return rc;
+  hipLaunchKernelGGL(fastq_rec_sum_kernel<Src>, dim3((uint32_t)n_blocks), dim3(256), 0, st, S, n_rec, block_sum);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fastq_rec_top_kernel, dim3(1), dim3(1024), 0, st, block_sum, n_blocks, d_totals);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fastq_rec_write_kernel<Src>, dim3((uint32_t)n_blocks), dim3(256), 0, st, S, n_rec, (const unsigned long long*)block_sum, *d_rec,
+                     F->d_table, d_totals);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(tot, d_totals, sizeof(*tot), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+// The buffers the totals size: the text, the block table and, on request, the quality buffer of the text's layout.  who: the
+// call's name, here and below.
+int layout_buffers(const FastqTotals& tot, bool keep_quality, sassy_hip_Reads* F, const char* who) {
+  F->longest = tot.longest;
+  F->text_bytes = tot.layout + 64;
+  if (int rc = own(&F->d_text, F->text_bytes, "text", who)) return rc;
+  if (keep_quality)
+    if (int rc = own(&F->d_qual, F->text_bytes, "quality", who)) return rc;
+  if (int rc = own(&F->d_rem, tot.layout / 64, "block table", who)) return rc;
+  if (tot.layout / 64 + 1 + 255 > 0xFFFFFFFFull * 256ull) return fail(SASSY_HIP_EUNSUPPORTED, std::string(who) + ": the layout is too long for a grid");
+  return 0;
+}
+// the record table's host copy; returns when it has landed.  lane: a searcher's, whose pinned buffers carry the copy as they
+// carry every result's; the parse has no searcher and copies plainly
+int take_records(const sassy_hip_ReadRecord* d_rec, uint64_t n_rec, hipStream_t st, ScanLane* lane, sassy_hip_Reads* F, const char* who) {
+  F->records.reset(new (std::nothrow) sassy_hip_ReadRecord[n_rec]);
+  if (!F->records) return fail(SASSY_HIP_ENOMEM, std::string(who) + ": out of host memory (" + std::to_string(n_rec) + " records)");
+  F->n_records = n_rec;
+  if (lane) return lane->download(F->records.get(), d_rec, n_rec * sizeof(sassy_hip_ReadRecord));
+  HIP_TRY(hipMemcpyAsync(F->records.get(), d_rec, n_rec * sizeof(sassy_hip_ReadRecord), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
 // last_is_nl: byte n - 1 is '\n'
-int parse_on_device(const uint8_t* d_raw, uint64_t n, bool last_is_nl, hipStream_t st, sassy_hip_Reads* F) {
+int parse_on_device(const uint8_t* d_raw, uint64_t n, bool last_is_nl, bool keep_quality, hipStream_t st, sassy_hip_Reads* F) {
   const uint64_t n_tiles = (n + kTile - 1) / kTile, n_super = (n + kSuper - 1) / kSuper;
-  Temps T;
+  Temps T("fastq_parse");
   uint32_t *tile_pre = nullptr, *super_sum = nullptr;
   unsigned long long* super_pre = nullptr;
   FastqTotals* d_totals = nullptr;
@@ -347,7 +441,7 @@ int parse_on_device(const uint8_t* d_raw, uint64_t n, bool last_is_nl, hipStream
   if (int rc = T.get(&super_sum, n_super)) return rc;
   if (int rc = T.get(&super_pre, n_super + 1)) return rc;
   if (int rc = T.get(&d_totals, 1)) return rc;
-  const FastqTotals zero{kNoBadLine, 0, 0};
+  const FastqTotals zero{kNoBadLine, 0, 0, kNoBadLine, 0};
   HIP_TRY(hipMemcpyAsync(d_totals, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(fastq_count_kernel, dim3((uint32_t)n_super), dim3(256), 0, st, d_raw, n, n_tiles, tile_pre, super_sum);
   HIP_TRY(hipGetLastError());
@@ -375,39 +469,26 @@ int parse_on_device(const uint8_t* d_raw, uint64_t n, bool last_is_nl, hipStream
     return malformed(n_lines, tot.bad_line);
   }
 
-  const uint64_t n_blocks = (n_rec + kRecBlock - 1) / kRecBlock, virt = fq_virtual_start(n, last_is_nl);
-  unsigned long long* block_sum = nullptr;
   sassy_hip_ReadRecord* d_rec = nullptr;
-  if (int rc = T.get(&block_sum, n_blocks + 1)) return rc;
-  if (int rc = T.get(&d_rec, n_rec)) return rc;
-  if (int rc = own(&F->d_table, 2 * n_rec, "read table")) return rc;
-  hipLaunchKernelGGL(fastq_rec_sum_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, (const uint64_t*)line_start, (const uint8_t*)line_cr, n_rec,
-                     virt, block_sum);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(fastq_rec_top_kernel, dim3(1), dim3(1024), 0, st, block_sum, n_blocks, d_totals);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(fastq_rec_write_kernel, dim3((uint32_t)n_blocks), dim3(256), 0, st, (const uint64_t*)line_start, (const uint8_t*)line_cr, n_rec,
-                     virt, (const unsigned long long*)block_sum, d_rec, F->d_table, d_totals);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(&tot, d_totals, sizeof(tot), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  const LineSource S{line_start, line_cr, n_rec, fq_virtual_start(n, last_is_nl), keep_quality};
+  if (int rc = layout_records(S, n_rec, st, T, F, d_totals, &tot, &d_rec)) return rc;
   if (tot.bad_line != kNoBadLine) return malformed(n_lines, tot.bad_line);  // (the lengths of such an input mean nothing)
+  if (tot.bad_qual != kNoBadLine)  // (looked at under SASSY_HIP_KEEP_QUALITY only, and behind every older verdict)
+    return fail(SASSY_HIP_EINVAL, "fastq_parse: record " + std::to_string(tot.bad_qual) +
+                                      ": its quality is not as long as its sequence (SASSY_HIP_KEEP_QUALITY keeps one quality byte per base)");
 
-  const uint64_t layout = tot.layout, text_blocks = layout / 64;
-  F->longest = tot.longest;
-  F->text_bytes = layout + 64;
-  if (int rc = own(&F->d_text, F->text_bytes, "text")) return rc;
-  if (int rc = own(&F->d_rem, text_blocks, "block table")) return rc;
-  if (text_blocks + 1 + 255 > 0xFFFFFFFFull * 256ull) return fail(SASSY_HIP_EUNSUPPORTED, "fastq_parse: the layout is too long for a grid");
-  hipLaunchKernelGGL(fastq_copy_kernel, dim3((uint32_t)((text_blocks + 1 + 255) / 256)), dim3(256), 0, st, d_raw, (n + 63) & ~63ull,
-                     (const uint64_t*)line_start, (const uint64_t*)F->d_table, (uint32_t)n_rec, text_blocks, F->d_text, F->d_rem);
+  if (int rc = layout_buffers(tot, keep_quality, F, T.who)) return rc;
+  const uint64_t text_blocks = tot.layout / 64;
+  const dim3 grid((uint32_t)((text_blocks + 1 + 255) / 256));
+  hipLaunchKernelGGL(fastq_copy_kernel, grid, dim3(256), 0, st, d_raw, (n + 63) & ~63ull, (const uint64_t*)line_start, 1u,
+                     (const uint64_t*)F->d_table, (uint32_t)n_rec, text_blocks, F->d_text, F->d_rem);
   HIP_TRY(hipGetLastError());
-  F->records.reset(new (std::nothrow) sassy_hip_ReadRecord[n_rec]);
-  if (!F->records) return fail(SASSY_HIP_ENOMEM, "fastq_parse: out of host memory (" + std::to_string(n_rec) + " records)");
-  F->n_records = n_rec;
-  HIP_TRY(hipMemcpyAsync(F->records.get(), d_rec, n_rec * sizeof(sassy_hip_ReadRecord), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return 0;
+  if (keep_quality) {
+    hipLaunchKernelGGL(fastq_copy_kernel, grid, dim3(256), 0, st, d_raw, (n + 63) & ~63ull, (const uint64_t*)line_start, 3u,
+                       (const uint64_t*)F->d_table, (uint32_t)n_rec, text_blocks, F->d_qual, (uint32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  return take_records(d_rec, n_rec, st, nullptr, F, T.who);
 }
 
 // ---- the batch calls over a handle ----
@@ -427,6 +508,26 @@ HamText reads_text(const sassy_hip_Reads* r) {
 
 }  // namespace
 
+// For merge_pairs.hip: a new handle of n reads whose lengths are the merged lengths of the pairs behind d_rec (the overlap
+// records of a call, on the device) and the two handles' length tables.  Leaves the table, the records and the longest read
+// in F and its text, quality and block buffers allocated, for the caller's kernel to fill; *n_merged: the reads that are not
+// empty.  n > 0.  lane: the searcher's, for its stream and its pinned buffers.
+int reads_layout_merged(const sassy_hip_ReadOverlap* d_rec, const uint64_t* d_len1, const uint64_t* d_len2, uint64_t n, ScanLane* lane,
+                        sassy_hip_Reads* F, uint64_t* n_merged) {
+  hipStream_t st = lane->stream;
+  Temps T("merge_pairs");
+  FastqTotals* d_totals = nullptr;
+  if (int rc = T.get(&d_totals, 1)) return rc;
+  const FastqTotals zero{kNoBadLine, 0, 0, kNoBadLine, 0};
+  HIP_TRY(hipMemcpyAsync(d_totals, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
+  FastqTotals tot{};
+  sassy_hip_ReadRecord* d_records = nullptr;
+  if (int rc = layout_records(MergedSource{d_rec, d_len1, d_len2}, n, st, T, F, d_totals, &tot, &d_records)) return rc;
+  if (int rc = layout_buffers(tot, true, F, T.who)) return rc;
+  *n_merged = tot.filled;
+  return take_records(d_records, n, st, lane, F, T.who);
+}
+
 }  // namespace sassy_hip
 
 using namespace sassy_hip;
@@ -436,8 +537,9 @@ extern "C" {
 int sassy_hip_fastq_parse(const void* raw, uint64_t n, uint32_t flags, void* hip_stream, sassy_hip_Reads** out) {
   if (out) *out = nullptr;
   if (!out || (!raw && n)) return fail(SASSY_HIP_EINVAL, "null argument");
-  if (flags & ~SASSY_HIP_TEXT_ON_DEVICE) return fail(SASSY_HIP_EINVAL, "fastq_parse takes SASSY_HIP_TEXT_ON_DEVICE only");
-  const bool on_device = (flags & SASSY_HIP_TEXT_ON_DEVICE) != 0;
+  if (flags & ~(SASSY_HIP_TEXT_ON_DEVICE | SASSY_HIP_KEEP_QUALITY))
+    return fail(SASSY_HIP_EINVAL, "fastq_parse takes SASSY_HIP_TEXT_ON_DEVICE only, and SASSY_HIP_KEEP_QUALITY");
+  const bool on_device = (flags & SASSY_HIP_TEXT_ON_DEVICE) != 0, keep_quality = (flags & SASSY_HIP_KEEP_QUALITY) != 0;
   if (on_device && ((uintptr_t)raw & 15) != 0) return fail(SASSY_HIP_EINVAL, "device pointer must be 16-byte aligned");
   if (n && !on_device && static_cast<const uint8_t*>(raw)[0] != '@') return fail(SASSY_HIP_EINVAL, "fastq_parse: the first byte is not '@'");
   if ((n + kSuper - 1) / kSuper > kMaxSuper)
@@ -460,6 +562,10 @@ int sassy_hip_fastq_parse(const void* raw, uint64_t n, uint32_t flags, void* hip
     F->text_bytes = 64;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&F->d_text), 64));
     HIP_TRY(hipMemsetAsync(F->d_text, 0, 64, st));
+    if (keep_quality) {
+      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&F->d_qual), 64));
+      HIP_TRY(hipMemsetAsync(F->d_qual, 0, 64, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
     *out = F.release();
     return 0;
@@ -486,7 +592,7 @@ int sassy_hip_fastq_parse(const void* raw, uint64_t n, uint32_t flags, void* hip
     }
     d_raw = d_up;
   }
-  const int rc = parse_on_device(d_raw, n, last == 0x0A, st, F.get());
+  const int rc = parse_on_device(d_raw, n, last == 0x0A, keep_quality, st, F.get());
   if (d_up) {
     if (rc != 0) (void)hipStreamSynchronize(st);
     (void)hipFree(d_up);
@@ -502,6 +608,7 @@ void* sassy_hip_reads_text(const sassy_hip_Reads* r) { return r ? r->d_text : nu
 uint64_t sassy_hip_reads_text_bytes(const sassy_hip_Reads* r) { return r ? r->text_bytes : 0; }
 uint64_t sassy_hip_reads_longest(const sassy_hip_Reads* r) { return r ? r->longest : 0; }
 const uint32_t* sassy_hip_reads_rem(const sassy_hip_Reads* r) { return r ? r->d_rem : nullptr; }
+const uint8_t* sassy_hip_reads_quality(const sassy_hip_Reads* r) { return r ? r->d_qual : nullptr; }
 void sassy_hip_reads_free(sassy_hip_Reads* r) {
   if (!r) return;
   r->release();

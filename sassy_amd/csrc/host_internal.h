@@ -9,6 +9,7 @@
 //   amplicons.hip     sassy_hip_hamming_amplicons: primer pairs joined on the sorted items of the Hamming scan (ham_walk_ranges, below)
 //   fastq_reads.hip   sassy_hip_fastq_parse: FASTQ into a resident read batch; sassy_hip_*_reads, the Hamming batch calls over it
 //   read_overlaps.hip sassy_hip_read_overlaps: the best overlap of read r of one resident batch with the reverse complement of read r of another
+//   merge_pairs.hip   sassy_hip_merge_pairs: every pair with an accepted overlap merged into a new resident batch, consensus sequence and quality
 //   c_abi.hip         the C-ABI of include/sassy.h + sassy_hip.h, the switch table, synthetic inputs
 #pragma once
 #include <hip/hip_runtime.h>
@@ -571,13 +572,15 @@ struct sassy_hip_Reads {
   uint64_t text_bytes = 0;      // the layout and the 64 spare bytes behind it
   uint64_t* d_table = nullptr;  // starts[n], then lens[n]: the order d_ham_texts has
   uint32_t* d_rem = nullptr;    // per block of the layout
+  uint8_t* d_qual = nullptr;    // the qualities in the text's layout, text_bytes of them; null where they were not kept
   uint64_t longest = 0;
   int device = -1;
   void release() {
     if (d_text) (void)hipFree(d_text);
     if (d_table) (void)hipFree(d_table);
     if (d_rem) (void)hipFree(d_rem);
-    d_text = nullptr; d_table = nullptr; d_rem = nullptr;
+    if (d_qual) (void)hipFree(d_qual);
+    d_text = nullptr; d_table = nullptr; d_rem = nullptr; d_qual = nullptr;
   }
 };
 
@@ -1370,6 +1373,15 @@ struct ReadsTexts {
   TextSource src;
 };
 int reads_as_source(sassy_SearcherType* s, const sassy_hip_Reads* reads, uint32_t flags, const char* who, ReadsTexts* out);
+// read_overlaps.hip, for merge_pairs.hip: the overlap call behind its refusals (device, stats, k's cut, the Dna look, the
+// kernel).  The records stay in s->d_overlaps; they are copied to `out` only where it is given.
+int overlaps_resident(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, size_t k,
+                      uint32_t max_permille, sassy_hip_ReadOverlap* out);
+// ... and what a refusal of overlap_step.h's ovl_refusal says and returns in a call named `who`
+int overlap_refused(uint32_t why, const struct OvlCall& c, const char* who);
+// fastq_reads.hip, for merge_pairs.hip: the layout of a new handle whose read r is the merged read of pair r (see there)
+int reads_layout_merged(const sassy_hip_ReadOverlap* d_rec, const uint64_t* d_len1, const uint64_t* d_len2, uint64_t n, ScanLane* lane,
+                        sassy_hip_Reads* F, uint64_t* n_merged);
 // c_abi.hip: sassy_hip_search_many behind its null checks
 int search_many_source(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, TextSource& src,
                        size_t k, uint32_t flags, sassy_hip_Result** out);

@@ -136,8 +136,8 @@ hipError_t launch_words(uint32_t W, const OverlapArgs& A, hipStream_t st) {
   return hipGetLastError();
 }
 
-std::string refusal_text(OvlRefusal why, const OvlCall& c) {
-  const std::string w = "read_overlaps";
+std::string refusal_text(OvlRefusal why, const OvlCall& c, const char* who) {
+  const std::string w = who;
   switch (why) {
     case kOvlNullSearcher: case kOvlNullReads: case kOvlNullOut: return "Pointers in " + w + "() must not be null";
     case kOvlFlags: return w + " takes no flags (both read batches are on the device)";
@@ -159,7 +159,8 @@ std::string refusal_text(OvlRefusal why, const OvlCall& c) {
   }
 }
 
-// The call behind its refusals.  Timing level >= 1: ev_line[0] -> [1] around the kernel (stats.scan_ms).
+// The call behind its refusals.  Timing level >= 1: ev_line[0] -> [1] around the kernel (stats.scan_ms).  out == nullptr (the
+// merge): the records stay on the device and, without timing, the stream is not waited for.
 int overlaps_run(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, uint32_t k, uint32_t max_permille,
                  sassy_hip_ReadOverlap* out) {
   hipStream_t st = s->stream;
@@ -189,8 +190,9 @@ int overlaps_run(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_h
   if (s->timing >= 1) HIP_TRY(hipEventRecord(s->ev_line[0], st));
   HIP_TRY(s->profile == PROFILE_IUPAC ? launch_words<true>(W, A, st) : launch_words<false>(W, A, st));
   if (s->timing >= 1) HIP_TRY(hipEventRecord(s->ev_line[1], st));
-  if (int rc = s->lanes[0].download(out, s->d_overlaps.p, n * sizeof(sassy_hip_ReadOverlap))) return rc;
-  HIP_TRY(hipStreamSynchronize(st));
+  if (out)
+    if (int rc = s->lanes[0].download(out, s->d_overlaps.p, n * sizeof(sassy_hip_ReadOverlap))) return rc;
+  if (out || s->timing >= 1) HIP_TRY(hipStreamSynchronize(st));
   if (s->timing >= 1) {
     float ms = 0;
     (void)hipEventElapsedTime(&ms, s->ev_line[0], s->ev_line[1]);
@@ -204,6 +206,20 @@ int overlaps_run(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_h
 }
 
 }  // namespace
+
+int overlap_refused(uint32_t why, const OvlCall& c, const char* who) {
+  return fail(why == kOvlOverhang || why == kOvlOnlyBest || why == kOvlNFrac ? SASSY_HIP_EUNSUPPORTED : SASSY_HIP_EINVAL,  // (as the family does)
+              refusal_text((OvlRefusal)why, c, who));
+}
+
+int overlaps_resident(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, size_t k,
+                      uint32_t max_permille, sassy_hip_ReadOverlap* out) {
+  const size_t lens[1] = {kOvlMaxLen};
+  return hamming_call(s, lens, 1, k, [&](uint32_t kk) {  // (k beyond the longest read accepts what k == 512 does)
+    return overlaps_run(s, r1, r2, min_overlap, kk, max_permille, out);
+  });
+}
+
 }  // namespace sassy_hip
 
 using namespace sassy_hip;
@@ -231,9 +247,7 @@ int sassy_hip_read_overlaps(sassy_SearcherType* s, const sassy_hip_Reads* r1, co
     c.device_s = s->device;
     why = ovl_refusal(c);
   }
-  if (why != kOvlOk)
-    return fail(why == kOvlOverhang || why == kOvlOnlyBest || why == kOvlNFrac ? SASSY_HIP_EUNSUPPORTED : SASSY_HIP_EINVAL,  // (as the family does)
-                refusal_text(why, c));
+  if (why != kOvlOk) return overlap_refused(why, c, "read_overlaps");
   SASSY_NO_TICKETS(s);
   if (r1->n_records == 0) return 0;
   const size_t lens[1] = {kOvlMaxLen};

@@ -444,10 +444,14 @@ class DeviceReadBatch:
     """Records of one FASTQ chunk, parsed on the device (sassy_amd.DeviceReads): `texts` is the resident read batch that
     search_hamming_many, hamming_best_pattern and hamming_counts_many scan where it lies; `sequence(i)` downloads a read.
     The ids are gathered out of the reader's reused buffer into one array when the batch is made (one numpy gather, no loop
-    over the reads); qualities are not kept."""
+    over the reads); qualities are not kept unless the reads were parsed with keep_quality (then they are on the device:
+    `texts.quality(i)`).  keep_chunk: the batch keeps a reference to `chunk`, not a copy, so that `record(i)` can hand out a
+    record's bytes as they stood in the file -- for a caller whose chunk is not written again while the batch lives
+    (fastq_pair_chunks yields copies; read_fastq_device_batches reuses its buffer and must not ask for it)."""
 
-    def __init__(self, reads, chunk: np.ndarray):
+    def __init__(self, reads, chunk: np.ndarray, keep_chunk: bool = False):
         self.texts = reads
+        self._chunk = chunk if keep_chunk else None
         lens = reads.id_lens.astype(np.int64)
         self._id_at = np.cumsum(lens) - lens
         self._id_lens = lens
@@ -463,6 +467,14 @@ class DeviceReadBatch:
 
     def sequence(self, i: int, start: int = 0, end: Optional[int] = None) -> bytes:
         return self.texts.download(i, start, end)
+
+    def record(self, i: int) -> bytes:
+        """Record i's four lines as they stood in the file, line ends included (a batch made with keep_chunk)."""
+        if self._chunk is None:
+            raise ValueError("DeviceReadBatch: the chunk was not kept")
+        a = int(self.texts.id_starts[i]) - 1
+        b = int(self.texts.id_starts[i + 1]) - 1 if i + 1 < len(self) else self._chunk.size
+        return self._chunk[a:b].tobytes()
 
     def free(self):
         self.texts.free()
@@ -579,10 +591,11 @@ def fastq_pair_chunks(fill1, fill2, batch_bytes: int, names=("R1", "R2")):
         want = batch_bytes
 
 
-def read_fastq_pair_device_batches(path1: str, path2: str, batch_bytes: int = 256 << 20):
+def read_fastq_pair_device_batches(path1: str, path2: str, batch_bytes: int = 256 << 20, keep_quality: bool = False):
     """Pairs of DeviceReadBatch of two FASTQ files (R1, R2) with equal record counts, both parsed on the device: what
     Searcher.read_overlaps takes as batch1.texts, batch2.texts.  Both files are cut at the same record number
-    (fastq_pair_chunks); files that end with different record counts raise ValueError."""
+    (fastq_pair_chunks); files that end with different record counts raise ValueError.  keep_quality: the qualities stay on
+    the device as well (what Searcher.merge_pairs takes), and each batch keeps its chunk (`record(i)`)."""
     from . import DeviceReads
     (fill1, fh1), (fill2, fh2) = _sources(path1), _sources(path2)
     try:
@@ -591,8 +604,8 @@ def read_fastq_pair_device_batches(path1: str, path2: str, batch_bytes: int = 25
             for path, chunk in ((path1, c1), (path2, c2)):
                 if chunk[:1].tobytes() != b"@":
                     raise ValueError(f"{path}: not FASTQ (first byte {chunk[:1].tobytes()!r}): the parse on the device takes FASTQ only")
-                reads = DeviceReads(chunk)
-                batches.append(DeviceReadBatch(reads, chunk))
+                reads = DeviceReads(chunk, keep_quality=keep_quality)
+                batches.append(DeviceReadBatch(reads, chunk, keep_chunk=keep_quality))
                 reads._raw = None
             if len(batches[0]) != len(batches[1]):
                 raise ValueError(f"{path1} and {path2}: a chunk parsed into {len(batches[0])} and {len(batches[1])} records (blank lines?)")
