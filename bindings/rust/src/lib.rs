@@ -87,6 +87,18 @@ pub struct ReadOverlap {
     pub mismatches: u32,
     pub n_accepted: u32,
 }
+/// What the trim leaves of one read (include/sassy_hip.h: sassy_hip_ReadTrim, 16 bytes); adapter == -1: no adapter found.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct ReadTrim {
+    pub length: u32,
+    pub quality_len: u32,
+    pub adapter_pos: u32,
+    pub adapter: i16,
+    pub overlap: u8,
+    pub mismatches: u8,
+}
+pub const TRIM_MAX_ADAPTERS: u32 = 64;
 #[repr(C)]
 struct RawSearcher {
     _p: [u8; 0],
@@ -211,6 +223,13 @@ extern "C" {
     /// every pair with an accepted overlap merged into a new resident batch (one record per pair; free it with sassy_hip_reads_free)
     pub fn sassy_hip_merge_pairs(s: *mut RawSearcher, r1: *const RawReads, r2: *const RawReads, min_overlap: u32, k: usize,
                                  max_permille: u32, flags: u32, out_overlaps: *mut ReadOverlap, out_merged: *mut *mut RawReads) -> c_int;
+    /// the 3' adapter and the low-quality tail cut off every read, into a new resident batch (one record per read)
+    pub fn sassy_hip_trim_reads(s: *mut RawSearcher, reads: *const RawReads, adapters: *const *const u8, adapter_lens: *const usize,
+                                n_adapters: usize, min_overlap: u32, k: usize, max_permille: u32, quality_cutoff: u32, min_length: u32,
+                                flags: u32, out_trims: *mut ReadTrim, out_trimmed: *mut *mut RawReads) -> c_int;
+    /// bytes [begins[r], begins[r] + lens[r]) of every read as a new resident batch
+    pub fn sassy_hip_reads_slice(reads: *const RawReads, begins: *const u64, lens: *const u64, hip_stream: *mut std::ffi::c_void,
+                                 out: *mut *mut RawReads) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

@@ -820,6 +820,65 @@ int sassy_hip_merge_pairs(sassy_SearcherType *s, const sassy_hip_Reads *r1, cons
                           sassy_hip_ReadOverlap *out_overlaps /* may be NULL; sassy_hip_reads_n(r1) */,
                           sassy_hip_Reads **out_merged);
 
+/* Adapter and quality trimming (sassy_amd/csrc/trim_reads.hip, arithmetic in trim_step.h): the 3' adapter and
+ * the low-quality tail cut off every read of a resident batch, what is left too short dropped, in a NEW read batch resident on
+ * the device that every _reads entry point, sassy_hip_merge_pairs and another trim take.  The definition is
+ * tests/helpers/trim_reads_ref.py.  Read a of la bytes with qualities q; adapters p_0 .. p_{A-1}, p_j of m_j bytes, written
+ * 5'->3' as they appear behind the insert.  Integers only, no floats.
+ *  - QUALITY (the BWA / cutadapt 3' rule, Phred+33 fixed): quality_cutoff == 0: lq = la.  Otherwise walk i = la - 1 .. 0 with
+ *    s += q[i] - 33 - quality_cutoff (signed), stop at the first i where s > 0; lq is the i of the strictly smallest s seen
+ *    before the stop (s < min, min starting at 0), la where no s was below 0;
+ *  - ADAPTER, on a[0:lq]: position c places p_j[0] under a[c]; ov = min(m_j, lq - c);
+ *      mm(c, j) = #{ i < ov : !match(p_j[i], a[c + i]) },   match: the searcher's profile relation, the adapter on the
+ *    pattern side (under Iupac an N in an adapter is a wildcard).  A position is ACCEPTED when ov >= min_overlap, mm <= k and
+ *    mm * 1000 <= max_permille * ov (sassy_hip_read_overlaps' rule).  The BEST accepted position: the smallest c (the
+ *    leftmost removes the most: fastp's and Trimmomatic's rule), then the lower density (mm1 * ov2 < mm2 * ov1), then the
+ *    larger ov, then the smaller j; the order is total;
+ *  - cut = c of the best, or lq where nothing is accepted; length = cut if cut >= min_length, else 0: a dropped read is an
+ *    empty record, as an unmerged pair is.  The trimmed read is a[0:length] with q[0:length];
+ *  - out_trims, where given, receives sassy_hip_reads_n(reads) records of 16 bytes;
+ *  - *out_trimmed: an ordinary sassy_hip_Reads on the searcher's device, ONE RECORD PER READ, with qualities kept iff the input
+ *    kept them.  id_start = id_len = 0 (the ids are the input's); under kept qualities qual_start = seq_start and
+ *    qual_len = seq_len index the handle's own quality buffer, otherwise both are 0.  Zero reads, or nothing left of any:
+ *    text_bytes == 64.  The caller frees it with sassy_hip_reads_free;
+ *  - limits: at most SASSY_HIP_TRIM_MAX_ADAPTERS adapters of 1 .. 64 bytes, none shorter than min_overlap; reads of at most
+ *    SASSY_HIP_OVERLAP_MAX_LEN bytes; k is not capped (k beyond 64 accepts what k = 64 does).  n_adapters == 0 is allowed:
+ *    quality and length trimming only.  The searcher's rc plays no part;
+ *  - refused before any device work, in this order, SASSY_HIP_EINVAL unless noted: s == NULL; any flag; min_overlap == 0;
+ *    max_permille > 1000; quality_cutoff > 93; too many adapters, a null, empty or over-long adapter, an adapter shorter than
+ *    min_overlap; an Ascii searcher; overhang, only_best_match, max_n_frac set (SASSY_HIP_EUNSUPPORTED); reads == NULL; a
+ *    handle made on another device than the searcher's; a read longer than SASSY_HIP_OVERLAP_MAX_LEN; quality_cutoff > 0 on a
+ *    handle parsed without SASSY_HIP_KEEP_QUALITY; out_trimmed == NULL; searches in flight on the searcher.  A Dna searcher
+ *    takes A, C, G, T only, in the adapters and in the batch (looked at on the device, as sassy_hip_read_overlaps looks);
+ *    anything else is SASSY_HIP_EINVAL and the message points to an iupac searcher.  *out_trimmed is NULL after every refusal;
+ *  - the input handle is only read.  Device work on the searcher's stream: the find kernel (one wavefront per read), the layout
+ *    scan of the parse over the records' lengths, one host wait for the layout's size, one write kernel indexed by 64-byte
+ *    block of the output.  Stats: candidates = the reads with an adapter found, scan_launches = 5, or 6 under a Dna searcher
+ *    whose batch has a block to look at (the look is a kernel as well, and is counted), word_rows = the words per plane of the
+ *    find kernel's instance.  Zero reads launch no kernel: scan_launches = 0. */
+#define SASSY_HIP_TRIM_MAX_ADAPTERS 64u
+typedef struct sassy_hip_ReadTrim {
+  uint32_t length;      /* of the trimmed read; 0: dropped by min_length (or nothing left) */
+  uint32_t quality_len; /* lq */
+  uint32_t adapter_pos; /* cut: c of the best position, or lq */
+  int16_t adapter;      /* j of the best position; -1: no adapter found */
+  uint8_t overlap;      /* its ov */
+  uint8_t mismatches;   /* its mm; both 0 where no adapter was found */
+} sassy_hip_ReadTrim;
+int sassy_hip_trim_reads(sassy_SearcherType *s, const sassy_hip_Reads *reads, const uint8_t *const *adapters,
+                         const size_t *adapter_lens, size_t n_adapters, uint32_t min_overlap, size_t k, uint32_t max_permille,
+                         uint32_t quality_cutoff, uint32_t min_length, uint32_t flags,
+                         sassy_hip_ReadTrim *out_trims /* may be NULL; sassy_hip_reads_n(reads) */,
+                         sassy_hip_Reads **out_trimmed);
+
+/* A window of every read as a NEW resident read batch: read r of *out is bytes [begins[r], begins[r] + lens[r]) of read r of
+ * `reads` (and of its quality where kept) -- fixed clipping, a leading UMI or barcode split off.  begins and lens are host
+ * arrays of sassy_hip_reads_n(reads) entries.  The layout scan and the write kernel are the trim's; the handle is as the
+ * trim's (ONE RECORD PER READ, id_start = id_len = 0).  SASSY_HIP_EINVAL: a null pointer, a window that reaches outside its
+ * read.  Runs on `hip_stream` on the handle's device and returns when the new handle is whole; the input is only read. */
+int sassy_hip_reads_slice(const sassy_hip_Reads *reads, const uint64_t *begins, const uint64_t *lens, void *hip_stream,
+                          sassy_hip_Reads **out);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is

@@ -169,6 +169,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_search_many_reads", "sassy_hip_min_costs_reads", "sassy_hip_best_pattern_reads", "sassy_hip_best_matches_reads",
     "sassy_hip_reads_relayout", "sassy_hip_read_overlaps",
     "sassy_hip_reads_quality", "sassy_hip_merge_pairs",
+    "sassy_hip_trim_reads", "sassy_hip_reads_slice",
 ]
 
 _lib = None
@@ -433,6 +434,11 @@ def lib():
     L.sassy_hip_read_overlaps.argtypes = [vp, vp, vp, C.c_uint32, sz, C.c_uint32, C.c_uint32, vp]
     L.sassy_hip_merge_pairs.restype = C.c_int
     L.sassy_hip_merge_pairs.argtypes = [vp, vp, vp, C.c_uint32, sz, C.c_uint32, C.c_uint32, vp, C.POINTER(vp)]
+    L.sassy_hip_trim_reads.restype = C.c_int
+    L.sassy_hip_trim_reads.argtypes = [vp, vp, C.POINTER(C.c_char_p), C.POINTER(sz), sz, C.c_uint32, sz, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       vp, C.POINTER(vp)]
+    L.sassy_hip_reads_slice.restype = C.c_int
+    L.sassy_hip_reads_slice.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
     L.sassy_hip_malloc.restype = vp
     L.sassy_hip_malloc.argtypes = [sz]
     L.sassy_hip_free.restype = None
@@ -542,7 +548,14 @@ def read_overlap_dtype():
     return np.dtype([("offset", "<i4"), ("overlap", "<u4"), ("mismatches", "<u4"), ("n_accepted", "<u4")])
 
 
+def read_trim_dtype():
+    """numpy view of include/sassy_hip.h: sassy_hip_ReadTrim (16 bytes)."""
+    import numpy as np
+    return np.dtype([("length", "<u4"), ("quality_len", "<u4"), ("adapter_pos", "<u4"), ("adapter", "<i2"), ("overlap", "u1"), ("mismatches", "u1")])
+
+
 OVERLAP_MAX_LEN = 512  # SASSY_HIP_OVERLAP_MAX_LEN
+TRIM_MAX_ADAPTERS = 64  # SASSY_HIP_TRIM_MAX_ADAPTERS
 
 
 def overlap_trims(rec, la: int, lb: int):
@@ -998,7 +1011,48 @@ def _byte_pattern(pattern) -> bytes:
     return bytes(pattern)
 
 
-class Searcher:
+class _ReadBatchCalls:
+    """The Searcher calls that turn one resident read batch into another (self._h: the searcher's handle).  They live in a base
+    class of Searcher: each makes a new DeviceReads out of a DeviceReads and keeps nothing of the search family's state."""
+
+    def trim_reads(self, reads, adapters, min_overlap: int = 3, k: int = OVERLAP_MAX_LEN, max_permille: int = 100, quality_cutoff: int = 0,
+                   min_length: int = 0, with_records: bool = False):
+        """The 3' adapter and the low-quality tail cut off every read on the device (sassy_hip_trim_reads).  Quality first
+        (`quality_cutoff` > 0: the BWA / cutadapt rule on Phred+33, which leaves lq bytes), then the adapters on what is left:
+        position c places an adapter's first byte under a[c], it overlaps in ov = min(m, lq - c) rows, and c is accepted with
+        at least `min_overlap` rows, at most `k` mismatches and at most `max_permille` per thousand of them.  The leftmost
+        accepted position wins, then the lower density, the longer overlap, the earlier adapter; the read is cut there, and
+        a read left shorter than `min_length` becomes empty.  Returns a new DeviceReads, ONE RECORD PER READ, with qualities
+        iff the input has them, which every call that takes a DeviceReads takes; with `with_records` also a numpy array of
+        `read_trim_dtype()`.  `reads`: a DeviceReads, or a list of sequences or of (sequence, quality) tuples.  `adapters`:
+        up to 64 byte strings of 1 .. 64 bytes, 5'->3' as they follow the insert; none: quality and length trimming only.
+        dna (A, C, G, T only) or iupac.  The definition is tests/helpers/trim_reads_ref.py."""
+        import numpy as np
+        adapters = [a.encode() if isinstance(a, str) else _byte_pattern(a) for a in adapters]
+        made = None
+        if not isinstance(reads, DeviceReads):
+            reads = list(reads)
+            paired = bool(reads) and isinstance(reads[0], tuple)
+            made = reads = DeviceReads.from_sequences([x[0] for x in reads], [x[1] for x in reads]) if paired else DeviceReads.from_sequences(reads)
+        try:
+            numbers = (min_overlap, max_permille, quality_cutoff, min_length)
+            if any(not 0 <= int(v) < (1 << 32) for v in numbers) or int(k) < 0:
+                raise SassyHipError("trim_reads: min_overlap, max_permille, quality_cutoff and min_length must fit 32 bits, and none of them nor k may be negative")
+            ptrs = (C.c_char_p * max(len(adapters), 1))(*adapters)
+            lens = (C.c_size_t * max(len(adapters), 1))(*[len(a) for a in adapters])
+            records = np.zeros(len(reads), dtype=read_trim_dtype()) if with_records else None
+            out = C.c_void_p()
+            _check(lib().sassy_hip_trim_reads(self._h, reads._handle(), ptrs, lens, len(adapters), int(min_overlap), int(k), int(max_permille),
+                                              int(quality_cutoff), int(min_length), 0,
+                                              records.ctypes.data if with_records and len(records) else None, C.byref(out)))
+            trimmed = DeviceReads._adopt(out)
+            return (trimmed, records) if with_records else trimmed
+        finally:
+            if made is not None:
+                made.free()
+
+
+class Searcher(_ReadBatchCalls):
     """Mirror of sassy.Searcher (src/python.rs:26-64) / Searcher::<P>::new (src/search.rs:486-503).
 
     Note the reference's Python default rc=True; ``new_fwd``-style searchers pass rc=False."""
@@ -2174,6 +2228,19 @@ class DeviceReads:
         if end <= start:
             return b""
         return DeviceText(self.ptr + int(self.seq_starts[i]) + start, end - start).download()
+
+    def slice(self, begins, lens, stream: int = 0):
+        """A new DeviceReads whose read r is bytes [begins[r], begins[r] + lens[r]) of this batch's read r, and of its quality
+        where kept (sassy_hip_reads_slice): fixed clipping, a leading UMI or barcode split off.  `begins`, `lens`: one entry
+        per read, or one number for all.  A window that reaches outside its read is refused."""
+        import numpy as np
+        self._live()
+        n = len(self)
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(begins, dtype=np.uint64), (n,)))
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(lens, dtype=np.uint64), (n,)))
+        out = C.c_void_p()
+        _check(lib().sassy_hip_reads_slice(self._h, b.ctypes.data if n else None, w.ctypes.data if n else None, stream or None, C.byref(out)))
+        return DeviceReads._adopt(out)
 
     def download_text(self) -> bytes:
         """The whole device buffer: the layout, pads and the 64 spare bytes included."""

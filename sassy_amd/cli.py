@@ -104,6 +104,15 @@ min(126, 33 + max(2, |q1 - q2|))) and the reverse complement of R2 behind it; a 
 alone.  Merged records go to `-o` (default stdout) under R1's id; pairs without an accepted offset are copied unchanged to
 `--unmerged1` / `--unmerged2` where these are given; `--tsv` writes `overlap`'s rows to MERGED.fq.tsv.
 
+`trim IN.fq -a ADAPTER [-a ...] [-o OUT.fq] [-q N] [-m N] [--min-overlap N] [-k K] [--max-permille P] [--alphabet dna|iupac]
+[--tsv]` cuts the 3' adapter and the low-quality tail off every read through `Searcher.trim_reads`, on the device: first the
+BWA / cutadapt quality rule under `-q` (Phred+33), then the leftmost position at which one of the adapters -- whole, or the
+prefix that runs off the read's end -- lies with at least `--min-overlap` rows, at most K mismatches and P per thousand of
+them.  Trimmed records go to `-o` (default stdout) under their own ids; reads left shorter than `-m`, or empty, are not
+written; `--tsv` writes one row per read to OUT.fq.tsv:
+
+    id  length  quality_len  adapter_pos  adapter  overlap  mismatches
+
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
 one block per match, sorted by (start, end): `PATH:LINE:COL:COST:` and the line(s) the match lies in -- LINE and the line's
@@ -616,6 +625,61 @@ def merge_parser(sub):
     return cp
 
 
+TRIM_HEADER = "id\tlength\tquality_len\tadapter_pos\tadapter\toverlap\tmismatches\n"
+
+
+def trim_rows(ids, records):
+    """The TSV rows of Searcher.trim_reads' records, one per read."""
+    return [f"{ids[i]}\t{int(r['length'])}\t{int(r['quality_len'])}\t{int(r['adapter_pos'])}\t{int(r['adapter'])}\t{int(r['overlap'])}\t{int(r['mismatches'])}\n"
+            for i, r in enumerate(records)]
+
+
+def run_trim(args, searcher, out) -> int:
+    """`trim`: every read cut at its 3' adapter and its low-quality tail, under its own id (Searcher.trim_reads; out: a binary
+    stream); a read left shorter than -m is not written."""
+    from . import reads_to_fastq
+    from .fastx import read_fastq_device_batches
+    tsv = open(args.tsv_path, "w") if args.tsv_path else None
+    adapters = [a.encode() for a in args.adapter]
+    try:
+        if tsv:
+            tsv.write(TRIM_HEADER)
+        for batch in read_fastq_device_batches(args.input, BATCH_BYTES, keep_quality=True):
+            trimmed = None
+            try:  # (a refused batch lets go of its device memory as well)
+                trimmed, records = searcher.trim_reads(batch.texts, adapters, args.min_overlap, args.k, args.max_permille, args.quality_cutoff,
+                                                       args.min_length, with_records=True)
+                ids = [batch.id(i) for i in range(len(batch))]
+                out.write(reads_to_fastq(trimmed, ids))
+                if tsv:
+                    tsv.writelines(trim_rows(ids, records))
+            finally:
+                if trimmed is not None:
+                    trimmed.free()
+                batch.free()
+        out.flush()
+    finally:
+        if tsv:
+            tsv.close()
+    return 0
+
+
+def trim_parser(sub):
+    cp = sub.add_parser("trim", help="cut the 3' adapter and the low-quality tail off every read of a FASTQ file")
+    cp.add_argument("input", metavar="IN.fq", help="FASTQ of the reads")
+    cp.add_argument("-a", "--adapter", action="append", default=[], metavar="ADAPTER",
+                    help="an adapter, 5'->3' as it follows the insert (up to 64 of 1 .. 64 bases; none: quality and length only)")
+    cp.add_argument("-o", "--output", default="", help="the trimmed FASTQ (default: stdout)")
+    cp.add_argument("-q", "--quality-cutoff", type=int, default=0, help="Phred quality the 3' end is trimmed below (default 0: not at all)")
+    cp.add_argument("-m", "--min-length", type=int, default=0, help="reads left shorter than this are dropped (default 0)")
+    cp.add_argument("--min-overlap", type=int, default=3, help="rows of an adapter an accepted position shows at least (default 3)")
+    cp.add_argument("-k", type=int, default=512, help="mismatches an accepted position has at most (default: no limit)")
+    cp.add_argument("--max-permille", type=int, default=100, help="mismatches per thousand rows an accepted position has at most (default 100)")
+    cp.add_argument("--alphabet", type=str.lower, choices=["dna", "iupac"], default="dna")
+    cp.add_argument("--tsv", action="store_true", help="also write one row per read from the records, to OUT.fq.tsv beside -o (needs -o)")
+    return cp
+
+
 def load_primers(path: str) -> List[Tuple[str, bytes, bytes]]:
     """PRIMERS of `amplicon`: rows of name<TAB>fwd<TAB>rev (empty lines and lines from `#` on skipped)."""
     pairs = []
@@ -724,7 +788,21 @@ def main(argv=None) -> int:
     cluster_parser(sub)
     overlap_parser(sub)
     merge_parser(sub)
+    trim_parser(sub)
     args = ap.parse_args(argv)
+    if args.cmd == "trim":
+        if args.min_overlap < 1 or args.k < 0 or not 0 <= args.max_permille <= 1000 or not 0 <= args.quality_cutoff <= 93 or args.min_length < 0:
+            ap.error("trim takes --min-overlap >= 1, -k >= 0, 0 <= --max-permille <= 1000, 0 <= -q <= 93 and -m >= 0")
+        if len(args.adapter) > 64 or any(not 1 <= len(a) <= 64 for a in args.adapter):
+            ap.error("trim takes up to 64 adapters of 1 .. 64 bases")
+        if args.tsv and not args.output:
+            ap.error("trim --tsv writes beside the trimmed file: it needs -o")
+        args.tsv_path = args.output + ".tsv" if args.tsv else ""
+        searcher = Searcher(args.alphabet, rc=False)
+        if args.output:
+            with open(args.output, "wb") as fh:
+                return run_trim(args, searcher, fh)
+        return run_trim(args, searcher, sys.stdout.buffer)
     if args.cmd == "merge":
         if args.min_overlap < 1 or args.k < 0 or not 0 <= args.max_permille <= 1000:
             ap.error("merge takes --min-overlap >= 1, -k >= 0 and 0 <= --max-permille <= 1000")

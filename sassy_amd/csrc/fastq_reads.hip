@@ -18,8 +18,9 @@
 //                        with 16-byte loads and stores, zeros behind the read's end and in the 64 spare bytes, rem[block].
 //                        Under SASSY_HIP_KEEP_QUALITY it runs once more, over line 4t + 3, into the handle's quality buffer
 // Two host waits size what cannot be sized before: the line table (L) and the text (layout bytes).
-// The record kernels take their lengths from a source: the lines of a file (the parse) or the overlap records of a batch of
-// pairs (reads_layout_merged, for merge_pairs.hip), so the layout rule and its two-level scan have one owner.
+// The record kernels take their lengths from a source: the lines of a file (the parse), the overlap records of a batch of
+// pairs (reads_layout_merged, for merge_pairs.hip), the trim records of a batch or a table of window lengths
+// (reads_layout_trimmed, reads_layout_windows, for trim_reads.hip), so the layout rule and its two-level scan have one owner.
 #include "host_internal.h"
 #include "fastq_step.h"
 #include "hamming_step.h"
@@ -45,7 +46,7 @@ struct FastqTotals {
   unsigned long long layout;    // bytes of the layout
   unsigned long long longest;   // the longest sequence
   unsigned long long bad_qual;  // the smallest record whose quality is not as long as its sequence (looked at on request)
-  unsigned long long filled;    // records that are not empty (counted for the sources that ask for it)
+  unsigned long long filled;    // records the source counts (merged pairs, reads with an adapter), for the sources that ask for it
 };
 
 // The lane's 64 bytes of a tile as words.  raw is 16-byte aligned and readable up to the next multiple of 64 behind n, so a
@@ -227,8 +228,33 @@ struct MergedSource {
     const uint32_t la = (uint32_t)min(len1[r], (uint64_t)kOvlMaxLen), lb = (uint32_t)min(len2[r], (uint64_t)kOvlMaxLen);
     return min(mrg_length(la, lb, OvlBest{o.offset, o.overlap, o.mismatches, o.n_accepted}), 2u * kOvlMaxLen);
   }
+  __device__ __forceinline__ bool counted(uint64_t, uint64_t seq_len) const { return seq_len != 0; }  // the merged pairs
   __device__ __forceinline__ sassy_hip_ReadRecord record(uint64_t, uint64_t at, uint64_t seq_len) const {
     return sassy_hip_ReadRecord{0, 0, at, seq_len, at, seq_len};
+  }
+};
+// ... or the trim records of a batch (trim_step.h): read r is what the trim leaves of read r, empty where it was dropped.  No
+// ids; a quality, where the handle keeps one, lies where the sequence lies.
+struct TrimSource {
+  const sassy_hip_ReadTrim* rec;
+  bool keep_quality;
+  static constexpr bool check_qual = false;
+  static constexpr bool kCountFilled = true;
+  __device__ __forceinline__ uint64_t len(uint64_t r) const { return min(rec[r].length, (uint32_t)kOvlMaxLen); }  // (a cut lies inside its read)
+  __device__ __forceinline__ bool counted(uint64_t r, uint64_t) const { return rec[r].adapter >= 0; }  // the reads with an adapter found
+  __device__ __forceinline__ sassy_hip_ReadRecord record(uint64_t, uint64_t at, uint64_t seq_len) const {
+    return sassy_hip_ReadRecord{0, 0, at, seq_len, keep_quality ? at : 0, keep_quality ? seq_len : 0};
+  }
+};
+// ... or a table of window lengths (sassy_hip_reads_slice), checked against the reads by the host
+struct WindowSource {
+  const uint64_t* lens;
+  bool keep_quality;
+  static constexpr bool check_qual = false;
+  static constexpr bool kCountFilled = false;
+  __device__ __forceinline__ uint64_t len(uint64_t r) const { return lens[r]; }
+  __device__ __forceinline__ sassy_hip_ReadRecord record(uint64_t, uint64_t at, uint64_t seq_len) const {
+    return sassy_hip_ReadRecord{0, 0, at, seq_len, keep_quality ? at : 0, keep_quality ? seq_len : 0};
   }
 };
 
@@ -285,7 +311,7 @@ __global__ __launch_bounds__(256) void fastq_rec_write_kernel(Src S, uint64_t n_
     lens[j] = r0 + j < n_rec ? S.len(r0 + j) : 0;
     mine += fq_round64(lens[j]);
     longest = max(longest, lens[j]);
-    filled += lens[j] != 0;
+    if constexpr (Src::kCountFilled) filled += r0 + j < n_rec && S.counted(r0 + j, lens[j]);
   }
   uint64_t total;
   uint64_t at = block_off[blockIdx.x] + block_scan256(mine, sh, &total);
@@ -526,6 +552,37 @@ int reads_layout_merged(const sassy_hip_ReadOverlap* d_rec, const uint64_t* d_le
   if (int rc = layout_buffers(tot, true, F, T.who)) return rc;
   *n_merged = tot.filled;
   return take_records(d_records, n, st, lane, F, T.who);
+}
+
+
+// For trim_reads.hip: a new handle of n reads whose lengths are the `length` of the trim records behind d_rec (on the device),
+// with a quality buffer where asked for; *n_found: the reads whose record names an adapter.  As reads_layout_merged otherwise.
+int reads_layout_trimmed(const sassy_hip_ReadTrim* d_rec, uint64_t n, bool keep_quality, ScanLane* lane, sassy_hip_Reads* F, uint64_t* n_found) {
+  hipStream_t st = lane->stream;
+  Temps T("trim_reads");
+  FastqTotals* d_totals = nullptr;
+  if (int rc = T.get(&d_totals, 1)) return rc;
+  const FastqTotals zero{kNoBadLine, 0, 0, kNoBadLine, 0};
+  HIP_TRY(hipMemcpyAsync(d_totals, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
+  FastqTotals tot{};
+  sassy_hip_ReadRecord* d_records = nullptr;
+  if (int rc = layout_records(TrimSource{d_rec, keep_quality}, n, st, T, F, d_totals, &tot, &d_records)) return rc;
+  if (int rc = layout_buffers(tot, keep_quality, F, T.who)) return rc;
+  *n_found = tot.filled;
+  return take_records(d_records, n, st, lane, F, T.who);
+}
+// ... and one whose lengths are a table on the device (sassy_hip_reads_slice: no searcher, so a plain stream)
+int reads_layout_windows(const uint64_t* d_lens, uint64_t n, bool keep_quality, hipStream_t st, sassy_hip_Reads* F) {
+  Temps T("reads_slice");
+  FastqTotals* d_totals = nullptr;
+  if (int rc = T.get(&d_totals, 1)) return rc;
+  const FastqTotals zero{kNoBadLine, 0, 0, kNoBadLine, 0};
+  HIP_TRY(hipMemcpyAsync(d_totals, &zero, sizeof(zero), hipMemcpyHostToDevice, st));
+  FastqTotals tot{};
+  sassy_hip_ReadRecord* d_records = nullptr;
+  if (int rc = layout_records(WindowSource{d_lens, keep_quality}, n, st, T, F, d_totals, &tot, &d_records)) return rc;
+  if (int rc = layout_buffers(tot, keep_quality, F, T.who)) return rc;
+  return take_records(d_records, n, st, nullptr, F, T.who);
 }
 
 }  // namespace sassy_hip

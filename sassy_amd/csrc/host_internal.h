@@ -730,6 +730,8 @@ struct sassy_SearcherType {
   // columns) and what is sized by the distinct sequences (their planes, counts, labels)
   DevBuf<uint8_t> d_umi_reads, d_umi_distinct;
   DevBuf<sassy_hip_ReadOverlap> d_overlaps;  // read overlaps (read_overlaps.hip): one record per pair
+  DevBuf<sassy_hip_ReadTrim> d_trims;        // trimming (trim_reads.hip): one record per read, and the adapter table
+  DevBuf<uint32_t> d_trim_tab;
   DevBuf<uint64_t> d_range;     // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
@@ -755,7 +757,7 @@ struct sassy_SearcherType {
     d_ham_tab.release(); d_ham_count.release(); d_ham_prefix.release(); d_ham_items.release(); d_ham_sorted.release(); d_ham_sort.release();
     d_ham_texts.release(); d_ham_rem.release(); d_ham_cells.release(); d_ham_bins.release();
     d_pairs_a.release(); d_pairs_t.release(); d_pairs_cells.release(); d_pairs_rows.release(); d_pairs_out.release();
-    d_umi_reads.release(); d_umi_distinct.release(); d_overlaps.release();
+    d_umi_reads.release(); d_umi_distinct.release(); d_overlaps.release(); d_trims.release(); d_trim_tab.release();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();
@@ -1382,6 +1384,10 @@ int overlap_refused(uint32_t why, const struct OvlCall& c, const char* who);
 // fastq_reads.hip, for merge_pairs.hip: the layout of a new handle whose read r is the merged read of pair r (see there)
 int reads_layout_merged(const sassy_hip_ReadOverlap* d_rec, const uint64_t* d_len1, const uint64_t* d_len2, uint64_t n, ScanLane* lane,
                         sassy_hip_Reads* F, uint64_t* n_merged);
+// ... for trim_reads.hip: the layout of a new handle whose read r is as long as trim record r says, or as a table of window
+// lengths says (see there)
+int reads_layout_trimmed(const sassy_hip_ReadTrim* d_rec, uint64_t n, bool keep_quality, ScanLane* lane, sassy_hip_Reads* F, uint64_t* n_found);
+int reads_layout_windows(const uint64_t* d_lens, uint64_t n, bool keep_quality, hipStream_t st, sassy_hip_Reads* F);
 // c_abi.hip: sassy_hip_search_many behind its null checks
 int search_many_source(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, TextSource& src,
                        size_t k, uint32_t flags, sassy_hip_Result** out);

@@ -480,10 +480,11 @@ class DeviceReadBatch:
         self.texts.free()
 
 
-def read_fastq_device_batches(path: str, batch_bytes: int = 256 << 20) -> Iterator[DeviceReadBatch]:
+def read_fastq_device_batches(path: str, batch_bytes: int = 256 << 20, keep_quality: bool = False) -> Iterator[DeviceReadBatch]:
     """read_fastx_batches for FASTQ with the parse on the device: the same chunks, cut at the same record boundaries; the raw
     bytes of a chunk are uploaded once and kernels find the records and lay the sequences out (sassy_hip_fastq_parse).
-    FASTA is refused: read_fasta_device_batches unwraps it."""
+    FASTA is refused: read_fasta_device_batches unwraps it.  keep_quality: the qualities stay on the device as well (what
+    Searcher.trim_reads takes for its quality rule and hands on)."""
     from . import DeviceReads
     # (read_fastx_batches' own loop over chunks, FASTQ only: that function stays as it is, so the loop is written out here)
     work = _Work()
@@ -515,7 +516,7 @@ def read_fastq_device_batches(path: str, batch_bytes: int = 256 << 20) -> Iterat
                 want *= 2  # a record longer than the batch: read on
                 m, raw = work.raw_buffer(carry + want, have)
             chunk = raw[:end]
-            reads = DeviceReads(chunk)
+            reads = DeviceReads(chunk, keep_quality=keep_quality)
             batch = DeviceReadBatch(reads, chunk)
             reads._raw = None  # (the reader's buffer is reused: the batch keeps the ids, not the chunk)
             rest = have - end
