@@ -99,6 +99,21 @@ pub struct ReadTrim {
     pub mismatches: u8,
 }
 pub const TRIM_MAX_ADAPTERS: u32 = 64;
+/// Which sample one read went to (include/sassy_hip.h: sassy_hip_ReadDemux, 16 bytes); sample == -1: unassigned,
+/// best == u32::MAX: the read has no window.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct ReadDemux {
+    pub sample: i32,
+    pub best: u32,
+    pub cost: u8,
+    pub second: u8,
+    pub n_best: u16,
+    pub index: u32,
+}
+pub const DEMUX_MAX_BARCODES: u32 = 4096;
+pub const DEMUX_END3: u32 = 1;
+pub const DEMUX_KEEP_BARCODE: u32 = 2;
 #[repr(C)]
 struct RawSearcher {
     _p: [u8; 0],
@@ -230,6 +245,13 @@ extern "C" {
     /// bytes [begins[r], begins[r] + lens[r]) of every read as a new resident batch
     pub fn sassy_hip_reads_slice(reads: *const RawReads, begins: *const u64, lens: *const u64, hip_stream: *mut std::ffi::c_void,
                                  out: *mut *mut RawReads) -> c_int;
+    /// record j = bytes [begins[j], begins[j] + lens[j]) of read src[j] (begins, lens null: whole reads) as a new resident batch
+    pub fn sassy_hip_reads_select(reads: *const RawReads, src: *const u64, begins: *const u64, lens: *const u64, n_out: u64,
+                                  hip_stream: *mut std::ffi::c_void, out: *mut *mut RawReads) -> c_int;
+    /// every read given to the sample whose barcode stands at a fixed place of one of its ends; a new resident batch sorted by sample
+    pub fn sassy_hip_demux_reads(s: *mut RawSearcher, reads: *const RawReads, barcodes: *const *const u8, barcode_len: usize,
+                                 n_barcodes: usize, at: u32, k: usize, min_delta: u32, flags: u32, out_assign: *mut ReadDemux,
+                                 out_order: *mut u64, out_bounds: *mut u64, out_sorted: *mut *mut RawReads) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

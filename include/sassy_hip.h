@@ -879,6 +879,70 @@ int sassy_hip_trim_reads(sassy_SearcherType *s, const sassy_hip_Reads *reads, co
 int sassy_hip_reads_slice(const sassy_hip_Reads *reads, const uint64_t *begins, const uint64_t *lens, void *hip_stream,
                           sassy_hip_Reads **out);
 
+/* A gather of reads as a NEW resident read batch: record j of *out is bytes [begins[j], begins[j] + lens[j]) of read src[j] of
+ * `reads` (and of its quality where kept).  src, begins and lens are host arrays of n_out entries; begins and lens NULL
+ * together means whole reads.  src may repeat, skip and reorder, so the call takes one sample out of a demultiplexed batch,
+ * puts a mate batch into the order of another, and drops the empty records a trim or a merge leaves.  n_out may be 0.  The
+ * layout scan and the write kernel are the trim's; the handle is as the trim's (id_start = id_len = 0, qualities iff the
+ * source keeps them, text_bytes == 64 when nothing is left).  SASSY_HIP_EINVAL: a null pointer, only one of begins and lens,
+ * src[j] >= sassy_hip_reads_n(reads), a window that reaches outside its read; the message names j.  There is no searcher: it
+ * runs on `hip_stream` on the handle's device and returns when the new handle is whole; the input is only read. */
+int sassy_hip_reads_select(const sassy_hip_Reads *reads, const uint64_t *src, const uint64_t *begins, const uint64_t *lens,
+                           uint64_t n_out, void *hip_stream, sassy_hip_Reads **out);
+
+/* Demultiplexing (sassy_amd/csrc/demux_reads.hip, arithmetic in demux_step.h): every read of a resident batch
+ * is given to the sample whose barcode stands at a fixed place at one of its ends, and the batch comes back as a NEW resident
+ * read batch SORTED BY SAMPLE with the barcode clipped off.  The definition is tests/helpers/demux_reads_ref.py.  Read a of la
+ * bytes; barcodes p_0 .. p_{B-1}, all of barcode_len = m bytes.  Integers only.
+ *  - WINDOW: from the 5' end w = at, under SASSY_HIP_DEMUX_END3 w = la - at - m; the read has a window iff at + m <= la;
+ *  - cost_j = #{ i < m : !match(p_j[i], a[w + i]) },  match: the searcher's profile relation, the barcode on the pattern side
+ *    (under Iupac an N in a barcode is a wildcard);
+ *  - best = the smallest j of the minimum cost, cost = that minimum, n_best = the barcodes at that cost, second = the minimum
+ *    over j != best, m + 1 when B == 1;
+ *  - ASSIGNED iff the read has a window, cost <= k and second - cost >= min_delta.  min_delta == 0: a tie goes to the smaller
+ *    index; min_delta >= 1: a tie is unassigned.  The label is best, or B: the unassigned bin comes last;
+ *  - order = the stable argsort of the labels; out_bounds[s], s = 0 .. B + 1, is the first place of label s, so sample s is
+ *    the records [out_bounds[s], out_bounds[s + 1]) of *out_sorted and the unassigned are [out_bounds[B], out_bounds[B + 1]);
+ *  - record j of *out_sorted is read order[j]: an assigned read without its barcode -- bytes [at + m, la) from the 5' end (what
+ *    lies in front of the barcode goes with it), [0, la - at - m) from the 3' end --, any other read whole, and every read
+ *    whole under SASSY_HIP_DEMUX_KEEP_BARCODE; the quality alongside where the handle keeps one;
+ *  - out_assign, where given, receives sassy_hip_reads_n(reads) records of 16 bytes in the INPUT's order; out_order, where
+ *    given, as many indices; out_bounds is required and has n_barcodes + 2 entries;
+ *  - *out_sorted: an ordinary sassy_hip_Reads as the trim's (id_start = id_len = 0, qual_start = seq_start under kept
+ *    qualities; text_bytes == 64 when nothing is left).  Take a sample out with sassy_hip_reads_select, put a mate batch in
+ *    the same order with it.  The caller frees it with sassy_hip_reads_free;
+ *  - limits: 1 .. SASSY_HIP_DEMUX_MAX_BARCODES barcodes of one length 1 .. 64; at + barcode_len <= 512; min_delta <= 65; reads
+ *    of at most SASSY_HIP_OVERLAP_MAX_LEN bytes; k is not capped (k beyond 64 accepts what k = 64 does).  The searcher's rc
+ *    plays no part;
+ *  - refused before any device work, in this order, SASSY_HIP_EINVAL unless noted: s == NULL; a flag other than the two above;
+ *    min_delta > 65; n_barcodes == 0 or > 4096; barcode_len == 0 or > 64; a null barcode; at + barcode_len > 512; an Ascii
+ *    searcher; overhang, only_best_match, max_n_frac set (SASSY_HIP_EUNSUPPORTED); reads == NULL; a handle made on another
+ *    device than the searcher's; a read longer than SASSY_HIP_OVERLAP_MAX_LEN; out_bounds or out_sorted NULL; searches in
+ *    flight on the searcher.  A Dna searcher takes A, C, G, T only, in the barcodes (looked at on the host) and in the batch
+ *    (looked at on the device, as the trim looks); anything else is SASSY_HIP_EINVAL and the message points to an iupac
+ *    searcher.  *out_sorted is NULL after every refusal;
+ *  - the input handle is only read.  Device work on the searcher's stream: the assign kernel (a lane per read), rocPRIM's
+ *    radix sort of (label, index), the bounds kernel, the place kernel, the layout scan of the parse over the new lengths, one
+ *    host wait for the layout's size, the trim's write kernel with a source table.  Stats: candidates = the assigned reads,
+ *    scan_launches = 8, or 9 under a Dna searcher whose batch has a block to look at: the look, the assign kernel, the sort
+ *    (the library's launches count as one), bounds, place, the three kernels of the layout scan, the write kernel.  Zero
+ *    reads launch no kernel: scan_launches = 0 and out_bounds is all zero. */
+#define SASSY_HIP_DEMUX_MAX_BARCODES 4096u
+#define SASSY_HIP_DEMUX_END3 1u         /* the barcode is counted from the 3' end */
+#define SASSY_HIP_DEMUX_KEEP_BARCODE 2u /* do not clip */
+typedef struct sassy_hip_ReadDemux {
+  int32_t sample;  /* best where assigned; -1: unassigned */
+  uint32_t best;   /* UINT32_MAX: the read has no window */
+  uint8_t cost;    /* 255: no window */
+  uint8_t second;  /* 255: no window */
+  uint16_t n_best; /* 0: no window */
+  uint32_t index;  /* where this read lies in *out_sorted: the inverse of the order */
+} sassy_hip_ReadDemux;
+int sassy_hip_demux_reads(sassy_SearcherType *s, const sassy_hip_Reads *reads, const uint8_t *const *barcodes, size_t barcode_len,
+                          size_t n_barcodes, uint32_t at, size_t k, uint32_t min_delta, uint32_t flags,
+                          sassy_hip_ReadDemux *out_assign /* may be NULL; n */, uint64_t *out_order /* may be NULL; n */,
+                          uint64_t *out_bounds /* required; n_barcodes + 2 */, sassy_hip_Reads **out_sorted);
+
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar
  * match_region = text[start..end), reverse-complemented for Rc matches unless `sam`; the cigar is

@@ -170,6 +170,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_reads_relayout", "sassy_hip_read_overlaps",
     "sassy_hip_reads_quality", "sassy_hip_merge_pairs",
     "sassy_hip_trim_reads", "sassy_hip_reads_slice",
+    "sassy_hip_reads_select", "sassy_hip_demux_reads",
 ]
 
 _lib = None
@@ -439,6 +440,10 @@ def lib():
                                        vp, C.POINTER(vp)]
     L.sassy_hip_reads_slice.restype = C.c_int
     L.sassy_hip_reads_slice.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
+    L.sassy_hip_reads_select.restype = C.c_int
+    L.sassy_hip_reads_select.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(vp)]
+    L.sassy_hip_demux_reads.restype = C.c_int
+    L.sassy_hip_demux_reads.argtypes = [vp, vp, C.POINTER(C.c_char_p), sz, sz, C.c_uint32, sz, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(vp)]
     L.sassy_hip_malloc.restype = vp
     L.sassy_hip_malloc.argtypes = [sz]
     L.sassy_hip_free.restype = None
@@ -554,8 +559,17 @@ def read_trim_dtype():
     return np.dtype([("length", "<u4"), ("quality_len", "<u4"), ("adapter_pos", "<u4"), ("adapter", "<i2"), ("overlap", "u1"), ("mismatches", "u1")])
 
 
+def read_demux_dtype():
+    """numpy view of include/sassy_hip.h: sassy_hip_ReadDemux (16 bytes)."""
+    import numpy as np
+    return np.dtype([("sample", "<i4"), ("best", "<u4"), ("cost", "u1"), ("second", "u1"), ("n_best", "<u2"), ("index", "<u4")])
+
+
 OVERLAP_MAX_LEN = 512  # SASSY_HIP_OVERLAP_MAX_LEN
 TRIM_MAX_ADAPTERS = 64  # SASSY_HIP_TRIM_MAX_ADAPTERS
+DEMUX_MAX_BARCODES = 4096  # SASSY_HIP_DEMUX_MAX_BARCODES
+DEMUX_END3 = 1  # SASSY_HIP_DEMUX_END3
+DEMUX_KEEP_BARCODE = 2  # SASSY_HIP_DEMUX_KEEP_BARCODE
 
 
 def overlap_trims(rec, la: int, lb: int):
@@ -2242,6 +2256,65 @@ class DeviceReads:
         _check(lib().sassy_hip_reads_slice(self._h, b.ctypes.data if n else None, w.ctypes.data if n else None, stream or None, C.byref(out)))
         return DeviceReads._adopt(out)
 
+    def select(self, src, begins=None, lens=None, stream: int = 0):
+        """A new DeviceReads whose record j is bytes [begins[j], begins[j] + lens[j]) of this batch's read src[j], and of its
+        quality where kept (sassy_hip_reads_select); without `begins` and `lens`, whole reads.  `src` may repeat, skip and
+        reorder: it takes one sample out of a demultiplexed batch, puts a mate batch into the order of another, drops empty
+        records.  `begins`, `lens`: one entry per output record, or one number for all.  An index that names no read, or a
+        window that reaches outside its read, is refused."""
+        import numpy as np
+        self._live()
+        if (begins is None) != (lens is None):
+            raise SassyHipError("select: begins and lens are given together, or neither (whole reads)")
+        src = np.ascontiguousarray(np.asarray(src, dtype=np.uint64).reshape(-1))
+        n = len(src)
+        b = w = None
+        if begins is not None:
+            b = np.ascontiguousarray(np.broadcast_to(np.asarray(begins, dtype=np.uint64), (n,)))
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(lens, dtype=np.uint64), (n,)))
+            if n == 0:  # (the pair is still given together)
+                b = w = np.zeros(1, dtype=np.uint64)
+        out = C.c_void_p()
+        _check(lib().sassy_hip_reads_select(self._h, src.ctypes.data if n else None, None if b is None else b.ctypes.data,
+                                            None if w is None else w.ctypes.data, n, stream or None, C.byref(out)))
+        return DeviceReads._adopt(out)
+
+    def nonempty(self, stream: int = 0):
+        """(reads, kept_indices): the records that hold a byte, in their order, as a new DeviceReads (a `select`), and which
+        they were -- what drops the empty records a trim or a merge leaves."""
+        import numpy as np
+        kept = np.flatnonzero(self.seq_lens).astype(np.uint64)
+        return self.select(kept, stream=stream), kept
+
+    def demux(self, searcher, barcodes, k: int = 1, min_delta: int = 1, at: int = 0, end3: bool = False, clip: bool = True,
+              with_records: bool = False):
+        """The batch split by sample barcode on the device (sassy_hip_demux_reads).  `barcodes`: 1 .. 4096 byte strings of ONE
+        length 1 .. 64.  A read's window is the barcode's length of bytes at distance `at` from its 5' end (`end3`: from its
+        3' end); a read is assigned to the barcode of the fewest mismatches (the smaller index among equals) when that cost
+        is at most `k` and the runner-up costs at least `min_delta` more.  Returns a `Demuxed`: `.reads` is a new DeviceReads
+        SORTED BY SAMPLE, the unassigned last, assigned reads without their barcode (and without what lies between it and
+        the read's end) unless clip=False; `.order[j]` is the read behind record j; sample s is the records
+        [bounds[s], bounds[s + 1]).  `searcher`: dna (A, C, G, T only) or iupac; it runs the call on its stream and keeps the
+        stats.  The definition is tests/helpers/demux_reads_ref.py."""
+        import numpy as np
+        self._live()
+        barcodes = [b.encode() if isinstance(b, str) else _byte_pattern(b) for b in barcodes]
+        if any(len(b) != len(barcodes[0]) for b in barcodes):
+            raise SassyHipError("demux: the barcodes must all have one length")
+        if any(not 0 <= int(v) < (1 << 32) for v in (min_delta, at)) or int(k) < 0:
+            raise SassyHipError("demux: min_delta and at must fit 32 bits, and none of them nor k may be negative")
+        n, nb = len(self), len(barcodes)
+        ptrs = (C.c_char_p * max(nb, 1))(*barcodes)
+        records = np.zeros(n, dtype=read_demux_dtype()) if with_records else None
+        order = np.zeros(n, dtype=np.uint64)
+        bounds = np.zeros(nb + 2, dtype=np.uint64)
+        out = C.c_void_p()
+        _check(lib().sassy_hip_demux_reads(searcher._h, self._h, ptrs, len(barcodes[0]) if nb else 0, nb, int(at), int(k), int(min_delta),
+                                           (DEMUX_END3 if end3 else 0) | (0 if clip else DEMUX_KEEP_BARCODE),
+                                           records.ctypes.data if with_records and n else None, order.ctypes.data if n else None,
+                                           bounds.ctypes.data, C.byref(out)))
+        return Demuxed(DeviceReads._adopt(out), order, bounds, records)
+
     def download_text(self) -> bytes:
         """The whole device buffer: the layout, pads and the 64 spare bytes included."""
         self._live()
@@ -2267,3 +2340,54 @@ class DeviceReads:
 
     def __del__(self):
         self.free()
+
+
+class Demuxed:
+    """What `DeviceReads.demux` returns: `.reads`, the batch sorted by sample (the unassigned last); `.order`, per record of it
+    the read of the input it was; `.bounds`, B + 2 places -- sample s is the records [bounds[s], bounds[s + 1]), the unassigned
+    are [bounds[B], bounds[B + 1]); `.records`, one `read_demux_dtype()` per INPUT read where asked for, else None."""
+
+    def __init__(self, reads, order, bounds, records=None):
+        self.reads, self.order, self.bounds, self.records = reads, order, bounds, records
+
+    @property
+    def n_samples(self) -> int:
+        return len(self.bounds) - 2
+
+    @property
+    def counts(self):
+        """Reads per sample as a numpy array of B + 1 entries, the unassigned last."""
+        import numpy as np
+        return np.diff(self.bounds.astype(np.int64))
+
+    def span(self, s: int):
+        """(first, end) of sample s among the records of `.reads`; s = -1: the unassigned."""
+        s = self.n_samples if s == -1 else int(s)
+        if not 0 <= s <= self.n_samples:
+            raise SassyHipError(f"Demuxed: sample {s} of {self.n_samples}")
+        return int(self.bounds[s]), int(self.bounds[s + 1])
+
+    def sample(self, s: int, stream: int = 0):
+        """Sample s as a DeviceReads of its own (a `select` of its range); s = -1: the unassigned."""
+        import numpy as np
+        a, b = self.span(s)
+        return self.reads.select(np.arange(a, b, dtype=np.uint64), stream=stream)
+
+    def free(self):
+        self.reads.free()
+
+
+def demux_reads(searcher, reads, barcodes, k: int = 1, min_delta: int = 1, at: int = 0, end3: bool = False, clip: bool = True,
+                with_records: bool = False):
+    """`DeviceReads.demux` for a DeviceReads, or for a list of sequences or of (sequence, quality) tuples, which goes through
+    `DeviceReads.from_sequences` first."""
+    made = None
+    if not isinstance(reads, DeviceReads):
+        reads = list(reads)
+        paired = bool(reads) and isinstance(reads[0], tuple)
+        made = reads = DeviceReads.from_sequences([x[0] for x in reads], [x[1] for x in reads]) if paired else DeviceReads.from_sequences(reads)
+    try:
+        return reads.demux(searcher, barcodes, k=k, min_delta=min_delta, at=at, end3=end3, clip=clip, with_records=with_records)
+    finally:
+        if made is not None:
+            made.free()

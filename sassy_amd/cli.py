@@ -127,6 +127,7 @@ Not mirrored: coloured output, --v2, threads.
 from __future__ import annotations
 
 import argparse
+import os
 import sys
 from typing import List, Tuple
 
@@ -680,6 +681,100 @@ def trim_parser(sub):
     return cp
 
 
+SPLIT_HEADER = "id\tsample\tbest\tcost\tsecond\tn_best\n"
+
+
+def split_rows(ids, names, records):
+    """The TSV rows of DeviceReads.demux's records, one per read: the sample by its barcode's id, `unassigned` where none."""
+    return [f"{ids[i]}\t{names[int(r['sample'])] if int(r['sample']) >= 0 else 'unassigned'}\t{int(r['best']) if int(r['n_best']) else -1}\t"
+            f"{int(r['cost'])}\t{int(r['second'])}\t{int(r['n_best'])}\n" for i, r in enumerate(records)]
+
+
+def split_names(barcodes):
+    """The file stems of `split`: the barcodes' ids up to their first blank, which must be distinct, free of path separators and
+    none of them `unassigned`."""
+    names = [(i.split() or [""])[0] for i, _ in barcodes]
+    for n in names:
+        if not n or "/" in n or os.sep in n or n in (".", "..") or n == "unassigned" or n.endswith("_2"):
+            raise SystemExit(f"split: barcode id {n!r} cannot name a file (empty, a path, `unassigned`, or ending in _2)")
+    if len(set(names)) != len(names):
+        raise SystemExit("split: the barcode ids must be distinct")
+    return names
+
+
+def run_split(args, searcher, barcodes) -> int:
+    """`split`: every read into OUTDIR/<barcode id>.fq without its barcode, or into OUTDIR/unassigned.fq (DeviceReads.demux);
+    with --mate the mates, whole, in the same order into <id>_2.fq.  The files are made anew, empty ones included, and every
+    batch appends to them."""
+    from . import reads_to_fastq
+    from .fastx import read_fastq_device_batches, read_fastq_pair_device_batches
+    import numpy as np
+    names = split_names(barcodes) + ["unassigned"]
+    os.makedirs(args.outdir, exist_ok=True)
+    suffixes = ("", "_2") if args.mate else ("",)
+    for name in names:
+        for suf in suffixes:
+            open(os.path.join(args.outdir, name + suf + ".fq"), "wb").close()
+    tsv = open(os.path.join(args.outdir, "assignments.tsv"), "w") if args.tsv else None
+    seqs = [b for _, b in barcodes]
+
+    def append(reads, ids, bounds, suf):
+        # one FASTQ of the whole sorted batch, cut at the samples' bounds by the records' sizes
+        lens = reads.seq_lens.astype(np.int64)
+        sizes = np.where(lens > 0, np.array([len(i.encode()) for i in ids], dtype=np.int64) + 2 * lens + 6, 0)
+        ends = np.concatenate([[0], np.cumsum(sizes)])
+        data = reads_to_fastq(reads, ids)
+        for s, name in enumerate(names):
+            a, b = int(ends[int(bounds[s])]), int(ends[int(bounds[s + 1])])
+            if b > a:
+                with open(os.path.join(args.outdir, name + suf + ".fq"), "ab") as fh:
+                    fh.write(data[a:b])
+
+    try:
+        if tsv:
+            tsv.write(SPLIT_HEADER)
+        batches = (read_fastq_pair_device_batches(args.input, args.mate, BATCH_BYTES, keep_quality=True) if args.mate
+                   else ((b, None) for b in read_fastq_device_batches(args.input, BATCH_BYTES, keep_quality=True)))
+        for b1, b2 in batches:
+            d = mates = None
+            try:  # (a refused batch lets go of its device memory as well)
+                d = b1.texts.demux(searcher, seqs, k=args.k, min_delta=args.min_delta, at=args.at, end3=args.end3, clip=not args.keep_barcode,
+                                   with_records=bool(tsv))
+                order = d.order.astype(np.int64).tolist()
+                ids = [b1.id(i) for i in range(len(b1))]
+                append(d.reads, [ids[r] for r in order], d.bounds, "")
+                if b2 is not None:
+                    mates = b2.texts.select(d.order)
+                    ids2 = [b2.id(i) for i in range(len(b2))]
+                    append(mates, [ids2[r] for r in order], d.bounds, "_2")
+                if tsv:
+                    tsv.writelines(split_rows(ids, names, d.records))
+            finally:
+                for x in (d, mates, b1, b2):
+                    if x is not None:
+                        x.free()
+    finally:
+        if tsv:
+            tsv.close()
+    return 0
+
+
+def split_parser(sub):
+    cp = sub.add_parser("split", help="demultiplex a FASTQ file by sample barcode into one FASTQ file per sample")
+    cp.add_argument("input", metavar="IN.fq", help="FASTQ of the reads that carry the barcode")
+    cp.add_argument("-f", "--barcodes", required=True, metavar="BARCODES.fa", help="FASTA of the barcodes, all of one length; the ids name the files")
+    cp.add_argument("-k", type=int, required=True, help="mismatches an assigned read's barcode has at most")
+    cp.add_argument("-o", "--outdir", required=True, metavar="OUTDIR", help="directory of <barcode id>.fq and unassigned.fq")
+    cp.add_argument("--mate", default="", metavar="R2.fq", help="FASTQ of the mates, in the same order: written whole to <id>_2.fq")
+    cp.add_argument("--at", type=int, default=0, help="bases between the read's end and the barcode (default 0)")
+    cp.add_argument("--end3", action="store_true", help="the barcode is counted from the 3' end")
+    cp.add_argument("--min-delta", type=int, default=1, help="mismatches the runner-up has at least more than the best (default 1: ties are unassigned)")
+    cp.add_argument("--keep-barcode", action="store_true", help="do not clip the barcode off")
+    cp.add_argument("--alphabet", type=str.lower, choices=["dna", "iupac"], default="dna")
+    cp.add_argument("--tsv", action="store_true", help="also write one row per read from the records, to OUTDIR/assignments.tsv")
+    return cp
+
+
 def load_primers(path: str) -> List[Tuple[str, bytes, bytes]]:
     """PRIMERS of `amplicon`: rows of name<TAB>fwd<TAB>rev (empty lines and lines from `#` on skipped)."""
     pairs = []
@@ -789,7 +884,18 @@ def main(argv=None) -> int:
     overlap_parser(sub)
     merge_parser(sub)
     trim_parser(sub)
+    split_parser(sub)
     args = ap.parse_args(argv)
+    if args.cmd == "split":
+        if args.k < 0 or args.at < 0 or not 0 <= args.min_delta <= 65:
+            ap.error("split takes -k >= 0, --at >= 0 and 0 <= --min-delta <= 65")
+        barcodes = list(read_fastx(args.barcodes))
+        lens = {len(b) for _, b in barcodes}
+        if not 1 <= len(barcodes) <= 4096 or len(lens) != 1 or not 1 <= min(lens) <= 64:
+            ap.error("split takes 1 .. 4096 barcodes of one length of 1 .. 64 bases")
+        if args.at + min(lens) > 512:
+            ap.error("split: --at and the barcode's length reach past 512 bases")
+        return run_split(args, Searcher(args.alphabet, rc=False), barcodes)
     if args.cmd == "trim":
         if args.min_overlap < 1 or args.k < 0 or not 0 <= args.max_permille <= 1000 or not 0 <= args.quality_cutoff <= 93 or args.min_length < 0:
             ap.error("trim takes --min-overlap >= 1, -k >= 0, 0 <= --max-permille <= 1000, 0 <= -q <= 93 and -m >= 0")

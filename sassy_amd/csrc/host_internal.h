@@ -732,6 +732,10 @@ struct sassy_SearcherType {
   DevBuf<sassy_hip_ReadOverlap> d_overlaps;  // read overlaps (read_overlaps.hip): one record per pair
   DevBuf<sassy_hip_ReadTrim> d_trims;        // trimming (trim_reads.hip): one record per read, and the adapter table
   DevBuf<uint32_t> d_trim_tab;
+  // demultiplexing (demux_reads.hip): the barcode table, and one area for the records, the labels, the order, the windows and
+  // the sort's own scratch
+  DevBuf<uint32_t> d_demux_tab;
+  DevBuf<uint8_t> d_demux;
   DevBuf<uint64_t> d_range;     // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
@@ -757,7 +761,7 @@ struct sassy_SearcherType {
     d_ham_tab.release(); d_ham_count.release(); d_ham_prefix.release(); d_ham_items.release(); d_ham_sorted.release(); d_ham_sort.release();
     d_ham_texts.release(); d_ham_rem.release(); d_ham_cells.release(); d_ham_bins.release();
     d_pairs_a.release(); d_pairs_t.release(); d_pairs_cells.release(); d_pairs_rows.release(); d_pairs_out.release();
-    d_umi_reads.release(); d_umi_distinct.release(); d_overlaps.release(); d_trims.release(); d_trim_tab.release();
+    d_umi_reads.release(); d_umi_distinct.release(); d_overlaps.release(); d_trims.release(); d_trim_tab.release(); d_demux_tab.release(); d_demux.release();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();
@@ -1388,6 +1392,10 @@ int reads_layout_merged(const sassy_hip_ReadOverlap* d_rec, const uint64_t* d_le
 // lengths says (see there)
 int reads_layout_trimmed(const sassy_hip_ReadTrim* d_rec, uint64_t n, bool keep_quality, ScanLane* lane, sassy_hip_Reads* F, uint64_t* n_found);
 int reads_layout_windows(const uint64_t* d_lens, uint64_t n, bool keep_quality, hipStream_t st, sassy_hip_Reads* F);
+// trim_reads.hip, for demux_reads.hip too: the write kernel over a laid-out handle F (see there), and the buffers of a handle
+// without a record
+int write_windows(const sassy_hip_Reads* reads, const uint64_t* d_src, const uint64_t* d_begin, sassy_hip_Reads* F, hipStream_t st);
+int reads_empty_buffers(sassy_hip_Reads* F, bool keep_quality, hipStream_t st);
 // c_abi.hip: sassy_hip_search_many behind its null checks
 int search_many_source(sassy_SearcherType* s, const uint8_t* const* patterns, const size_t* pattern_lens, size_t n_patterns, TextSource& src,
                        size_t k, uint32_t flags, sassy_hip_Result** out);

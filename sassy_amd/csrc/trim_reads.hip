@@ -22,10 +22,11 @@
 //                                           the record table, the longest read, the layout's size  -> host (one wait)
 //   reads_window_write_kernel   a lane per 64-byte block of the OUTPUT, as fastq_copy_kernel and merge_write_kernel: the block's
 //              read by ham_text_of over the new starts, its 64 bytes from [begin, begin + length) of the source read -- a slice
-//              (<true>): five 16-byte loads shifted by fq_shift_block; a trim (<false>: begin = 0, so source and block are
+//              (SHIFTED): five 16-byte loads shifted by fq_shift_block; a trim (not SHIFTED: begin = 0, so source and block are
 //              64-byte aligned): four aligned loads per buffer, all issued before the first store; every load bounded by the source's text size --,
 //              four 16-byte stores into the text and, where kept, the quality buffer, zeros behind the read's end, rem[block];
 //              one extra lane zeroes the 64 spare bytes.  No buffer is cleared as a whole.
+//              GATHER (demux_reads.hip: a select, a demux): the block's read comes from read src[t] of the source handle.
 // The input handle is only read.  Every load of a read's bytes is bounded by the handle's length table and its text size,
 // every store by the block count.
 #include <hip/hip_runtime.h>
@@ -164,18 +165,21 @@ hipError_t launch_words(uint32_t W, const TrimArgs& A, hipStream_t st) {
 struct WindowArgs {
   const uint8_t *src_text, *src_qual;  // src_qual: null where the qualities are not kept
   const uint64_t* src_start;           // the source handle's starts
-  const uint64_t* begin;               // per read, on the device; null: every window begins its read
+  const uint64_t* begin;               // per read of the new handle, on the device; null: every window begins its read
+  const uint64_t* src;                 // GATHER: per read of the new handle its read of the source handle
+  uint32_t n_src;                      // reads of the source handle
   uint64_t src_bytes;                  // the source handle's text size (a multiple of 64)
   const uint64_t* table;               // of the new handle: starts[n], then lens[n]
-  uint32_t n;
+  uint32_t n;                          // reads of the new handle
   uint64_t n_blocks;                   // of the new layout; block n_blocks is the spare one
   uint8_t *text, *qual;
   uint32_t* rem;
 };
 
 // SHIFTED: the windows begin anywhere in their reads (a slice).  Otherwise every window begins its read (a trim: A.begin is
-// null), a read starts at a multiple of 64 and so does the block within it: four aligned loads, no shift.
-template <bool SHIFTED>
+// null), a read starts at a multiple of 64 and so does the block within it: four aligned loads, no shift.  GATHER: read t of
+// the output is a window of read src[t] of the source (a select, a demux); otherwise t is its own source.
+template <bool SHIFTED, bool GATHER>
 __global__ __launch_bounds__(256) void reads_window_write_kernel(WindowArgs A) {
   const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b > A.n_blocks) return;
@@ -193,7 +197,9 @@ __global__ __launch_bounds__(256) void reads_window_write_kernel(WindowArgs A) {
   const uint64_t start = A.table[t];
   const uint32_t left = ham_rem(b, start, A.table[(uint64_t)A.n + t]);
   A.rem[b] = left;
-  const uint64_t src = A.src_start[t] + (SHIFTED ? A.begin[t] : 0ull) + (b * 64 - start);
+  uint64_t from = t;
+  if constexpr (GATHER) from = min(A.src[t], (uint64_t)A.n_src - 1u);  // (the host checked a select's table; a demux's is a permutation)
+  const uint64_t src = A.src_start[from] + (SHIFTED ? A.begin[t] : 0ull) + (b * 64 - start);
   const uint32_t keep = min(left, 64u);
   const uint8_t* base = A.src_text;
   const auto load16 = [&](uint64_t at, uint32_t* w) {
@@ -229,8 +235,10 @@ __global__ __launch_bounds__(256) void reads_window_write_kernel(WindowArgs A) {
   }
 }
 
+}  // namespace
+
 // a handle without a record or without a byte: the 64 spare bytes of its buffers
-int empty_buffers(sassy_hip_Reads* F, bool keep_quality, hipStream_t st) {
+int reads_empty_buffers(sassy_hip_Reads* F, bool keep_quality, hipStream_t st) {
   F->text_bytes = 64;
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&F->d_text), 64));
   HIP_TRY(hipMemsetAsync(F->d_text, 0, 64, st));
@@ -241,22 +249,28 @@ int empty_buffers(sassy_hip_Reads* F, bool keep_quality, hipStream_t st) {
   return 0;
 }
 
-// the write kernel over a laid-out handle F whose read r is a window of read r of `reads`
-int write_windows(const sassy_hip_Reads* reads, const uint64_t* d_begin, sassy_hip_Reads* F, hipStream_t st) {
+// the write kernel over a laid-out handle F whose read r is a window of read r of `reads`, or of read d_src[r] where that
+// table is given (n_records of F entries, each below n_records of `reads`, which then holds a read)
+int write_windows(const sassy_hip_Reads* reads, const uint64_t* d_src, const uint64_t* d_begin, sassy_hip_Reads* F, hipStream_t st) {
   WindowArgs A;
   A.src_text = reads->d_text; A.src_qual = F->d_qual ? reads->d_qual : nullptr;
   A.src_start = reads->d_table; A.begin = d_begin;
+  A.src = d_src; A.n_src = (uint32_t)reads->n_records;
   A.src_bytes = reads->text_bytes;
   A.table = F->d_table;
-  A.n = (uint32_t)reads->n_records;
+  A.n = (uint32_t)F->n_records;
   A.n_blocks = (F->text_bytes - 64) / 64;
   A.text = F->d_text; A.qual = F->d_qual; A.rem = F->d_rem;
   const dim3 grid((uint32_t)((A.n_blocks + 1 + 255) / 256));
-  if (d_begin) hipLaunchKernelGGL(reads_window_write_kernel<true>, grid, dim3(256), 0, st, A);
-  else hipLaunchKernelGGL(reads_window_write_kernel<false>, grid, dim3(256), 0, st, A);
+  if (d_src && d_begin) hipLaunchKernelGGL((reads_window_write_kernel<true, true>), grid, dim3(256), 0, st, A);
+  else if (d_src) hipLaunchKernelGGL((reads_window_write_kernel<false, true>), grid, dim3(256), 0, st, A);
+  else if (d_begin) hipLaunchKernelGGL((reads_window_write_kernel<true, false>), grid, dim3(256), 0, st, A);
+  else hipLaunchKernelGGL((reads_window_write_kernel<false, false>), grid, dim3(256), 0, st, A);
   HIP_TRY(hipGetLastError());
   return 0;
 }
+
+namespace {
 
 std::string refusal_text(TrmRefusal why, const TrmCall& c, size_t which) {
   const std::string a = "trim_reads: adapter " + std::to_string(which);
@@ -305,7 +319,7 @@ int trim_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t*
       if (!acgt_only(adapters[j], adapter_lens[j]))
         return fail(SASSY_HIP_EINVAL, "trim_reads: adapter " + std::to_string(j) + " holds other bytes than A, C, G, T: use an iupac searcher");
   if (n == 0) {
-    if (int rc = empty_buffers(F, keep_quality, st)) return rc;
+    if (int rc = reads_empty_buffers(F, keep_quality, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     s->stats.total_ms = now_ms() - t0;
     return 0;
@@ -341,7 +355,7 @@ int trim_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t*
   if (s->timing >= 1) HIP_TRY(hipEventRecord(s->ev_line[1], st));
   uint64_t n_found = 0;
   if (int rc = reads_layout_trimmed(s->d_trims.p, n, keep_quality, &s->lanes[0], F, &n_found)) return rc;  // (waits: `tab` has landed)
-  if (int rc = write_windows(reads, nullptr, F, st)) return rc;
+  if (int rc = write_windows(reads, nullptr, nullptr, F, st)) return rc;
   if (out_trims)
     if (int rc = s->lanes[0].download(out_trims, s->d_trims.p, n * sizeof(sassy_hip_ReadTrim))) return rc;
   HIP_TRY(hipStreamSynchronize(st));  // (the handle is whole when the call returns, and the records are free again)
@@ -364,7 +378,7 @@ int slice_run(const sassy_hip_Reads* reads, const uint64_t* begins, const uint64
   const bool keep_quality = reads->d_qual != nullptr;
   F->device = reads->device;
   if (n == 0) {
-    if (int rc = empty_buffers(F, keep_quality, st)) return rc;
+    if (int rc = reads_empty_buffers(F, keep_quality, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
   }
@@ -378,7 +392,7 @@ int slice_run(const sassy_hip_Reads* reads, const uint64_t* begins, const uint64
   if (e == hipSuccess) e = hipMemcpyAsync(d_win + n, lens, n * sizeof(uint64_t), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (windows)");
   if (rc == 0) rc = reads_layout_windows(d_win + n, n, keep_quality, st, F);
-  if (rc == 0) rc = write_windows(reads, d_win, F, st);
+  if (rc == 0) rc = write_windows(reads, nullptr, d_win, F, st);
   const hipError_t done = hipStreamSynchronize(st);
   (void)hipFree(d_win);
   if (rc == 0 && done != hipSuccess) rc = hip_fail(done, "hipStreamSynchronize (reads_slice)");
