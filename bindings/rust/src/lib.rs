@@ -114,6 +114,7 @@ pub struct ReadDemux {
 pub const DEMUX_MAX_BARCODES: u32 = 4096;
 pub const DEMUX_END3: u32 = 1;
 pub const DEMUX_KEEP_BARCODE: u32 = 2;
+pub const DEDUP_END3: u32 = 1;
 #[repr(C)]
 struct RawSearcher {
     _p: [u8; 0],
@@ -252,6 +253,14 @@ extern "C" {
     pub fn sassy_hip_demux_reads(s: *mut RawSearcher, reads: *const RawReads, barcodes: *const *const u8, barcode_len: usize,
                                  n_barcodes: usize, at: u32, k: usize, min_delta: u32, flags: u32, out_assign: *mut ReadDemux,
                                  out_order: *mut u64, out_bounds: *mut u64, out_sorted: *mut *mut RawReads) -> c_int;
+    /// sassy_hip_umi_groups over a window of every read of a resident batch: the four columns per read, mapped back
+    pub fn sassy_hip_umi_groups_reads(s: *mut RawSearcher, reads: *const RawReads, at: u32, m: usize, k: usize, method: u32, flags: u32,
+                                      out_label: *mut u32, out_size: *mut u32, out_rep: *mut u32, out_count: *mut u32, n_unique: *mut usize,
+                                      n_groups: *mut usize) -> c_int;
+    /// ... and of every group the read with the highest score kept, as a new resident batch (out_kept: which reads those are)
+    pub fn sassy_hip_dedup_reads(s: *mut RawSearcher, reads: *const RawReads, at: u32, m: usize, k: usize, method: u32, flags: u32,
+                                 out_label: *mut u32, out_size: *mut u32, out_rep: *mut u32, out_count: *mut u32, out_kept: *mut u64,
+                                 n_unique: *mut usize, n_groups: *mut usize, out_dedup: *mut *mut RawReads) -> c_int;
     fn sassy_hip_search_shard_begin(s: *mut RawSearcher, pattern: *const u8, pattern_len: usize, d_text: *const u8,
                                     halo_len: u64, shard_len: u64, global_offset: u64, total_len: u64, k: usize,
                                     flags: u32, out: *mut *mut RawTicket) -> c_int;

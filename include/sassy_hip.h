@@ -102,7 +102,8 @@ typedef struct sassy_hip_Stats {
                             10: the link walk of sassy_hip_hamming_clusters (hamming_pairs.hip + clusters.hip: no text);
                             11: the link walk of sassy_hip_edit_clusters (edit_pairs.hip + clusters.hip: no text);
                             12: sassy_hip_umi_groups (umi_groups.hip: the collapse, then hamming_pairs.hip's walk over the
-                                distinct sequences: no text) */
+                                distinct sequences: no text); sassy_hip_umi_groups_reads and sassy_hip_dedup_reads as well
+                                (dedup_reads.hip: the same device work over the windows of a resident read batch) */
   double filter_ms;      /* HIP-event time of the prefilter kernel (part of scan_ms); a search in flight whose text pass
                             was served by several launches (see pass_patterns): the sum of their durations */
   uint64_t hit_blocks;   /* text blocks in which an exact pattern piece ends */
@@ -942,6 +943,58 @@ int sassy_hip_demux_reads(sassy_SearcherType *s, const sassy_hip_Reads *reads, c
                           size_t n_barcodes, uint32_t at, size_t k, uint32_t min_delta, uint32_t flags,
                           sassy_hip_ReadDemux *out_assign /* may be NULL; n */, uint64_t *out_order /* may be NULL; n */,
                           uint64_t *out_bounds /* required; n_barcodes + 2 */, sassy_hip_Reads **out_sorted);
+
+/* UMI grouping and deduplication of a resident read batch (sassy_amd/csrc/dedup_reads.hip, arithmetic in dedup_step.h;
+ * DESIGN.md 5.8h): sassy_hip_umi_groups over a window of every read, with no byte of the batch leaving the device, and of
+ * every group ONE read kept, as a NEW resident read batch.  The definition is tests/helpers/dedup_reads_ref.py.  Integers only.
+ *  - KEY: the key of read r, of la bytes, is its window of m bytes at w; from the 5' end w = at, under SASSY_HIP_DEDUP_END3
+ *    w = la - at - m (the demux's window).  It may be a UMI alone or a UMI and the first bases of the insert: the call does not
+ *    care.  A read with la < at + m has no window and takes no part: its label and rep are UINT32_MAX, its size and count 0,
+ *    and it is never kept;
+ *  - GROUPS: let r_0 < r_1 < ... be the reads that have a window.  The four columns, *n_unique and *n_groups are exactly what
+ *    sassy_hip_umi_groups returns for the host list of their windows under the same searcher, k and method, every index j of
+ *    that result mapped to r_j (ascending order is kept, so "smallest index" stays smallest).  An rc searcher: neighbours on
+ *    either strand, as there.  k >= m is cut to m;
+ *  - KEPT READ (sassy_hip_dedup_reads): of every group the member with the highest score, on a tie the smallest index; the
+ *    score is the sum of the read's raw quality bytes where the handle keeps qualities, otherwise the read's length -- as one
+ *    64-bit key, score << 32 | (0xFFFFFFFF - r), maximised.  out_kept (may be NULL; n entries, the first *n_groups written)
+ *    lists the kept reads in ascending read index; record j of *out_dedup is read out_kept[j] whole: the handle
+ *    sassy_hip_reads_select makes for src = out_kept (id_start = id_len = 0, qualities iff the source keeps them,
+ *    text_bytes == 64 when nothing is kept).  The caller frees it with sassy_hip_reads_free;
+ *  - the columns have sassy_hip_reads_n(reads) entries.  sassy_hip_umi_groups_reads requires out_label; in
+ *    sassy_hip_dedup_reads all four may be NULL.  n_unique and n_groups may be NULL;
+ *  - limits: 1 <= m <= 128; at + m <= 512; reads of at most SASSY_HIP_OVERLAP_MAX_LEN bytes; at most 2^31 - 1 reads
+ *    (SASSY_HIP_EUNSUPPORTED beyond);
+ *  - refused before any device work, in this order, SASSY_HIP_EINVAL unless noted: s == NULL; a flag other than
+ *    SASSY_HIP_DEDUP_END3; an unknown method; m == 0 or m > 128; at + m > 512; an Ascii searcher (use a dna or an iupac one);
+ *    overhang, only_best_match, max_n_frac set (SASSY_HIP_EUNSUPPORTED); reads == NULL; a handle made on another device than
+ *    the searcher's; a read longer than SASSY_HIP_OVERLAP_MAX_LEN; out_label NULL (the groups call), out_dedup NULL (the dedup
+ *    call); searches in flight on the searcher.  A Dna searcher takes batches of A, C, G, T only, looked at on the device as
+ *    the trim looks; anything else is SASSY_HIP_EINVAL and the message points to an iupac searcher.  *out_dedup is NULL after
+ *    every refusal;
+ *  - zero reads, or no read with a window (the handle's longest read is shorter than at + m): success, no kernel launched,
+ *    the counts zero, the columns the sentinels, an empty handle;
+ *  - the input handle is only read.  Device work on the searcher's stream: the flag kernel, a scan, one host wait for the
+ *    count, the encode kernel (a lane per read: the window into the pair family's bit planes), sassy_hip_umi_groups' device
+ *    part over those planes, the scatter kernel; the dedup call then: the score kernel (one 64-bit atomic max per read), the
+ *    keep kernel, a scan, one host wait, a compaction, the layout scan of the parse, the trim's write kernel with a source
+ *    table;
+ *  - sassy_hip_get_stats afterwards: everything sassy_hip_umi_groups leaves (filtered = 12, candidates, hit_blocks = n_unique,
+ *    blocks, chunks, grid, the three timing spans at level 2), text_bytes = windows x m, and scan_launches = what that call's
+ *    walk leaves there (0 UNIQUE, 1 CLUSTER, DIRECTIONAL 1 or 2: 2 where the distinct keys have a pair record) plus this
+ *    unit's own launches: 6 for the groups call (flag, the scan's three, encode, scatter), 16 for the dedup call (those and
+ *    score, keep, the scan's three, compaction, the layout scan's three, write), one more under a Dna searcher whose batch
+ *    has a block to look at.  Zero reads or no window: scan_launches = 0. */
+#define SASSY_HIP_DEDUP_END3 1u   /* the window is counted from the 3' end */
+int sassy_hip_umi_groups_reads(sassy_SearcherType *s, const sassy_hip_Reads *reads, uint32_t at, size_t m, size_t k,
+                               uint32_t method, uint32_t flags,
+                               uint32_t *out_label, uint32_t *out_size, uint32_t *out_rep, uint32_t *out_count, /* n each */
+                               size_t *n_unique, size_t *n_groups);
+int sassy_hip_dedup_reads(sassy_SearcherType *s, const sassy_hip_Reads *reads, uint32_t at, size_t m, size_t k,
+                          uint32_t method, uint32_t flags,
+                          uint32_t *out_label, uint32_t *out_size, uint32_t *out_rep, uint32_t *out_count, /* may all be NULL here */
+                          uint64_t *out_kept /* may be NULL; n entries, the first *n_groups written */,
+                          size_t *n_unique, size_t *n_groups, sassy_hip_Reads **out_dedup);
 
 /* One row of the reference CLI's match table (bin/grep.rs:465-470 header, :710-757 rows):
  *   pat_id  text_id  cost  strand  start  end  match_region  cigar

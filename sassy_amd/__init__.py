@@ -171,6 +171,7 @@ EXPORTED_SYMBOLS = [
     "sassy_hip_reads_quality", "sassy_hip_merge_pairs",
     "sassy_hip_trim_reads", "sassy_hip_reads_slice",
     "sassy_hip_reads_select", "sassy_hip_demux_reads",
+    "sassy_hip_umi_groups_reads", "sassy_hip_dedup_reads",
 ]
 
 _lib = None
@@ -444,6 +445,10 @@ def lib():
     L.sassy_hip_reads_select.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, C.POINTER(vp)]
     L.sassy_hip_demux_reads.restype = C.c_int
     L.sassy_hip_demux_reads.argtypes = [vp, vp, C.POINTER(C.c_char_p), sz, sz, C.c_uint32, sz, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(vp)]
+    L.sassy_hip_umi_groups_reads.restype = C.c_int
+    L.sassy_hip_umi_groups_reads.argtypes = [vp, vp, C.c_uint32, sz, sz, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(sz)]
+    L.sassy_hip_dedup_reads.restype = C.c_int
+    L.sassy_hip_dedup_reads.argtypes = [vp, vp, C.c_uint32, sz, sz, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(vp)]
     L.sassy_hip_malloc.restype = vp
     L.sassy_hip_malloc.argtypes = [sz]
     L.sassy_hip_free.restype = None
@@ -569,6 +574,7 @@ OVERLAP_MAX_LEN = 512  # SASSY_HIP_OVERLAP_MAX_LEN
 TRIM_MAX_ADAPTERS = 64  # SASSY_HIP_TRIM_MAX_ADAPTERS
 DEMUX_MAX_BARCODES = 4096  # SASSY_HIP_DEMUX_MAX_BARCODES
 DEMUX_END3 = 1  # SASSY_HIP_DEMUX_END3
+DEDUP_END3 = 1  # SASSY_HIP_DEDUP_END3
 DEMUX_KEEP_BARCODE = 2  # SASSY_HIP_DEMUX_KEEP_BARCODE
 
 
@@ -2315,6 +2321,50 @@ class DeviceReads:
                                            bounds.ctypes.data, C.byref(out)))
         return Demuxed(DeviceReads._adopt(out), order, bounds, records)
 
+    def _dedup_args(self, who, umi_len, k, method, at):
+        if method not in UMI_METHODS:
+            raise SassyHipError(f"{who}: method must be one of {', '.join(UMI_METHODS)} (got {method!r})")
+        if any(not 0 <= int(v) < (1 << 32) for v in (umi_len, at)) or int(k) < 0:
+            raise SassyHipError(f"{who}: umi_len and at must fit 32 bits, and none of them nor k may be negative")
+
+    def umi_groups(self, searcher, umi_len: int, k: int = 1, method: str = "directional", at: int = 0, end3: bool = False):
+        """UMI grouping of the batch on the device (sassy_hip_umi_groups_reads): the key of a read is its window of `umi_len`
+        bytes (1 .. 128) at distance `at` from its 5' end (`end3`: from its 3' end), and the groups are exactly what
+        `Searcher.umi_groups` makes of the list of windows under the same searcher, k and method, with every index mapped back
+        to its read.  Returns (label, size, rep, count, n_unique, n_groups): four uint32 arrays of len(self) entries and two
+        numbers.  A read too short for a window takes no part: label = rep = 2^32 - 1, size = count = 0.  `searcher`: dna
+        (A, C, G, T only) or iupac; rc=True groups across both strands.  The definition is tests/helpers/dedup_reads_ref.py."""
+        import numpy as np
+        self._live()
+        self._dedup_args("umi_groups", umi_len, k, method, at)
+        n = len(self)
+        label, size, rep, count = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(4))
+        n_unique, n_groups = C.c_size_t(0), C.c_size_t(0)
+        _check(lib().sassy_hip_umi_groups_reads(searcher._h, self._h, int(at), int(umi_len), int(k), UMI_METHODS[method], DEDUP_END3 if end3 else 0,
+                                                label.ctypes.data, size.ctypes.data, rep.ctypes.data, count.ctypes.data, C.byref(n_unique),
+                                                C.byref(n_groups)))
+        return label[:n], size[:n], rep[:n], count[:n], int(n_unique.value), int(n_groups.value)
+
+    def dedup(self, searcher, umi_len: int, k: int = 1, method: str = "directional", at: int = 0, end3: bool = False, with_columns: bool = False):
+        """The batch deduplicated by UMI on the device (sassy_hip_dedup_reads): the groups of `umi_groups`, and of every group
+        the read with the highest score kept -- the sum of its quality bytes where the batch keeps qualities, else its
+        length; on a tie the smallest index.  Returns a `Deduped`: `.reads` is a new DeviceReads whose record j is read
+        `.kept[j]` whole (ascending), `.n_unique`, `.n_groups`, and with_columns=True `.label`, `.size`, `.rep`, `.count` as
+        `umi_groups` returns them.  Clip the key off afterwards with `slice`.  The definition is
+        tests/helpers/dedup_reads_ref.py."""
+        import numpy as np
+        self._live()
+        self._dedup_args("dedup", umi_len, k, method, at)
+        n = len(self)
+        cols = tuple(np.zeros(n, dtype=np.uint32) for _ in range(4)) if with_columns else None
+        ptr = lambda i: cols[i].ctypes.data if with_columns and n else None
+        kept = np.zeros(max(n, 1), dtype=np.uint64)
+        n_unique, n_groups = C.c_size_t(0), C.c_size_t(0)
+        out = C.c_void_p()
+        _check(lib().sassy_hip_dedup_reads(searcher._h, self._h, int(at), int(umi_len), int(k), UMI_METHODS[method], DEDUP_END3 if end3 else 0,
+                                           ptr(0), ptr(1), ptr(2), ptr(3), kept.ctypes.data, C.byref(n_unique), C.byref(n_groups), C.byref(out)))
+        return Deduped(DeviceReads._adopt(out), kept[:int(n_groups.value)].copy(), int(n_unique.value), int(n_groups.value), cols)
+
     def download_text(self) -> bytes:
         """The whole device buffer: the layout, pads and the 64 spare bytes included."""
         self._live()
@@ -2375,6 +2425,40 @@ class Demuxed:
 
     def free(self):
         self.reads.free()
+
+
+class Deduped:
+    """What `DeviceReads.dedup` returns: `.reads`, the kept reads as a new DeviceReads; `.kept`, per record of it the read of
+    the input it is (ascending); `.n_unique`, the distinct keys; `.n_groups`, the groups (= len(kept)); `.label`, `.size`,
+    `.rep`, `.count`, one entry per INPUT read where asked for, else None."""
+
+    def __init__(self, reads, kept, n_unique, n_groups, columns=None):
+        self.reads, self.kept, self.n_unique, self.n_groups = reads, kept, n_unique, n_groups
+        self.label, self.size, self.rep, self.count = columns if columns is not None else (None, None, None, None)
+
+    def free(self):
+        self.reads.free()
+
+
+def _as_device_reads(reads):
+    """(reads as a DeviceReads, the one made here or None)"""
+    if isinstance(reads, DeviceReads):
+        return reads, None
+    reads = list(reads)
+    paired = bool(reads) and isinstance(reads[0], tuple)
+    made = DeviceReads.from_sequences([x[0] for x in reads], [x[1] for x in reads]) if paired else DeviceReads.from_sequences(reads)
+    return made, made
+
+
+def dedup_reads(searcher, reads, umi_len: int, k: int = 1, method: str = "directional", at: int = 0, end3: bool = False, with_columns: bool = False):
+    """`DeviceReads.dedup` for a DeviceReads, or for a list of sequences or of (sequence, quality) tuples, which goes through
+    `DeviceReads.from_sequences` first."""
+    reads, made = _as_device_reads(reads)
+    try:
+        return reads.dedup(searcher, umi_len, k=k, method=method, at=at, end3=end3, with_columns=with_columns)
+    finally:
+        if made is not None:
+            made.free()
 
 
 def demux_reads(searcher, reads, barcodes, k: int = 1, min_delta: int = 1, at: int = 0, end3: bool = False, clip: bool = True,

@@ -113,6 +113,16 @@ written; `--tsv` writes one row per read to OUT.fq.tsv:
 
     id  length  quality_len  adapter_pos  adapter  overlap  mismatches
 
+`dedup IN.fq --umi-len N [--at N] [--end3] [-k K] [--method unique|cluster|directional] [--alphabet dna|iupac] -o OUT.fq
+[--mate R2.fq --mate-out OUT2.fq] [--tsv FILE]` keeps one read per UMI group through `DeviceReads.dedup`, on the device: the key
+of a read is its N bases at distance `--at` from its 5' end (`--end3`: its 3' end), the groups are `cluster --umi`'s over the
+keys, and of every group the read with the highest quality sum stays (on a tie the first).  Groups are formed per batch of the
+input.  Kept records go to `-o` under their own ids, whole; their mates to `--mate-out`; `--tsv` writes one row per read --
+`label_id` the id of the read whose key opened the group (`-`: the read is too short for a key), `size` the group's reads,
+`count` the reads that carry the row's key, `kept` 1 for the read that stays:
+
+    read_id  label_id  size  count  kept
+
 `agrep [-i] [-C N] PATTERN K [PATH ...]` mirrors `sassy agrep` (bin/grep.rs:132-307, README "To fuzzy search plain ASCII
 files"): every file (no path or `-`: stdin) is read whole and searched forward with the `ascii` profile (`-i`: `ascii_ci`);
 one block per match, sorted by (start, end): `PATH:LINE:COL:COST:` and the line(s) the match lies in -- LINE and the line's
@@ -775,6 +785,69 @@ def split_parser(sub):
     return cp
 
 
+DEDUP_HEADER = "read_id\tlabel_id\tsize\tcount\tkept\n"
+
+
+def dedup_rows(ids, label, size, count, kept):
+    """The TSV rows of DeviceReads.dedup's columns, one per read: the id of the read that labels its group (`-` where the read
+    has no window), the group's reads, the reads that carry its key, and 1 where it is the kept one."""
+    is_kept = set(int(r) for r in kept)
+    return [f"{ids[r]}\t{ids[int(label[r])] if int(label[r]) != 0xFFFFFFFF else '-'}\t{int(size[r])}\t{int(count[r])}\t{1 if r in is_kept else 0}\n"
+            for r in range(len(ids))]
+
+
+def run_dedup(args, searcher) -> int:
+    """`dedup`: of every UMI group of a batch the best read into OUT.fq (DeviceReads.dedup); with --mate the mates of the kept
+    reads into --mate-out.  Groups are formed per batch of the input."""
+    from . import reads_to_fastq
+    from .fastx import read_fastq_device_batches, read_fastq_pair_device_batches
+    out = open(args.output, "wb")
+    out2 = open(args.mate_out, "wb") if args.mate else None
+    tsv = open(args.tsv, "w") if args.tsv else None
+    try:
+        if tsv:
+            tsv.write(DEDUP_HEADER)
+        batches = (read_fastq_pair_device_batches(args.input, args.mate, BATCH_BYTES, keep_quality=True) if args.mate
+                   else ((b, None) for b in read_fastq_device_batches(args.input, BATCH_BYTES, keep_quality=True)))
+        for b1, b2 in batches:
+            d = mates = None
+            try:  # (a refused batch lets go of its device memory as well)
+                d = b1.texts.dedup(searcher, args.umi_len, k=args.k, method=args.method, at=args.at, end3=args.end3, with_columns=bool(tsv))
+                kept = d.kept.astype("int64").tolist()
+                ids = [b1.id(i) for i in range(len(b1))]
+                out.write(reads_to_fastq(d.reads, [ids[r] for r in kept]))
+                if b2 is not None:
+                    mates = b2.texts.select(d.kept)
+                    out2.write(reads_to_fastq(mates, [b2.id(r) for r in kept]))
+                if tsv:
+                    tsv.writelines(dedup_rows(ids, d.label, d.size, d.count, kept))
+            finally:
+                for x in (d, mates, b1, b2):
+                    if x is not None:
+                        x.free()
+    finally:
+        for fh in (out, out2, tsv):
+            if fh:
+                fh.close()
+    return 0
+
+
+def dedup_parser(sub):
+    cp = sub.add_parser("dedup", help="keep one read per UMI group of a FASTQ file")
+    cp.add_argument("input", metavar="IN.fq", help="FASTQ of the reads that carry the UMI")
+    cp.add_argument("--umi-len", type=int, required=True, metavar="N", help="bases of the key: the UMI, or the UMI and the first bases behind it (1 .. 128)")
+    cp.add_argument("--at", type=int, default=0, help="bases between the read's end and the key (default 0)")
+    cp.add_argument("--end3", action="store_true", help="the key is counted from the 3' end")
+    cp.add_argument("-k", type=int, default=1, help="mismatches two neighbouring keys have at most (default 1)")
+    cp.add_argument("--method", choices=["unique", "cluster", "directional"], default="directional")
+    cp.add_argument("--alphabet", type=str.lower, choices=["dna", "iupac"], default="dna")
+    cp.add_argument("-o", "--output", required=True, metavar="OUT.fq", help="the kept reads")
+    cp.add_argument("--mate", default="", metavar="R2.fq", help="FASTQ of the mates, in the same order")
+    cp.add_argument("--mate-out", default="", metavar="OUT2.fq", help="the mates of the kept reads (with --mate)")
+    cp.add_argument("--tsv", default="", metavar="FILE", help="also write one row per read: read_id label_id size count kept")
+    return cp
+
+
 def load_primers(path: str) -> List[Tuple[str, bytes, bytes]]:
     """PRIMERS of `amplicon`: rows of name<TAB>fwd<TAB>rev (empty lines and lines from `#` on skipped)."""
     pairs = []
@@ -885,7 +958,16 @@ def main(argv=None) -> int:
     merge_parser(sub)
     trim_parser(sub)
     split_parser(sub)
+    dedup_parser(sub)
     args = ap.parse_args(argv)
+    if args.cmd == "dedup":
+        if not 1 <= args.umi_len <= 128 or args.at < 0 or args.k < 0:
+            ap.error("dedup takes 1 <= --umi-len <= 128, --at >= 0 and -k >= 0")
+        if args.at + args.umi_len > 512:
+            ap.error("dedup: --at and --umi-len reach past 512 bases")
+        if bool(args.mate) != bool(args.mate_out):
+            ap.error("dedup: --mate and --mate-out are given together")
+        return run_dedup(args, Searcher(args.alphabet, rc=False))
     if args.cmd == "split":
         if args.k < 0 or args.at < 0 or not 0 <= args.min_delta <= 65:
             ap.error("split takes -k >= 0, --at >= 0 and 0 <= --min-delta <= 65")

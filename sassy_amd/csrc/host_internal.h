@@ -736,6 +736,9 @@ struct sassy_SearcherType {
   // the sort's own scratch
   DevBuf<uint32_t> d_demux_tab;
   DevBuf<uint8_t> d_demux;
+  // deduplication (dedup_reads.hip): one area for the window flags and their scan, the reads' table, the columns per read, the
+  // scores, the groups' best keys, the kept flags and their scan, the kept reads' table and lengths
+  DevBuf<uint8_t> d_dedup;
   DevBuf<uint64_t> d_range;     // N counting on device-resident text
   DevBuf<uint32_t> d_ncount;
   // HIP-event timing of the call's phases: 0 none, 1 the dominant kernel only (filter / streaming
@@ -762,6 +765,7 @@ struct sassy_SearcherType {
     d_ham_texts.release(); d_ham_rem.release(); d_ham_cells.release(); d_ham_bins.release();
     d_pairs_a.release(); d_pairs_t.release(); d_pairs_cells.release(); d_pairs_rows.release(); d_pairs_out.release();
     d_umi_reads.release(); d_umi_distinct.release(); d_overlaps.release(); d_trims.release(); d_trim_tab.release(); d_demux_tab.release(); d_demux.release();
+    d_dedup.release();
     d_range.release(); d_ncount.release(); d_tables.release(); d_multi_bitmap.release(); d_multi_bits.release();
     d_tiled_peq.release(); d_tiled_pat.release(); d_tiled_cnt.release(); d_tiled_sel.release(); d_tiled_list.release(); d_tiled_rtext.release();
     d_min_cells.release(); d_min_out.release();
@@ -1323,6 +1327,15 @@ int pairs_upload_self(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_
 int pairs_resident_link(sassy_SearcherType* s, const uint32_t* d_a, const uint32_t* d_t, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent);
 int pairs_resident_records(sassy_SearcherType* s, const uint32_t* d_a, const uint32_t* d_t, size_t n, uint32_t m, uint32_t k, const char* who,
                            unsigned long long* total);
+// umi_groups.hip, for dedup_reads.hip: the grouping call behind the list's upload, over planes that lie on the device
+// (d_planes [n][P W]; d_targets [S n][P W], read by an rc searcher only).  out_label == NULL: no column is copied back and
+// *n_groups is not counted.  *dev: the four columns on the device, n entries each, until the searcher's next grouping call.
+struct UmiColumns {
+  const uint32_t *label, *size, *rep, *count;
+};
+int umi_groups_resident(sassy_SearcherType* s, const uint32_t* d_planes, const uint32_t* d_targets, size_t n, uint32_t m, uint32_t k, uint32_t method,
+                        uint32_t* out_label, uint32_t* out_size, uint32_t* out_rep, uint32_t* out_count, size_t* n_unique, size_t* n_groups,
+                        UmiColumns* dev);
 uint64_t pairs_scan_blocks(uint64_t n);
 int pairs_scan_u64(sassy_SearcherType* s, const unsigned long long* in, uint64_t n, unsigned long long* block_sum, unsigned long long* out);
 int edit_link_components(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint32_t k, uint32_t* d_parent);

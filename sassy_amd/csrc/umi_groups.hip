@@ -242,17 +242,21 @@ struct DistinctArrays {
   }
 };
 
-// The call behind its refusals.  Timing level 2: ev_line[0] -> [1] the collapse (upload excluded: the table's clearing, insert, lookup,
-// scan, gather), [1] -> [2] the walk passes over the distinct sequences, [2] -> [3] the relaxation (CLUSTER: the flatten) with the
-// group and expand kernels.
-int umi_run(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint32_t k, uint32_t method, uint32_t* out_label, uint32_t* out_size,
-            uint32_t* out_rep, uint32_t* out_count, size_t* n_unique, size_t* n_groups) {
+}  // namespace
+
+// The call behind its refusals and behind the list's upload (host_internal.h; dedup_reads.hip calls it over planes that a kernel
+// made): d_planes [n][P W], d_targets [S n][P W] lie on the device (an rc searcher reads d_targets; one strand: the planes
+// serve).  out_label == NULL: no column goes to the host and *n_groups is left alone.  dev, where given: where the four columns
+// lie on the device until the searcher's next grouping call.  Timing level 2: ev_line[0] -> [1] the collapse (the table's
+// clearing, insert, lookup, scan, gather), [1] -> [2] the walk passes over the distinct sequences, [2] -> [3] the relaxation
+// (CLUSTER: the flatten) with the group and expand kernels.
+int umi_groups_resident(sassy_SearcherType* s, const uint32_t* d_planes, const uint32_t* d_targets, size_t n, uint32_t m, uint32_t k, uint32_t method,
+                        uint32_t* out_label, uint32_t* out_size, uint32_t* out_rep, uint32_t* out_count, size_t* n_unique, size_t* n_groups,
+                        UmiColumns* dev) {
   hipStream_t st = s->stream;
   const char* who = "umi_groups";
   s->stats.filtered = 12;
   const uint32_t S = s->rc ? 2u : 1u, PW = pairs_planes(s->profile) * pairs_words(m);
-  const uint32_t *d_planes = nullptr, *d_targets = nullptr;
-  if (int rc = pairs_upload_self(s, a, n, m, &d_planes, &d_targets)) return rc;
 
   // ---- the collapse ----
   const uint64_t n_slots = collapse_slots_for(n, s->sw.collapse_slots);
@@ -331,7 +335,7 @@ int umi_run(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint3
   hipLaunchKernelGGL(umi_expand_kernel, read_grid, dim3(256), 0, st, EA);
   HIP_TRY(hipGetLastError());
   if (s->timing >= 2) HIP_TRY(hipEventRecord(s->ev_line[3], st));
-  HIP_TRY(hipMemcpyAsync(out_label, R.out_label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (out_label) HIP_TRY(hipMemcpyAsync(out_label, R.out_label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   if (out_size) HIP_TRY(hipMemcpyAsync(out_size, R.out_size, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   if (out_rep) HIP_TRY(hipMemcpyAsync(out_rep, R.rep, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   if (out_count) HIP_TRY(hipMemcpyAsync(out_count, R.out_count, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -350,12 +354,22 @@ int umi_run(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint3
   s->stats.blocks = rounds;
   s->stats.text_bytes = (uint64_t)n * m;
   if (n_unique) *n_unique = (size_t)n_u;
-  if (n_groups) {
+  if (n_groups && out_label) {
     size_t roots = 0;
     for (size_t i = 0; i < n; ++i) roots += out_label[i] == i;
     *n_groups = roots;
   }
+  if (dev) *dev = UmiColumns{R.out_label, R.out_size, R.rep, R.out_count};
   return 0;
+}
+
+namespace {
+// the list's upload, then the part above
+int umi_run(sassy_SearcherType* s, const uint8_t* a, size_t n, uint32_t m, uint32_t k, uint32_t method, uint32_t* out_label, uint32_t* out_size,
+            uint32_t* out_rep, uint32_t* out_count, size_t* n_unique, size_t* n_groups) {
+  const uint32_t *d_planes = nullptr, *d_targets = nullptr;
+  if (int rc = pairs_upload_self(s, a, n, m, &d_planes, &d_targets)) return rc;
+  return umi_groups_resident(s, d_planes, d_targets, n, m, k, method, out_label, out_size, out_rep, out_count, n_unique, n_groups, nullptr);
 }
 
 }  // namespace
