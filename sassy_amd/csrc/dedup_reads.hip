@@ -41,12 +41,10 @@ struct ReadTable {
   uint64_t n;
   uint32_t at, m, end3;
 };
-// the read's length as the kernels take it: the host refused longer reads; a read that does not fit its text counts as empty
+// the read's first byte and its length as the kernels take it (reads_fit_len)
 __device__ __forceinline__ uint32_t table_len(const ReadTable& T, uint64_t r, uint64_t* s0) {
   *s0 = T.start[r];
-  const uint64_t l = T.len[r];
-  const bool fits = l <= kOvlMaxLen && *s0 <= T.bytes && l <= T.bytes - *s0;
-  return fits ? (uint32_t)l : 0u;
+  return reads_fit_len(*s0, T.len[r], T.bytes, kOvlMaxLen);
 }
 
 __global__ __launch_bounds__(256) void dedup_flag_kernel(ReadTable T, unsigned long long* has_window) {
@@ -74,11 +72,7 @@ __global__ __launch_bounds__(256) void dedup_encode_kernel(EncodeArgs A) {
   if (idx >= A.n_w) return;  // (never: the scan numbered exactly n_w reads)
   uint64_t s0;
   const uint32_t la = table_len(A.T, r, &s0);
-  const uint8_t* base = A.text;
-  const auto load16 = [&](uint64_t at, uint32_t* w) {
-    const uint4 v = *reinterpret_cast<const uint4*>(base + at);
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-  };
+  const TrmLoad16 load16{A.text};
   const uint64_t at = s0 + dmx_window(la, A.T.at, A.T.m, A.T.end3 != 0u);
   const uint32_t W = A.W, PW = P * W;
   uint32_t fw[P][4], rv[P][4];
@@ -180,24 +174,15 @@ __global__ __launch_bounds__(256) void dedup_compact_kernel(uint64_t n, uint64_t
   kept_len[j] = len[r];
 }
 
+// what a refusal of the calls' own checks says
 std::string refusal_text(DdpRefusal why, const DdpCall& c, const std::string& who) {
-  if (why == kDdpNullSearcher || why == kDdpNullReads) return "Pointers in " + who + "() must not be null";
+  if (why == kDdpNullSearcher) return "Pointers in " + who + "() must not be null";
   if (why == kDdpFlags) return who + " takes SASSY_HIP_DEDUP_END3 only (the read batch is on the device)";
   if (why == kDdpMethod) return who + ": unknown method " + std::to_string(c.method) + " (0 unique, 1 cluster, 2 directional)";
   if (why == kDdpLen) return who + ": m must be 1 .. " + std::to_string(kDdpMaxLen) + " (got " + std::to_string(c.m) + ")";
   if (why == kDdpAt)
     return who + ": at + m = " + std::to_string((uint64_t)c.at + c.m) + " reaches past the longest read a batch may hold (" + std::to_string(kOvlMaxLen) + ")";
-  if (why == kDdpAscii) return who + ": the keys are DNA; use a dna or an iupac searcher";
-  if (why == kDdpOverhang) return "the Hamming search does not take overhang (alpha): " + who + " compares windows that lie inside the reads";
-  if (why == kDdpOnlyBest) return who + " groups every read: only_best_match is not supported";
-  if (why == kDdpNFrac) return who + " does not take max_n_frac: there is no text span for it to apply to";
-  if (why == kDdpDevice)
-    return who + ": the reads were made on device " + std::to_string(c.device_r) + ", the searcher is on device " + std::to_string(c.device_s);
-  if (why == kDdpTooLong)
-    return who + " takes reads of at most " + std::to_string(kOvlMaxLen) + " bytes (SASSY_HIP_OVERLAP_MAX_LEN; the longest has " + std::to_string(c.longest) +
-           ")";
   if (why == kDdpNullOut) return "Pointers in " + who + "() must not be null (" + (who == "dedup_reads" ? "out_dedup" : "out_label") + ")";
-  if (why == kDdpInFlight) return "searches are in flight on this searcher (sassy_hip_search_shard_begin): finish them first";
   return who + ": refused";
 }
 
@@ -209,14 +194,13 @@ struct DdpOut {
   size_t *n_unique, *n_groups;           // may be NULL
 };
 
-// The calls behind their refusals, inside hamming_call (the device, fresh stats, k cut to m).  F: a fresh handle where the
-// kept reads are wanted (it is the caller's to release where this fails), NULL for the groups alone.
+// The calls behind their refusals, inside reads_new_batch (the device, fresh stats, k cut to m).  F: the fresh handle where the
+// kept reads are wanted, NULL for the groups alone.
 int dedup_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, uint32_t at, uint32_t m, uint32_t k, uint32_t method, uint32_t flags, const DdpOut& O,
               sassy_hip_Reads* F, const char* who) {
   hipStream_t st = s->stream;
   const uint64_t n = reads->n_records;
   const bool keep_quality = reads->d_qual != nullptr;
-  if (F) F->device = s->device;
   if (O.n_unique) *O.n_unique = 0;
   if (O.n_groups) *O.n_groups = 0;
   // no read, or none that is long enough for a window (the longest is not): no kernel
@@ -235,15 +219,9 @@ int dedup_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, uint32_t at, 
     return 0;
   }
   if (n > 0x7FFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, std::string(who) + " takes at most 2^31 - 1 reads (" + std::to_string(n) + ")");
-  const bool dna_look = s->profile == PROFILE_DNA && reads->text_bytes > 64;  // (reads_plain launches over the layout's blocks)
-  if (s->profile == PROFILE_DNA) {
-    TextSource src;
-    src.reads = reads;
-    bool plain = false;
-    if (int rc = reads_plain(s, src, &plain)) return rc;
-    if (!plain)
-      return fail(SASSY_HIP_EINVAL, std::string(who) + ": the reads hold other bytes than A, C, G, T, which a dna searcher cannot encode: use an iupac searcher");
-  }
+  // the flag kernel, the scan's three, the encode kernel, the scatter kernel; the Dna look where it runs; below, the walk's own
+  uint32_t launches = 6;
+  if (int rc = reads_require_plain(s, reads, who, "the reads hold", "encode", &launches)) return rc;
 
   // one area: the flags and their scan (used twice: the windows, then the kept reads), the block sums, the reads' table, the four
   // columns, the keys, the groups' best keys, the kept reads' table and lengths
@@ -306,8 +284,7 @@ int dedup_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, uint32_t at, 
   if (O.size) HIP_TRY(hipMemcpyAsync(O.size, d_size, n * 4, hipMemcpyDeviceToHost, st));
   if (O.rep) HIP_TRY(hipMemcpyAsync(O.rep, d_rep, n * 4, hipMemcpyDeviceToHost, st));
   if (O.count) HIP_TRY(hipMemcpyAsync(O.count, d_count, n * 4, hipMemcpyDeviceToHost, st));
-  // the look where it ran, the flag kernel, the scan's three, the encode kernel, the walk's own, the scatter kernel
-  uint32_t launches = 6u + (dna_look ? 1u : 0u) + walk_launches;
+  launches += walk_launches;
   size_t n_groups = 0;
 
   if (!F) {
@@ -346,39 +323,22 @@ int dedup_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, uint32_t at, 
 int dedup_call(sassy_SearcherType* s, const sassy_hip_Reads* reads, uint32_t at, size_t m, size_t k, uint32_t method, uint32_t flags, const DdpOut& O,
                bool have_out, sassy_hip_Reads** out_dedup, const char* who) {
   DdpCall c{};
-  c.have_searcher = s != nullptr; c.have_reads = reads != nullptr; c.have_out = have_out;
+  c.have_searcher = s != nullptr; c.have_out = have_out;
   c.flags = flags; c.method = method; c.at = at; c.m = m;
-  if (s) {
-    c.profile = s->profile == PROFILE_DNA ? kHamDna : s->profile == PROFILE_IUPAC ? kHamIupac : 0u;
-    c.overhang = !std::isnan(s->alpha) || s->max_overhang >= 0;
-    c.only_best = s->only_best;
-    c.max_n_frac = !std::isnan(s->max_n_frac);
-    c.in_flight = tickets_open(s);
-  }
+  c.gate = reads_gate_of(s, 1, reads, nullptr);
   // the searcher and the numbers first: the batch is read only once nothing in front of it is wrong
-  DdpRefusal why = ddp_refusal(c);
-  if (why == kDdpOk || why == kDdpNullOut || why == kDdpInFlight) {
-    DeviceGuard on_device(s);  // (first use binds the searcher to the thread's device)
-    c.device_s = s->device; c.device_r = reads->device;
-    c.longest = reads->longest;
-    c.handle_read = true;
-    why = ddp_refusal(c);
+  ReadsRefusal gate = kRdsOk;
+  DdpRefusal why = ddp_refusal(c, &gate);
+  if (why == kDdpOk || why == kDdpNullOut || (why == kDdpGate && gate == kRdsInFlight)) {
+    reads_gate_read(s, reads, nullptr, &c.gate);
+    why = ddp_refusal(c, &gate);
   }
-  if (why != kDdpOk)
-    return fail(why == kDdpOverhang || why == kDdpOnlyBest || why == kDdpNFrac ? SASSY_HIP_EUNSUPPORTED : SASSY_HIP_EINVAL, refusal_text(why, c, who));
-  std::unique_ptr<sassy_hip_Reads> F(out_dedup ? new sassy_hip_Reads : nullptr);
-  const size_t lens[1] = {m};
-  const int rc = pairs_guarded(who, [&]() -> int {
-    return hamming_call(s, lens, 1, k, [&](uint32_t kk) {  // (k >= m: every two distinct keys are neighbours)
-      return dedup_run(s, reads, at, (uint32_t)m, kk, method, flags, O, F.get(), who);
-    });
+  if (why == kDdpGate)
+    return reads_refused(gate, c.gate, ReadsWho{who, "the keys are DNA", "compares windows that lie inside the reads", "groups every read"});
+  if (why != kDdpOk) return fail(SASSY_HIP_EINVAL, refusal_text(why, c, who));
+  return reads_new_batch(s, m, k, out_dedup, [&](uint32_t kk, sassy_hip_Reads* F) {  // (k >= m: every two distinct keys are neighbours)
+    return pairs_guarded(who, [&]() -> int { return dedup_run(s, reads, at, (uint32_t)m, kk, method, flags, O, F, who); });
   });
-  if (rc != 0) {
-    if (F) F->release();
-    return rc;
-  }
-  if (out_dedup) *out_dedup = F.release();
-  return 0;
 }
 
 }  // namespace

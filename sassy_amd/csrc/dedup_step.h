@@ -27,37 +27,22 @@ struct DdpCall {
   bool have_searcher;
   uint32_t flags, method, at;
   size_t m;
-  uint32_t profile;                       // kHamDna, kHamIupac; anything else is an Ascii searcher
-  bool overhang, only_best, max_n_frac;   // the searcher's reporting modes that are set
-  bool have_reads;
-  bool handle_read;                       // the fields below that come out of the handle are filled in
-  int device_s, device_r;
-  uint64_t longest;
+  ReadsGate gate;                         // the searcher and the handle (reads_gate.h)
   bool have_out;                          // out_label (the groups call), out_dedup (the dedup call) != NULL
-  bool in_flight;                         // tickets are open on the searcher
 };
-enum DdpRefusal : uint32_t {
-  kDdpOk = 0, kDdpNullSearcher, kDdpFlags, kDdpMethod, kDdpLen, kDdpAt, kDdpAscii, kDdpOverhang, kDdpOnlyBest, kDdpNFrac, kDdpNullReads,
-  kDdpDevice, kDdpTooLong, kDdpNullOut, kDdpInFlight
-};
+enum DdpRefusal : uint32_t { kDdpOk = 0, kDdpNullSearcher, kDdpFlags, kDdpMethod, kDdpLen, kDdpAt, kDdpGate /* *gate says which */, kDdpNullOut };
 // The handle is read only once nothing in front of it is wrong.
-inline DdpRefusal ddp_refusal(const DdpCall& c) {
+inline DdpRefusal ddp_refusal(const DdpCall& c, ReadsRefusal* gate) {
+  *gate = kRdsOk;
   if (!c.have_searcher) return kDdpNullSearcher;
   if (c.flags & ~kDdpEnd3) return kDdpFlags;
   if (c.method > kDdpMaxMethod) return kDdpMethod;
   if (c.m == 0 || c.m > kDdpMaxLen) return kDdpLen;
   if ((uint64_t)c.at + c.m > kOvlMaxLen) return kDdpAt;
-  if (c.profile != kHamDna && c.profile != kHamIupac) return kDdpAscii;
-  if (c.overhang) return kDdpOverhang;
-  if (c.only_best) return kDdpOnlyBest;
-  if (c.max_n_frac) return kDdpNFrac;
-  if (!c.have_reads) return kDdpNullReads;
-  if (c.handle_read) {
-    if (c.device_r != c.device_s) return kDdpDevice;
-    if (c.longest > kOvlMaxLen) return kDdpTooLong;
-  }
+  if ((*gate = reads_gate_searcher(c.gate)) != kRdsOk) return kDdpGate;
+  if ((*gate = reads_gate_handles(c.gate)) != kRdsOk) return kDdpGate;
   if (!c.have_out) return kDdpNullOut;
-  if (c.in_flight) return kDdpInFlight;
+  if ((*gate = reads_gate_tickets(c.gate)) != kRdsOk) return kDdpGate;
   return kDdpOk;
 }
 

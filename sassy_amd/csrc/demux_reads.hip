@@ -61,10 +61,7 @@ __global__ __launch_bounds__(256) void demux_assign_kernel(AssignArgs A) {
   uint32_t la = 0;
   if (live) {
     s0 = A.start[read];
-    const uint64_t l = A.len[read];
-    // (the host refused longer reads; a read that does not fit its text counts as empty)
-    const bool fits = l <= kOvlMaxLen && s0 <= A.bytes && l <= A.bytes - s0;
-    la = fits ? (uint32_t)l : 0u;
+    la = reads_fit_len(s0, A.len[read], A.bytes, kOvlMaxLen);
   }
   const bool has_window = live & dmx_has_window(la, A.at, A.m);
 
@@ -73,12 +70,7 @@ __global__ __launch_bounds__(256) void demux_assign_kernel(AssignArgs A) {
 #pragma unroll
   for (int j = 0; j < 16; ++j) blk[j] = 0u;
   if (has_window) {
-    const uint8_t* base = A.text;
-    const auto load16 = [&](uint64_t at, uint32_t* w) {
-      const uint4 v = *reinterpret_cast<const uint4*>(base + at);
-      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    };
-    trm_window_block(load16, s0 + dmx_window(la, A.at, A.m, A.end3 != 0u), A.bytes, A.m, blk);
+    trm_window_block(TrmLoad16{A.text}, s0 + dmx_window(la, A.at, A.m, A.end3 != 0u), A.bytes, A.m, blk);
   }
   uint32_t rw[P + 1][2];
   dmx_planes<P>(profile, blk, rw);
@@ -126,8 +118,9 @@ __global__ __launch_bounds__(256) void demux_place_kernel(PlaceArgs A) {
   A.out_len[j] = c.len;
 }
 
+// what a refusal of the call's own checks says
 std::string refusal_text(DmxRefusal why, const DmxCall& c, size_t which) {
-  if (why == kDmxNullSearcher || why == kDmxNullReads) return "Pointers in demux_reads() must not be null";
+  if (why == kDmxNullSearcher) return "Pointers in demux_reads() must not be null";
   if (why == kDmxFlags) return "demux_reads takes SASSY_HIP_DEMUX_END3 and SASSY_HIP_DEMUX_KEEP_BARCODE only (the read batch is on the device)";
   if (why == kDmxDelta) return "demux_reads: min_delta must be <= " + std::to_string(kDmxMaxDelta) + " (got " + std::to_string(c.min_delta) + ")";
   if (why == kDmxCount)
@@ -137,33 +130,18 @@ std::string refusal_text(DmxRefusal why, const DmxCall& c, size_t which) {
   if (why == kDmxAt)
     return "demux_reads: at + barcode_len = " + std::to_string((uint64_t)c.at + c.barcode_len) + " reaches past the longest read a batch may hold (" +
            std::to_string(kOvlMaxLen) + ")";
-  if (why == kDmxAscii) return "demux_reads: barcodes are DNA; use a dna or an iupac searcher";
-  if (why == kDmxOverhang) return "the Hamming search does not take overhang (alpha): demux_reads compares the barcode with a window that lies inside the read";
-  if (why == kDmxOnlyBest) return "demux_reads reports the best barcode of every read: only_best_match is not supported";
-  if (why == kDmxNFrac) return "demux_reads does not take max_n_frac: there is no text span for it to apply to";
-  if (why == kDmxDevice)
-    return "demux_reads: the reads were made on device " + std::to_string(c.device_r) + ", the searcher is on device " + std::to_string(c.device_s);
-  if (why == kDmxTooLong)
-    return "demux_reads takes reads of at most " + std::to_string(kOvlMaxLen) + " bytes (SASSY_HIP_OVERLAP_MAX_LEN; the longest has " +
-           std::to_string(c.longest) + ")";
   if (why == kDmxNullOut) return "Pointers in demux_reads() must not be null (out_bounds, out_sorted)";
-  if (why == kDmxInFlight) return "searches are in flight on this searcher (sassy_hip_search_shard_begin): finish them first";
   return "demux_reads: refused";
 }
 
 size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// The call behind its refusals.  F: a fresh handle; it is the caller's to release where this fails.
-int demux_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t* const* barcodes, uint32_t m, uint32_t B, uint32_t at, size_t k,
+// The call behind its refusals, inside reads_new_batch (the device, fresh stats, k cut to the longest barcode, the fresh handle F).
+int demux_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t* const* barcodes, uint32_t m, uint32_t B, uint32_t at, uint32_t k,
               uint32_t min_delta, uint32_t flags, sassy_hip_ReadDemux* out_assign, uint64_t* out_order, uint64_t* out_bounds, sassy_hip_Reads* F) {
-  DeviceGuard on_device(s);
-  const double t0 = now_ms();
-  reset_stats(s);
-  if (int rc = s->ensure_device()) return rc;
   hipStream_t st = s->stream;
   const uint64_t n = reads->n_records;
   const bool keep_quality = reads->d_qual != nullptr;
-  F->device = s->device;
   if (s->profile == PROFILE_DNA)  // the 2-bit codes are exact on A, C, G, T only: the barcodes first, whatever the batch holds
     for (uint32_t j = 0; j < B; ++j)
       if (!acgt_only(barcodes[j], m))
@@ -172,18 +150,13 @@ int demux_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t
   if (n == 0) {
     if (int rc = reads_empty_buffers(F, keep_quality, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    s->stats.total_ms = now_ms() - t0;
     return 0;
   }
   const uint32_t profile = s->profile == PROFILE_IUPAC ? kHamIupac : kHamDna;
-  const bool dna_look = s->profile == PROFILE_DNA && reads->text_bytes > 64;  // (reads_plain launches over the layout's blocks)
-  if (s->profile == PROFILE_DNA) {
-    TextSource src;
-    src.reads = reads;
-    bool plain = false;
-    if (int rc = reads_plain(s, src, &plain)) return rc;
-    if (!plain) return fail(SASSY_HIP_EINVAL, "demux_reads: the reads hold other bytes than A, C, G, T, which a dna searcher cannot encode: use an iupac searcher");
-  }
+  // the assign kernel, the sort (the library's launches count as one), the bounds and the place kernel, the three kernels of the
+  // layout scan, the write kernel; the Dna look where it runs
+  uint32_t launches = 8;
+  if (int rc = reads_require_plain(s, reads, "demux_reads", "the reads hold", "encode", &launches)) return rc;
   const uint32_t E = dmx_entry_words(profile);
   std::vector<uint32_t> tab((size_t)B * E, 0u);
   for (uint32_t j = 0; j < B; ++j) dmx_encode_barcode(profile, barcodes[j], m, tab.data() + (size_t)j * E);
@@ -212,7 +185,7 @@ int demux_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t
   A.n = n;
   A.tab = s->d_demux_tab.p;
   A.n_barcodes = B; A.m = m; A.at = at; A.end3 = (flags & kDmxEnd3) ? 1u : 0u;
-  A.k = (uint32_t)std::min<size_t>(k, kDmxMaxLen);  // (k beyond the longest barcode accepts what k == 64 does)
+  A.k = k;
   A.min_delta = min_delta;
   A.rec = d_rec; A.label = d_key; A.idx = d_idx;
   const dim3 per_read((uint32_t)((n + 255) / 256)), block(256);
@@ -243,49 +216,12 @@ int demux_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t
     (void)hipEventElapsedTime(&ms, s->ev_line[0], s->ev_line[1]);
     s->stats.scan_ms = ms;
   }
-  // the Dna look where it ran, the assign kernel, the sort (the library's launches count as one), the bounds and the place
-  // kernel, the three kernels of the layout scan, the write kernel
-  s->stats.scan_launches = 8u + (dna_look ? 1u : 0u);
+  s->stats.scan_launches = launches;
   s->stats.candidates = out_bounds[B];
   s->stats.blocks = (n + 255) / 256;
   s->stats.word_rows = 2;
   s->stats.text_bytes = reads->text_bytes - 64;
-  s->stats.total_ms = now_ms() - t0;
   return 0;
-}
-
-int select_run(const sassy_hip_Reads* reads, const uint64_t* src, const uint64_t* begins, const uint64_t* lens, uint64_t n_out, hipStream_t st,
-               sassy_hip_Reads* F) {
-  const bool keep_quality = reads->d_qual != nullptr;
-  F->device = reads->device;
-  if (n_out == 0) {
-    if (int rc = reads_empty_buffers(F, keep_quality, st)) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-  }
-  std::vector<uint64_t> whole;
-  if (!lens) {  // whole reads: their lengths from the handle's own table
-    whole.resize(n_out);
-    for (uint64_t j = 0; j < n_out; ++j) whole[j] = reads->records[src[j]].seq_len;
-    lens = whole.data();
-  }
-  const uint64_t parts = begins ? 3 : 2;
-  uint64_t* d_win = nullptr;  // src[n_out], lens[n_out], then begins[n_out] where given
-  if (hipMalloc(reinterpret_cast<void**>(&d_win), parts * n_out * sizeof(uint64_t)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SASSY_HIP_ENOMEM, "reads_select: out of device memory (" + std::to_string(parts * n_out * sizeof(uint64_t)) + " bytes of windows)");
-  }
-  int rc = 0;
-  hipError_t e = hipMemcpyAsync(d_win, src, n_out * sizeof(uint64_t), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_win + n_out, lens, n_out * sizeof(uint64_t), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && begins) e = hipMemcpyAsync(d_win + 2 * n_out, begins, n_out * sizeof(uint64_t), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (windows)");
-  if (rc == 0) rc = reads_layout_windows(d_win + n_out, n_out, keep_quality, st, F);  // (waits: `whole` has landed)
-  if (rc == 0) rc = write_windows(reads, d_win, begins ? d_win + 2 * n_out : nullptr, F, st);
-  const hipError_t done = hipStreamSynchronize(st);
-  (void)hipFree(d_win);
-  if (rc == 0 && done != hipSuccess) rc = hip_fail(done, "hipStreamSynchronize (reads_select)");
-  return rc;
 }
 
 }  // namespace
@@ -300,38 +236,25 @@ int sassy_hip_demux_reads(sassy_SearcherType* s, const sassy_hip_Reads* reads, c
                           uint64_t* out_bounds, sassy_hip_Reads** out_sorted) {
   if (out_sorted) *out_sorted = nullptr;
   DmxCall c{};
-  c.have_searcher = s != nullptr; c.have_reads = reads != nullptr; c.have_bounds = out_bounds != nullptr; c.have_sorted = out_sorted != nullptr;
+  c.have_searcher = s != nullptr; c.have_bounds = out_bounds != nullptr; c.have_sorted = out_sorted != nullptr;
   c.flags = flags; c.min_delta = min_delta; c.at = at;
   c.n_barcodes = n_barcodes; c.barcode_len = barcode_len; c.barcodes = barcodes;
-  if (s) {
-    c.profile = s->profile == PROFILE_DNA ? kHamDna : s->profile == PROFILE_IUPAC ? kHamIupac : 0u;
-    c.overhang = !std::isnan(s->alpha) || s->max_overhang >= 0;
-    c.only_best = s->only_best;
-    c.max_n_frac = !std::isnan(s->max_n_frac);
-    c.in_flight = tickets_open(s);
-  }
+  c.gate = reads_gate_of(s, 1, reads, nullptr);
   // the searcher, the numbers and the barcodes first: the batch is read only once nothing in front of it is wrong
   size_t which = 0;
-  DmxRefusal why = dmx_refusal(c, &which);
-  if (why == kDmxOk || why == kDmxNullOut || why == kDmxInFlight) {
-    DeviceGuard on_device(s);  // (first use binds the searcher to the thread's device)
-    c.device_s = s->device; c.device_r = reads->device;
-    c.longest = reads->longest;
-    c.handle_read = true;
-    why = dmx_refusal(c, &which);
+  ReadsRefusal gate = kRdsOk;
+  DmxRefusal why = dmx_refusal(c, &which, &gate);
+  if (why == kDmxOk || why == kDmxNullOut || (why == kDmxGate && gate == kRdsInFlight)) {
+    reads_gate_read(s, reads, nullptr, &c.gate);
+    why = dmx_refusal(c, &which, &gate);
   }
-  if (why != kDmxOk)
-    return fail(why == kDmxOverhang || why == kDmxOnlyBest || why == kDmxNFrac ? SASSY_HIP_EUNSUPPORTED : SASSY_HIP_EINVAL, refusal_text(why, c, which));
-  std::unique_ptr<sassy_hip_Reads> F(new sassy_hip_Reads);
-  const int rc = demux_run(s, reads, barcodes, (uint32_t)barcode_len, (uint32_t)n_barcodes, at, k, min_delta, flags, out_assign, out_order, out_bounds,
-                           F.get());
-  if (rc != 0) {
-    (void)hipStreamSynchronize(s->stream);
-    F->release();
-    return rc;
-  }
-  *out_sorted = F.release();
-  return 0;
+  if (why == kDmxGate)
+    return reads_refused(gate, c.gate, ReadsWho{"demux_reads", "barcodes are DNA", "compares the barcode with a window that lies inside the read",
+                                                "reports the best barcode of every read"});
+  if (why != kDmxOk) return fail(SASSY_HIP_EINVAL, refusal_text(why, c, which));
+  return reads_new_batch(s, kDmxMaxLen, k, out_sorted, [&](uint32_t kk, sassy_hip_Reads* F) {  // (k beyond the longest barcode accepts what k == 64 does)
+    return demux_run(s, reads, barcodes, (uint32_t)barcode_len, (uint32_t)n_barcodes, at, kk, min_delta, flags, out_assign, out_order, out_bounds, F);
+  });
 }
 
 int sassy_hip_reads_select(const sassy_hip_Reads* reads, const uint64_t* src, const uint64_t* begins, const uint64_t* lens, uint64_t n_out,
@@ -349,19 +272,7 @@ int sassy_hip_reads_select(const sassy_hip_Reads* reads, const uint64_t* src, co
       return fail(SASSY_HIP_EINVAL, "reads_select: window " + std::to_string(j) + " [" + std::to_string(begins[j]) + ", +" + std::to_string(lens[j]) +
                                         ") reaches outside its read of " + std::to_string(have) + " bytes");
   }
-  int cur = 0, prev = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != reads->device) {  // the handle's device, for the length of the call
-    HIP_TRY(hipSetDevice(reads->device));
-    prev = cur;
-  }
-  std::unique_ptr<sassy_hip_Reads> F(new sassy_hip_Reads);
-  const int rc = select_run(reads, src, begins, lens, n_out, reinterpret_cast<hipStream_t>(hip_stream), F.get());
-  if (rc != 0) F->release();
-  if (prev >= 0) (void)hipSetDevice(prev);
-  if (rc != 0) return rc;
-  *out = F.release();
-  return 0;
+  return windows_from_host(reads, src, begins, lens, n_out, reinterpret_cast<hipStream_t>(hip_stream), "reads_select", out);
 }
 
 }  // extern "C"

@@ -30,22 +30,16 @@ struct DmxCall {
   uint32_t flags, min_delta, at;
   size_t n_barcodes, barcode_len;
   const uint8_t* const* barcodes;
-  uint32_t profile;                       // kHamDna, kHamIupac; anything else is an Ascii searcher
-  bool overhang, only_best, max_n_frac;   // the searcher's reporting modes that are set
-  bool have_reads;
-  bool handle_read;                       // the fields below that come out of the handle are filled in
-  int device_s, device_r;
-  uint64_t longest;
+  ReadsGate gate;                         // the searcher and the handle (reads_gate.h)
   bool have_bounds, have_sorted;          // out_bounds, out_sorted != NULL
-  bool in_flight;                         // tickets are open on the searcher
 };
 enum DmxRefusal : uint32_t {
-  kDmxOk = 0, kDmxNullSearcher, kDmxFlags, kDmxDelta, kDmxCount, kDmxLen, kDmxNullBarcode, kDmxAt, kDmxAscii, kDmxOverhang, kDmxOnlyBest,
-  kDmxNFrac, kDmxNullReads, kDmxDevice, kDmxTooLong, kDmxNullOut, kDmxInFlight
+  kDmxOk = 0, kDmxNullSearcher, kDmxFlags, kDmxDelta, kDmxCount, kDmxLen, kDmxNullBarcode, kDmxAt, kDmxGate /* *gate says which */, kDmxNullOut
 };
 // *which: the barcode a refusal of the barcodes names.  The handle is read only once nothing in front of it is wrong.
-inline DmxRefusal dmx_refusal(const DmxCall& c, size_t* which) {
+inline DmxRefusal dmx_refusal(const DmxCall& c, size_t* which, ReadsRefusal* gate) {
   *which = 0;
+  *gate = kRdsOk;
   if (!c.have_searcher) return kDmxNullSearcher;
   if (c.flags & ~(kDmxEnd3 | kDmxKeepBarcode)) return kDmxFlags;
   if (c.min_delta > kDmxMaxDelta) return kDmxDelta;
@@ -58,17 +52,10 @@ inline DmxRefusal dmx_refusal(const DmxCall& c, size_t* which) {
       return kDmxNullBarcode;
     }
   if ((uint64_t)c.at + c.barcode_len > kOvlMaxLen) return kDmxAt;
-  if (c.profile != kHamDna && c.profile != kHamIupac) return kDmxAscii;
-  if (c.overhang) return kDmxOverhang;
-  if (c.only_best) return kDmxOnlyBest;
-  if (c.max_n_frac) return kDmxNFrac;
-  if (!c.have_reads) return kDmxNullReads;
-  if (c.handle_read) {
-    if (c.device_r != c.device_s) return kDmxDevice;
-    if (c.longest > kOvlMaxLen) return kDmxTooLong;
-  }
+  if ((*gate = reads_gate_searcher(c.gate)) != kRdsOk) return kDmxGate;
+  if ((*gate = reads_gate_handles(c.gate)) != kRdsOk) return kDmxGate;
   if (!c.have_bounds || !c.have_sorted) return kDmxNullOut;
-  if (c.in_flight) return kDmxInFlight;
+  if ((*gate = reads_gate_tickets(c.gate)) != kRdsOk) return kDmxGate;
   return kDmxOk;
 }
 

@@ -36,6 +36,7 @@
 #include "pass_planner.h"
 #include "scan_route.h"
 #include "hamming_plan.h"
+#include "reads_gate.h"
 
 namespace sassy_hip {
 // (thread_local LaunchEvents g_launch_events: defined in scan_driver.hip, declared in common.h)
@@ -1392,12 +1393,48 @@ struct ReadsTexts {
   TextSource src;
 };
 int reads_as_source(sassy_SearcherType* s, const sassy_hip_Reads* reads, uint32_t flags, const char* who, ReadsTexts* out);
-// read_overlaps.hip, for merge_pairs.hip: the overlap call behind its refusals (device, stats, k's cut, the Dna look, the
-// kernel).  The records stay in s->d_overlaps; they are copied to `out` only where it is given.
-int overlaps_resident(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, size_t k,
+// reads_call.hip: what surrounds the refusal predicate of every call on a resident read batch (reads_gate.h).
+// The gate off the searcher and the handles as pointers (s may be NULL; r2 == NULL with handles == 1) ...
+ReadsGate reads_gate_of(const sassy_SearcherType* s, uint32_t handles, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2);
+// ... and off the handles themselves, once nothing in front of them is wrong (first use binds the searcher to the thread's device)
+void reads_gate_read(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, ReadsGate* g);
+// What a refusal of the gate says and returns in the call `name`; the sentences that are the call's own come with it.
+struct ReadsWho {
+  const char *name, *ascii, *overhang, *only_best;
+};
+int reads_refused(ReadsRefusal why, const ReadsGate& g, const ReadsWho& who);
+// The Dna look: a dna searcher takes reads of A, C, G, T only (reads_plain, on the device).  The refusal reads
+// "<who>: <subject> other bytes than A, C, G, T, which a dna searcher cannot <verb>: use an iupac searcher".  *launches, where
+// given, grows by the look's kernel where it ran.
+int reads_require_plain(sassy_SearcherType* s, const sassy_hip_Reads* reads, const char* who, const char* subject, const char* verb, uint32_t* launches);
+// sassy_hip_reads_slice and _select behind their own checks: record j of *out is [begins[j], +lens[j]) of read src[j] of `reads`
+// (src == NULL: of read j; begins == NULL: whole reads), on the handle's device for the length of the call.
+int windows_from_host(const sassy_hip_Reads* reads, const uint64_t* src, const uint64_t* begins, const uint64_t* lens, uint64_t n_out, hipStream_t st,
+                      const char* who, sassy_hip_Reads** out);
+// A call that returns a new resident batch, behind its refusals: hamming_call's frame (k cut to `longest`) around
+// run(k, F), F a fresh handle on the searcher's device -- released where run fails, *out where it succeeds.  out == NULL: no
+// handle is wanted, F == NULL.
+template <typename Run>
+int reads_new_batch(sassy_SearcherType* s, size_t longest, size_t k, sassy_hip_Reads** out, Run&& run) {
+  std::unique_ptr<sassy_hip_Reads> F(out ? new sassy_hip_Reads : nullptr);
+  const size_t lens[1] = {longest};
+  const int rc = hamming_call(s, lens, 1, k, [&](uint32_t kk) {
+    if (F) F->device = s->device;
+    return run(kk, F.get());
+  });
+  if (rc != 0) {
+    if (F) F->release();
+    return rc;
+  }
+  if (out) *out = F.release();
+  return 0;
+}
+// read_overlaps.hip, for merge_pairs.hip: the overlap call behind its refusals and inside the caller's frame (the Dna look,
+// the kernel; k cut already).  The records stay in s->d_overlaps; they are copied to `out` only where it is given.
+int overlaps_resident(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, uint32_t k,
                       uint32_t max_permille, sassy_hip_ReadOverlap* out);
 // ... and what a refusal of overlap_step.h's ovl_refusal says and returns in a call named `who`
-int overlap_refused(uint32_t why, const struct OvlCall& c, const char* who);
+int overlap_refused(uint32_t why, ReadsRefusal gate, const struct OvlCall& c, const char* who);
 // fastq_reads.hip, for merge_pairs.hip: the layout of a new handle whose read r is the merged read of pair r (see there)
 int reads_layout_merged(const sassy_hip_ReadOverlap* d_rec, const uint64_t* d_len1, const uint64_t* d_len2, uint64_t n, ScanLane* lane,
                         sassy_hip_Reads* F, uint64_t* n_merged);

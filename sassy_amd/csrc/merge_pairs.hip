@@ -106,28 +106,17 @@ __global__ __launch_bounds__(256) void merge_write_kernel(MergeArgs A) {
   }
 }
 
-// The call behind its refusals.  F: a fresh handle; it is the caller's to release where this fails.
-int merge_run(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, size_t k, uint32_t max_permille,
+// The call behind its refusals, inside reads_new_batch (the device, fresh stats, k cut to the longest read, the fresh handle F).
+int merge_run(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, uint32_t k, uint32_t max_permille,
               sassy_hip_ReadOverlap* out_overlaps, sassy_hip_Reads* F) {
-  DeviceGuard on_device(s);
-  const double t0 = now_ms();
+  hipStream_t st = s->stream;
   const uint64_t n = r1->n_records;
   if (n == 0) {  // no pair: the 64 spare bytes of both buffers
-    reset_stats(s);
-    if (int rc = s->ensure_device()) return rc;
-    F->device = s->device;
-    F->text_bytes = 64;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&F->d_text), 64));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&F->d_qual), 64));
-    HIP_TRY(hipMemsetAsync(F->d_text, 0, 64, s->stream));
-    HIP_TRY(hipMemsetAsync(F->d_qual, 0, 64, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->stats.total_ms = now_ms() - t0;
+    if (int rc = reads_empty_buffers(F, true, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
     return 0;
   }
   if (int rc = overlaps_resident(s, r1, r2, min_overlap, k, max_permille, out_overlaps)) return rc;
-  hipStream_t st = s->stream;
-  F->device = s->device;
   uint64_t n_merged = 0;
   if (int rc = reads_layout_merged(s->d_overlaps.p, r1->d_table + n, r2->d_table + n, n, &s->lanes[0], F, &n_merged)) return rc;
   MergeArgs A;
@@ -145,10 +134,9 @@ int merge_run(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_
   else hipLaunchKernelGGL(merge_write_kernel<false>, grid, block, 0, st, A);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));  // (the handle is whole when the call returns, and the records behind A.rec are free again)
-  // (overlaps_run counts its kernel and, as every _reads call, not the Dna look; zero pairs launch nothing and count nothing)
+  // (the overlap counts its kernel and, as every _reads call, not the Dna look; zero pairs launch nothing and count nothing)
   s->stats.scan_launches += 4;  // the three kernels of the layout scan and the write kernel
   s->stats.candidates = n_merged;  // (sassy_hip_Stats has no field of its own for it)
-  s->stats.total_ms = now_ms() - t0;
   return 0;
 }
 
@@ -163,44 +151,30 @@ int sassy_hip_merge_pairs(sassy_SearcherType* s, const sassy_hip_Reads* r1, cons
                           uint32_t max_permille, uint32_t flags, sassy_hip_ReadOverlap* out_overlaps, sassy_hip_Reads** out_merged) {
   if (out_merged) *out_merged = nullptr;
   MrgCall c{};
-  c.ovl.have_searcher = s != nullptr; c.ovl.have_r1 = r1 != nullptr; c.ovl.have_r2 = r2 != nullptr;
+  c.ovl.have_searcher = s != nullptr;
   c.ovl.have_out = true;  // (the records stay on the device: out_overlaps may be null)
   c.ovl.min_overlap = min_overlap; c.ovl.max_permille = max_permille; c.ovl.flags = flags;
+  c.ovl.gate = reads_gate_of(s, 2, r1, r2);
   c.have_merged = out_merged != nullptr;
-  if (s) {
-    c.ovl.profile = s->profile == PROFILE_DNA ? kHamDna : s->profile == PROFILE_IUPAC ? kHamIupac : 0u;
-    c.ovl.overhang = !std::isnan(s->alpha) || s->max_overhang >= 0;
-    c.ovl.only_best = s->only_best;
-    c.ovl.max_n_frac = !std::isnan(s->max_n_frac);
-  }
   // the searcher, the numbers and the pointers first: the batches are read only once nothing else is wrong with the call
   OvlRefusal why_ovl = kOvlOk;
-  MrgRefusal why = mrg_refusal(c, &why_ovl);
+  ReadsRefusal gate = kRdsOk;
+  MrgRefusal why = mrg_refusal(c, &why_ovl, &gate);
   if (why != kMrgOverlap) {
     c.ovl.n1 = r1->n_records; c.ovl.n2 = r2->n_records;
-    c.ovl.longest1 = r1->longest; c.ovl.longest2 = r2->longest;
-    c.ovl.device1 = r1->device; c.ovl.device2 = r2->device;
-    DeviceGuard on_device(s);  // (first use binds the searcher to the thread's device)
-    c.ovl.device_s = s->device;
-    c.handles_read = true;
+    reads_gate_read(s, r1, r2, &c.ovl.gate);
     c.qual1 = r1->d_qual != nullptr; c.qual2 = r2->d_qual != nullptr;
-    why = mrg_refusal(c, &why_ovl);
+    why = mrg_refusal(c, &why_ovl, &gate);
   }
-  if (why == kMrgOverlap) return overlap_refused(why_ovl, c.ovl, "merge_pairs");
+  if (why == kMrgOverlap) return overlap_refused(why_ovl, gate, c.ovl, "merge_pairs");
   if (why == kMrgNoQuality)
     return fail(SASSY_HIP_EINVAL, std::string("merge_pairs: ") + (c.qual1 ? "r2" : "r1") +
                                       " was parsed without SASSY_HIP_KEEP_QUALITY: a merge needs the base qualities of both batches");
   if (why == kMrgNullMerged) return fail(SASSY_HIP_EINVAL, "Pointers in merge_pairs() must not be null (out_merged)");
   SASSY_NO_TICKETS(s);
-  std::unique_ptr<sassy_hip_Reads> F(new sassy_hip_Reads);
-  const int rc = merge_run(s, r1, r2, min_overlap, k, max_permille, out_overlaps, F.get());
-  if (rc != 0) {
-    (void)hipStreamSynchronize(s->stream);
-    F->release();
-    return rc;
-  }
-  *out_merged = F.release();
-  return 0;
+  return reads_new_batch(s, kOvlMaxLen, k, out_merged, [&](uint32_t kk, sassy_hip_Reads* F) {  // (k beyond the longest read accepts what k == 512 does)
+    return merge_run(s, r1, r2, min_overlap, kk, max_permille, out_overlaps, F);
+  });
 }
 
 }  // extern "C"

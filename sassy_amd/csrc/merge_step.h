@@ -21,15 +21,14 @@ namespace sassy_hip {
 // to set), then what the merge adds: both handles keep their qualities, and there is a place for the new handle.
 struct MrgCall {
   OvlCall ovl;
-  bool handles_read;       // the fields below that come out of the handles are filled in
-  bool qual1, qual2;       // the handles own a quality buffer (SASSY_HIP_KEEP_QUALITY)
+  bool qual1, qual2;       // the handles own a quality buffer (SASSY_HIP_KEEP_QUALITY); read with the gate's handle fields
   bool have_merged;        // out_merged != NULL
 };
-enum MrgRefusal : uint32_t { kMrgOk = 0, kMrgOverlap /* *why says which */, kMrgNoQuality, kMrgNullMerged };
-SASSY_HAM_HD MrgRefusal mrg_refusal(const MrgCall& c, OvlRefusal* why) {
-  *why = ovl_refusal(c.ovl);
+enum MrgRefusal : uint32_t { kMrgOk = 0, kMrgOverlap /* *why says which, and *gate where that is kOvlGate */, kMrgNoQuality, kMrgNullMerged };
+SASSY_HAM_HD MrgRefusal mrg_refusal(const MrgCall& c, OvlRefusal* why, ReadsRefusal* gate) {
+  *why = ovl_refusal(c.ovl, gate);
   if (*why != kOvlOk) return kMrgOverlap;
-  if (c.handles_read && (!c.qual1 || !c.qual2)) return kMrgNoQuality;
+  if (c.ovl.gate.handle_read && (!c.qual1 || !c.qual2)) return kMrgNoQuality;
   if (!c.have_merged) return kMrgNullMerged;
   return kMrgOk;
 }

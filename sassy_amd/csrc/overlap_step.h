@@ -19,10 +19,12 @@
 #include <cstdint>
 
 #include "pairs_step.h"
+#include "reads_gate.h"
 
 namespace sassy_hip {
 
 constexpr uint32_t kOvlMaxLen = 512;     // longest read (SASSY_HIP_OVERLAP_MAX_LEN): 16 words per plane
+static_assert(kOvlMaxLen == kReadsMaxLen, "the gate refuses what the kernels do not take");
 constexpr uint32_t kOvlMaxWords = kOvlMaxLen / 32;
 constexpr uint32_t kOvlWave = 64;        // offsets of a round: one per lane
 constexpr uint32_t kOvlPairsPerGroup = 4;  // pairs of a workgroup: one per wavefront
@@ -35,31 +37,23 @@ SASSY_HAM_HD uint32_t ovl_planes(uint32_t profile) { return profile == kHamIupac
 
 // ---- what the call refuses, before any device work, in this order ----
 struct OvlCall {
-  bool have_searcher, have_r1, have_r2, have_out;
-  uint32_t profile;                          // kHamDna, kHamIupac; anything else is an Ascii searcher
-  bool overhang, only_best, max_n_frac;      // the searcher's reporting modes that are set
+  bool have_searcher, have_out;
   uint32_t min_overlap, max_permille, flags;
-  uint64_t n1, n2, longest1, longest2;       // of the handles
-  int device_s, device1, device2;
+  uint64_t n1, n2;                           // of the handles
+  ReadsGate gate;                            // the searcher and the two handles (reads_gate.h)
 };
-enum OvlRefusal : uint32_t {
-  kOvlOk = 0, kOvlNullSearcher, kOvlFlags, kOvlMinOverlap, kOvlPermille, kOvlAscii, kOvlOverhang, kOvlOnlyBest, kOvlNFrac, kOvlNullReads,
-  kOvlCounts, kOvlDevice, kOvlTooLong, kOvlNullOut
-};
+enum OvlRefusal : uint32_t { kOvlOk = 0, kOvlNullSearcher, kOvlFlags, kOvlMinOverlap, kOvlPermille, kOvlGate /* *gate says which */, kOvlCounts, kOvlNullOut };
 // The searcher and the numbers first, then the handles, then what is read out of the handles.  Zero pairs need no `out`.
-SASSY_HAM_HD OvlRefusal ovl_refusal(const OvlCall& c) {
+// (The tickets come behind all of it, in the entry points.)
+SASSY_HAM_HD OvlRefusal ovl_refusal(const OvlCall& c, ReadsRefusal* gate) {
+  *gate = kRdsOk;
   if (!c.have_searcher) return kOvlNullSearcher;
   if (c.flags) return kOvlFlags;
   if (c.min_overlap == 0) return kOvlMinOverlap;
   if (c.max_permille > 1000) return kOvlPermille;
-  if (c.profile != kHamDna && c.profile != kHamIupac) return kOvlAscii;
-  if (c.overhang) return kOvlOverhang;
-  if (c.only_best) return kOvlOnlyBest;
-  if (c.max_n_frac) return kOvlNFrac;
-  if (!c.have_r1 || !c.have_r2) return kOvlNullReads;
+  if ((*gate = reads_gate_searcher(c.gate)) != kRdsOk) return kOvlGate;
   if (c.n1 != c.n2) return kOvlCounts;
-  if (c.device1 != c.device_s || c.device2 != c.device_s) return kOvlDevice;
-  if (c.longest1 > kOvlMaxLen || c.longest2 > kOvlMaxLen) return kOvlTooLong;
+  if ((*gate = reads_gate_handles(c.gate)) != kRdsOk) return kOvlGate;
   if (c.n1 && !c.have_out) return kOvlNullOut;
   return kOvlOk;
 }

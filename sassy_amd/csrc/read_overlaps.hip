@@ -136,27 +136,14 @@ hipError_t launch_words(uint32_t W, const OverlapArgs& A, hipStream_t st) {
   return hipGetLastError();
 }
 
-std::string refusal_text(OvlRefusal why, const OvlCall& c, const char* who) {
-  const std::string w = who;
-  switch (why) {
-    case kOvlNullSearcher: case kOvlNullReads: case kOvlNullOut: return "Pointers in " + w + "() must not be null";
-    case kOvlFlags: return w + " takes no flags (both read batches are on the device)";
-    case kOvlMinOverlap: return w + ": min_overlap must be at least 1";
-    case kOvlPermille: return w + ": max_permille must be <= 1000 (got " + std::to_string(c.max_permille) + ")";
-    case kOvlAscii: return w + ": the ascii alphabets have no complement; use a dna or an iupac searcher";
-    case kOvlOverhang: return "the Hamming search does not take overhang (alpha): " + w + " scores whole overlaps";
-    case kOvlOnlyBest: return w + " reports the best offset of every pair: only_best_match is not supported";
-    case kOvlNFrac: return w + " does not take max_n_frac: there is no text span for it to apply to";
-    case kOvlCounts:
-      return w + ": r1 holds " + std::to_string(c.n1) + " reads, r2 holds " + std::to_string(c.n2) + " (pair r is read r of both)";
-    case kOvlDevice:
-      return w + ": the reads were made on devices " + std::to_string(c.device1) + " and " + std::to_string(c.device2) +
-             ", the searcher is on device " + std::to_string(c.device_s);
-    case kOvlTooLong:
-      return w + " takes reads of at most " + std::to_string(kOvlMaxLen) + " bytes (SASSY_HIP_OVERLAP_MAX_LEN; the longest are " +
-             std::to_string(c.longest1) + " and " + std::to_string(c.longest2) + ")";
-    default: return w + ": refused";
-  }
+// what a refusal of the call's own checks says in a call named `who`
+std::string refusal_text(OvlRefusal why, const OvlCall& c, const std::string& w) {
+  if (why == kOvlNullSearcher || why == kOvlNullOut) return "Pointers in " + w + "() must not be null";
+  if (why == kOvlFlags) return w + " takes no flags (both read batches are on the device)";
+  if (why == kOvlMinOverlap) return w + ": min_overlap must be at least 1";
+  if (why == kOvlPermille) return w + ": max_permille must be <= 1000 (got " + std::to_string(c.max_permille) + ")";
+  if (why == kOvlCounts) return w + ": r1 holds " + std::to_string(c.n1) + " reads, r2 holds " + std::to_string(c.n2) + " (pair r is read r of both)";
+  return w + ": refused";
 }
 
 // The call behind its refusals.  Timing level >= 1: ev_line[0] -> [1] around the kernel (stats.scan_ms).  out == nullptr (the
@@ -165,17 +152,8 @@ int overlaps_run(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_h
                  sassy_hip_ReadOverlap* out) {
   hipStream_t st = s->stream;
   const uint64_t n = r1->n_records;
-  if (s->profile == PROFILE_DNA) {  // the 2-bit codes and the complement are exact on A, C, G, T only
-    for (const sassy_hip_Reads* r : {r1, r2}) {
-      TextSource src;
-      src.reads = r;
-      bool plain = false;
-      if (int rc = reads_plain(s, src, &plain)) return rc;
-      if (!plain)
-        return fail(SASSY_HIP_EINVAL, std::string("read_overlaps: ") + (r == r1 ? "r1" : "r2") +
-                                          " holds other bytes than A, C, G, T, which a dna searcher cannot complement: use an iupac searcher");
-    }
-  }
+  for (const sassy_hip_Reads* r : {r1, r2})  // (as every _reads call, the look is not counted in scan_launches)
+    if (int rc = reads_require_plain(s, r, "read_overlaps", r == r1 ? "r1 holds" : "r2 holds", "complement", nullptr)) return rc;
   if ((n + kOvlPairsPerGroup - 1) / kOvlPairsPerGroup > 0x7FFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "read_overlaps: too many pairs for a grid");
   if (int rc = s->d_overlaps.reserve(n)) return rc;
   OverlapArgs A;
@@ -207,17 +185,15 @@ int overlaps_run(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_h
 
 }  // namespace
 
-int overlap_refused(uint32_t why, const OvlCall& c, const char* who) {
-  return fail(why == kOvlOverhang || why == kOvlOnlyBest || why == kOvlNFrac ? SASSY_HIP_EUNSUPPORTED : SASSY_HIP_EINVAL,  // (as the family does)
-              refusal_text((OvlRefusal)why, c, who));
+int overlap_refused(uint32_t why, ReadsRefusal gate, const OvlCall& c, const char* who) {
+  if (why == kOvlGate)
+    return reads_refused(gate, c.gate, ReadsWho{who, "the ascii alphabets have no complement", "scores whole overlaps", "reports the best offset of every pair"});
+  return fail(SASSY_HIP_EINVAL, refusal_text((OvlRefusal)why, c, who));
 }
 
-int overlaps_resident(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, size_t k,
+int overlaps_resident(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, uint32_t k,
                       uint32_t max_permille, sassy_hip_ReadOverlap* out) {
-  const size_t lens[1] = {kOvlMaxLen};
-  return hamming_call(s, lens, 1, k, [&](uint32_t kk) {  // (k beyond the longest read accepts what k == 512 does)
-    return overlaps_run(s, r1, r2, min_overlap, kk, max_permille, out);
-  });
+  return overlaps_run(s, r1, r2, min_overlap, k, max_permille, out);
 }
 
 }  // namespace sassy_hip
@@ -229,25 +205,18 @@ extern "C" {
 int sassy_hip_read_overlaps(sassy_SearcherType* s, const sassy_hip_Reads* r1, const sassy_hip_Reads* r2, uint32_t min_overlap, size_t k,
                             uint32_t max_permille, uint32_t flags, sassy_hip_ReadOverlap* out) {
   OvlCall c{};
-  c.have_searcher = s != nullptr; c.have_r1 = r1 != nullptr; c.have_r2 = r2 != nullptr; c.have_out = out != nullptr;
+  c.have_searcher = s != nullptr; c.have_out = out != nullptr;
   c.min_overlap = min_overlap; c.max_permille = max_permille; c.flags = flags;
-  if (s) {
-    c.profile = s->profile == PROFILE_DNA ? kHamDna : s->profile == PROFILE_IUPAC ? kHamIupac : 0u;
-    c.overhang = !std::isnan(s->alpha) || s->max_overhang >= 0;
-    c.only_best = s->only_best;
-    c.max_n_frac = !std::isnan(s->max_n_frac);
-  }
+  c.gate = reads_gate_of(s, 2, r1, r2);
   // the searcher, the numbers and the pointers first: the batches are read only once nothing else is wrong with the call
-  OvlRefusal why = ovl_refusal(c);
+  ReadsRefusal gate = kRdsOk;
+  OvlRefusal why = ovl_refusal(c, &gate);
   if (why == kOvlOk) {
     c.n1 = r1->n_records; c.n2 = r2->n_records;
-    c.longest1 = r1->longest; c.longest2 = r2->longest;
-    c.device1 = r1->device; c.device2 = r2->device;
-    DeviceGuard on_device(s);  // (first use binds the searcher to the thread's device)
-    c.device_s = s->device;
-    why = ovl_refusal(c);
+    reads_gate_read(s, r1, r2, &c.gate);
+    why = ovl_refusal(c, &gate);
   }
-  if (why != kOvlOk) return overlap_refused(why, c, "read_overlaps");
+  if (why != kOvlOk) return overlap_refused(why, gate, c, "read_overlaps");
   SASSY_NO_TICKETS(s);
   if (r1->n_records == 0) return 0;
   const size_t lens[1] = {kOvlMaxLen};

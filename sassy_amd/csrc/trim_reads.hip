@@ -69,10 +69,7 @@ __global__ __launch_bounds__(256) void trim_find_kernel(TrimArgs A) {
   uint32_t la = 0;
   if (live) {
     s0 = A.start[read];
-    const uint64_t l = A.len[read];
-    // (the host refused longer reads; a read that does not fit the instance or its text counts as empty)
-    const bool fits = l <= 32u * W && s0 <= A.bytes && l <= A.bytes - s0;
-    la = fits ? (uint32_t)l : 0u;
+    la = reads_fit_len(s0, A.len[read], A.bytes, 32u * W);  // (what does not fit the instance counts as empty too)
   }
 
   // ---- quality ----
@@ -201,18 +198,14 @@ __global__ __launch_bounds__(256) void reads_window_write_kernel(WindowArgs A) {
   if constexpr (GATHER) from = min(A.src[t], (uint64_t)A.n_src - 1u);  // (the host checked a select's table; a demux's is a permutation)
   const uint64_t src = A.src_start[from] + (SHIFTED ? A.begin[t] : 0ull) + (b * 64 - start);
   const uint32_t keep = min(left, 64u);
-  const uint8_t* base = A.src_text;
-  const auto load16 = [&](uint64_t at, uint32_t* w) {
-    const uint4 v = *reinterpret_cast<const uint4*>(base + at);
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-  };
+  TrmLoad16 load16{A.src_text};
   if constexpr (SHIFTED) {
     uint32_t out[16];
     trm_window_block(load16, src, A.src_bytes, keep, out);
 #pragma unroll
     for (int j = 0; j < 4; ++j) dst_t[j] = make_uint4(out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]);
     if (A.qual) {
-      base = A.src_qual;
+      load16.base = A.src_qual;
       trm_window_block(load16, src, A.src_bytes, keep, out);
 #pragma unroll
       for (int j = 0; j < 4; ++j) dst_q[j] = make_uint4(out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]);
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(256) void reads_window_write_kernel(WindowArgs A) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) trm_aligned_quarter(load16, src, A.src_bytes, keep, q, wt[q]);
     if (A.qual) {
-      base = A.src_qual;
+      load16.base = A.src_qual;
 #pragma unroll
       for (int q = 0; q < 4; ++q) trm_aligned_quarter(load16, src, A.src_bytes, keep, q, wq[q]);
     }
@@ -272,9 +265,10 @@ int write_windows(const sassy_hip_Reads* reads, const uint64_t* d_src, const uin
 
 namespace {
 
+// what a refusal of the call's own checks says
 std::string refusal_text(TrmRefusal why, const TrmCall& c, size_t which) {
   const std::string a = "trim_reads: adapter " + std::to_string(which);
-  if (why == kTrmNullSearcher || why == kTrmNullReads) return "Pointers in trim_reads() must not be null";
+  if (why == kTrmNullSearcher) return "Pointers in trim_reads() must not be null";
   if (why == kTrmFlags) return "trim_reads takes no flags (the read batch is on the device)";
   if (why == kTrmMinOverlap) return "trim_reads: min_overlap must be at least 1";
   if (why == kTrmPermille) return "trim_reads: max_permille must be <= 1000 (got " + std::to_string(c.max_permille) + ")";
@@ -287,33 +281,18 @@ std::string refusal_text(TrmRefusal why, const TrmCall& c, size_t which) {
     return a + " has " + std::to_string(c.adapter_lens[which]) + " bytes: an adapter has at most " + std::to_string(kTrmMaxAdapterLen);
   if (why == kTrmShortAdapter)
     return a + " has " + std::to_string(c.adapter_lens[which]) + " bytes, fewer than min_overlap = " + std::to_string(c.min_overlap) + ": it could never be accepted";
-  if (why == kTrmAscii) return "trim_reads: adapters are DNA; use a dna or an iupac searcher";
-  if (why == kTrmOverhang) return "the Hamming search does not take overhang (alpha): trim_reads scores the adapter's overlap with the read's end itself";
-  if (why == kTrmOnlyBest) return "trim_reads reports the best position of every read: only_best_match is not supported";
-  if (why == kTrmNFrac) return "trim_reads does not take max_n_frac: there is no text span for it to apply to";
-  if (why == kTrmDevice)
-    return "trim_reads: the reads were made on device " + std::to_string(c.device_r) + ", the searcher is on device " + std::to_string(c.device_s);
-  if (why == kTrmTooLong)
-    return "trim_reads takes reads of at most " + std::to_string(kOvlMaxLen) + " bytes (SASSY_HIP_OVERLAP_MAX_LEN; the longest has " +
-           std::to_string(c.longest) + ")";
   if (why == kTrmNoQuality) return "trim_reads: the reads were parsed without SASSY_HIP_KEEP_QUALITY: quality_cutoff needs the base qualities";
   if (why == kTrmNullTrimmed) return "Pointers in trim_reads() must not be null (out_trimmed)";
-  if (why == kTrmInFlight) return "searches are in flight on this searcher (sassy_hip_search_shard_begin): finish them first";
   return "trim_reads: refused";
 }
 
-// The call behind its refusals.  F: a fresh handle; it is the caller's to release where this fails.
+// The call behind its refusals, inside reads_new_batch (the device, fresh stats, k cut to the longest adapter, the fresh handle F).
 int trim_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t* const* adapters, const size_t* adapter_lens, size_t n_adapters,
-             uint32_t min_overlap, size_t k, uint32_t max_permille, uint32_t cutoff, uint32_t min_length, sassy_hip_ReadTrim* out_trims,
+             uint32_t min_overlap, uint32_t k, uint32_t max_permille, uint32_t cutoff, uint32_t min_length, sassy_hip_ReadTrim* out_trims,
              sassy_hip_Reads* F) {
-  DeviceGuard on_device(s);
-  const double t0 = now_ms();
-  reset_stats(s);
-  if (int rc = s->ensure_device()) return rc;
   hipStream_t st = s->stream;
   const uint64_t n = reads->n_records;
   const bool keep_quality = reads->d_qual != nullptr;
-  F->device = s->device;
   if (s->profile == PROFILE_DNA)  // the 2-bit codes are exact on A, C, G, T only: the adapters first, whatever the batch holds
     for (size_t j = 0; j < n_adapters; ++j)
       if (!acgt_only(adapters[j], adapter_lens[j]))
@@ -321,18 +300,11 @@ int trim_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t*
   if (n == 0) {
     if (int rc = reads_empty_buffers(F, keep_quality, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    s->stats.total_ms = now_ms() - t0;
     return 0;
   }
   const uint32_t profile = s->profile == PROFILE_IUPAC ? kHamIupac : kHamDna;
-  const bool dna_look = s->profile == PROFILE_DNA && reads->text_bytes > 64;  // (reads_plain launches over the layout's blocks)
-  if (s->profile == PROFILE_DNA) {
-    TextSource src;
-    src.reads = reads;
-    bool plain = false;
-    if (int rc = reads_plain(s, src, &plain)) return rc;
-    if (!plain) return fail(SASSY_HIP_EINVAL, "trim_reads: the reads hold other bytes than A, C, G, T, which a dna searcher cannot encode: use an iupac searcher");
-  }
+  uint32_t launches = 5;  // the find kernel, the three kernels of the layout scan, the write kernel; the Dna look where it runs
+  if (int rc = reads_require_plain(s, reads, "trim_reads", "the reads hold", "encode", &launches)) return rc;
   if ((n + kTrmReadsPerGroup - 1) / kTrmReadsPerGroup > 0x7FFFFFFFull) return fail(SASSY_HIP_EUNSUPPORTED, "trim_reads: too many reads for a grid");
   std::vector<uint32_t> tab(std::max<size_t>(n_adapters, 1) * kTrmTableWords, 0u);
   for (size_t j = 0; j < n_adapters; ++j) trm_encode_adapter(profile, adapters[j], (uint32_t)adapter_lens[j], tab.data() + j * kTrmTableWords);
@@ -346,7 +318,7 @@ int trim_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t*
   A.n = n;
   A.tab = s->d_trim_tab.p;
   A.n_adapters = (uint32_t)n_adapters; A.min_overlap = min_overlap;
-  A.k = (uint32_t)std::min<size_t>(k, kTrmMaxAdapterLen);  // (k beyond the longest adapter accepts what k == 64 does)
+  A.k = k;
   A.max_permille = max_permille; A.cutoff = cutoff; A.min_length = min_length;
   A.out = reinterpret_cast<TrmRecord*>(s->d_trims.p);
   const uint32_t W = ovl_words((uint32_t)reads->longest);
@@ -364,39 +336,12 @@ int trim_run(sassy_SearcherType* s, const sassy_hip_Reads* reads, const uint8_t*
     (void)hipEventElapsedTime(&ms, s->ev_line[0], s->ev_line[1]);
     s->stats.scan_ms = ms;
   }
-  s->stats.scan_launches = 5u + (dna_look ? 1u : 0u);  // the Dna look where it ran, the find kernel, the three kernels of the layout scan, the write kernel
+  s->stats.scan_launches = launches;
   s->stats.candidates = n_found;
   s->stats.blocks = (n + kTrmReadsPerGroup - 1) / kTrmReadsPerGroup;
   s->stats.word_rows = W;
   s->stats.text_bytes = reads->text_bytes - 64;
-  s->stats.total_ms = now_ms() - t0;
   return 0;
-}
-
-int slice_run(const sassy_hip_Reads* reads, const uint64_t* begins, const uint64_t* lens, hipStream_t st, sassy_hip_Reads* F) {
-  const uint64_t n = reads->n_records;
-  const bool keep_quality = reads->d_qual != nullptr;
-  F->device = reads->device;
-  if (n == 0) {
-    if (int rc = reads_empty_buffers(F, keep_quality, st)) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-  }
-  uint64_t* d_win = nullptr;  // begins[n], then lens[n]
-  if (hipMalloc(reinterpret_cast<void**>(&d_win), 2 * n * sizeof(uint64_t)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(SASSY_HIP_ENOMEM, "reads_slice: out of device memory (" + std::to_string(2 * n * sizeof(uint64_t)) + " bytes of windows)");
-  }
-  int rc = 0;
-  hipError_t e = hipMemcpyAsync(d_win, begins, n * sizeof(uint64_t), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_win + n, lens, n * sizeof(uint64_t), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync (windows)");
-  if (rc == 0) rc = reads_layout_windows(d_win + n, n, keep_quality, st, F);
-  if (rc == 0) rc = write_windows(reads, nullptr, d_win, F, st);
-  const hipError_t done = hipStreamSynchronize(st);
-  (void)hipFree(d_win);
-  if (rc == 0 && done != hipSuccess) rc = hip_fail(done, "hipStreamSynchronize (reads_slice)");
-  return rc;
 }
 
 }  // namespace
@@ -411,38 +356,26 @@ int sassy_hip_trim_reads(sassy_SearcherType* s, const sassy_hip_Reads* reads, co
                          uint32_t flags, sassy_hip_ReadTrim* out_trims, sassy_hip_Reads** out_trimmed) {
   if (out_trimmed) *out_trimmed = nullptr;
   TrmCall c{};
-  c.have_searcher = s != nullptr; c.have_reads = reads != nullptr; c.have_trimmed = out_trimmed != nullptr;
+  c.have_searcher = s != nullptr; c.have_trimmed = out_trimmed != nullptr;
   c.flags = flags; c.min_overlap = min_overlap; c.max_permille = max_permille; c.quality_cutoff = quality_cutoff;
   c.adapters = adapters; c.adapter_lens = adapter_lens; c.n_adapters = n_adapters;
-  if (s) {
-    c.profile = s->profile == PROFILE_DNA ? kHamDna : s->profile == PROFILE_IUPAC ? kHamIupac : 0u;
-    c.overhang = !std::isnan(s->alpha) || s->max_overhang >= 0;
-    c.only_best = s->only_best;
-    c.max_n_frac = !std::isnan(s->max_n_frac);
-    c.in_flight = tickets_open(s);
-  }
+  c.gate = reads_gate_of(s, 1, reads, nullptr);
   // the searcher, the numbers and the adapters first: the batch is read only once nothing in front of it is wrong
   size_t which = 0;
-  TrmRefusal why = trm_refusal(c, &which);
-  if (why == kTrmOk || why == kTrmNullTrimmed || why == kTrmInFlight) {
-    DeviceGuard on_device(s);  // (first use binds the searcher to the thread's device)
-    c.device_s = s->device; c.device_r = reads->device;
-    c.longest = reads->longest;
+  ReadsRefusal gate = kRdsOk;
+  TrmRefusal why = trm_refusal(c, &which, &gate);
+  if (why == kTrmOk || why == kTrmNullTrimmed || (why == kTrmGate && gate == kRdsInFlight)) {
+    reads_gate_read(s, reads, nullptr, &c.gate);
     c.kept_quality = reads->d_qual != nullptr;
-    c.handle_read = true;
-    why = trm_refusal(c, &which);
+    why = trm_refusal(c, &which, &gate);
   }
-  if (why != kTrmOk)
-    return fail(why == kTrmOverhang || why == kTrmOnlyBest || why == kTrmNFrac ? SASSY_HIP_EUNSUPPORTED : SASSY_HIP_EINVAL, refusal_text(why, c, which));
-  std::unique_ptr<sassy_hip_Reads> F(new sassy_hip_Reads);
-  const int rc = trim_run(s, reads, adapters, adapter_lens, n_adapters, min_overlap, k, max_permille, quality_cutoff, min_length, out_trims, F.get());
-  if (rc != 0) {
-    (void)hipStreamSynchronize(s->stream);
-    F->release();
-    return rc;
-  }
-  *out_trimmed = F.release();
-  return 0;
+  if (why == kTrmGate)
+    return reads_refused(gate, c.gate, ReadsWho{"trim_reads", "adapters are DNA", "scores the adapter's overlap with the read's end itself",
+                                                "reports the best position of every read"});
+  if (why != kTrmOk) return fail(SASSY_HIP_EINVAL, refusal_text(why, c, which));
+  return reads_new_batch(s, kTrmMaxAdapterLen, k, out_trimmed, [&](uint32_t kk, sassy_hip_Reads* F) {  // (k beyond the longest adapter accepts what k == 64 does)
+    return trim_run(s, reads, adapters, adapter_lens, n_adapters, min_overlap, kk, max_permille, quality_cutoff, min_length, out_trims, F);
+  });
 }
 
 int sassy_hip_reads_slice(const sassy_hip_Reads* reads, const uint64_t* begins, const uint64_t* lens, void* hip_stream, sassy_hip_Reads** out) {
@@ -454,19 +387,7 @@ int sassy_hip_reads_slice(const sassy_hip_Reads* reads, const uint64_t* begins, 
       return fail(SASSY_HIP_EINVAL, "reads_slice: window " + std::to_string(r) + " [" + std::to_string(begins[r]) + ", +" + std::to_string(lens[r]) +
                                         ") reaches outside its read of " + std::to_string(have) + " bytes");
   }
-  int cur = 0, prev = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != reads->device) {  // the handle's device, for the length of the call
-    HIP_TRY(hipSetDevice(reads->device));
-    prev = cur;
-  }
-  std::unique_ptr<sassy_hip_Reads> F(new sassy_hip_Reads);
-  const int rc = slice_run(reads, begins, lens, reinterpret_cast<hipStream_t>(hip_stream), F.get());
-  if (rc != 0) F->release();
-  if (prev >= 0) (void)hipSetDevice(prev);
-  if (rc != 0) return rc;
-  *out = F.release();
-  return 0;
+  return windows_from_host(reads, nullptr, begins, lens, reads->n_records, reinterpret_cast<hipStream_t>(hip_stream), "reads_slice", out);
 }
 
 }  // extern "C"

@@ -33,24 +33,18 @@ struct TrmCall {
   const uint8_t* const* adapters;
   const size_t* adapter_lens;
   size_t n_adapters;
-  uint32_t profile;                       // kHamDna, kHamIupac; anything else is an Ascii searcher
-  bool overhang, only_best, max_n_frac;   // the searcher's reporting modes that are set
-  bool have_reads;
-  bool handle_read;                       // the fields below that come out of the handle are filled in
-  int device_s, device_r;
-  uint64_t longest;
-  bool kept_quality;
+  ReadsGate gate;                         // the searcher and the handle (reads_gate.h)
+  bool kept_quality;                      // read with the gate's handle fields
   bool have_trimmed;                      // out_trimmed != NULL
-  bool in_flight;                         // tickets are open on the searcher
 };
 enum TrmRefusal : uint32_t {
   kTrmOk = 0, kTrmNullSearcher, kTrmFlags, kTrmMinOverlap, kTrmPermille, kTrmCutoff, kTrmTooMany, kTrmNullAdapter, kTrmEmptyAdapter,
-  kTrmLongAdapter, kTrmShortAdapter, kTrmAscii, kTrmOverhang, kTrmOnlyBest, kTrmNFrac, kTrmNullReads, kTrmDevice, kTrmTooLong, kTrmNoQuality,
-  kTrmNullTrimmed, kTrmInFlight
+  kTrmLongAdapter, kTrmShortAdapter, kTrmGate /* *gate says which */, kTrmNoQuality, kTrmNullTrimmed
 };
 // *which: the adapter a refusal of the adapters names.  The handle is read only once nothing in front of it is wrong.
-inline TrmRefusal trm_refusal(const TrmCall& c, size_t* which) {
+inline TrmRefusal trm_refusal(const TrmCall& c, size_t* which, ReadsRefusal* gate) {
   *which = 0;
+  *gate = kRdsOk;
   if (!c.have_searcher) return kTrmNullSearcher;
   if (c.flags) return kTrmFlags;
   if (c.min_overlap == 0) return kTrmMinOverlap;
@@ -66,18 +60,11 @@ inline TrmRefusal trm_refusal(const TrmCall& c, size_t* which) {
     if (c.adapter_lens[j] < c.min_overlap) return kTrmShortAdapter;
   }
   *which = 0;
-  if (c.profile != kHamDna && c.profile != kHamIupac) return kTrmAscii;
-  if (c.overhang) return kTrmOverhang;
-  if (c.only_best) return kTrmOnlyBest;
-  if (c.max_n_frac) return kTrmNFrac;
-  if (!c.have_reads) return kTrmNullReads;
-  if (c.handle_read) {
-    if (c.device_r != c.device_s) return kTrmDevice;
-    if (c.longest > kOvlMaxLen) return kTrmTooLong;
-    if (c.quality_cutoff && !c.kept_quality) return kTrmNoQuality;
-  }
+  if ((*gate = reads_gate_searcher(c.gate)) != kRdsOk) return kTrmGate;
+  if ((*gate = reads_gate_handles(c.gate)) != kRdsOk) return kTrmGate;
+  if (c.gate.handle_read && c.quality_cutoff && !c.kept_quality) return kTrmNoQuality;
   if (!c.have_trimmed) return kTrmNullTrimmed;
-  if (c.in_flight) return kTrmInFlight;
+  if ((*gate = reads_gate_tickets(c.gate)) != kRdsOk) return kTrmGate;
   return kTrmOk;
 }
 
@@ -198,6 +185,16 @@ SASSY_HAM_HD TrmRecord trm_record(const TrmBest& best, uint32_t lq, uint32_t min
 // ---- one 64-byte block of a window: bytes src .. src + 63 of a buffer of `bytes` bytes (a multiple of 16) ----
 // Five 16-byte pieces from src rounded down to 16, each loaded only where it begins inside the buffer (load16(at, w): four
 // words from byte `at`), shifted by fq_shift_block; bytes at or behind `keep` are zero.
+#if defined(__HIPCC__)
+// load16 over a device buffer, for the kernels: one 16-byte load (at: a multiple of 16)
+struct TrmLoad16 {
+  const uint8_t* base;
+  __device__ __forceinline__ void operator()(uint64_t at, uint32_t* w) const {
+    const uint4 v = *reinterpret_cast<const uint4*>(base + at);
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+  }
+};
+#endif
 template <typename Load16>
 SASSY_HAM_HD void trm_window_block(const Load16& load16, uint64_t src, uint64_t bytes, uint32_t keep, uint32_t (&out)[16]) {
   const uint64_t al = src & ~15ull;

@@ -193,18 +193,24 @@ static void walk_reductions(Counts& n) {
   }
 }
 
+// every refusal as the pair (the call's own code, the gate's code)
 static void walk_refusals(Counts& n) {
   DdpCall ok{};
-  ok.have_searcher = true; ok.flags = kDdpEnd3; ok.method = 2; ok.at = 384; ok.m = 128; ok.profile = kHamDna;
-  ok.have_reads = true; ok.handle_read = true; ok.device_s = 1; ok.device_r = 1; ok.longest = 512; ok.have_out = true;
-  CHECK(ddp_refusal(ok) == kDdpOk);
+  ok.have_searcher = true; ok.flags = kDdpEnd3; ok.method = 2; ok.at = 384; ok.m = 128; ok.have_out = true;
+  ok.gate.handles = 1; ok.gate.profile = kHamDna;
+  ok.gate.have_reads[0] = true; ok.gate.handle_read = true; ok.gate.device_s = 1; ok.gate.device_r[0] = 1; ok.gate.longest[0] = 512;
+  ReadsRefusal gate = kRdsTooLong;
+  CHECK(ddp_refusal(ok, &gate) == kDdpOk && gate == kRdsOk);
   ++n.refusals;
   // everything wrong at once: taking the faults away one at a time from the front shows each refusal in its place
   DdpCall c = ok;
-  c.have_searcher = false; c.flags = 2; c.method = 3; c.m = 0; c.at = 600; c.profile = 0; c.overhang = c.only_best = c.max_n_frac = true;
-  c.have_reads = false; c.device_r = 0; c.longest = 513; c.have_out = false; c.in_flight = true;
-  const auto expect = [&](DdpRefusal want) {
-    CHECK(ddp_refusal(c) == want, (long)ddp_refusal(c), (long)want);
+  ReadsGate& g = c.gate;
+  c.have_searcher = false; c.flags = 2; c.method = 3; c.m = 0; c.at = 600; g.profile = 0; g.overhang = g.only_best = g.max_n_frac = true;
+  g.have_reads[0] = false; g.device_r[0] = 0; g.longest[0] = 513; c.have_out = false; g.in_flight = true;
+  const auto expect = [&](DdpRefusal want, ReadsRefusal want_gate = kRdsOk) {
+    ReadsRefusal got_gate = kRdsTooLong;
+    const DdpRefusal got = ddp_refusal(c, &got_gate);
+    CHECK(got == want && got_gate == want_gate, (long)got, (long)want, (long)got_gate);
     ++n.refusals;
   };
   expect(kDdpNullSearcher); c.have_searcher = true;
@@ -212,18 +218,18 @@ static void walk_refusals(Counts& n) {
   expect(kDdpMethod); c.method = 0;
   expect(kDdpLen); c.m = 129; expect(kDdpLen); c.m = 1;
   expect(kDdpAt); c.at = 512; expect(kDdpAt); c.at = 511;
-  expect(kDdpAscii); c.profile = kHamAsciiCi; expect(kDdpAscii); c.profile = kHamIupac;
-  expect(kDdpOverhang); c.overhang = false;
-  expect(kDdpOnlyBest); c.only_best = false;
-  expect(kDdpNFrac); c.max_n_frac = false;
-  expect(kDdpNullReads); c.have_reads = true;
-  c.handle_read = false;
+  expect(kDdpGate, kRdsAscii); g.profile = kHamAsciiCi; expect(kDdpGate, kRdsAscii); g.profile = kHamIupac;
+  expect(kDdpGate, kRdsOverhang); g.overhang = false;
+  expect(kDdpGate, kRdsOnlyBest); g.only_best = false;
+  expect(kDdpGate, kRdsNFrac); g.max_n_frac = false;
+  expect(kDdpGate, kRdsNullReads); g.have_reads[0] = true;
+  g.handle_read = false;
   expect(kDdpNullOut);  // (the handle's fields count only once they were read)
-  c.handle_read = true;
-  expect(kDdpDevice); c.device_r = 1;
-  expect(kDdpTooLong); c.longest = 512;
+  g.handle_read = true;
+  expect(kDdpGate, kRdsDevice); g.device_r[0] = 1;
+  expect(kDdpGate, kRdsTooLong); g.longest[0] = 512;
   expect(kDdpNullOut); c.have_out = true;
-  expect(kDdpInFlight); c.in_flight = false;
+  expect(kDdpGate, kRdsInFlight); g.in_flight = false;
   expect(kDdpOk);
 }
 

@@ -233,13 +233,17 @@ static void walk_refusals(Counts& n) {
   const uint8_t* good[2] = {bc0, bc0};
   const uint8_t* holed[2] = {bc0, nullptr};
   DmxCall c{};  // everything wrong at once: each refusal hides the ones behind it
-  c.have_searcher = false; c.flags = 4; c.min_delta = 66; c.n_barcodes = 0; c.barcode_len = 0; c.barcodes = nullptr; c.at = 600; c.profile = 0;
-  c.overhang = c.only_best = c.max_n_frac = true; c.have_reads = false; c.handle_read = false; c.device_s = 0; c.device_r = 1; c.longest = 513;
-  c.have_bounds = c.have_sorted = false; c.in_flight = true;
+  c.have_searcher = false; c.flags = 4; c.min_delta = 66; c.n_barcodes = 0; c.barcode_len = 0; c.barcodes = nullptr; c.at = 600;
+  ReadsGate& g = c.gate;
+  g.handles = 1; g.profile = 0;
+  g.overhang = g.only_best = g.max_n_frac = true; g.have_reads[0] = false; g.handle_read = false; g.device_s = 0; g.device_r[0] = 1; g.longest[0] = 513;
+  c.have_bounds = c.have_sorted = false; g.in_flight = true;
   size_t which = 7;
-  const auto expect = [&](DmxRefusal want, size_t want_which = 0) {
-    const DmxRefusal got = dmx_refusal(c, &which);
-    CHECK(got == want && which == want_which, (long)got, (long)want, (long)which);
+  // (the call's own code, the gate's code, the barcode named)
+  const auto expect = [&](DmxRefusal want, ReadsRefusal want_gate = kRdsOk, size_t want_which = 0) {
+    ReadsRefusal gate = kRdsTooLong;
+    const DmxRefusal got = dmx_refusal(c, &which, &gate);
+    CHECK(got == want && gate == want_gate && which == want_which, (long)got, (long)gate, (long)which);
     n.refusals++;
   };
   expect(kDmxNullSearcher); c.have_searcher = true;
@@ -250,24 +254,24 @@ static void walk_refusals(Counts& n) {
   expect(kDmxLen); c.barcode_len = 65;
   expect(kDmxLen); c.barcode_len = 4;
   expect(kDmxNullBarcode); c.barcodes = holed;
-  expect(kDmxNullBarcode, 1); c.barcodes = good;
+  expect(kDmxNullBarcode, kRdsOk, 1); c.barcodes = good;
   expect(kDmxAt); c.at = 509;
   expect(kDmxAt); c.at = 508;
-  expect(kDmxAscii); c.profile = kHamAsciiCi;
-  expect(kDmxAscii); c.profile = kHamIupac;
-  expect(kDmxOverhang); c.overhang = false;
-  expect(kDmxOnlyBest); c.only_best = false;
-  expect(kDmxNFrac); c.max_n_frac = false;
-  expect(kDmxNullReads); c.have_reads = true;
+  expect(kDmxGate, kRdsAscii); g.profile = kHamAsciiCi;
+  expect(kDmxGate, kRdsAscii); g.profile = kHamIupac;
+  expect(kDmxGate, kRdsOverhang); g.overhang = false;
+  expect(kDmxGate, kRdsOnlyBest); g.only_best = false;
+  expect(kDmxGate, kRdsNFrac); g.max_n_frac = false;
+  expect(kDmxGate, kRdsNullReads); g.have_reads[0] = true;
   expect(kDmxNullOut);  // (the handle is not read yet: what it holds is judged late)
-  c.handle_read = true;
-  expect(kDmxDevice); c.device_r = 0;
-  expect(kDmxTooLong); c.longest = 512;
+  g.handle_read = true;
+  expect(kDmxGate, kRdsDevice); g.device_r[0] = 0;
+  expect(kDmxGate, kRdsTooLong); g.longest[0] = 512;
   expect(kDmxNullOut); c.have_bounds = true;
   expect(kDmxNullOut); c.have_sorted = true;
-  expect(kDmxInFlight); c.in_flight = false;
+  expect(kDmxGate, kRdsInFlight); g.in_flight = false;
   expect(kDmxOk);
-  c.profile = kHamDna; c.flags = 0; c.min_delta = 0;
+  g.profile = kHamDna; c.flags = 0; c.min_delta = 0;
   expect(kDmxOk);
   CHECK(dmx_shifted(0) && !dmx_shifted(kDmxEnd3) && !dmx_shifted(kDmxKeepBarcode) && !dmx_shifted(kDmxEnd3 | kDmxKeepBarcode));
 }

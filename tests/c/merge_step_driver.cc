@@ -211,22 +211,29 @@ static uint64_t check_consensus() {
   return n;
 }
 
+// every refusal as (the merge's code, the overlap's code, the gate's code)
 static uint32_t check_refusals() {
   uint32_t n = 0;
   MrgCall ok{};
-  ok.ovl.have_searcher = ok.ovl.have_r1 = ok.ovl.have_r2 = ok.ovl.have_out = true;
-  ok.ovl.profile = kHamDna;
+  ok.ovl.have_searcher = ok.ovl.have_out = true;
   ok.ovl.min_overlap = 10; ok.ovl.max_permille = 200;
-  ok.ovl.n1 = ok.ovl.n2 = 5; ok.ovl.longest1 = ok.ovl.longest2 = 512;
-  ok.handles_read = true; ok.qual1 = ok.qual2 = true; ok.have_merged = true;
-  OvlRefusal why = kOvlOk;
-  CHECK(mrg_refusal(ok, &why) == kMrgOk && why == kOvlOk);
-  auto expect = [&](MrgCall c, MrgRefusal want, OvlRefusal want_ovl) {
-    OvlRefusal w = kOvlOk;
-    CHECK(mrg_refusal(c, &w) == want && w == want_ovl);
+  ok.ovl.n1 = ok.ovl.n2 = 5;
+  ReadsGate& g = ok.ovl.gate;
+  g.handles = 2;
+  g.have_reads[0] = g.have_reads[1] = g.handle_read = true;
+  g.profile = kHamDna;
+  g.longest[0] = g.longest[1] = 512;
+  ok.qual1 = ok.qual2 = true; ok.have_merged = true;
+  OvlRefusal why = kOvlFlags;
+  ReadsRefusal gate = kRdsTooLong;
+  CHECK(mrg_refusal(ok, &why, &gate) == kMrgOk && why == kOvlOk && gate == kRdsOk);
+  auto expect = [&](MrgCall c, MrgRefusal want, OvlRefusal want_ovl, ReadsRefusal want_gate = kRdsOk) {
+    OvlRefusal w = kOvlFlags;
+    ReadsRefusal gw = kRdsTooLong;
+    CHECK(mrg_refusal(c, &w, &gw) == want && w == want_ovl && gw == want_gate);
     // whatever read_overlaps refuses comes first: the merge's own two never hide it
     c.qual1 = false; c.have_merged = false;
-    if (want == kMrgOverlap) CHECK(mrg_refusal(c, &w) == kMrgOverlap && w == want_ovl);
+    if (want == kMrgOverlap) CHECK(mrg_refusal(c, &w, &gw) == kMrgOverlap && w == want_ovl && gw == want_gate);
     ++n;
   };
   MrgCall c = ok;
@@ -234,24 +241,24 @@ static uint32_t check_refusals() {
   c = ok; c.ovl.flags = 32; expect(c, kMrgOverlap, kOvlFlags);
   c = ok; c.ovl.min_overlap = 0; expect(c, kMrgOverlap, kOvlMinOverlap);
   c = ok; c.ovl.max_permille = 1001; expect(c, kMrgOverlap, kOvlPermille);
-  c = ok; c.ovl.profile = 0; expect(c, kMrgOverlap, kOvlAscii);
-  c = ok; c.ovl.profile = kHamAsciiCi; expect(c, kMrgOverlap, kOvlAscii);
-  c = ok; c.ovl.overhang = true; expect(c, kMrgOverlap, kOvlOverhang);
-  c = ok; c.ovl.only_best = true; expect(c, kMrgOverlap, kOvlOnlyBest);
-  c = ok; c.ovl.max_n_frac = true; expect(c, kMrgOverlap, kOvlNFrac);
-  c = ok; c.ovl.have_r1 = false; expect(c, kMrgOverlap, kOvlNullReads);
-  c = ok; c.ovl.have_r2 = false; expect(c, kMrgOverlap, kOvlNullReads);
+  c = ok; c.ovl.gate.profile = 0; expect(c, kMrgOverlap, kOvlGate, kRdsAscii);
+  c = ok; c.ovl.gate.profile = kHamAsciiCi; expect(c, kMrgOverlap, kOvlGate, kRdsAscii);
+  c = ok; c.ovl.gate.overhang = true; expect(c, kMrgOverlap, kOvlGate, kRdsOverhang);
+  c = ok; c.ovl.gate.only_best = true; expect(c, kMrgOverlap, kOvlGate, kRdsOnlyBest);
+  c = ok; c.ovl.gate.max_n_frac = true; expect(c, kMrgOverlap, kOvlGate, kRdsNFrac);
+  c = ok; c.ovl.gate.have_reads[0] = false; expect(c, kMrgOverlap, kOvlGate, kRdsNullReads);
+  c = ok; c.ovl.gate.have_reads[1] = false; expect(c, kMrgOverlap, kOvlGate, kRdsNullReads);
   c = ok; c.ovl.n2 = 4; expect(c, kMrgOverlap, kOvlCounts);
-  c = ok; c.ovl.device2 = 1; expect(c, kMrgOverlap, kOvlDevice);
-  c = ok; c.ovl.longest1 = 513; expect(c, kMrgOverlap, kOvlTooLong);
-  c = ok; c.ovl.longest2 = 513; expect(c, kMrgOverlap, kOvlTooLong);
+  c = ok; c.ovl.gate.device_r[1] = 1; expect(c, kMrgOverlap, kOvlGate, kRdsDevice);
+  c = ok; c.ovl.gate.longest[0] = 513; expect(c, kMrgOverlap, kOvlGate, kRdsTooLong);
+  c = ok; c.ovl.gate.longest[1] = 513; expect(c, kMrgOverlap, kOvlGate, kRdsTooLong);
   // the merge's own, in their order: the qualities, then the place for the handle
   c = ok; c.qual1 = false; expect(c, kMrgNoQuality, kOvlOk);
   c = ok; c.qual2 = false; expect(c, kMrgNoQuality, kOvlOk);
   c = ok; c.qual2 = false; c.have_merged = false; expect(c, kMrgNoQuality, kOvlOk);
   c = ok; c.have_merged = false; expect(c, kMrgNullMerged, kOvlOk);
   // before the handles are read their qualities are not asked for
-  c = ok; c.handles_read = false; c.qual1 = c.qual2 = false; expect(c, kMrgOk, kOvlOk);
+  c = ok; c.ovl.gate.handle_read = false; c.qual1 = c.qual2 = false; expect(c, kMrgOk, kOvlOk);
   c.have_merged = false; expect(c, kMrgNullMerged, kOvlOk);
   return n;
 }

@@ -195,41 +195,52 @@ static void check_small_things() {
   CHECK(c.d == 0 && c.ov == 0 && c.mm == 0 && c.n == 0);
 }
 
+// every refusal as the pair (the call's own code, the gate's code)
 static uint64_t check_refusals() {
   OvlCall ok{};
-  ok.have_searcher = ok.have_r1 = ok.have_r2 = ok.have_out = true;
-  ok.profile = kHamDna;
+  ok.have_searcher = ok.have_out = true;
   ok.min_overlap = 10; ok.max_permille = 200;
-  ok.n1 = ok.n2 = 7; ok.longest1 = 512; ok.longest2 = 150;
-  ok.device_s = ok.device1 = ok.device2 = 1;
-  CHECK(ovl_refusal(ok) == kOvlOk);
+  ok.n1 = ok.n2 = 7;
+  ReadsGate& g = ok.gate;
+  g.handles = 2;
+  g.have_reads[0] = g.have_reads[1] = g.handle_read = true;
+  g.profile = kHamDna;
+  g.longest[0] = 512; g.longest[1] = 150;
+  g.device_s = g.device_r[0] = g.device_r[1] = 1;
+  ReadsRefusal gate = kRdsTooLong;
+  CHECK(ovl_refusal(ok, &gate) == kOvlOk && gate == kRdsOk);
   uint64_t n = 0;
-  auto refused = [&](OvlRefusal want, auto&& change) {
+  auto refused = [&](OvlRefusal want, ReadsRefusal want_gate, auto&& change) {
     OvlCall c = ok;
     change(c);
-    CHECK(ovl_refusal(c) == want);
+    ReadsRefusal got = kRdsTooLong;
+    CHECK(ovl_refusal(c, &got) == want && got == want_gate);
     ++n;
   };
-  refused(kOvlNullSearcher, [](OvlCall& c) { c.have_searcher = false; c.flags = 1; });
-  refused(kOvlFlags, [](OvlCall& c) { c.flags = 1u << 20; c.min_overlap = 0; });
-  refused(kOvlMinOverlap, [](OvlCall& c) { c.min_overlap = 0; c.max_permille = 1001; });
-  refused(kOvlPermille, [](OvlCall& c) { c.max_permille = 1001; c.profile = 0; });
-  refused(kOvlAscii, [](OvlCall& c) { c.profile = 0; c.overhang = true; });
-  refused(kOvlAscii, [](OvlCall& c) { c.profile = kHamAsciiCi; });
-  refused(kOvlOverhang, [](OvlCall& c) { c.profile = kHamIupac; c.overhang = c.only_best = true; });
-  refused(kOvlOnlyBest, [](OvlCall& c) { c.only_best = c.max_n_frac = true; });
-  refused(kOvlNFrac, [](OvlCall& c) { c.max_n_frac = true; c.have_r1 = false; });
-  refused(kOvlNullReads, [](OvlCall& c) { c.have_r1 = false; c.n1 = 0; });
-  refused(kOvlNullReads, [](OvlCall& c) { c.have_r2 = false; });
-  refused(kOvlCounts, [](OvlCall& c) { c.n2 = 8; c.device1 = 0; });
-  refused(kOvlDevice, [](OvlCall& c) { c.device1 = 0; c.longest1 = 513; });
-  refused(kOvlDevice, [](OvlCall& c) { c.device2 = 2; });
-  refused(kOvlDevice, [](OvlCall& c) { c.device_s = 0; });
-  refused(kOvlTooLong, [](OvlCall& c) { c.longest1 = 513; c.have_out = false; });
-  refused(kOvlTooLong, [](OvlCall& c) { c.longest2 = 1ull << 40; });
-  refused(kOvlNullOut, [](OvlCall& c) { c.have_out = false; });
-  refused(kOvlOk, [](OvlCall& c) { c.have_out = false; c.n1 = c.n2 = 0; });          // zero pairs need no `out`
-  refused(kOvlOk, [](OvlCall& c) { c.profile = kHamIupac; c.max_permille = 1000; c.min_overlap = 0xFFFFFFFFu; });
+  refused(kOvlNullSearcher, kRdsOk, [](OvlCall& c) { c.have_searcher = false; c.flags = 1; });
+  refused(kOvlFlags, kRdsOk, [](OvlCall& c) { c.flags = 1u << 20; c.min_overlap = 0; });
+  refused(kOvlMinOverlap, kRdsOk, [](OvlCall& c) { c.min_overlap = 0; c.max_permille = 1001; });
+  refused(kOvlPermille, kRdsOk, [](OvlCall& c) { c.max_permille = 1001; c.gate.profile = 0; });
+  refused(kOvlGate, kRdsAscii, [](OvlCall& c) { c.gate.profile = 0; c.gate.overhang = true; });
+  refused(kOvlGate, kRdsAscii, [](OvlCall& c) { c.gate.profile = kHamAsciiCi; });
+  refused(kOvlGate, kRdsOverhang, [](OvlCall& c) { c.gate.profile = kHamIupac; c.gate.overhang = c.gate.only_best = true; });
+  refused(kOvlGate, kRdsOnlyBest, [](OvlCall& c) { c.gate.only_best = c.gate.max_n_frac = true; });
+  refused(kOvlGate, kRdsNFrac, [](OvlCall& c) { c.gate.max_n_frac = true; c.gate.have_reads[0] = false; });
+  refused(kOvlGate, kRdsNullReads, [](OvlCall& c) { c.gate.have_reads[0] = false; c.n1 = 0; });
+  refused(kOvlGate, kRdsNullReads, [](OvlCall& c) { c.gate.have_reads[1] = false; });
+  refused(kOvlCounts, kRdsOk, [](OvlCall& c) { c.n2 = 8; c.gate.device_r[0] = 0; });
+  refused(kOvlGate, kRdsDevice, [](OvlCall& c) { c.gate.device_r[0] = 0; c.gate.longest[0] = 513; });
+  refused(kOvlGate, kRdsDevice, [](OvlCall& c) { c.gate.device_r[1] = 2; });
+  refused(kOvlGate, kRdsDevice, [](OvlCall& c) { c.gate.device_s = 0; });
+  refused(kOvlGate, kRdsTooLong, [](OvlCall& c) { c.gate.longest[0] = 513; c.have_out = false; });
+  refused(kOvlGate, kRdsTooLong, [](OvlCall& c) { c.gate.longest[1] = 1ull << 40; });
+  refused(kOvlNullOut, kRdsOk, [](OvlCall& c) { c.have_out = false; });
+  refused(kOvlOk, kRdsOk, [](OvlCall& c) { c.have_out = false; c.n1 = c.n2 = 0; });          // zero pairs need no `out`
+  refused(kOvlOk, kRdsOk, [](OvlCall& c) { c.gate.profile = kHamIupac; c.max_permille = 1000; c.min_overlap = 0xFFFFFFFFu; });
+  // the tickets are not this function's: the entry points look at them behind all of it
+  refused(kOvlOk, kRdsOk, [](OvlCall& c) { c.gate.in_flight = true; });
+  // before the handles are read nothing of theirs is judged
+  refused(kOvlOk, kRdsOk, [](OvlCall& c) { c.gate.handle_read = false; c.gate.device_r[0] = 0; c.gate.longest[1] = 513; });
   return n;
 }
 

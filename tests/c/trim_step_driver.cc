@@ -225,39 +225,42 @@ static uint64_t check_refusals() {
   TrmCall c{};
   c.have_searcher = false; c.flags = 1; c.min_overlap = 0; c.max_permille = 1001; c.quality_cutoff = 94;
   c.adapters = nullptr; c.adapter_lens = nullptr; c.n_adapters = 65;
-  c.profile = 0; c.overhang = c.only_best = c.max_n_frac = true;
-  c.have_reads = false; c.handle_read = true; c.device_s = 0; c.device_r = 1; c.longest = 513; c.kept_quality = false;
-  c.have_trimmed = false; c.in_flight = true;
+  c.gate.handles = 1;
+  c.gate.profile = 0; c.gate.overhang = c.gate.only_best = c.gate.max_n_frac = true;
+  c.gate.have_reads[0] = false; c.gate.handle_read = true; c.gate.device_s = 0; c.gate.device_r[0] = 1; c.gate.longest[0] = 513; c.kept_quality = false;
+  c.have_trimmed = false; c.gate.in_flight = true;
   size_t which = 9;
+  ReadsRefusal gate = kRdsOk;
   uint64_t n = 0;
-#define EXPECT(code, j) do { CHECK(trm_refusal(c, &which) == (code)); CHECK(which == (size_t)(j)); ++n; } while (0)
-  EXPECT(kTrmNullSearcher, 0); c.have_searcher = true;
-  EXPECT(kTrmFlags, 0); c.flags = 0;
-  EXPECT(kTrmMinOverlap, 0); c.min_overlap = 3;
-  EXPECT(kTrmPermille, 0); c.max_permille = 1000;
-  EXPECT(kTrmCutoff, 0); c.quality_cutoff = 93;
-  EXPECT(kTrmTooMany, 0); c.n_adapters = 2;
-  EXPECT(kTrmNullAdapter, 0); c.adapters = with_null; c.adapter_lens = lens;
-  EXPECT(kTrmNullAdapter, 1); c.adapters = good; c.adapter_lens = zero;
-  EXPECT(kTrmEmptyAdapter, 1); c.adapter_lens = longer;
-  EXPECT(kTrmLongAdapter, 1); c.adapter_lens = shorter;
-  EXPECT(kTrmShortAdapter, 1); c.adapter_lens = lens;
-  EXPECT(kTrmAscii, 0); c.profile = kHamIupac;
-  EXPECT(kTrmOverhang, 0); c.overhang = false;
-  EXPECT(kTrmOnlyBest, 0); c.only_best = false;
-  EXPECT(kTrmNFrac, 0); c.max_n_frac = false;
-  EXPECT(kTrmNullReads, 0); c.have_reads = true;
-  EXPECT(kTrmDevice, 0); c.device_r = 0;
-  EXPECT(kTrmTooLong, 0); c.longest = 512;
-  EXPECT(kTrmNoQuality, 0); c.quality_cutoff = 0;
-  EXPECT(kTrmNullTrimmed, 0); c.quality_cutoff = 20; c.kept_quality = true;
-  EXPECT(kTrmNullTrimmed, 0); c.have_trimmed = true;
-  EXPECT(kTrmInFlight, 0); c.in_flight = false;
-  EXPECT(kTrmOk, 0);
+  // (the call's own code, the gate's code, the adapter named)
+#define EXPECT(code, gate_code, j) do { CHECK(trm_refusal(c, &which, &gate) == (code)); CHECK(gate == (gate_code) && which == (size_t)(j)); ++n; } while (0)
+  EXPECT(kTrmNullSearcher, kRdsOk, 0); c.have_searcher = true;
+  EXPECT(kTrmFlags, kRdsOk, 0); c.flags = 0;
+  EXPECT(kTrmMinOverlap, kRdsOk, 0); c.min_overlap = 3;
+  EXPECT(kTrmPermille, kRdsOk, 0); c.max_permille = 1000;
+  EXPECT(kTrmCutoff, kRdsOk, 0); c.quality_cutoff = 93;
+  EXPECT(kTrmTooMany, kRdsOk, 0); c.n_adapters = 2;
+  EXPECT(kTrmNullAdapter, kRdsOk, 0); c.adapters = with_null; c.adapter_lens = lens;
+  EXPECT(kTrmNullAdapter, kRdsOk, 1); c.adapters = good; c.adapter_lens = zero;
+  EXPECT(kTrmEmptyAdapter, kRdsOk, 1); c.adapter_lens = longer;
+  EXPECT(kTrmLongAdapter, kRdsOk, 1); c.adapter_lens = shorter;
+  EXPECT(kTrmShortAdapter, kRdsOk, 1); c.adapter_lens = lens;
+  EXPECT(kTrmGate, kRdsAscii, 0); c.gate.profile = kHamIupac;
+  EXPECT(kTrmGate, kRdsOverhang, 0); c.gate.overhang = false;
+  EXPECT(kTrmGate, kRdsOnlyBest, 0); c.gate.only_best = false;
+  EXPECT(kTrmGate, kRdsNFrac, 0); c.gate.max_n_frac = false;
+  EXPECT(kTrmGate, kRdsNullReads, 0); c.gate.have_reads[0] = true;
+  EXPECT(kTrmGate, kRdsDevice, 0); c.gate.device_r[0] = 0;
+  EXPECT(kTrmGate, kRdsTooLong, 0); c.gate.longest[0] = 512;
+  EXPECT(kTrmNoQuality, kRdsOk, 0); c.quality_cutoff = 0;
+  EXPECT(kTrmNullTrimmed, kRdsOk, 0); c.quality_cutoff = 20; c.kept_quality = true;
+  EXPECT(kTrmNullTrimmed, kRdsOk, 0); c.have_trimmed = true;
+  EXPECT(kTrmGate, kRdsInFlight, 0); c.gate.in_flight = false;
+  EXPECT(kTrmOk, kRdsOk, 0);
   c.n_adapters = 0; c.adapters = nullptr; c.adapter_lens = nullptr;  // no adapter at all is a call
-  EXPECT(kTrmOk, 0);
-  c.handle_read = false; c.longest = 9999;  // before the handle is read nothing of it is judged
-  EXPECT(kTrmOk, 0);
+  EXPECT(kTrmOk, kRdsOk, 0);
+  c.gate.handle_read = false; c.gate.longest[0] = 9999;  // before the handle is read nothing of it is judged
+  EXPECT(kTrmOk, kRdsOk, 0);
 #undef EXPECT
   return n;
 }

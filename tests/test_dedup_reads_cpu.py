@@ -179,9 +179,14 @@ def test_source_layout():
         assert len(re.findall(r"__global__[^;{]*\b" + kernel + r"\(", unit)) == 1, kernel
     assert code.count("__global__") == 6
     assert code.count("__hip_atomic_fetch_max(") == 1 and "__HIP_MEMORY_SCOPE_AGENT" in code and code.count("atomic") == 1
-    for call in ("ddp_refusal(", "ddp_window_planes<P, RC>(", "dmx_window(", "dmx_has_window(", "umi_groups_resident(", "pairs_scan_u64(", "reads_plain(",
-                 "reads_layout_windows(", "write_windows(", "reads_empty_buffers(", "hamming_call("):
+    for call in ("ddp_refusal(", "ddp_window_planes<P, RC>(", "dmx_window(", "dmx_has_window(", "umi_groups_resident(", "pairs_scan_u64(", "reads_require_plain(",
+                 "reads_layout_windows(", "write_windows(", "reads_empty_buffers(", "reads_new_batch("):
         assert call in code, call
+    shared = open(os.path.join(CSRC, "reads_call.hip")).read()
+    assert len(re.findall(r"\nint reads_require_plain\(", shared)) == 1 and shared.count("reads_plain(") == 1   # the Dna look: one owner, called here
+    frame = open(os.path.join(CSRC, "host_internal.h")).read()
+    frame = frame[frame.index("\nint reads_new_batch("):]
+    assert frame[:frame.index("\n}\n")].count("hamming_call(") == 1 and frame.count("\nint reads_new_batch(") == 1   # the frame: one owner, called here
     assert "fastq_rec_" not in code and "reads_window_write_kernel<" not in code and "pairs_upload" not in code and "uint4" in code
     host = open(os.path.join(CSRC, "host_internal.h")).read()
     assert "int umi_groups_resident(" in host and "DevBuf<uint8_t> d_dedup;" in host and "int pairs_upload_self(" in host

@@ -175,7 +175,9 @@ def test_source_layout():
         assert len(re.findall(r"__global__[^;{]*\b" + kernel + r"\(", unit)) == 1, kernel
     assert code.count("__global__") == 3
     assert "rocprim::radix_sort_pairs(" in code and "dmx_refusal(" in code and "dmx_combine(" in code and "trm_window_block(" in code
-    assert "reads_layout_windows(" in code and "write_windows(" in code and "reads_plain(" in code and "dmx_lower_bound(" in code
+    assert "reads_layout_windows(" in code and "write_windows(" in code and "reads_require_plain(" in code and "dmx_lower_bound(" in code
+    shared = open(os.path.join(CSRC, "reads_call.hip")).read()
+    assert len(re.findall(r"\nint reads_require_plain\(", shared)) == 1 and shared.count("reads_plain(") == 1   # the Dna look: one owner, called here
     assert "fastq_rec_" not in code and "reads_window_write_kernel<" not in code and "hipMemset(" not in code   # no scan, no write kernel of its own
     host = open(os.path.join(CSRC, "host_internal.h")).read()
     for decl in ("int write_windows(", "int reads_empty_buffers(", "int reads_layout_windows("):

@@ -149,7 +149,7 @@ def test_step_header_is_free_of_hip_and_the_driver_stands_alone():
     for fn in ("mrg_length", "mrg_sources", "mrg_consensus", "mrg_refusal", "mrg_word"):
         assert re.search(r"\b" + fn + r"\s*\(", src), fn
     # the refusals and the complement are overlap_step.h's: called, not copied
-    assert "ovl_refusal(c.ovl)" in src and "ovl_complement(profile," in src and "'A' ? 'T'" not in src
+    assert "ovl_refusal(c.ovl, gate)" in src and "ovl_complement(profile," in src and "'A' ? 'T'" not in src
     # the consensus is branch-free: selects on scalars, no `if`, no struct-valued ?:
     body = src[src.index("SASSY_HAM_HD MrgByte mrg_consensus("):src.index("// One column out of what covers it")]
     assert "if (" not in body and "&&" not in body and "||" not in body
@@ -173,7 +173,9 @@ def test_source_layout():
     for decl in ("int overlaps_resident(", "int reads_layout_merged(", "int overlap_refused("):
         assert decl in host, decl
     overlaps = open(os.path.join(CSRC, "read_overlaps.hip")).read()
-    assert overlaps.count("reads_plain(") == 1 and "int overlaps_resident(" in overlaps
+    assert overlaps.count("reads_require_plain(") == 1 and "int overlaps_resident(" in overlaps
+    shared = open(os.path.join(CSRC, "reads_call.hip")).read()
+    assert len(re.findall(r"\nint reads_require_plain\(", shared)) == 1 and shared.count("reads_plain(") == 1   # the Dna look: one owner, called here
     fastq = open(os.path.join(CSRC, "fastq_reads.hip")).read()
     assert len(re.findall(r"__global__[^;{]*\bfastq_copy_kernel\(", fastq)) == 1          # one copy kernel, for both lines
     assert len(re.findall(r"__global__[^;{]*\bfastq_rec_(?:sum|top|write)_kernel\(", fastq)) == 3   # one scan, two sources

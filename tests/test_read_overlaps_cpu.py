@@ -120,7 +120,7 @@ def test_step_arithmetic_against_a_byte_wise_brute_force_under_sanitizers(tmp_pa
     # themselves once; 511 and 512 meet the 14 borders up to 193 and themselves --, each length against itself and a random one,
     # and 512 x 511 both ways at the end
     assert fields["pairs"] == 2 * (14 * 31 + 120 * 32 + 2 * 29 + 136 * 2 + 2), fields
-    assert fields["offsets"] > 3000000 and fields["bests"] == 6 * fields["pairs"] and fields["refusals"] == 20
+    assert fields["offsets"] > 3000000 and fields["bests"] == 6 * fields["pairs"] and fields["refusals"] == 22
     r = subprocess.run([exe, "complement"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0
     tables = dict(line.split() for line in r.stdout.splitlines())
@@ -133,7 +133,8 @@ def test_step_header_is_free_of_hip_and_the_driver_stands_alone():
     src = open(os.path.join(CSRC, "overlap_step.h")).read()
     assert "#include <hip" not in src and "hipStream" not in src and "getenv" not in src
     assert "__builtin_amdgcn" not in src and "__HIP_DEVICE_COMPILE__" not in src and "asm" not in re.sub(r"//.*", "", src)
-    assert [l for l in src.splitlines() if l.startswith("#include")] == ["#include <cstddef>", "#include <cstdint>", '#include "pairs_step.h"']
+    assert [l for l in src.splitlines() if l.startswith("#include")] == ["#include <cstddef>", "#include <cstdint>", '#include "pairs_step.h"',
+                                                                         '#include "reads_gate.h"']
     for fn in ("ovl_refusal", "ovl_complement", "ovl_row_code", "ovl_offsets", "ovl_overlap", "ovl_shifted_word", "ovl_mismatch_word", "ovl_accepts",
                "ovl_better", "ovl_combine", "ovl_words"):
         assert re.search(r"\b" + fn + r"\s*\(", src), fn
@@ -152,7 +153,9 @@ def test_source_layout():
     assert len(re.findall(r"__global__[^;{]*\bread_overlaps_kernel\(", unit)) == 1
     entry = unit[unit.index("int " + NAME + "("):]
     assert entry.index("ovl_refusal(") < entry.index("SASSY_NO_TICKETS") < entry.index("hamming_call(") < entry.index("overlaps_run(")
-    assert unit.count("reads_plain(") == 1 and "for (const sassy_hip_Reads* r : {r1, r2})" in unit
+    assert unit.count("reads_require_plain(") == 1 and "for (const sassy_hip_Reads* r : {r1, r2})" in unit
+    shared = open(os.path.join(CSRC, "reads_call.hip")).read()
+    assert len(re.findall(r"\nint reads_require_plain\(", shared)) == 1 and shared.count("reads_plain(") == 1   # the Dna look: one owner, called here
     for name in ("ovl_row_code(", "ovl_shifted_word(", "ovl_mismatch_word<", "ovl_accepts(", "ovl_combine(", "ovl_offsets(", "__ballot(", "__shfl_xor("):
         assert name in unit, name
     # every word count ovl_words can return is instantiated

@@ -174,7 +174,10 @@ def test_source_layout():
     assert len(re.findall(r"__global__[^;{]*\btrim_find_kernel\(", unit)) == 1 and len(re.findall(r"__global__[^;{]*\breads_window_write_kernel\(", unit)) == 1
     assert code.count("__global__") == 2
     assert "ovl_accepts(" in code and "trm_refusal(" in code and "trm_combine(" in code and "trm_window_block(" in code
-    assert "reads_layout_trimmed(" in code and "reads_layout_windows(" in code and "reads_plain(" in code
+    assert "reads_layout_trimmed(" in code and "windows_from_host(" in code and "reads_require_plain(" in code
+    shared = open(os.path.join(CSRC, "reads_call.hip")).read()
+    assert len(re.findall(r"\nint reads_require_plain\(", shared)) == 1 and shared.count("reads_plain(") == 1   # the Dna look: one owner, called here
+    assert len(re.findall(r"\nint windows_from_host\(", shared)) == 1 and shared.count("reads_layout_windows(") == 1   # the slice's layout: likewise
     assert "ham_text_of(" in code and "ham_rem(" in code and "hipMemset(" not in code
     assert "fastq_rec_" not in code                                    # no scan of its own
     host = open(os.path.join(CSRC, "host_internal.h")).read()
