@@ -59,7 +59,7 @@ UNITS = [
     ("dedup_reads.hip", "dedup_reads.o", []),
     ("c_abi.hip", "c_abi.o", []),
 ]
-HEADERS = ["common.h", "profiles.h", "profile_masks.h", "hamming_step.h", "hamming_plan.h", "pairs_step.h", "edit_pairs_step.h", "cluster_step.h", "collapse_step.h", "umi_step.h", "amplicon_step.h", "fasta_step.h", "fastq_step.h", "relayout_step.h", "reads_gate.h", "overlap_step.h", "merge_step.h", "trim_step.h", "demux_step.h", "dedup_step.h", "piece_pair_step.h", "tiled_step.h", "switches.h", "pass_planner.h", "pass_lds.h", "plane_cache.h", "scan_route.h", "host_internal.h", os.path.join("..", "..", "include", "sassy.h"),
+HEADERS = ["common.h", "profiles.h", "profile_masks.h", "hamming_step.h", "hamming_plan.h", "pairs_step.h", "edit_pairs_step.h", "cluster_step.h", "collapse_step.h", "umi_step.h", "amplicon_step.h", "fasta_step.h", "fastq_step.h", "relayout_step.h", "reads_gate.h", "overlap_step.h", "merge_step.h", "trim_step.h", "demux_step.h", "dedup_step.h", "piece_pair_step.h", "hit_cols_step.h", "tiled_step.h", "switches.h", "pass_planner.h", "pass_lds.h", "plane_cache.h", "scan_route.h", "host_internal.h", os.path.join("..", "..", "include", "sassy.h"),
            os.path.join("..", "..", "include", "sassy_hip.h")]
 
 

@@ -3,6 +3,7 @@
 // Mirror of the reference's Searcher<P>::search path (src/search.rs:510-937).
 #include "host_internal.h"
 #include "pass_lds.h"
+#include "hit_cols_step.h"
 
 PinPool g_pin_pool;
 
@@ -61,6 +62,8 @@ int stream_geometry(ScanParams& P, uint64_t owned, uint32_t extra_front, uint32_
     if (t) bpl = t;
   }
   if (bpl > 0xFFFFFFFFull / 2) return fail(SASSY_HIP_EUNSUPPORTED, "text too large for one launch");
+  // (the grouped pass computes a lane's columns in 32 bits relative to its chunk: hit_cols_step.h states the domain)
+  if (!hit_cols_fits(bpl)) return fail(SASSY_HIP_EUNSUPPORTED, "text too large for one launch");
   P.bpl = (uint32_t)bpl;
   P.n_chunks = (owned + bpl - 1) / bpl;
   P.n_iter = extra_front + 1 + P.bpl;

@@ -42,6 +42,7 @@
 #include "pass_lds.h"
 #include "profile_masks.h"
 #include "piece_pair_step.h"
+#include "hit_cols_step.h"
 
 namespace sassy_hip {
 
@@ -1575,10 +1576,28 @@ constexpr uint32_t kRunCont = 0x40000000u;  // (bit 30 of w) the pending run con
 // press_at: a lane whose entry gets this index or a later one raises kRunPressure -- the wave then runs the chunk DP
 // over its queue at the next block pair instead of at the end of its text range (the queue never overflows: between
 // two looks at the flag every lane adds at most two entries).
+// ORIGIN: the lane's origin as int64_t col_base, or -- the grouped pass -- as rep2 {HitBase::zero_rel, HitBase::base_blk}: the
+// same window from 32-bit arithmetic (hit_cols_step.h: hit_window; tests/c/hit_cols_driver.cc compares the two forms).
+typedef uint32_t rep2 __attribute__((ext_vector_type(2)));
+template <typename ORIGIN>
 __device__ __forceinline__ rep4 fuse_emit(uint2* queue, uint32_t* qcount, uint32_t* fuse_word, uint32_t cap, uint32_t press_at,
-                                          uint32_t mk, int64_t col_base, rep4 st, uint32_t x, uint32_t y) {
+                                          uint32_t mk, ORIGIN col_base, rep4 st, uint32_t x, uint32_t y) {
   // (65536: the lane's first own column, see col_base)
   const uint32_t margin = ((st.w & kRunCont) || x < 65536u + 2u * 64u) ? kFuseMargin : 0u;
+  if constexpr (std::is_same<ORIGIN, rep2>::value) {
+    HitBase hb;
+    hb.max_rel = 0u;  // (the window needs the buffer's beginning only)
+    hb.zero_rel = col_base.x;
+    hb.base_blk = col_base.y;
+    const HitWindow w = hit_window(x, y, margin, mk, hb);
+    if (w.nv > kFuseMaxBlocks) atomicOr(fuse_word, kFuseOverflow);  // (cannot happen: runs are split before they get there)
+    const uint32_t idx = atomicAdd(qcount, 1u);
+    if (idx < cap) queue[idx] = make_uint2(w.first, w.word);
+    else atomicOr(fuse_word, kFuseOverflow);
+    st.z = y + 1u;
+    st.w = x | ((idx >= press_at || (st.w & kRunPressure)) ? kRunPressure : 0u);  // (kRunCont: set by the caller that splits)
+    return st;
+  } else {
   uint32_t nv = (y - x + margin + mk + 2u + 63u) / 64u;
   if (nv > kFuseMaxBlocks) atomicOr(fuse_word, kFuseOverflow);  // (cannot happen: runs are split before they get there)
   const int64_t end = col_base + (int64_t)y;
@@ -1599,10 +1618,12 @@ __device__ __forceinline__ rep4 fuse_emit(uint2* queue, uint32_t* qcount, uint32
   st.z = y + 1u;
   st.w = x | ((idx >= press_at || (st.w & kRunPressure)) ? kRunPressure : 0u);  // (kRunCont: set by the caller that splits)
   return st;
+  }
 }
 // adds the columns [lo, hi] (lo = kRunNone: nothing to add, only queue the pending run)
+template <typename ORIGIN>
 __device__ __noinline__ rep4 fuse_add_range(uint2* queue, uint32_t* qcount, uint32_t* fuse_word, uint32_t cap, uint32_t press_at,
-                                            uint32_t mk, int64_t col_base, uint32_t first_col, rep4 st, uint32_t lo, uint32_t hi) {
+                                            uint32_t mk, ORIGIN col_base, uint32_t first_col, rep4 st, uint32_t lo, uint32_t hi) {
   if (lo == kRunNone) {
     if (st.x != kRunNone) {
       st = fuse_emit(queue, qcount, fuse_word, cap, press_at, mk, col_base, st, st.x, st.y);
@@ -1859,10 +1880,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     }
   }
   const uint32_t press_at = Pk->fuse_press;
+  // (G = 2) The hit path in 32-bit columns relative to col_base (hit_cols_step.h), everything it needs once per segment:
+  // the lane's view of the buffer, the iterations it evaluates [ev_lo, ev_hi), the first column the chunk DP owns, and --
+  // wave-uniform -- per slot the two column offsets as bytes, the members' slots, m + k of both and the queue capacity.
+  HitBase hbase = {};
+  rep2 origin = {0u, 0u};
+  uint32_t ev_lo = 1u, ev_hi = 0u, first_col = 0u;
+  uint32_t slot_lo[2] = {0u, 0u}, slot_hi[2] = {0u, 0u}, slot_member = 0u, mk01 = 0u, queue_cap = 0u;
+  if constexpr (G == 2) {
+    hbase = hit_base(col_base, (int64_t)(Pk->n_blocks * 64));
+    origin.x = hbase.zero_rel;
+    origin.y = hbase.base_blk;
+    if (has_chunk) {
+      ev_lo = (uint32_t)(own_lo - blk0);
+      ev_hi = (uint32_t)(own_hi - blk0);
+    }
+    const int64_t fc = (int64_t)(Pk->dp_first_owned * 64) - col_base;
+    first_col = fc > 0 ? (uint32_t)fc : 0u;
+    slot_member = Pk->piece_member;
+    static_assert(kFuseGroupMaxWords * 32u + kHitColsMaxK + 1u < 256u, "rows behind a piece + k + 1: a byte per slot");
+#pragma unroll
+    for (int pp = 0; pp < NP; ++pp) {
+      const uint32_t kq = ((slot_member >> pp) & 1u) ? Pk->member1.k : Pk->k;
+      slot_lo[pp >> 2] |= (hit_add_lo(Pk->piece_rem[pp], kq) & 0xFFu) << (8 * (pp & 3));
+      slot_hi[pp >> 2] |= (hit_add_hi(Pk->piece_rem[pp], kq) & 0xFFu) << (8 * (pp & 3));
+    }
+    mk01 = (Pk->m + Pk->k) | ((Pk->member1.m + Pk->member1.k) << 16);
+    queue_cap = Pk->fuse_queue_cap;
+  }
 
   // software pipeline: the loads of the next staging step are in flight while this one is processed
   uint4 nxt[kStageInstr];
-  uint4 pln[kPlaneAhead + 2];  // (kPlaneRead) [0], [1]: the block pair at work; behind them the planes on their way
+  // (kPlaneRead) G = 1: [0], [1]: the block pair at work; behind them the planes on their way.  G = 2: two pairs, [0], [1] and
+  // [2], [3], that take turns -- the pair at work and the pair on its way
+  constexpr int kPlaneRegs = G == 2 ? kPlaneAhead : kPlaneAhead + 2;
+  constexpr int kPlaneFirst = G == 2 ? 0 : 2;  // the register the segment's first block is loaded into
+  static_assert(G != 2 || kPlaneAhead == 4, "the pair trips of the grouped pass alternate between two register sets");
+  uint4 pln[kPlaneRegs];
 #pragma unroll
   for (int i = 0; i < kStageInstr; ++i) {
     nxt[i] = make_uint4(0u, 0u, 0u, 0u);
@@ -1871,9 +1925,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
   }
   if constexpr (SRC == kPlaneRead) {
 #pragma unroll
-    for (int j = 0; j < kPlaneAhead + 2; ++j) {
+    for (int j = 0; j < kPlaneRegs; ++j) {
       pln[j] = make_uint4(0u, 0u, 0u, 0u);
-      if (j >= 2 && seg_it + (uint32_t)(j - 2) < n_iter) pln[j] = stream_load16<true>(plane_base + (uint64_t)(seg_it + (uint32_t)(j - 2)) * 1024u + lane * 16u);
+      if (j >= kPlaneFirst && seg_it + (uint32_t)(j - kPlaneFirst) < n_iter)
+        pln[j] = stream_load16<true>(plane_base + (uint64_t)(seg_it + (uint32_t)(j - kPlaneFirst)) * 1024u + lane * 16u);
     }
   }
   uint32_t npure = 0;  // (CHECK) how many blocks of nothing but N the lane has just walked over
@@ -1881,8 +1936,135 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     if (!first_segment) npure = (reinterpret_cast<const uint32_t*>(tile + kSegState) + lane)[384];
   }
 
-  uint32_t bl[G == 2 ? NP : 1] = {}, bh[G == 2 ? NP : 1] = {};  // (G = 2) the pair's second block's masks, until its turn
   uint32_t it = seg_it;
+  if constexpr (G == 2) {
+    // The grouped pass takes a block PAIR per trip: stage or load, test both blocks together -- every constant then serves
+    // four independent accumulators, from a vector register (piece_pair_step.h) -- then the occurrences of the first block,
+    // then those of the second, each from its own masks; the pressure vote ends the trip.  `it` is even throughout.
+    // A pair whose second block lies behind n_iter (n_iter is odd when `back` is 1) still has that block's text in the tile
+    // -- the staging reads whole pairs -- or, reading planes, whatever its registers held: its masks are never looked at, its
+    // planes are not stored, and nothing is read behind n_iter.
+    // the occurrences of one block (masks ml / mh, iteration itb): the columns per member, then the members' runs
+    auto pair_hits = [&](const uint32_t (&ml)[NP], const uint32_t (&mh)[NP], uint32_t itb) __attribute__((always_inline)) {
+      uint32_t hit = 0;
+#pragma unroll
+      for (int pp = 0; pp < NP; ++pp) hit |= ml[pp] | mh[pp];
+      const bool evaluate = itb >= ev_lo && itb < ev_hi;
+      if (evaluate && hit != 0) {
+        const uint32_t bcol = hit_block_col(0u - ev_lo, itb);
+        uint32_t lo = kRunNone, hi = 0;
+        uint32_t lo1 = kRunNone, hi1 = 0;  // (member 1's columns)
+#pragma unroll
+        for (int pp = 0; pp < NP; ++pp) {
+          if ((ml[pp] | mh[pp]) != 0u) {
+            const HitCols r = hit_end_cols(ml[pp], mh[pp], bcol, (slot_lo[pp >> 2] >> (8 * (pp & 3))) & 0xFFu,
+                                           (slot_hi[pp >> 2] >> (8 * (pp & 3))) & 0xFFu, hbase);
+            if ((slot_member >> pp) & 1u) {
+              lo1 = min(lo1, r.lo);
+              hi1 = max(hi1, r.hi);
+            } else {
+              lo = min(lo, r.lo);
+              hi = max(hi, r.hi);
+            }
+          }
+        }
+        if (lo != kRunNone)
+          run = fuse_add_range(queue, qcount, Pk->cand_count + kCtlFuseWord, queue_cap, press_at, mk01 & 0xFFFFu, origin, first_col, run, lo, hi);
+        if (lo1 != kRunNone)
+          run1 = fuse_add_range(queue1, qcount1, Pk->member1.cand_count + kCtlFuseWord, queue_cap, press_at, mk01 >> 16, origin, first_col, run1,
+                                lo1, hi1);
+      }
+    };
+    // One trip, for the pair at `it`.  (kPlaneRead) ca / cb: the pair's planes, in one of two register sets that take
+    // turns: the set is asked for the pair four iterations on as soon as the test has read it, so the pair at work and
+    // the pair on its way are all a lane holds, and no set is ever copied into another.  Returns the pressure vote.
+    auto pair_trip = [&](uint4& ca, uint4& cb) __attribute__((always_inline)) -> bool {
+      if constexpr (SRC != kPlaneRead) {
+        if (interior) {
+#pragma unroll
+          for (int i = 0; i < kStageInstr; ++i) *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = nxt[i];
+          if (it + SB < n_iter) {
+#pragma unroll
+            for (int i = 0; i < kStageInstr; ++i)
+              nxt[i] = stream_load16<SASSY_NT_DNA>(text_base + (uint64_t)(it + SB) * 64 + soff[i]);
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < kStageInstr; ++i) {
+            const uint64_t off = wave_blk0 * 64 + (uint64_t)it * 64 + soff[i];
+            uint4 v;
+            if (off + 16 <= Pk->text_len) v = *reinterpret_cast<const uint4*>(Pk->text + off);
+            else v = load_tail16(Pk->text, off, Pk->text_len);  // (bytes behind the end of the text read as 'X')
+            *reinterpret_cast<uint4*>(tile + i * 1024 + lane * 16) = v;
+          }
+        }
+      }
+      uint32_t al[NP], ah[NP], bl[NP], bh[NP];
+      PiecePlanes pa, pb;
+      if constexpr (SRC == kPlaneRead) {
+        pa = PiecePlanes{ca.x, ca.y, ca.z, ca.w};
+        pb = PiecePlanes{cb.x, cb.y, cb.z, cb.w};
+      } else {
+        auto tile_planes = [&](uint32_t half) {
+          const uint32_t hs = (((half << 2) ^ (fsw & 4u)) << 4);
+          uint32_t x[16];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const uint4 v = *reinterpret_cast<const uint4*>(tile + rc[c] + hs);
+            x[4 * c] = v.x; x[4 * c + 1] = v.y; x[4 * c + 2] = v.z; x[4 * c + 3] = v.w;
+          }
+          const uint2 c0 = bit_plane<1>(x), c1 = bit_plane<2>(x);
+          return PiecePlanes{c0.x, c0.y, c1.x, c1.y};
+        };
+        pa = tile_planes(0u);
+        pb = tile_planes(1u);
+        if constexpr (SRC == kPlaneWrite) {
+          uint8_t* const at = const_cast<uint8_t*>(plane_base) + (uint64_t)it * 1024u + lane * 16u;
+          *reinterpret_cast<uint4*>(at) = make_uint4(pa.p0l, pa.p0h, pa.p1l, pa.p1h);
+          if (it + 1u < n_iter) *reinterpret_cast<uint4*>(at + 1024u) = make_uint4(pb.p0l, pb.p0h, pb.p1l, pb.p1h);
+        }
+      }
+      // (the table's address, opaque to the optimiser inside the loop: its words are read here, per pair, not held
+      // in 2 * Q * pieces registers across the loop)
+      uint32_t tab_at = 0;
+      asm volatile("" : "+v"(tab_at));
+      piece_pair_step<Q, NP>(pa, pb, prev0, prev1, piece_row_table_lds<Q, NP>() + tab_at, al, ah, bl, bh);
+      // (The second block's masks are complete HERE, and the loads are issued from here on: left to itself the compiler
+      // moves that block's half of the test behind the first block's occurrences, reads the whole table in front of both
+      // halves and keeps it in scratch memory, and asks for the planes before the test has let go of their registers.)
+      uint32_t lane16 = lane * 16u;
+      asm volatile("" : "+v"(al[0]), "+v"(al[1]), "+v"(al[2]), "+v"(al[3]), "+v"(al[4]), "+v"(al[5]), "+v"(al[6]), "+v"(al[7]),
+                        "+v"(ah[0]), "+v"(ah[1]), "+v"(ah[2]), "+v"(ah[3]), "+v"(ah[4]), "+v"(ah[5]), "+v"(ah[6]), "+v"(ah[7]));
+      asm volatile("" : "+v"(lane16),"+v"(bl[0]), "+v"(bl[1]), "+v"(bl[2]), "+v"(bl[3]), "+v"(bl[4]), "+v"(bl[5]), "+v"(bl[6]), "+v"(bl[7]),
+                        "+v"(bh[0]), "+v"(bh[1]), "+v"(bh[2]), "+v"(bh[3]), "+v"(bh[4]), "+v"(bh[5]), "+v"(bh[6]), "+v"(bh[7]));
+      static_assert(NP == 8, "the statement above names every slot");
+      if constexpr (SRC == kPlaneRead) {
+        if (it + (uint32_t)kPlaneAhead < n_iter) ca = stream_load16<true>(plane_base + (uint64_t)(it + (uint32_t)kPlaneAhead) * 1024u + lane16);
+        if (it + (uint32_t)kPlaneAhead + 1u < n_iter) cb = stream_load16<true>(plane_base + (uint64_t)(it + (uint32_t)kPlaneAhead + 1u) * 1024u + lane16);
+      }
+      pair_hits(al, ah, it);
+      if (it + 1u < n_iter) pair_hits(bl, bh, it + 1u);  // (wave-uniform)
+      // the queue is filling up: the block pair is done with the tile -- the chunk DP may have it
+      return __any(((run.w | run1.w) & kRunPressure) != 0u);
+    };
+    for (;;) {
+      if (it >= n_iter) break;
+      bool press = pair_trip(pln[0], pln[1]);
+      it += 2u;
+      if (press) break;
+      if constexpr (SRC == kPlaneRead) {  // (the other register set's turn)
+        if (it >= n_iter) break;
+        press = pair_trip(pln[2], pln[3]);
+        it += 2u;
+        if (press) break;
+      }
+    }
+    if (it > n_iter) it = n_iter;  // (an odd n_iter: the last pair's second block was no iteration)
+  } else {
+    if constexpr (SRC == kPlaneRead) {
+      static_assert(kPlaneRegs == kPlaneAhead + 2 && kPlaneAhead % 2 == 0, "the lone reader's ring moves up by a pair: the pair at work, kPlaneAhead blocks behind it");
+    }
+  // one member: a block per trip, the constants as scalars, the 64-bit hit path
   for (; it < n_iter; ++it) {
     const uint32_t sub = it & 1u;
     if constexpr (SRC == kPlaneRead) {
@@ -1917,47 +2099,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     uint2 t0, t1;
     uint32_t dsum = 0;  // (CHECK) != 0: the block holds other letters
     uint32_t al[NP], ah[NP];
-    if constexpr (G == 2) {
-      // The grouped pass tests the blocks of a pair together, in the pair's first iteration: every constant then serves
-      // four independent accumulators, from a vector register.  The second iteration takes its masks from there and goes
-      // on as ever.  A pair whose second block lies behind n_iter (n_iter is odd when `back` is 1) still has that block's
-      // text in the tile -- the staging reads whole pairs -- or, reading planes, whatever pln[1] held: its masks are never
-      // looked at, its planes are not stored, and nothing is read behind n_iter.
-      if (sub == 0) {
-        PiecePlanes pa, pb;
-        if constexpr (SRC == kPlaneRead) {
-          pa = PiecePlanes{pln[0].x, pln[0].y, pln[0].z, pln[0].w};
-          pb = PiecePlanes{pln[1].x, pln[1].y, pln[1].z, pln[1].w};
-        } else {
-          auto tile_planes = [&](uint32_t half) {
-            const uint32_t hs = (((half << 2) ^ (fsw & 4u)) << 4);
-            uint32_t x[16];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const uint4 v = *reinterpret_cast<const uint4*>(tile + rc[c] + hs);
-              x[4 * c] = v.x; x[4 * c + 1] = v.y; x[4 * c + 2] = v.z; x[4 * c + 3] = v.w;
-            }
-            const uint2 c0 = bit_plane<1>(x), c1 = bit_plane<2>(x);
-            return PiecePlanes{c0.x, c0.y, c1.x, c1.y};
-          };
-          pa = tile_planes(0u);
-          pb = tile_planes(1u);
-          if constexpr (SRC == kPlaneWrite) {
-            uint8_t* const at = const_cast<uint8_t*>(plane_base) + (uint64_t)it * 1024u + lane * 16u;
-            *reinterpret_cast<uint4*>(at) = make_uint4(pa.p0l, pa.p0h, pa.p1l, pa.p1h);
-            if (it + 1u < n_iter) *reinterpret_cast<uint4*>(at + 1024u) = make_uint4(pb.p0l, pb.p0h, pb.p1l, pb.p1h);
-          }
-        }
-        // (the table's address, opaque to the optimiser inside the loop: its words are read here, per pair, not held
-        // in 2 * Q * pieces registers across the loop)
-        uint32_t tab_at = 0;
-        asm volatile("" : "+v"(tab_at));
-        piece_pair_step<Q, NP>(pa, pb, prev0, prev1, piece_row_table_lds<Q, NP>() + tab_at, al, ah, bl, bh);
-      } else {
-#pragma unroll
-        for (int pp = 0; pp < NP; ++pp) { al[pp] = bl[pp]; ah[pp] = bh[pp]; }
-      }
-    } else {
     if constexpr (SRC == kPlaneRead) {
       const uint4 pv = sub ? pln[1] : pln[0];
       t0 = make_uint2(pv.x, pv.y);
@@ -2096,7 +2237,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     }
     prev0 = t0.y;
     prev1 = t1.y;
-    }
     uint32_t hit = 0;
 #pragma unroll
     for (int pp = 0; pp < NP; ++pp) hit |= al[pp] | ah[pp];
@@ -2144,26 +2284,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
           lo = (uint32_t)((int64_t)(bb * 64) - col_base);
           hi = (uint32_t)(c_hi - col_base);
         }
-        uint32_t lo1 = kRunNone, hi1 = 0;  // (G = 2: member 1's columns)
-        if constexpr (G == 2) {
-#pragma unroll
-          for (int pp = 0; pp < NP; ++pp) {
-            const uint64_t bits = ((uint64_t)ah[pp] << 32) | al[pp];
-            if (bits != 0) {
-              const bool m1 = (Pk->piece_member >> pp) & 1u;
-              const uint2 r = piece_end_cols(bits, b, (int64_t)Pk->piece_rem[pp], (int64_t)(m1 ? Pk->member1.k : Pk->k),
-                                             (int64_t)(Pk->n_blocks * 64), col_base);
-              if (m1) {
-                lo1 = min(lo1, r.x);
-                hi1 = max(hi1, r.y);
-              } else {
-                lo = min(lo, r.x);
-                hi = max(hi, r.y);
-              }
-            }
-          }
-        }
-        if (G == 1 && !n_inside) {
+        if (!n_inside) {
 #pragma unroll
         for (int pp = 0; pp < NP; ++pp) {
           const uint64_t bits = ((uint64_t)ah[pp] << 32) | al[pp];
@@ -2191,11 +2312,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
         if (lo != kRunNone)
           run = fuse_add_range(queue, qcount, Pk->cand_count + kCtlFuseWord, Pk->fuse_queue_cap, press_at, Pk->m + Pk->k, col_base,
                                fc > 0 ? (uint32_t)fc : 0u, run, lo, hi);
-        if constexpr (G == 2) {
-          if (lo1 != kRunNone)
-            run1 = fuse_add_range(queue1, qcount1, Pk->member1.cand_count + kCtlFuseWord, Pk->fuse_queue_cap, press_at,
-                                  Pk->member1.m + Pk->member1.k, col_base, fc > 0 ? (uint32_t)fc : 0u, run1, lo1, hi1);
-        }
       } else {
 #pragma unroll
         for (int pp = 0; pp < NP; ++pp) {
@@ -2211,9 +2327,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
     }
     if constexpr (FUSED) {
       // the queue is filling up: the block pair is done with the tile -- the chunk DP may have it
-      if (sub == 1u && __any(((run.w | (G == 2 ? run1.w : 0u)) & kRunPressure) != 0u)) { ++it; break; }
+      if (sub == 1u && __any((run.w & kRunPressure) != 0u)) { ++it; break; }
     }
   }
+  }  // G = 1
   if constexpr (!FUSED) break;
 
   if constexpr (FUSED) {
@@ -2238,13 +2355,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((CHECK || P
                                fc > 0 ? (uint32_t)fc : 0u, run, (uint32_t)(c_lo - col_base), (uint32_t)(c_hi - col_base));
         }
       }
-      if (run.x != kRunNone)
-        run = fuse_add_range(queue, qcount, Pk->cand_count + kCtlFuseWord, Pk->fuse_queue_cap, 0xFFFFFFFFu, Pk->m + Pk->k, col_base, 0u, run,
-                             kRunNone, 0u);
       if constexpr (G == 2) {
+        if (run.x != kRunNone)
+          run = fuse_add_range(queue, qcount, Pk->cand_count + kCtlFuseWord, Pk->fuse_queue_cap, 0xFFFFFFFFu, Pk->m + Pk->k, origin, 0u, run,
+                               kRunNone, 0u);
         if (run1.x != kRunNone)
           run1 = fuse_add_range(queue1, qcount1, Pk->member1.cand_count + kCtlFuseWord, Pk->fuse_queue_cap, 0xFFFFFFFFu,
-                                Pk->member1.m + Pk->member1.k, col_base, 0u, run1, kRunNone, 0u);
+                                Pk->member1.m + Pk->member1.k, origin, 0u, run1, kRunNone, 0u);
+      } else {
+        if (run.x != kRunNone)
+          run = fuse_add_range(queue, qcount, Pk->cand_count + kCtlFuseWord, Pk->fuse_queue_cap, 0xFFFFFFFFu, Pk->m + Pk->k, col_base, 0u, run,
+                               kRunNone, 0u);
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
